@@ -17,6 +17,9 @@ and `early_stop_fraction` say how much of the 2 x 20 480 steps an iteration exec
                    net, 4096 envs over 8 GPUs = 512 envs per GPU; a "step" = one rollout (512 x 2048 env steps) + PPO-Lagrangian update of
                    learn(), value = env-steps/s of learn(); ranks all-reduce once per rollout + update
   --mode seeds     north_star's other fan-out: rank r runs an independent ICRL run with seed s + r, NO collective; value = sum over ranks
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the headline path holds after its last step (policy and constraint-net
+                   parameters, Adam moments, nu, running moments, the last rollout buffer, the last iteration's metrics) as DIR/<name>.npy;
+                   the same arguments give the same inputs, so two builds can be compared output for output
 With one GPU the line also carries, as extras that are never `value`: `configs2` (BASELINE configs[2]: AntWall-v0, 256 envs, constraint
 net [40, 40], batch 128, 20 epochs; README.md:50 flags), `configs3_one_gpu` (configs[3]'s 2048 envs whole on this GPU) and `configs4`
 (configs[4]'s 512-env shard), each timed the same way.
@@ -110,11 +113,59 @@ def timed_iterations(cfg, warmup, steps, world=1):
     t0 = time.time()
     steps0 = st["timesteps"]
     for it in range(warmup, warmup + steps):
-        I.outer_iteration(st, it)
+        st["last_metrics"] = I.outer_iteration(st, it)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     return st, time.time() - t0, st["timesteps"] - steps0
+
+
+DUMP_BYTES_MAX = 64 << 20
+DUMP_ELEMS_MAX = 1 << 19       # larger arrays are dumped as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, agent, constraint_net=None, metrics=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step (icrl() returns the agent, the constraint net,
+    the train env and the metrics; cpg's learn() the agent) as out_dir/<name>.npy, float32 or float64 — parameters, Adam moments,
+    the dual variable, the running moments and the last rollout buffer; arrays above DUMP_ELEMS_MAX elements as a seeded sample."""
+    torch.cuda.synchronize()
+    arrs = {}
+
+    def put(name, x):
+        x = x.detach().reshape(-1) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)).reshape(-1)
+        if x.numel() > DUMP_ELEMS_MAX:
+            idx = np.sort(np.random.default_rng(0).choice(x.numel(), DUMP_ELEMS_MAX, replace=False, shuffle=False))
+            arrs[f"sample_idx_{x.numel()}"] = idx.astype(np.float64)      # (one index set per array size, shared by all arrays of that size)
+            x = x[torch.as_tensor(idx, device=x.device)]
+        a = x.cpu().numpy()
+        arrs[name] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+
+    pol = agent.policy
+    for k in ("params", "exp_avg", "exp_avg_sq"):
+        put(f"policy_{k}", getattr(pol, k))
+    put("dual_nu", [agent.dual.nu().item()])
+    for name in ("obs_rms", "ret_rms", "cost_rms"):
+        r = getattr(agent.env, name)
+        put(f"env_{name}", np.concatenate([np.atleast_1d(r.mean), np.atleast_1d(r.var), [r.count]]))
+    rb = agent.rollout_buffer
+    for k in ("observations", "actions", "log_probs", "rewards", "costs", "reward_values", "cost_values", "reward_advantages",
+              "cost_advantages", "reward_returns", "cost_returns", "dones"):
+        put(f"rollout_{k}", getattr(rb, k))
+    if constraint_net is not None:
+        for k in ("params", "exp_avg", "exp_avg_sq"):
+            put(f"cn_{k}", getattr(constraint_net, k))
+    if metrics is not None:      # (wall-clock entries left out: they differ from run to run by nature)
+        keys = sorted(k for k, v in metrics.items() if isinstance(v, (int, float, np.integer, np.floating))
+                      and not k.startswith(("time(", "time/")) and "fps" not in k)
+        put("metrics", [float(metrics[k]) for k in keys])
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_BYTES_MAX, f"dump of {total} bytes exceeds {DUMP_BYTES_MAX}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    if metrics is not None:
+        with open(os.path.join(out_dir, "metrics_keys.json"), "w") as f:
+            json.dump(keys, f)
 
 
 def update_summary(st, cfg):
@@ -510,6 +561,9 @@ def main():
     ap.add_argument("--no_scale_anchor", action="store_true", help="skip the one-rank anchors of the N > 1 lines (configs[3] / configs[4] shards through a 1-rank RCCL group)")
     ap.add_argument("--no_generic", action="store_true", help="skip the generic-shape extra (a non-default net_arch at toy size)")
     ap.add_argument("--envs_per_gpu", type=int, default=None, help="override the env count per GPU (e.g. 2048: BASELINE configs[3] whole on one GPU)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline path computed in its last step as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "<= 64 MB, large arrays as a fixed seeded sample): same arguments, same inputs, so two builds can be compared output for output")
     a = ap.parse_args()
 
     # ONE JSON line on stdout, whatever the libraries print: RCCL writes its version banner to the C-level stdout when its first
@@ -549,6 +603,8 @@ def main():
         dt, env_steps = reduce_over_ranks(dt, env_steps)
         if rank != 0:
             return
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, model)
         u, extra = cpg_summary(model, cfg, dt, env_steps, a.steps, a.warmup)
         sweep = gae_sweep_point()
         par = (f"env-shards x{world}, 1 all-reduce / rollout + update" if not seeds else f"independent seeds x{world}, no collective")
@@ -585,6 +641,8 @@ def main():
                            state_sha=h.hexdigest(), nu=float(ag.dual.nu().item()), adam_step=int(ag.policy.adam_step), env_steps=float(st["timesteps"])), f)
     if rank != 0:
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, st["agent"], st["constraint_net"], st.get("last_metrics"))
 
     # ---- roofline of the GAE kernel from the in-loop launches (events recorded on the launch stream)
     gae_us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in st["agent"].gae_events]

@@ -68,17 +68,21 @@ def test_configs4_cpg_transfer_two_ranks():
     assert r["us_per_optimizer_step"] > 0 and r["optimizer_steps_per_iteration"] > 0 and "all-reduce / rollout" in r["config"]["parallelism"]
 
 
-def test_eight_ranks_own_eight_shards_and_agree_after_the_reduce(tmp_path):
-    """The driver's 8-GPU launch line with eight ranks on ONE GPU (gloo transport, 8 envs per rank, forward_timesteps = one rollout): every rank
-    steps its own env-key range [seed + 8 r, seed + 8 r + 8), the whole-job value counts all eight shards, the N > 1 line carries per_gpu_value /
+MANY_RANKS = 4      # ranks sharing ONE GPU: with this test's own process that is 5 processes holding the device, within a shared box's limit of 6
+
+
+def test_many_ranks_own_their_shards_and_agree_after_the_reduce(tmp_path):
+    """The driver's N-GPU launch line with MANY_RANKS ranks on ONE GPU (gloo transport, 8 envs per rank, forward_timesteps = one rollout): every
+    rank steps its own env-key range [seed + 8 r, seed + 8 r + 8), the whole-job value counts every shard, the N > 1 line carries per_gpu_value /
     scale_anchor_ref / the measured all-reduce, and after the last outer iteration's single all-reduce all ranks hold the SAME policy, moments,
     constraint net, observation statistics and Lagrange multiplier."""
-    r = _launch(["--envs_per_gpu", "8"], nproc=8, timeout=1500, dump_dir=tmp_path)
-    assert r["n_gpus"] == 8 and r["config"]["baseline_config"] == 3 and r["scaling"] == "weak"
-    assert r["per_gpu_value"] == pytest.approx(r["value"] / 8, rel=1e-3) and isinstance(r["scale_anchor_ref"], str)
+    n = MANY_RANKS
+    r = _launch(["--envs_per_gpu", "8"], nproc=n, timeout=1500, dump_dir=tmp_path)
+    assert r["n_gpus"] == n and r["config"]["baseline_config"] == 3 and r["scaling"] == "weak"
+    assert r["per_gpu_value"] == pytest.approx(r["value"] / n, rel=1e-3) and isinstance(r["scale_anchor_ref"], str)
     assert r["allreduce"]["calls"] == 1 and r["allreduce"]["ms_per_iteration"] > 0
-    dumps = [json.load(open(os.path.join(tmp_path, f"rank{k}.json"))) for k in range(8)]
+    dumps = [json.load(open(os.path.join(tmp_path, f"rank{k}.json"))) for k in range(n)]
     ranges = sorted(tuple(d["env_keys"]) for d in dumps)
-    assert ranges == [(8 * k, 8 * k + 8, 8) for k in range(8)], ranges          # seed 0: eight disjoint, contiguous key ranges of 8 distinct keys
+    assert ranges == [(8 * k, 8 * k + 8, 8) for k in range(n)], ranges          # seed 0: disjoint, contiguous key ranges of 8 distinct keys
     assert len({d["state_sha"] for d in dumps}) == 1 and len({d["nu"] for d in dumps}) == 1 and len({d["adam_step"] for d in dumps}) == 1
     assert _steps(r) == pytest.approx(sum(d["env_steps"] for d in dumps) / 2, rel=1e-3)      # (warm-up + timed iteration in every rank's count)
