@@ -1,7 +1,12 @@
 """bench.py — env-steps/s of the ICRL outer loop (HCWithPos-v0 shapes, synthetic env) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config {1,3,4}] [--mode {shards,seeds}]
+    python bench.py --gpus 1 --steps K --warmup W [--config {1,3,4}] [--mode {shards,seeds}] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the line; what it adds to the
+line beyond the headline is read off the timed steps' own events (roofline_ppo, early stops, the all-reduce).  Everything
+that takes runs of its own (the GAE roofline and its size sweep, the CPU baseline, the extra configurations, the generic
+shape, the scale anchor, the seed batch) runs only with --full; there the --no_* flags still switch single parts off.
 
 A "step" is ONE outer ICRL iteration of BASELINE.json configs[1] (README.md:38 flags of the reference):
 64 vectorised envs per GPU, forward_timesteps 2e5 (= 2 rollouts of 64 x 2048 + 2 PPO-Lagrangian updates of 10 epochs x
@@ -20,11 +25,12 @@ and `early_stop_fraction` say how much of the 2 x 20 480 steps an iteration exec
   --dump-outputs DIR  after the timed steps, rank 0 writes what the headline path holds after its last step (policy and constraint-net
                    parameters, Adam moments, nu, running moments, the last rollout buffer, the last iteration's metrics) as DIR/<name>.npy;
                    the same arguments give the same inputs, so two builds can be compared output for output
-With one GPU the line also carries, as extras that are never `value`: `configs2` (BASELINE configs[2]: AntWall-v0, 256 envs, constraint
+  --full           also run the extras and figures below (the line of a plain run holds none of them; cpu_baseline is null)
+With one GPU and --full the line also carries, as extras that are never `value`: `configs2` (BASELINE configs[2]: AntWall-v0, 256 envs, constraint
 net [40, 40], batch 128, 20 epochs; README.md:50 flags), `configs3_one_gpu` (configs[3]'s 2048 envs whole on this GPU) and `configs4`
 (configs[4]'s 512-env shard), each timed the same way.
 
-The JSON line also carries
+The JSON line also carries (roofline and cpu_baseline with --full only)
   roofline      the dual-GAE kernel (the kernel BASELINE.json's metric names): algorithmic 36 B/transition / live event timing
                 of the in-loop launches, plus the same kernel at N = 131 072 envs where the 9.7 GB working set streams from HBM
   roofline_ppo  the persistent PPO-Lagrangian kernel (where the time goes): fp32 MFMA flops vs the 3 CUs it occupies
@@ -553,6 +559,9 @@ def main():
                     help="BASELINE configs[] index of the headline workload: 1 = 64 HCWithPos envs per GPU (default on one GPU), 3 = 256 per GPU = "
                          "2048 over 8 GPUs (default with --gpus > 1), 4 = the AntWall -> AntBroken transfer, 512 envs per GPU")
     ap.add_argument("--mode", default="shards", choices=("shards", "seeds"), help="shards: env shards + one all-reduce per outer iteration; seeds: independent runs, no collective")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: GAE roofline and size sweep, CPU baseline, the other BASELINE configs, the generic "
+                         "shape, the scale anchor, the seed batch (each still switched off by its --no_* flag); off: the headline alone")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_seed_batch", action="store_true")
     ap.add_argument("--no_configs2", action="store_true")
@@ -606,17 +615,18 @@ def main():
         if a.dump_outputs:
             dump_outputs(a.dump_outputs, model)
         u, extra = cpg_summary(model, cfg, dt, env_steps, a.steps, a.warmup)
-        sweep = gae_sweep_point()
         par = (f"env-shards x{world}, 1 all-reduce / rollout + update" if not seeds else f"independent seeds x{world}, no collective")
         out = dict(metric="env-steps/sec (cpg learn(), AntWallBroken-v0)", value=round(env_steps / dt, 1), unit="env-steps/s", n_gpus=world,
                    steps=a.steps, warmup=a.warmup, ms_per_step=round(1e3 * dt / a.steps, 2), higher_is_better=True, scaling="weak",
                    vs_baseline=None, dtype="f32", data="synthetic",
                    config=dict(workload=CPG_WORKLOAD.format(n=cfg.num_threads), envs_per_gpu=cfg.num_threads, n_steps=cfg.n_steps,
-                               batch_size=cfg.batch_size, n_epochs=cfg.n_epochs, baseline_config=4, mode=a.mode, parallelism=par),
-                   roofline=gae_roofline(sweep, None), **extra)
+                               batch_size=cfg.batch_size, n_epochs=cfg.n_epochs, baseline_config=4, mode=a.mode, parallelism=par))
+        if a.full:
+            out["roofline"] = gae_roofline(gae_sweep_point(), None)
+        out.update(extra)
         out["cpu_baseline"] = None
         out["per_gpu_value"] = round(env_steps / dt / world, 1)
-        out["scale_anchor_ref"] = "scale_anchor.configs4.value of the N = 1 line (`python bench.py`): the same 512-env shard on one rank through this code path"
+        out["scale_anchor_ref"] = "scale_anchor.configs4.value of the N = 1 line of `python bench.py --full`: the same 512-env shard on one rank through this code path"
         out["allreduce"] = allreduce_summary(getattr(model, "sync_events", None), a.steps)
         emit(out)
         return
@@ -644,19 +654,21 @@ def main():
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, st["agent"], st["constraint_net"], st.get("last_metrics"))
 
-    # ---- roofline of the GAE kernel from the in-loop launches (events recorded on the launch stream)
-    gae_us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in st["agent"].gae_events]
     T, N = cfg.n_steps, cfg.num_threads
-    gae_bytes = T * N * 36
-    gae_ach = gae_bytes / (np.mean(gae_us) * 1e-6) / 1e9
-    sweep = gae_sweep_point()
-    size_sweep = gae_size_sweep() if world == 1 else None
-    _GAE_BUFFERS.clear()
-    torch.cuda.empty_cache()
-    roofline = gae_roofline(sweep, dict(achieved=round(gae_ach, 1), frac=round(gae_ach / HBM_PEAK_GBS, 5), us_per_launch=round(float(np.mean(gae_us)), 1),
-                                        launches=len(gae_us), bytes_per_launch=gae_bytes,
-                                        note="the launch the loop itself makes (cache-resident, latency-bound): two-level scan, "
-                                             "time axis split over workgroups x 8 waves, rows register-resident (gae_dual_regsplit_kernel)"), size_sweep)
+    roofline = None
+    if a.full:
+        # ---- roofline of the GAE kernel from the in-loop launches (events recorded on the launch stream)
+        gae_us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in st["agent"].gae_events]
+        gae_bytes = T * N * 36
+        gae_ach = gae_bytes / (np.mean(gae_us) * 1e-6) / 1e9
+        sweep = gae_sweep_point()
+        size_sweep = gae_size_sweep() if world == 1 else None
+        _GAE_BUFFERS.clear()
+        torch.cuda.empty_cache()
+        roofline = gae_roofline(sweep, dict(achieved=round(gae_ach, 1), frac=round(gae_ach / HBM_PEAK_GBS, 5), us_per_launch=round(float(np.mean(gae_us)), 1),
+                                            launches=len(gae_us), bytes_per_launch=gae_bytes,
+                                            note="the launch the loop itself makes (cache-resident, latency-bound): two-level scan, "
+                                                 "time axis split over workgroups x 8 waves, rows register-resident (gae_dual_regsplit_kernel)"), size_sweep)
     # ---- the PPO kernel: algorithmic flops per optimiser step (update_flops) / the events around icrl_ppo_lag_train
     u = update_summary(st, cfg)
     B = cfg.batch_size
@@ -688,11 +700,11 @@ def main():
                optimizer_steps_per_iteration=round(u["optimizer_steps"] / a.steps, 1),
                early_stop_fraction=round(1.0 - u["optimizer_steps"] / max(1, u["full_steps"]), 4),
                value_no_early_stop=round(no_early_stop(env_steps / world, dt, u) * world, 1),      # (rank 0's step counts stand for every rank's)
-               roofline=roofline, roofline_ppo=roofline_ppo)
-    out["cpu_baseline"] = None if (a.no_cpu_baseline or world > 1) else cpu_baseline()      # reported at N = 1 only
+               **({} if roofline is None else dict(roofline=roofline)), roofline_ppo=roofline_ppo)
+    out["cpu_baseline"] = None if (not a.full or a.no_cpu_baseline or world > 1) else cpu_baseline()      # reported at N = 1 only
     out["per_gpu_value"] = round(env_steps / dt / world, 1)
     if world > 1:
-        out["scale_anchor_ref"] = ("scale_anchor.configs3.value of the N = 1 line (`python bench.py`): the same 256-env shard on one rank through this code path"
+        out["scale_anchor_ref"] = ("scale_anchor.configs3.value of the N = 1 line of `python bench.py --full`: the same 256-env shard on one rank through this code path"
                                    if config_id == 3 and envs == 256 else "a one-rank run of this line's own flags")
         out["allreduce"] = allreduce_summary(st["sync_events"], a.steps)
     if out["cpu_baseline"] is not None:       # no published number exists for this metric: the ratio to the reference-equivalent CPU figure
@@ -700,6 +712,9 @@ def main():
         out["vs_baseline_note"] = "value / cpu_baseline.reference_equivalent (the reference's CPU path on this host, via the port: BASELINE.md section 4); BASELINE.md publishes no number for this metric"
     del st
     torch.cuda.empty_cache()
+    if not a.full:
+        emit(out)
+        return
     if world == 1 and not a.no_configs2:
         out["configs2"] = configs2_leg(a.seed)
     if world == 1 and not a.no_configs3 and config_id == 1 and a.envs_per_gpu is None:

@@ -34,7 +34,7 @@ def _steps(r):
 
 
 def test_default_multi_gpu_config_is_baseline_configs3():
-    r = _launch(["--envs_per_gpu", "8"])
+    r = _launch(["--envs_per_gpu", "8", "--full"])
     assert r["n_gpus"] == 2 and r["steps"] == 1 and r["warmup"] == 1 and r["scaling"] == "weak" and r["higher_is_better"] is True
     assert r["config"]["baseline_config"] == 3 and r["config"]["mode"] == "shards" and "all-reduce" in r["config"]["parallelism"]
     # whole-job value: both ranks' env steps (forward_timesteps 2e5 -> 13 rollouts of 8 x 2048 per rank) / the slower rank's time
@@ -53,6 +53,7 @@ def test_without_overrides_the_shard_is_256_envs():
     """no --envs_per_gpu: the per-GPU shard of configs[3] (2048 envs / 8 GPUs); checked on the parsed workload, one rank is enough."""
     r = _launch([], nproc=2)
     assert r["config"]["envs_per_gpu"] == 256 and r["config"]["baseline_config"] == 3
+    assert "roofline" not in r and r["cpu_baseline"] is None              # a plain run: the headline alone, no sweep of its own
     assert _steps(r) == pytest.approx(2 * 256 * 2048, rel=1e-3)
 
 

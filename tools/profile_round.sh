@@ -4,9 +4,13 @@
 # tables; outputs under gpurun_out/, summarised afterwards with tools/summarize_profiles.py <tag> and
 # tools/summarize_pmc_train.py <tag> into profiles/.
 tag=$1
+# the folder of the bench trace (second argument): the one tools/summarize_profiles.py reads, where the passes below write too
+out=${2:?"usage: bash tools/profile_round.sh <tag> <output folder>"}
+out=$(realpath -m "$out")
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$tag -- python3 $R/bench.py --steps 2 --warmup 1 --no_cpu_baseline --no_seed_batch --no_configs2 --no_configs3 --no_configs4 --no_generic > $R/gpurun_out/prof_$tag.log 2>&1
+# the bench trace: --full for the GAE sweep and the scale anchor it traces, the other extras switched off
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$tag -- python3 $R/bench.py --full --steps 2 --warmup 1 --no_cpu_baseline --no_seed_batch --no_configs2 --no_configs3 --no_configs4 --no_generic > $out/prof_$tag.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_${tag}_f -- python3 $R/tools/gae_once.py > $R/gpurun_out/pmc_${tag}_f.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_${tag}_w -- python3 $R/tools/gae_once.py > $R/gpurun_out/pmc_${tag}_w.log 2>&1
 export GAE_N=32768      # the register-resident split scan (mid range): does it read every byte once?

@@ -66,7 +66,7 @@ def kernel_stats(tag, which="bench"):
                     "(ppo_lag.py:293-297) ended their epoch loops early." if us else ".") +
                    (" The short launches in front of the first update are the placement calibration (`tune_sync_placement` was on in this run)." if tuned else ""))
     head = (f"# rocprofv3 --kernel-trace --stats — bench.py --steps 2 --warmup 1 ({tag})\n\n"
-            "command: `rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_<tag> -- python3 bench.py --steps 2 "
+            "command: `rocprofv3 --kernel-trace --stats --output-format csv -d <output folder>/prof_<tag> -- python3 bench.py --full --steps 2 "
             "--warmup 1 --no_cpu_baseline --no_seed_batch --no_configs2 --no_configs3 --no_configs4 --no_generic` (3 outer iterations traced incl. warm-up, plus the GAE sweep launches at N = 131 072)\n\n"
             if which == "bench" else
             f"# rocprofv3 --kernel-trace --stats — BASELINE configs[2] (AntWall-v0, 256 envs, batch 128, [40, 40]) ({tag})\n\n"
