@@ -21,7 +21,7 @@ from . import callbacks, distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
 from .true_constraint_net import get_true_cost_function, null_cost
-from . import spaces
+from . import envs, spaces
 
 
 class _History(callbacks.BaseCallback):
@@ -48,12 +48,14 @@ def setup(config, log=print):
     logger.configure()          # a fresh scalar log per run (the reference configures its logger in learn())
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
+    envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=True,
                                      base_seed=config.seed, num_threads=config.num_threads,
                                      normalize_obs=not config.dont_normalize_obs, normalize_reward=not config.dont_normalize_reward,
                                      normalize_cost=not config.dont_normalize_cost, cost_info_str=config.cost_info_str,
                                      reward_gamma=config.reward_gamma, cost_gamma=config.cost_gamma,
-                                     env_index_offset=rank * config.num_threads, device=dev)
+                                     env_index_offset=rank * config.num_threads, device=dev,
+                                     dummy_vec_env=getattr(config, "dummy_vec_env", False))
     eval_env = utils.make_eval_env(env_id=config.eval_env_id, use_cost_wrapper=True, normalize_obs=not config.dont_normalize_obs,
                                    seed=config.seed + rank * config.num_threads, device=dev)
     is_discrete = isinstance(train_env.action_space, spaces.Discrete)
@@ -165,6 +167,8 @@ def build_parser():
     a("--cn_device", "-cd", type=str, default=None); a("--load_gail", "-lg", action="store_true")
     a("--save_dir", type=str, default=None); a("--eval_every_rollouts", type=int, default=0)
     a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
+    a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
+    a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     return p
 
 

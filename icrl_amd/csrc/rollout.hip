@@ -3040,6 +3040,203 @@ __global__ void __launch_bounds__(192) sample_episodes_batch_kernel(const Sample
   sample_episodes_body<OCT>(a);
 }
 
+// =================================================================================================================
+// rollout over host envs (icrl_host_step): one launch per env step, one workgroup per env, no waiting between workgroups.
+// Launch k finishes step k - 1 from the staging block (the statistics pass of rollout_persistent_body, replicated, reading the
+// observation columns straight from the staging block in global memory) and then runs act_step_kernel's work for step k minus
+// the env step.  What every workgroup reads and one workgroup writes — running statistics, the returns, the raw costs of the
+// previous launch — lives in two copies selected by step parity (HostCopy).
+// =================================================================================================================
+struct HostStepArgs {
+  ActStepArgs act;
+  icrl_norm_t nm;
+  icrl_host_step_t hs;
+  int N;
+};
+
+// one copy of the state carried between launches, in doubles: obs mean [O] | obs var [O] | obs count | ret_stats [3] |
+// cost_stats [3] | ret [N] | cost_ret [N] | raw cost [N]
+__host__ __device__ inline size_t host_copy_doubles(int N, int O) { return (size_t)2 * O + 7 + (size_t)3 * N; }
+struct HostCopy {
+  double *mean, *var, *count, *ret_stats, *cost_stats, *ret, *cost_ret, *cost;
+  __device__ HostCopy(double* base, int N, int O)
+      : mean(base), var(base + O), count(base + 2 * O), ret_stats(base + 2 * O + 1), cost_stats(base + 2 * O + 4),
+        ret(base + 2 * O + 7), cost_ret(base + 2 * O + 7 + N), cost(base + 2 * O + 7 + 2 * N) {}
+};
+
+template <int OCT, int CIT>
+__global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
+  __shared__ ActShared sh;
+  __shared__ double vec[2][128], dev2[2][128], ret_s[128], cret_s[128], rawr_s[128];
+  __shared__ float rawc_s[128];
+  __shared__ double dens[2];
+  __shared__ int done_s[128];
+  __shared__ int last_done_s;
+  const ActStepArgs& a = h.act;
+  const icrl_norm_t& nm = h.nm;
+  WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
+  WaveRegs<OCT, CIT>& C = R;
+  const int T = h.hs.T;
+  if (k < T) {
+    load_pol_regs<OCT>(a.pl, a.PT, R);
+    if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
+  }
+  const int n = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int O = a.pl.O, A = a.pl.A, N = h.N;
+  const int AS = a.buf.act_store;
+  const bool has_cost = a.has_cn != 0;
+  double* const ws = reinterpret_cast<double*>(h.hs.ws);
+  const size_t CP = host_copy_doubles(N, O);
+  const HostCopy src(ws + (size_t)((k + 1) & 1) * CP, N, O);      // written by launch k - 1
+  const HostCopy dst(ws + (size_t)(k & 1) * CP, N, O);            // written here (workgroup 0), read by launch k + 1
+  const double* const st_obs = reinterpret_cast<const double*>(h.hs.stage);
+  const double* const st_rew = st_obs + (size_t)N * O;
+  const uint8_t* const st_done = reinterpret_cast<const uint8_t*>(st_rew + N);
+  if (k == 0) {
+    // the rollout's first launch: the state as the previous rollout (or reset) left it
+    for (int i = tid; i < MAX_OBS; i += 256) {
+      sh.x[i] = i < O ? (float)a.ag.last_obs[(size_t)n * O + i] : 0.f;
+      if (i < O) sh.s_old[i] = h.hs.s[(size_t)n * O + i];
+    }
+    if (tid == 0) last_done_s = a.ag.last_dones[n];
+    if (n == 0) {        // launch 1 reads copy 0
+      if (tid < O) { dst.mean[tid] = nm.obs_mean[tid]; dst.var[tid] = nm.obs_var[tid]; }
+      if (tid == 0) dst.count[0] = nm.obs_count[0];
+      if (tid < 3) { dst.ret_stats[tid] = nm.ret_stats[tid]; if (has_cost) dst.cost_stats[tid] = nm.cost_stats[tid]; }
+      if (tid < N) { dst.ret[tid] = nm.ret[tid]; if (has_cost) dst.cost_ret[tid] = nm.cost_ret[tid]; }
+    }
+  } else {
+    // ---------------- finish step k - 1 (rollout_persistent_body's phase B over the staging block) ----------------
+    const size_t tn = (size_t)(k - 1) * N + n;
+    double o_mean = 0.0, o_var = 1.0, o_cnt = 0.0;
+    if (tid < O) { o_mean = src.mean[tid]; o_var = src.var[tid]; o_cnt = src.count[0]; }
+    double st_m = 0.0, st_v = 1.0, st_c = 0.0;
+    if (w == 3) { st_m = src.ret_stats[0]; st_v = src.ret_stats[1]; st_c = src.ret_stats[2]; }
+    if (w == 2 && has_cost) { st_m = src.cost_stats[0]; st_v = src.cost_stats[1]; st_c = src.cost_stats[2]; }
+    if (tid < N) {
+      const double rr = st_rew[tid];
+      const float rc = has_cost ? (float)src.cost[tid] : 0.f;
+      const double r0 = src.ret[tid], c0 = has_cost ? src.cost_ret[tid] : 0.0;
+      ret_s[tid] = r0; cret_s[tid] = c0;
+      rawr_s[tid] = rr; rawc_s[tid] = rc; done_s[tid] = (int)st_done[tid];
+      double r = r0, c = c0;
+      if (nm.training) {
+        r = r * nm.reward_gamma + rr;
+        if (has_cost) c = c * nm.cost_gamma + (double)rc;
+      }
+      vec[0][tid] = r; vec[1][tid] = c;
+    }
+    __syncthreads();
+    if (nm.training) {
+      if (tid < O) {           // obs_rms.update: rows added in order (numpy's axis-0 reduction)
+        double bm, bv;
+        column_moments(st_obs + tid, O, N, bm, bv);
+        chan_merge(o_mean, o_var, o_cnt, bm, bv, (double)N);
+        o_cnt = (double)N + o_cnt;
+      }
+      if (w == 3 || (w == 2 && has_cost)) {     // ret_rms / cost_rms: numpy pairwise order
+        const int v = w == 3 ? 0 : 1;
+        const double bm = np_leaf_sum_wave(vec[v], N) / (double)N;
+        for (int i = lane; i < N; i += 64) { const double d = vec[v][i] - bm; dev2[v][i] = d * d; }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        const double bv = np_leaf_sum_wave(dev2[v], N) / (double)N;
+        chan_merge(st_m, st_v, st_c, bm, bv, (double)N);
+        st_c = (double)N + st_c;
+      }
+    }
+    if (lane == 0 && w == 3) dens[0] = sqrt(st_v + nm.epsilon);
+    if (lane == 0 && w == 2) dens[1] = sqrt(st_v + nm.epsilon);
+    if (tid >= O && tid < MAX_OBS) sh.x[tid] = 0.f;      // pad = 0 (the forward reads whole float4 rows against zero pad weights)
+    if (tid < O) {             // own env: normalise + clip, next policy input
+      const double raw = st_obs[(size_t)n * O + tid];
+      double o = raw;
+      if (nm.norm_obs) o = fmin(fmax((o - o_mean) / sqrt(o_var + nm.epsilon), -nm.clip_obs), nm.clip_obs);
+      sh.x[tid] = (float)o;
+      sh.s_old[tid] = raw;
+      a.buf.new_observations[tn * O + tid] = (float)o;
+      a.buf.new_orig_observations[tn * O + tid] = (float)raw;
+      a.ag.last_obs[(size_t)n * O + tid] = o;
+      h.hs.s[(size_t)n * O + tid] = raw;
+    }
+    __syncthreads();
+    if (tid < N) {
+      const int d = done_s[tid];
+      if (nm.training || d) { ret_s[tid] = d ? 0.0 : vec[0][tid]; if (has_cost) cret_s[tid] = d ? 0.0 : vec[1][tid]; }
+    }
+    if (tid == 0) {
+      double r = rawr_s[n];
+      if (nm.norm_reward) r = fmin(fmax(r / dens[0], -nm.clip_reward), nm.clip_reward);
+      a.buf.rewards[tn] = (float)r;
+      if (has_cost) {
+        double c = (double)rawc_s[n];
+        if (nm.norm_cost) c = fmin(fmax(c / dens[1], -nm.clip_cost), nm.clip_cost);
+        a.buf.costs[tn] = (float)c;
+      }
+      last_done_s = done_s[n];
+      a.ag.last_dones[n] = (uint8_t)done_s[n];
+      a.ag.raw_rew[n] = rawr_s[n];
+      a.ag.dones[n] = (uint8_t)done_s[n];
+    }
+    if (n == 0) {              // the statistics for launch k + 1; after the rollout's last step also the normaliser's own arrays
+      const bool last = k == T;
+      if (tid < O) {
+        dst.mean[tid] = o_mean; dst.var[tid] = o_var;
+        if (last) { nm.obs_mean[tid] = o_mean; nm.obs_var[tid] = o_var; }
+      }
+      if (tid == 0) { dst.count[0] = o_cnt; if (last) nm.obs_count[0] = o_cnt; }
+      if (lane == 0 && w == 3) {
+        dst.ret_stats[0] = st_m; dst.ret_stats[1] = st_v; dst.ret_stats[2] = st_c;
+        if (last) { nm.ret_stats[0] = st_m; nm.ret_stats[1] = st_v; nm.ret_stats[2] = st_c; }
+      }
+      if (lane == 0 && w == 2 && has_cost) {
+        dst.cost_stats[0] = st_m; dst.cost_stats[1] = st_v; dst.cost_stats[2] = st_c;
+        if (last) { nm.cost_stats[0] = st_m; nm.cost_stats[1] = st_v; nm.cost_stats[2] = st_c; }
+      }
+    }
+    __syncthreads();
+    if (n == 0 && tid < N) {
+      dst.ret[tid] = ret_s[tid];
+      if (has_cost) dst.cost_ret[tid] = cret_s[tid];
+      if (k == T) { nm.ret[tid] = ret_s[tid]; if (has_cost) nm.cost_ret[tid] = cret_s[tid]; }
+    }
+  }
+  if (k >= T) return;
+  // ---------------- act for step k: act_step_kernel minus the env step ----------------
+  __syncthreads();
+  const size_t tn = (size_t)k * N + n;
+  const float* noise_row = a.noise + tn * (a.pl.discrete ? 1 : A);
+  policy_forward_block<OCT>(a.pl, R, sh, noise_row, 0, a.alow, a.ahigh);
+  __syncthreads();
+  if (w == 0) {
+    const int AH = a.pl.discrete ? 1 : A;       // the host reads the clipped action (the index when discrete) after its sync
+    if (lane < AH) h.hs.act_host[(size_t)n * AH + lane] = sh.act_clip[lane];
+  } else if (w == 3) {
+    float cost = 0.f;
+    if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+    if (lane == 0) {
+      a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
+      dst.cost[n] = (double)cost;              // read by every workgroup of launch k + 1 (ag.raw_cost[n] is rewritten by launch k + 1)
+    }
+  } else if (w == 2) {
+    float* ob = a.buf.observations + tn * O;
+    float* oob = a.buf.orig_observations + tn * O;
+    for (int i = lane; i < O; i += WAVE) { ob[i] = sh.x[i]; oob[i] = (float)sh.s_old[i]; }
+    if (lane < AS) a.buf.actions[tn * AS + lane] = sh.act_raw[lane];
+    if (lane < A && !a.pl.discrete) a.ag.act_clipped[(size_t)n * A + lane] = sh.act_clip[lane];
+    if (lane == 0) {
+      a.buf.dones[tn] = (float)last_done_s;
+      a.buf.reward_values[tn] = sh.scal[0];
+      a.buf.cost_values[tn] = sh.scal[1];
+      a.buf.log_probs[tn] = sh.scal[2];
+      a.ag.last_v_r[n] = sh.scal[0];
+      a.ag.last_v_c[n] = sh.scal[1];
+    }
+  }
+}
+
 // rows from which icrl_policy_forward / icrl_policy_evaluate take the 16-rows-per-pass MFMA kernel (below: one workgroup per row)
 constexpr int ROWS_KERNEL_MIN = 64;
 
@@ -3835,4 +4032,47 @@ extern "C" int icrl_rollout_collect(const icrl_env_t* env, const icrl_norm_t* nm
                                     void* stream) {
   return icrl_rollout_collect_ex(env, nm, pol, cn, buf, ag, noise, action_low, action_high, reward_gamma, reward_gae_lambda,
                                  cost_gamma, cost_gae_lambda, 1, stream);
+}
+
+// ---- rollout over host envs: one launch per env step (host_step_kernel) ----
+extern "C" size_t icrl_host_step_ws_bytes(int N, int obs_dim) {
+  return N < 1 || obs_dim < 1 ? 0 : 2 * host_copy_doubles(N, obs_dim) * sizeof(double);
+}
+
+extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
+                              const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
+                              const float* action_high, int k, void* stream) {
+  if (nm == nullptr || pol == nullptr || buf == nullptr || ag == nullptr || hs == nullptr) return fail("icrl_host_step: NULL descriptor");
+  const int N = buf->N, O = buf->obs_dim, T = hs->T;
+  if (policy_is_wide(pol) || !dims_ok(pol)) return bad_dims("icrl_host_step", pol);
+  if (cn != nullptr && (costnet_is_wide(cn) || !cn_ok(cn))) return bad_cn("icrl_host_step", cn);
+  if (N < 1 || N > 128 || O < 1 || O > MAX_OBS || pol->obs_dim != O)
+    return fail("icrl_host_step: %d envs (1..128), obs_dim %d (1..%d), policy obs_dim %d: other shapes take the per-step loop", N, O, MAX_OBS, pol->obs_dim);
+  if (!nm->training) return fail("icrl_host_step: the normaliser is not training (statistics frozen): the per-step loop serves that");
+  if (T < 1 || buf->T != T || k < 0 || k > T) return fail("icrl_host_step: launch k = %d of T = %d (buffer T = %d)", k, T, buf->T);
+  if (buf->act_store != (pol->discrete ? 1 : pol->act_dim)) return fail("icrl_host_step: buffer act_store %d vs policy act_dim %d", buf->act_store, pol->act_dim);
+  if (hs->stage == nullptr || hs->s == nullptr || hs->act_host == nullptr || hs->ws == nullptr || pol->params_t == nullptr || (k < T && noise == nullptr) ||
+      (size_t)hs->ws_bytes < icrl_host_step_ws_bytes(N, O))
+    return fail("icrl_host_step: staging / raw-obs / action / workspace pointers, transposed policy, noise and %zu workspace bytes are required (got %lld)",
+                icrl_host_step_ws_bytes(N, O), hs->ws_bytes);
+  HostStepArgs h{};
+  ActStepArgs& a = h.act;
+  a.env.n_envs = N; a.env.obs_dim = O; a.env.act_dim = pol->discrete ? 1 : pol->act_dim;
+  a.buf = *buf; a.ag = *ag;
+  a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
+  a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
+  a.has_cn = cn != nullptr;
+  if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
+  h.nm = *nm; h.hs = *hs; h.N = N;
+  // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
+  void* act_dev = nullptr;
+  if (hipHostGetDevicePointer(&act_dev, hs->act_host, 0) != hipSuccess || act_dev == nullptr) {
+    (void)hipGetLastError();
+    return fail("icrl_host_step: act_host %p is not page-locked host memory mapped for the device (hipHostMalloc / hipHostRegister)", (void*)hs->act_host);
+  }
+  h.hs.act_host = reinterpret_cast<float*>(act_dev);
+  hipStream_t s = (hipStream_t)stream;
+  if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
+  else hipLaunchKernelGGL((host_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, h, k);
+  return (int)hipGetLastError();
 }

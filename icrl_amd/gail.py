@@ -19,7 +19,7 @@ import types
 import numpy as np
 import torch
 
-from . import callbacks, distributed as D, logger, spaces, utils
+from . import callbacks, distributed as D, envs, logger, spaces, utils
 from .gail_utils import GailCallback, GailDiscriminator
 from .ppo_lag import PPOLagrangian
 from .true_constraint_net import get_true_cost_function
@@ -45,11 +45,13 @@ def gail(config, log=print):
     logger.configure()
     rank = getattr(config, "rank", 0)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
+    envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=False,
                                      base_seed=config.seed, num_threads=config.num_threads,
                                      normalize_obs=not config.dont_normalize_obs, normalize_reward=not config.dont_normalize_reward,
                                      normalize_cost=False, reward_gamma=config.reward_gamma,
-                                     env_index_offset=rank * config.num_threads, device=dev)
+                                     env_index_offset=rank * config.num_threads, device=dev,
+                                     dummy_vec_env=getattr(config, "dummy_vec_env", False))
     eval_env = utils.make_eval_env(env_id=config.eval_env_id, use_cost_wrapper=False, normalize_obs=not config.dont_normalize_obs,
                                    seed=config.seed + rank * config.num_threads, device=dev)
     is_discrete = isinstance(train_env.action_space, spaces.Discrete)
@@ -128,6 +130,8 @@ def build_parser():
     a("--expert_rollouts", "-er", type=int, default=20); a("--num_spurious_features", "-nsf", type=int, default=None)
     a("--use_cost_shaping_callback", "-ucsc", action="store_true"); a("--use_cost_net", "-ucn", action="store_true")
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
+    a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
+    a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     return p
 
 

@@ -22,19 +22,21 @@ from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
 from .true_constraint_net import get_true_cost_function, mean_cost, null_cost
 from .vec_env import VecNormalize, sync_envs_normalization
-from . import spaces
+from . import envs, spaces
 
 
 def setup(config):
     """everything of icrl() before the loop (ref: icrl/icrl.py:45-197): env stacks, expert data, constraint net, nominal agent."""
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
+    envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=True,
                                      base_seed=config.seed, num_threads=config.num_threads,
                                      normalize_obs=not config.dont_normalize_obs, normalize_reward=not config.dont_normalize_reward,
                                      normalize_cost=not config.dont_normalize_cost, cost_info_str=config.cost_info_str,
                                      reward_gamma=config.reward_gamma, cost_gamma=config.cost_gamma,
-                                     env_index_offset=rank * config.num_threads, device=dev)
+                                     env_index_offset=rank * config.num_threads, device=dev,
+                                     dummy_vec_env=getattr(config, "dummy_vec_env", False))
     sampling_env = utils.make_eval_env(env_id=config.train_env_id, use_cost_wrapper=False, normalize_obs=not config.dont_normalize_obs,
                                        seed=config.seed + rank * config.num_threads, device=dev)
     eval_env = utils.make_eval_env(env_id=config.eval_env_id, use_cost_wrapper=False, normalize_obs=not config.dont_normalize_obs,
@@ -261,6 +263,8 @@ def build_parser():
     # additions of this build
     a("--expert_agent_path", type=str, default=None, help="agent zip / npz with policy.pth for the KL metrics")
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
+    a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
+    a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     return p
 
 

@@ -20,8 +20,8 @@ from . import _lib, logger, spaces
 from .buffers import RolloutBufferWithCost
 from .dual_variable import DualVariable, PIDLagrangian
 from .policies import ActorTwoCriticsPolicy
-from .structs import AgentT, PpoHyperT, p
-from .vec_env import HipSynthVecEnv, VecCostWrapper, VecEnv, VecNormalize, VecNormalizeWithCost
+from .structs import AgentT, HostStepT, PpoHyperT, p
+from .vec_env import HipSynthVecEnv, HostVecEnv, VecCostWrapper, VecEnv, VecNormalize, VecNormalizeWithCost
 
 
 def _const_fn(v):
@@ -134,6 +134,19 @@ class PPOLagrangian:
             return None
         return env, cw, cw.venv
 
+    def _host_chain(self):
+        """the counterpart of _fused_chain over host envs: VecNormalizeWithCost -> [VecCostWrapper with a device ConstraintNet] ->
+        HostVecEnv (without the cost wrapper: the GAIL chain)."""
+        env = self.env
+        if not isinstance(env, VecNormalizeWithCost):
+            return None
+        cw = env.venv
+        if isinstance(cw, HostVecEnv):
+            return env, None, cw
+        if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HostVecEnv) or cw.constraint_net() is None:
+            return None
+        return env, cw, cw.venv
+
     # ---- noise / permutation streams -------------------------------------------------------------------------------------
     def _draw_action_noise(self, T):
         N = self.n_envs
@@ -156,6 +169,10 @@ class PPOLagrangian:
         """ref: on_policy_algorithm.py:340-421."""
         assert self._last_obs is not None, "No previous observation was provided"
         if not self._fused_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
+            if self._host_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
+                return self._collect_rollouts_host(env, callback, rollout_buffer, n_rollout_steps, noise)
+            if noise is None and self._host_chain() is not None and isinstance(cost_function, str) and n_rollout_steps == rollout_buffer.buffer_size:
+                noise = self._draw_action_noise(n_rollout_steps)     # (a host chain the kernel does not serve: the fused path's draws)
             return self._collect_rollouts_stepped(env, callback, rollout_buffer, n_rollout_steps, cost_function, noise)
         job = self._rollout_begin(callback, rollout_buffer, n_rollout_steps, noise)
         self._rollout_launch(job)
@@ -234,6 +251,102 @@ class PPOLagrangian:
             self._ag["status"].zero_()
             raise RuntimeError("icrl_rollout_collect: inter-workgroup exchange timed out (a workgroup of the persistent "
                                "rollout was not resident); rollout buffer and normaliser statistics are invalid")
+
+    def _host_rollout_ok(self, cost_function, n_rollout_steps, rollout_buffer):
+        """what icrl_host_step serves: a host chain, a string cost key, a full rollout, a training normaliser, the policy / constraint-net
+        shapes of the one-workgroup-per-env kernels, <= 128 envs and observations."""
+        chain = self._host_chain()
+        if chain is None or not isinstance(cost_function, str) or n_rollout_steps != rollout_buffer.buffer_size:
+            return False
+        nenv, cw, henv = chain
+        cn = cw.constraint_net() if cw is not None else None
+        # the limits icrl_host_step checks (csrc/rollout.hip: dims_ok / cn_ok — obs <= MAX_OBS 128, act <= MAX_ACT 16, hidden <= MAX_H 64
+        # (`wide`), cost-net inputs <= MAX_CN_IN 160 — and N <= 128); other shapes take the per-step loop
+        pol_ok = not self.policy.wide and self.policy.obs_dim <= 128 and self.policy.act_dim <= 16
+        cn_ok = cn is None or (not cn.wide and cn.input_dims <= 160 and cn.obs_dim <= 128 and cn.acs_dim <= 16)
+        return bool(nenv.training) and pol_ok and cn_ok and henv.num_envs <= 128 and henv.obs_dim <= 128
+
+    def _collect_rollouts_host(self, env, callback, rollout_buffer, n_rollout_steps, noise=None):
+        """The rollout over a host chain: T + 1 launches of icrl_host_step with the T host env steps between them.  Per env step: the
+        host reads the clipped actions the previous launch wrote into pinned memory (after one stream synchronisation), steps the
+        envs, fills the pinned staging block, and enqueues ONE host-to-device copy and ONE launch (which finishes that step — normaliser,
+        buffer row — and acts for the next).  The noise is drawn up front like the fused rollout's, so a host run repeats a device
+        run with the same seed.  Afterwards GAE, and the wrapper-visible state as _rollout_end leaves it (the next rollout may take
+        any path).  No graph capture: every launch waits for the host anyway."""
+        nenv, cw, henv = self._host_chain()
+        rollout_buffer.reset()
+        if callback is not None:
+            callback.on_rollout_start()
+        T, N, O = n_rollout_steps, henv.num_envs, henv.obs_dim
+        if noise is None:
+            noise = self._draw_action_noise(T)
+        st = henv.staging()
+        lib, b = _lib.lib(), _lib.byref
+        ws_bytes = int(lib.icrl_host_step_ws_bytes(N, O))
+        if getattr(self, "_host_ws", None) is None or self._host_ws.numel() * 8 < ws_bytes:
+            self._host_ws = torch.zeros((ws_bytes + 7) // 8, dtype=torch.float64, device=self.device)
+        self._last_obs = self._last_obs.to(device=self.device, dtype=torch.float64).contiguous()
+        hs = HostStepT(T, 0, p(st["dev"]), p(henv.s), st["act"].data_ptr(), p(self._host_ws), self._host_ws.numel() * 8)
+        nm, pol, buf = nenv.struct(), self.policy.struct(), rollout_buffer.struct()
+        cn = cw.constraint_net().struct() if cw is not None else None
+        ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
+                    p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
+                    p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
+        stream = _lib.current_stream()
+        cs = torch.cuda.current_stream()
+        act = st["act"].numpy()
+
+        def launch(k):
+            _lib.check(lib.icrl_host_step(b(nm), b(pol), b(cn) if cn is not None else None, b(buf), b(ag), b(hs), p(noise), p(self._alow),
+                                          p(self._ahigh), k, stream), "icrl_host_step")
+
+        launch(0)
+        for k in range(1, T + 1):
+            cs.synchronize()                    # the actions of step k - 1 are in pinned memory; the staging block is free again
+            obs, rew, done, _infos = henv.step_host(act)
+            st["obs"][:] = obs
+            st["rew"][:] = rew
+            st["done"][:] = done
+            st["dev"].copy_(st["pin"], non_blocking=True)
+            launch(k)
+            self.num_timesteps += N
+            if callback is not None and hasattr(callback, "on_step") and callback.on_step() is False:
+                # the rollout ends after k env steps: the normaliser's arrays get the statistics launch k computed (only the last
+                # launch of a full rollout writes them), the wrappers the last step's state — as the per-step loop leaves them.
+                # _last_obs / _last_original_obs / _last_dones describe the envs after that step (the per-step loop returns before it
+                # updates its own copies, one step behind the envs)
+                self._host_stats_to_normaliser(k, nenv, cw is not None, N, O)
+                self._host_wrapper_state(nenv, cw, henv)
+                return False
+        rollout_buffer.compute_returns_and_advantage(self._ag["last_v_r"], self._ag["last_v_c"], self._ag["last_dones"])
+        self._keepalive = (noise,)
+        rollout_buffer.pos, rollout_buffer.full = T, True
+        self._host_wrapper_state(nenv, cw, henv)
+        if callback is not None:
+            callback.on_rollout_end()
+        return True
+
+    def _host_wrapper_state(self, nenv, cw, henv):
+        """wrapper-visible "last step" state after a host rollout, as _rollout_end leaves it after a device one."""
+        last_raw = henv.s.clone()        # (a copy: the per-step loop's env.step rewrites henv.s before it reads the previous observation)
+        nenv.old_obs, nenv.old_reward, nenv.old_cost = last_raw, self._ag["raw_rew"], self._ag["raw_cost"]
+        if cw is not None:
+            cw.previous_obs = last_raw
+        self._last_original_obs = last_raw
+        self._last_dones = self._ag["last_dones"]
+
+    def _host_stats_to_normaliser(self, k, nenv, has_cost, N, O):
+        """copy the running statistics and returns launch k of icrl_host_step left in its parity copy of the workspace (csrc/rollout.hip,
+        HostCopy: obs mean [O] | obs var [O] | obs count | ret_stats [3] | cost_stats [3] | ret [N] | cost_ret [N] | raw cost [N])
+        into the normaliser's arrays."""
+        cp = 2 * O + 7 + 3 * N
+        c = self._host_ws[(k & 1) * cp:((k & 1) + 1) * cp]
+        nenv.obs_rms.d_mean.copy_(c[:O]); nenv.obs_rms.d_var.copy_(c[O:2 * O]); nenv.obs_rms.d_count.copy_(c[2 * O:2 * O + 1])
+        nenv.ret_rms.d_stats.copy_(c[2 * O + 1:2 * O + 4])
+        nenv.ret.copy_(c[2 * O + 7:2 * O + 7 + N])
+        if has_cost:
+            nenv.cost_rms.d_stats.copy_(c[2 * O + 4:2 * O + 7])
+            nenv.cost_ret.copy_(c[2 * O + 7 + N:2 * O + 7 + 2 * N])
 
     def _collect_rollouts_stepped(self, env, callback, rollout_buffer, n_rollout_steps, cost_function, noise=None):
         """The reference's per-step loop, kept for everything the fused launch does not cover: a callable `cost_function`

@@ -12,7 +12,7 @@ import shutil
 
 import numpy as np
 
-from . import utils
+from . import envs, utils
 
 
 def save_rollouts(model, env, n_rollouts, save_dir, reward_threshold=None, length_threshold=None, max_tries=None):
@@ -67,6 +67,7 @@ def run_policy(args):
     shutil.rmtree(save_dir, ignore_errors=True)
     os.makedirs(save_dir)
     env_id = args.env_id or config.eval_env_id
+    envs.import_modules(getattr(args, "env_module", None))
     env = utils.make_eval_env(env_id, use_cost_wrapper=False, normalize_obs=False)
     if not getattr(config, "dont_normalize_obs", False):
         env = VecNormalize.load(os.path.join(load_dir, "train_env_stats.pkl"), env)        # restore the training statistics
@@ -95,6 +96,7 @@ def build_parser():
     a("--n_rollouts", "-nr", type=int, default=3); a("--dont_make_video", "-dmv", action="store_true")
     a("--dont_save_trajs", "-dst", action="store_true"); a("--save_using_airl_scheme", "-suas", action="store_true")
     a("--reward_threshold", "-rt", type=float, default=None); a("--length_threshold", "-lt", type=int, default=None)
+    a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     return p
 
 

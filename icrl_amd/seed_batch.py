@@ -32,7 +32,14 @@ from . import _lib, logger, utils
 from .streams import PrivateStreams
 from .structs import CnTrainJobT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
 from .true_constraint_net import mean_cost
-from .vec_env import sync_envs_normalization
+from .vec_env import ENV_IDS, HostVecEnv, sync_envs_normalization
+
+
+def _refuse_host_envs(*env_ids):
+    host = [i for i in env_ids if i not in ENV_IDS]
+    if host:
+        raise ValueError(f"seed batch: {host} are not device-resident envs (vec_env.ENV_IDS); the batched launches step device envs only — "
+                         "run host envs (--env_module) one run at a time")
 
 
 def setup_runs(configs, on_setup=None):
@@ -41,6 +48,7 @@ def setup_runs(configs, on_setup=None):
     from . import icrl as I
     states = []
     for cfg in configs:
+        _refuse_host_envs(cfg.train_env_id, cfg.eval_env_id)
         if getattr(cfg, "streams", None) is None:
             cfg.streams = PrivateStreams(cfg.seed, discrete=cfg.train_env_id in ("LGW-v0", "CLGW-v0"))
         if getattr(cfg, "warmup_timesteps", None) is not None and not hasattr(cfg.streams, "rollout_noise"):
@@ -85,6 +93,8 @@ TUNE_PLACEMENT_IN_BATCH = os.environ.get("ICRL_SEED_TUNE", "0") == "1"
 class SeedBatch:
     def __init__(self, configs=None, states=None, on_setup=None):
         self.states = setup_runs(configs, on_setup) if states is None else states
+        if any(isinstance(st["train_env"].unwrapped, HostVecEnv) for st in self.states):
+            _refuse_host_envs(*[st["config"].train_env_id for st in self.states])
         c0 = self.states[0]["config"]
         for st in self.states[1:]:
             c = st["config"]

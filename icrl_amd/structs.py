@@ -43,6 +43,11 @@ class AgentT(C.Structure):
                 ("last_v_r", vp), ("last_v_c", vp), ("act_clipped", vp), ("status", vp), ("xch_ws", vp), ("xch_ws_bytes", C.c_longlong)]
 
 
+class HostStepT(C.Structure):
+    """icrl_host_step_t: the transfer buffers of the rollout over host envs (icrl_host_step)."""
+    _fields_ = [("T", i32), ("_pad", i32), ("stage", vp), ("s", vp), ("act_host", vp), ("ws", vp), ("ws_bytes", C.c_longlong)]
+
+
 class PpoHyperT(C.Structure):
     _fields_ = [("batch_size", i32), ("n_epochs", i32), ("use_target_kl", i32), ("_pad", i32),
                 ("clip_range", C.c_float), ("ent_coef", C.c_float), ("reward_vf_coef", C.c_float), ("cost_vf_coef", C.c_float),

@@ -16,19 +16,34 @@ import torch
 from . import _lib, spaces
 from .policies import ActorTwoCriticsPolicy
 from .structs import EnvT, p
-from .vec_env import HipSynthVecEnv, VecCostWrapper, VecNormalize, VecNormalizeWithCost
+from . import envs
+from .vec_env import ENV_IDS, DummyVecEnv, HipSynthVecEnv, HostVecEnv, SubprocVecEnv, VecCostWrapper, VecNormalize, VecNormalizeWithCost
+
+
+def make_vec_env(env_id, n_envs, seed, device="cuda", env_index_offset=0, dummy_vec_env=False):
+    """the bottom of an env chain: a device-resident HipSynthVecEnv for the ids of vec_env.ENV_IDS (exactly as before), else a host
+    VecEnv of n_envs registered envs (envs.register): SubprocVecEnv, or DummyVecEnv with dummy_vec_env (SB3 make_vec_env's
+    vec_env_cls); env i is seeded seed + env_index_offset + i.  Building the envs draws from no global random generator."""
+    if env_id in ENV_IDS:
+        return HipSynthVecEnv.make(env_id, n_envs, seed, device, env_index_offset=env_index_offset)
+    fns = [envs.spec(env_id)] * n_envs        # (raises, listing the known ids, for an unknown id)
+    cls = DummyVecEnv if dummy_vec_env else SubprocVecEnv
+    venv = cls(fns, device=device, env_index_offset=env_index_offset)
+    venv.seed(seed)
+    return venv
 
 
 def make_train_env(env_id, save_dir, use_cost_wrapper, base_seed=0, num_threads=1, normalize_obs=True, normalize_reward=True,
                    normalize_cost=True, env_index_offset=0, device="cuda", **kwargs):
-    """ref: icrl/utils.py:265-288.  SubprocVecEnv[num_threads] of gym envs -> one batched device env; env i is seeded
-    base_seed + env_index_offset + i (the offset shards envs across GPUs)."""
+    """ref: icrl/utils.py:265-288.  SubprocVecEnv[num_threads] of gym envs -> one batched device env (ids of vec_env.ENV_IDS) or a
+    host VecEnv of registered envs (make_vec_env; dummy_vec_env=True: DummyVecEnv); env i is seeded base_seed + env_index_offset + i
+    (the offset shards envs across GPUs)."""
     # ref: icrl/utils.py:256-263 — make_env() calls set_random_seed(base_seed) (common/utils.py:23-39): python, numpy and torch
     # generators are seeded HERE, so whatever is built next without a seed of its own (the ConstraintNet, icrl.py:88-117) is
     # initialised reproducibly per seed
     import random
     random.seed(base_seed); np.random.seed(base_seed); torch.manual_seed(base_seed)
-    env = HipSynthVecEnv.make(env_id, num_threads, base_seed, device, env_index_offset=env_index_offset)
+    env = make_vec_env(env_id, num_threads, base_seed, device, env_index_offset, dummy_vec_env=kwargs.pop("dummy_vec_env", False))
     if use_cost_wrapper:
         env = VecCostWrapper(env)
     if normalize_reward and normalize_cost:
@@ -43,7 +58,7 @@ def make_train_env(env_id, save_dir, use_cost_wrapper, base_seed=0, num_threads=
 
 def make_eval_env(env_id, use_cost_wrapper, normalize_obs=True, seed=0, device="cuda"):
     """ref: icrl/utils.py:290-303 — one env, statistics frozen, rewards / costs not normalised."""
-    env = HipSynthVecEnv.make(env_id, 1, seed, device)
+    env = make_vec_env(env_id, 1, seed, device, dummy_vec_env=True)
     if use_cost_wrapper:
         env = VecCostWrapper(env)
     return VecNormalizeWithCost(env, training=False, norm_obs=normalize_obs, norm_reward=False, norm_cost=False)
@@ -219,6 +234,11 @@ class SteppedEpisodeRun:
 
 
 def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel):
+    if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: the reference's own loop over the device-tensor API
+        if env.unwrapped.max_steps is None:
+            raise ValueError("sampling / evaluation over a host env needs its episode limit: register it with max_episode_steps "
+                             "(or give the env spec.max_episode_steps / _max_episode_steps)")
+        return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
     # (policies of the generic-shape path take the same launch: icrl_sample_episodes runs its persistent loop with the table-driven
     # forward, csrc/rollout.hip sample_episodes_generic_kernel; SteppedEpisodeRun is the same loop from the host, kept as the check)
     run = EpisodeRun(agent, env, n_episodes, deterministic, noise, parallel).prepare()

@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib, spaces
+from ._subproc_worker import max_episode_steps, space_fields, step_env
+from .envs import ENV_IDS as _ENV_IDS
 from .structs import EnvT, NormT, p
 
 # kind -> obs, act (width of the action vector handed to the env), max_episode_steps, reward form (icrl_env_t.reward_form)
@@ -27,12 +29,7 @@ KINDS = {"hc": (18, 6, 1000, 0), "ant": (113, 8, 500, 1),
          # LapGridWorld / ConstrainedLapGridWorld restated exactly (custom_envs/envs/lap_grid_world.py:29-240): Discrete(2)
          "lgw": (1, 1, 200, 2), "clgw": (1, 1, 200, 3)}
 DISCRETE_ACTIONS = {"lgw": 2, "clgw": 2}
-ENV_IDS = {  # reference gym ids (custom_envs/__init__.py:43-57,194-224,357-370) -> (kind, early termination, broken)
-    "HCWithPos-v0": ("hc", False, False), "HCWithPosTest-v0": ("hc", True, False),
-    "AntWall-v0": ("ant", False, False), "AntWallTest-v0": ("ant", True, False),
-    "AntWallBroken-v0": ("ant", False, True), "AntWallBrokenTest-v0": ("ant", True, True),
-    "LGW-v0": ("lgw", False, False), "CLGW-v0": ("clgw", True, False),
-}
+ENV_IDS = _ENV_IDS   # reference gym ids -> (kind, early termination, broken); defined in envs.py (no torch there)
 
 
 def dynamics_matrix(kind):
@@ -181,6 +178,274 @@ class HipSynthVecEnv(VecEnv):
         _lib.check(_lib.lib().icrl_synth_env_step(_lib.byref(e), p(self._actions), p(self.raw_rew), p(self.dones),
                                                   _lib.current_stream()), "icrl_synth_env_step")
         return self.s.clone(), self.raw_rew.clone(), self.dones.clone(), BatchedInfos(self.num_envs)
+
+
+# ---- host-side envs (Python simulators): the reference's DummyVecEnv / SubprocVecEnv under the device-tensor VecEnv API ----------
+def _to_space(fields):
+    if fields["kind"] == "discrete":
+        return spaces.Discrete(fields["n"])
+    dt = np.dtype(fields["dtype"]).type
+    return spaces.Box(np.asarray(fields["low"]), np.asarray(fields["high"]), tuple(fields["shape"]), dt)
+
+
+class HostInfos(BatchedInfos):
+    """infos of a host VecEnv: infos[i] is env i's own dict merged with the per-key device tensors of the wrappers (infos[i]['cost'])."""
+
+    def __init__(self, env_infos):
+        super().__init__(len(env_infos))
+        self.env_infos = env_infos
+
+    def __getitem__(self, i):
+        d = dict(self.env_infos[i])
+        d.update(super().__getitem__(i))
+        return d
+
+
+class HostVecEnv(VecEnv):
+    """N duck-typed envs (reset(), step(a) -> (obs, rew, done, info), seed(s), observation_space, action_space: gym envs qualify)
+    stepped on the host.  Two layers:
+
+      numpy:  reset_host() -> obs f64 [N, O];  step_host(actions) -> obs f64 [N, O], rew f64 [N], done bool [N], list of info dicts
+      device: reset / step_async / step_wait of VecEnv -> float64 obs, float64 rewards, uint8 dones on `device`, HostInfos
+
+    so that VecCostWrapper, VecNormalize[WithCost], the per-step rollout and SteppedEpisodeRun run over it unchanged; PPOLagrangian
+    runs its rollout over such a chain as one kernel launch per env step (ppo_lag._collect_rollouts_host).
+
+    Numerics: what the reference's SubprocVecEnv returns, np.stack of what the envs produced — observations and rewards are kept in
+    float64, never rounded through float32 / observation-space-dtype buffers as SB3's DummyVecEnv does (the reference never trains
+    through that one).  DummyVecEnv and SubprocVecEnv are therefore interchangeable bit for bit.
+
+    Env i is seeded seed + env_index_offset + i (HipSynthVecEnv.seed; the offset shards envs over ranks).  Device memory (the raw
+    observation array `s`, the pinned staging of the host rollout path) is allocated on first device use: the numpy layer runs on a
+    machine without a GPU."""
+
+    def __init__(self, num_envs, obs_fields, act_fields, max_steps=None, env_index_offset=0, device="cuda"):
+        obs_space, act_space = _to_space(obs_fields), _to_space(act_fields)
+        if not isinstance(obs_space, spaces.Box) or len(obs_space.shape) != 1:
+            raise NotImplementedError(f"host VecEnv: observation space {obs_space!r}; only 1-D Box observations are supported")
+        super().__init__(num_envs, obs_space, act_space)
+        self.device = torch.device(device)
+        self.obs_dim = int(obs_space.shape[0])
+        self.discrete = isinstance(act_space, spaces.Discrete)
+        self.act_dim = 1 if self.discrete else int(act_space.shape[0])
+        self.max_steps = None if max_steps is None else int(max_steps)
+        self._index_offset = int(env_index_offset)
+        self._actions = None
+        self._s = None
+        self._stage = None
+
+    # -- subclass hooks: the N envs
+    def _reset_envs(self):
+        raise NotImplementedError
+
+    def _step_envs(self, actions):
+        raise NotImplementedError
+
+    def _seed_envs(self, seeds):
+        raise NotImplementedError
+
+    # -- numpy layer
+    def _env_actions(self, actions):
+        a = actions.cpu().numpy() if torch.is_tensor(actions) else np.asarray(actions)
+        if self.discrete:
+            return a.reshape(self.num_envs).astype(np.int64)
+        return a.reshape(self.num_envs, self.act_dim).copy()
+
+    def reset_host(self):
+        return np.stack(self._reset_envs()).astype(np.float64, copy=False).reshape(self.num_envs, self.obs_dim)
+
+    def step_host(self, actions):
+        res = self._step_envs(self._env_actions(actions))
+        obs, rews, dones, infos = zip(*res)
+        return (np.stack(obs).astype(np.float64, copy=False).reshape(self.num_envs, self.obs_dim), np.stack(rews).astype(np.float64, copy=False),
+                np.stack(dones).astype(bool), list(infos))
+
+    def seed(self, seed=None, env_index_offset=None):
+        seed = 0 if seed is None else int(seed)
+        if env_index_offset is not None:
+            self._index_offset = int(env_index_offset)
+        seeds = [seed + self._index_offset + i for i in range(self.num_envs)]
+        self._seed_envs(seeds)
+        return seeds
+
+    # -- device layer
+    @property
+    def s(self):
+        """device float64 [N, O]: the raw observations the envs returned last (HipSynthVecEnv.s)."""
+        if self._s is None:
+            self._s = torch.zeros(self.num_envs, self.obs_dim, dtype=torch.float64, device=self.device)
+        return self._s
+
+    def reset(self):
+        self.s.copy_(torch.from_numpy(self.reset_host()))
+        return self.s.clone()
+
+    def step_async(self, actions):
+        self._actions = actions
+
+    def step_wait(self):
+        obs, rew, done, infos = self.step_host(self._actions)
+        N, O = self.num_envs, self.obs_dim
+        blk = torch.from_numpy(np.concatenate([obs, rew[:, None], done[:, None].astype(np.float64)], axis=1)).to(self.device)
+        self.s.copy_(blk[:, :O])
+        return self.s.clone(), blk[:, O].contiguous(), blk[:, O + 1].to(torch.uint8), HostInfos(infos)
+
+    def staging(self):
+        """the host rollout path's transfer buffers (icrl_host_step_t), allocated on first use: a pinned block [obs f64 N x O | rew f64 N |
+        done u8 N] copied to its device twin once per env step, and a pinned, device-visible float32 [N, act] the kernel writes the
+        clipped actions (Discrete: the index) into — icrl_host_step maps its host address with hipHostGetDevicePointer, which serves
+        torch's pinned allocations whether they come from hipHostMalloc or from host registration."""
+        if self._stage is None:
+            N, O = self.num_envs, self.obs_dim
+            nbytes = (8 * N * O + 8 * N + N + 7) // 8 * 8
+            pin = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            dev = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+            npin = pin.numpy()
+            self._stage = dict(pin=pin, dev=dev, nbytes=nbytes,
+                               obs=npin[:8 * N * O].view(np.float64).reshape(N, O), rew=npin[8 * N * O:8 * N * O + 8 * N].view(np.float64),
+                               done=npin[8 * N * O + 8 * N:8 * N * O + 9 * N],
+                               act=torch.zeros(N, self.act_dim, dtype=torch.float32).pin_memory())
+        return self._stage
+
+
+class DummyVecEnv(HostVecEnv):
+    """ref: stable_baselines3/common/vec_env/dummy_vec_env.py:13-118 — the envs stepped one after the other in this process (see
+    HostVecEnv for the numerics: float64 kept, no float32 buffers)."""
+
+    def __init__(self, env_fns, device="cuda", env_index_offset=0):
+        self.envs = [fn() for fn in env_fns]
+        e0 = self.envs[0]
+        super().__init__(len(self.envs), space_fields(e0.observation_space), space_fields(e0.action_space), max_episode_steps(e0),
+                         env_index_offset, device)
+
+    def _reset_envs(self):
+        return [env.reset() for env in self.envs]
+
+    def _step_envs(self, actions):
+        return [step_env(env, actions[i]) for i, env in enumerate(self.envs)]
+
+    def _seed_envs(self, seeds):
+        for env, s in zip(self.envs, seeds):
+            env.seed(s)
+
+    def _targets(self, indices):
+        if indices is None:
+            indices = range(self.num_envs)
+        elif isinstance(indices, int):
+            indices = [indices]
+        return [self.envs[i] for i in indices]
+
+    def get_attr(self, attr_name, indices=None):
+        return [getattr(env, attr_name) for env in self._targets(indices)]
+
+    def set_attr(self, attr_name, value, indices=None):
+        for env in self._targets(indices):
+            setattr(env, attr_name, value)
+
+    def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
+        return [getattr(env, method_name)(*method_args, **method_kwargs) for env in self._targets(indices)]
+
+    def close(self):
+        for env in self.envs:
+            if hasattr(env, "close"):
+                env.close()
+
+
+class SubprocVecEnv(HostVecEnv):
+    """ref: stable_baselines3/common/vec_env/subproc_vec_env.py:14-177 — one worker process per env (icrl_amd/_subproc_worker.py:
+    numpy + cloudpickle only, no torch, no GPU).  Env factories travel with cloudpickle.  start_method: forkserver where available,
+    else spawn; fork is refused once this process has initialised the GPU."""
+
+    def __init__(self, env_fns, start_method=None, device="cuda", env_index_offset=0):
+        import multiprocessing as mp
+        import cloudpickle
+        from . import _subproc_worker
+        if start_method is None:
+            start_method = "forkserver" if "forkserver" in mp.get_all_start_methods() else "spawn"
+        if start_method == "fork" and torch.cuda.is_initialized():
+            raise ValueError("SubprocVecEnv: start_method 'fork' after the GPU was initialised in this process; use forkserver or spawn")
+        ctx = mp.get_context(start_method)
+        self.waiting, self.closed = False, False
+        n = len(env_fns)
+        self.remotes, work_remotes = zip(*[ctx.Pipe() for _ in range(n)])
+        self.processes = []
+        for work_remote, remote, fn in zip(work_remotes, self.remotes, env_fns):
+            proc = ctx.Process(target=_subproc_worker.worker, args=(work_remote, remote, cloudpickle.dumps(fn)), daemon=True)
+            proc.start()
+            self.processes.append(proc)
+            work_remote.close()
+        self.remotes[0].send(("spaces", None))
+        obs_fields, act_fields, max_steps = self.remotes[0].recv()
+        super().__init__(n, obs_fields, act_fields, max_steps, env_index_offset, device)
+
+    def _reset_envs(self):
+        for remote in self.remotes:
+            remote.send(("reset", None))
+        return [remote.recv() for remote in self.remotes]
+
+    def _step_envs(self, actions):
+        for remote, a in zip(self.remotes, actions):
+            remote.send(("step", a))
+        self.waiting = True
+        res = [remote.recv() for remote in self.remotes]
+        self.waiting = False
+        return res
+
+    def _seed_envs(self, seeds):
+        for remote, s in zip(self.remotes, seeds):
+            remote.send(("seed", s))
+        for remote in self.remotes:
+            remote.recv()
+
+    def _targets(self, indices):
+        if indices is None:
+            indices = range(self.num_envs)
+        elif isinstance(indices, int):
+            indices = [indices]
+        return [self.remotes[i] for i in indices]
+
+    def get_attr(self, attr_name, indices=None):
+        targets = self._targets(indices)
+        for remote in targets:
+            remote.send(("get_attr", attr_name))
+        return [remote.recv() for remote in targets]
+
+    def set_attr(self, attr_name, value, indices=None):
+        targets = self._targets(indices)
+        for remote in targets:
+            remote.send(("set_attr", (attr_name, value)))
+        for remote in targets:
+            remote.recv()
+
+    def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
+        targets = self._targets(indices)
+        for remote in targets:
+            remote.send(("env_method", (method_name, method_args, method_kwargs)))
+        return [remote.recv() for remote in targets]
+
+    def worker_modules(self, names):
+        """which of `names` are imported in each worker (the tests check that no worker loads torch)."""
+        for remote in self.remotes:
+            remote.send(("modules", list(names)))
+        return [remote.recv() for remote in self.remotes]
+
+    def close(self):
+        if self.closed:
+            return
+        if self.waiting:
+            for remote in self.remotes:
+                remote.recv()
+        for remote in self.remotes:
+            remote.send(("close", None))
+        for proc in self.processes:
+            proc.join()
+        self.closed = True
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class VecCostWrapper(VecEnvWrapper):

@@ -268,6 +268,34 @@ int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t* nm, const 
                             double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
                             int do_gae, void* stream);
 
+/* Rollout over HOST envs (Python simulators, vec_env.HostVecEnv): one launch per env step, T + 1 launches per rollout
+ * (k = 0 .. T), one workgroup of 256 threads per env, no inter-workgroup waiting inside a launch.  Launch k
+ *   - finishes step k - 1 (k >= 1): reads the staging block the host copied in before the launch (raw obs f64 [N, O] | raw rew
+ *     f64 [N] | done u8 [N]) and the raw costs launch k - 1 computed, updates the normaliser's statistics (replicated in every
+ *     workgroup, numpy's order, as icrl_rollout_collect_ex does), normalises its env and writes buffer row k - 1 (new_observations,
+ *     new_orig_observations, rewards, costs), ag.last_obs / last_dones / raw_rew / dones and row n of `s`;
+ *   - acts for step k (k < T): policy forward on noise row k, cost net on (s, clipped action), the pre-step fields of buffer row k,
+ *     ag.raw_cost / act_clipped / last_v_r / last_v_c, and the clipped action (Discrete: the index) into `act_host`.
+ * The running statistics and the returns ret / cost_ret travel between launches in two copies in `ws` (step parity); the last
+ * launch (k == T) also writes them to the icrl_norm_t arrays.  No GAE: the caller runs icrl_gae_dual after launch T.
+ * Served: policies / constraint nets of the one-workgroup-per-env image (icrl_rollout_collect_ex's fused shapes), N <= 128,
+ * obs_dim <= 128, nm->training; anything else is refused with a reason (the host then runs the per-step loop). */
+typedef struct icrl_host_step_t {
+  int T;                 /* rollout length: launches k = 0 .. T */
+  int _pad;
+  const void* stage;     /* device copy of the staging block: raw obs f64 [N, O] | raw rew f64 [N] | done u8 [N] */
+  double* s;             /* [N, O] float64: the raw observations of the envs' last step (HostVecEnv.s, VecCostWrapper.previous_obs) */
+  float* act_host;       /* HOST address of page-locked memory (hipHostMalloc / hipHostRegister; the call maps it with hipHostGetDevicePointer):
+                            [N, act] float32 clipped actions ([N, 1] action index when discrete) */
+  void* ws;              /* icrl_host_step_ws_bytes(N, O) bytes of device memory */
+  long long ws_bytes;
+} icrl_host_step_t;
+
+size_t icrl_host_step_ws_bytes(int N, int obs_dim);
+int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
+                   const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
+                   const float* action_high, int k, void* stream);
+
 /* ActorTwoCriticsPolicy.evaluate_actions (policies.py:752-767): values, log-prob of the GIVEN actions and the entropy of
  * the action distribution (used by compute_kl, icrl/utils.py:421-437).  actions [N,act_store] float32. */
 int icrl_policy_evaluate(const icrl_policy_t* pol, const double* obs, const float* actions, int N, float* v_r, float* v_c,

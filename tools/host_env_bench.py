@@ -1,0 +1,94 @@
+"""Per-env-step cost of rollouts over host envs, one process, one GPU ("Host envs"):
+
+  (a) host path      PPOLagrangian._collect_rollouts_host (one staging copy + one icrl_host_step launch per env step)
+  (b) stepped path   PPOLagrangian._collect_rollouts_stepped over the same host env (policy.forward, env.step through the wrappers)
+  (c) env alone      HostVecEnv.step_host over the same envs
+  (d) device env     the persistent rollout over HipSynthVecEnv (HCWithPos-v0), for reference
+
+The host env is a do-nothing HC-shaped numpy env (obs 18, act 6), so (a) - (c) is device and transfer overhead.  Each figure is
+one timed rollout of T steps after a warm-up rollout.  usage: python tools/host_env_bench.py [--T 1024] [--N 8 64 128]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+class NullHC:
+    """HC-shaped, no dynamics: zeros in, zeros out, never done."""
+
+    def __init__(self):
+        from icrl_amd import spaces
+        self.observation_space = spaces.Box(-np.inf, np.inf, (18,), np.float64)
+        self.action_space = spaces.Box(-1.0, 1.0, (6,), np.float32)
+        self._max_episode_steps = 1000
+        self._obs = np.zeros(18, np.float64)
+
+    def seed(self, s=None):
+        return [s]
+
+    def reset(self):
+        return self._obs
+
+    def step(self, a):
+        return self._obs, 0.0, False, {}
+
+
+def _agent(env, T):
+    import torch
+    from icrl_amd.constraint_net import ConstraintNet
+    from icrl_amd.ppo_lag import PPOLagrangian
+    lo = -np.ones(6, np.float32)
+    torch.manual_seed(0)
+    cn = ConstraintNet(18, 6, [64, 64], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
+    env.set_cost_function(cn.cost_function)
+    agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0)
+    agent._setup_learn(10 * T * env.num_envs)
+    return agent
+
+
+def _time(fn):
+    import torch
+    fn()                                   # warm-up rollout
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=1024)
+    ap.add_argument("--N", type=int, nargs="+", default=[8, 64, 128])
+    args = ap.parse_args()
+    import torch
+    from icrl_amd import utils
+    from icrl_amd.vec_env import DummyVecEnv, VecCostWrapper, VecNormalizeWithCost
+    T, rows = args.T, []
+    for N in args.N:
+        env = VecNormalizeWithCost(VecCostWrapper(DummyVecEnv([NullHC] * N)))
+        agent = _agent(env, T)
+        henv = env.unwrapped
+        assert agent._host_rollout_ok("cost", T, agent.rollout_buffer)
+        a = _time(lambda: agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost"))
+        b = _time(lambda: agent._collect_rollouts_stepped(env, None, agent.rollout_buffer, T, "cost",
+                                                          noise=agent._draw_action_noise(T)))
+        act = np.zeros((N, 6), np.float32)
+        c = _time(lambda: [henv.step_host(act) for _ in range(T)])
+        denv = utils.make_train_env("HCWithPos-v0", None, True, 0, N, cost_info_str="cost", reward_gamma=0.99, cost_gamma=0.99)
+        dagent = _agent(denv, T)
+        d = _time(lambda: dagent.collect_rollouts(denv, None, dagent.rollout_buffer, T, "cost"))
+        row = dict(N=N, T=T, host_path_us=1e6 * a / T, stepped_path_us=1e6 * b / T, env_alone_us=1e6 * c / T, device_env_us=1e6 * d / T)
+        rows.append(row)
+        print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+    return rows
+
+
+if __name__ == "__main__":
+    main()
