@@ -39,6 +39,7 @@ SIGNATURES = {
     "icrl_rollout_collect_ex": [c_void_p] * 9 + [c_double] * 4 + [c_int, c_void_p],
     "icrl_host_step_ws_bytes": [c_int, c_int],
     "icrl_host_step": [c_void_p] * 9 + [c_int, c_void_p],
+    "icrl_host_episode_step": [c_void_p] * 6 + [c_int, c_int, c_void_p],
     "icrl_ppo_lag_train": [c_void_p] * 11,
     "icrl_ppo_generic_row_floats": [c_void_p],
     "icrl_cn_prepare": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],

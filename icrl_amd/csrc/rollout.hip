@@ -3237,6 +3237,60 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
   }
 }
 
+// =================================================================================================================
+// sampling / evaluation episodes over ONE host env (icrl_host_episode_step): one launch per env step, one workgroup.  Launch k is
+// one pass of sample_episodes_body around the env step — same expressions, same order — with the raw observation read from the
+// staging block instead of produced by env_step_wave: normalise (frozen statistics), record row k - 1, forward, action out.
+// Nothing is carried between launches on the device (the statistics are frozen, the episode sums are the host's); no cost wave.
+// =================================================================================================================
+struct HostEpisodeArgs {
+  icrl_norm_t nm;          // training must be 0: statistics are only read
+  icrl_host_episode_t he;  // act_host: the device's mapping of the host address
+  PolLayout pl;
+  const float* PT;
+  const float* noise;      // [rows][act] or NULL (deterministic)
+  const float* alow;
+  const float* ahigh;
+};
+
+template <int OCT>
+__global__ void __launch_bounds__(256) host_episode_kernel(HostEpisodeArgs h, int k, int act) {
+  __shared__ ActShared sh;
+  PolRegs<OCT> R;                      // waves 0..2; wave 3 only takes part in the barriers
+  if (act) load_pol_regs<OCT>(h.pl, h.PT, R);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int O = h.pl.O, A = h.pl.A;
+  const int AS = h.pl.discrete ? 1 : A;
+  const icrl_norm_t& nm = h.nm;
+  const double* const st_obs = reinterpret_cast<const double*>(h.he.stage);
+  if (tid >= O && tid < MAX_OBS) sh.x[tid] = 0.f;        // pad = 0 (the forward reads whole float4 rows against zero pad weights)
+  if (tid < O) {
+    const double raw = st_obs[tid];
+    double o = raw;
+    if (nm.norm_obs) {
+      const double n_mean = nm.obs_mean[tid], n_den = sqrt(nm.obs_var[tid] + nm.epsilon);
+      o = fmin(fmax((raw - n_mean) / n_den, -nm.clip_obs), nm.clip_obs);
+    }
+    sh.x[tid] = (float)o;
+    if (k >= 1) {                      // the observation after step k - 1
+      h.he.orig_obs[(size_t)(k - 1) * O + tid] = raw;
+      h.he.obs[(size_t)(k - 1) * O + tid] = o;
+    }
+  }
+  if (!act) return;
+  __syncthreads();
+  const bool has_box = h.alow != nullptr && h.ahigh != nullptr;
+  policy_forward_block<OCT>(h.pl, R, sh, h.noise != nullptr ? h.noise + (size_t)k * AS : nullptr, h.he.deterministic || h.noise == nullptr,
+                            has_box ? h.alow : nullptr, has_box ? h.ahigh : nullptr);
+  __syncthreads();
+  if (w == 0 && lane < AS) {           // the host reads the clipped action (the index when discrete) after its sync
+    const float c = sh.act_clip[lane];
+    h.he.act_host[lane] = c;
+    h.he.actions[(size_t)k * AS + lane] = c;
+  }
+}
+
 // rows from which icrl_policy_forward / icrl_policy_evaluate take the 16-rows-per-pass MFMA kernel (below: one workgroup per row)
 constexpr int ROWS_KERNEL_MIN = 64;
 
@@ -4074,5 +4128,35 @@ extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, c
   hipStream_t s = (hipStream_t)stream;
   if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
   else hipLaunchKernelGGL((host_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, h, k);
+  return (int)hipGetLastError();
+}
+
+// ---- sampling / evaluation episodes over one host env: one launch per env step (host_episode_kernel) ----
+extern "C" int icrl_host_episode_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_host_episode_t* he, const float* noise,
+                                      const float* action_low, const float* action_high, int k, int act, void* stream) {
+  if (nm == nullptr || pol == nullptr || he == nullptr) return fail("icrl_host_episode_step: NULL descriptor");
+  const int O = he->obs_dim, rows = he->rows;
+  if (policy_is_wide(pol) || !dims_ok(pol)) return bad_dims("icrl_host_episode_step", pol);
+  if (he->num_envs != 1 || O < 1 || O > MAX_OBS || pol->obs_dim != O)
+    return fail("icrl_host_episode_step: %d envs (1), obs_dim %d (1..%d), policy obs_dim %d: other shapes take the per-step loop", he->num_envs, O, MAX_OBS, pol->obs_dim);
+  if (nm->training) return fail("icrl_host_episode_step: the normaliser must be frozen (training = %d)", nm->training);
+  if (rows < 1 || k < 0 || k > rows || (act && k == rows)) return fail("icrl_host_episode_step: launch k = %d (act = %d) of %d rows", k, act, rows);
+  if (he->stage == nullptr || he->act_host == nullptr || he->orig_obs == nullptr || he->obs == nullptr || he->actions == nullptr || pol->params_t == nullptr)
+    return fail("icrl_host_episode_step: staging / action / output pointers and the transposed policy are required");
+  HostEpisodeArgs h{};
+  h.nm = *nm; h.he = *he;
+  h.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
+  h.PT = pol->params_t; h.noise = noise; h.alow = action_low; h.ahigh = action_high;
+  // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
+  void* act_dev = nullptr;
+  if (hipHostGetDevicePointer(&act_dev, he->act_host, 0) != hipSuccess || act_dev == nullptr) {
+    (void)hipGetLastError();
+    return fail("icrl_host_episode_step: act_host %p is not page-locked host memory mapped for the device (hipHostMalloc / hipHostRegister)", (void*)he->act_host);
+  }
+  h.he.act_host = reinterpret_cast<float*>(act_dev);
+  hipStream_t s = (hipStream_t)stream;
+  // (host_step_kernel's <2, 2> / <8, 10> split by observation width; its second parameter sizes the cost wave, which is absent here)
+  if (h.pl.O <= 32) hipLaunchKernelGGL(host_episode_kernel<2>, dim3(1), dim3(256), 0, s, h, k, act);
+  else hipLaunchKernelGGL(host_episode_kernel<8>, dim3(1), dim3(256), 0, s, h, k, act);
   return (int)hipGetLastError();
 }

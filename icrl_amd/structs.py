@@ -48,6 +48,12 @@ class HostStepT(C.Structure):
     _fields_ = [("T", i32), ("_pad", i32), ("stage", vp), ("s", vp), ("act_host", vp), ("ws", vp), ("ws_bytes", C.c_longlong)]
 
 
+class HostEpisodeT(C.Structure):
+    """icrl_host_episode_t: the transfer buffers and outputs of the episode loop over one host env (icrl_host_episode_step)."""
+    _fields_ = [("num_envs", i32), ("obs_dim", i32), ("rows", i32), ("deterministic", i32), ("stage", vp), ("act_host", vp),
+                ("orig_obs", vp), ("obs", vp), ("actions", vp)]
+
+
 class PpoHyperT(C.Structure):
     _fields_ = [("batch_size", i32), ("n_epochs", i32), ("use_target_kl", i32), ("_pad", i32),
                 ("clip_range", C.c_float), ("ent_coef", C.c_float), ("reward_vf_coef", C.c_float), ("cost_vf_coef", C.c_float),

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, spaces
 from .policies import ActorTwoCriticsPolicy
-from .structs import EnvT, p
+from .structs import EnvT, HostEpisodeT, p
 from . import envs
 from .vec_env import ENV_IDS, DummyVecEnv, HipSynthVecEnv, HostVecEnv, SubprocVecEnv, VecCostWrapper, VecNormalize, VecNormalizeWithCost
 
@@ -191,8 +191,10 @@ class EpisodeRun:
 
 class SteppedEpisodeRun:
     """EpisodeRun's results from the reference's own loop (icrl/utils.py:323-357, evaluation.py:10-67) over the per-step env chain —
-    policy.forward + env.step, one launch sequence and one host read of `done` per step.  Not used by the product path any more (the
-    sampler kernels serve every policy shape); tests run it beside EpisodeRun: same rows, same episode sums.  The env is reset before
+    policy.forward + env.step, one launch sequence and one host read of `done` per step.  Device envs never take it (the sampler
+    kernels serve every policy shape).  Host envs take it where HostEpisodeRun does not serve (host_episodes_ok: a generic-shape
+    policy, more than 128 observations or 16 actions, another wrapper chain, a cost wrapper around a plain Python callable) and with
+    ICRL_HOST_EPISODES_STEPPED=1; tests run it beside EpisodeRun and HostEpisodeRun: same rows, same episode sums.  The env is reset before
     the first episode only; the later ones start from the auto-reset observation, like the sequential loop the sampler kernel reproduces."""
 
     def __init__(self, agent, env, n_episodes, deterministic, noise):
@@ -233,11 +235,123 @@ class SteppedEpisodeRun:
         return self.out[name]
 
 
+def _host_episode_chain(env):
+    """(normaliser, cost wrapper or None, host env) when `env` is VecNormalize[WithCost] -> [VecCostWrapper] -> HostVecEnv, else None."""
+    if not isinstance(env, VecNormalize):
+        return None
+    cw = env.venv
+    if isinstance(cw, HostVecEnv):
+        return env, None, cw
+    if isinstance(cw, VecCostWrapper) and isinstance(cw.venv, HostVecEnv):
+        return env, cw, cw.venv
+    return None
+
+
+def host_episodes_ok(agent, env):
+    """what icrl_host_episode_step serves: one host env under VecNormalize[WithCost] and an optional VecCostWrapper without a cost
+    function or with a ConstraintNet's (episodes never read a cost, so its forward is skipped; an arbitrary Python callable may have
+    side effects and keeps being called: the per-step loop), and a policy of the one-workgroup-per-env kernels (csrc/rollout.hip
+    dims_ok: not `wide`, obs <= MAX_OBS 128, act <= MAX_ACT 16).  ICRL_HOST_EPISODES_STEPPED=1 forces the per-step loop."""
+    if os.environ.get("ICRL_HOST_EPISODES_STEPPED", "0") not in ("", "0"):
+        return False
+    chain = _host_episode_chain(env)
+    if chain is None:
+        return False
+    _nenv, cw, henv = chain
+    if cw is not None and cw.cost_function is not None and cw.constraint_net() is None:
+        return False
+    pol = agent.policy
+    return (not pol.wide and pol.obs_dim <= 128 and pol.act_dim <= 16 and henv.num_envs == 1 and henv.obs_dim == pol.obs_dim
+            and henv.max_steps is not None)
+
+
+class HostEpisodeRun:
+    """SteppedEpisodeRun's results over a host env chain (host_episodes_ok) with ONE staging copy, ONE launch (icrl_host_episode_step)
+    and ONE stream synchronisation per env step: the host reads the clipped action the previous launch wrote into pinned memory, steps
+    the env through HostVecEnv.step_host (numpy, no device upload), fills the pinned staging block and enqueues the copy and the
+    launch that records the step (frozen-statistics normalisation, output row) and acts for the next.  Rewards and done flags never
+    leave the host: the episode return is summed here in float64 in step order, as the per-step loop and the device sampler sum it.
+    The wrappers above the host env are not stepped; afterwards they hold what the per-step loop would have left in them (the cost
+    wrapper's forward is skipped, so VecNormalize.old_cost keeps its value)."""
+
+    def __init__(self, agent, env, n_episodes, deterministic, noise):
+        assert env.num_envs == 1, "You must pass only one environment when using this function"
+        nenv, cw, henv = _host_episode_chain(env)
+        pol, dev = agent.policy, henv.device
+        max_steps, O = henv.max_steps, henv.obs_dim
+        A = 1 if pol.discrete else pol.act_dim
+        rows = n_episodes * max_steps
+        if noise is None and not deterministic:
+            noise = torch.rand(rows, device=dev) if pol.discrete else torch.randn(rows, A, device=dev)
+        if noise is not None:
+            noise = torch.as_tensor(noise, device=dev).float().reshape(rows, -1).contiguous()
+        was_training = env.training
+        env.training = False
+        nm = env.struct()
+        env.training = was_training
+        ps = pol.struct()
+        lo = hi = None
+        if not pol.discrete:
+            lo = torch.as_tensor(pol.action_space.low, device=dev).float().contiguous()
+            hi = torch.as_tensor(pol.action_space.high, device=dev).float().contiguous()
+        out = dict(orig_obs=torch.empty(rows, O, dtype=torch.float64, device=dev), obs=torch.empty(rows, O, dtype=torch.float64, device=dev),
+                   actions=torch.empty(rows, A, device=dev))
+        st = henv.staging()
+        he = HostEpisodeT(1, O, rows, int(bool(deterministic)), p(st["dev"]), st["act"].data_ptr(), p(out["orig_obs"]), p(out["obs"]),
+                          p(out["actions"]))
+        pin_obs, dev_obs = st["pin"][:8 * O], st["dev"][:8 * O]      # the kernel reads the observation only
+        lib, b = _lib.lib(), _lib.byref
+        stream, cs = _lib.current_stream(), torch.cuda.current_stream()
+        act = st["act"].numpy()
+
+        def launch(k, acting):
+            dev_obs.copy_(pin_obs, non_blocking=True)
+            _lib.check(lib.icrl_host_episode_step(b(nm), b(ps), b(he), p(noise), p(lo), p(hi), k, acting, stream), "icrl_host_episode_step")
+
+        cs.synchronize()                       # (an earlier copy out of the staging block may still be in flight)
+        st["obs"][:] = henv.reset_host()
+        launch(0, 1)
+        ep_rewards, lengths, k, rew = [], [], 0, 0.0
+        for ep in range(n_episodes):
+            done, ep_r, ep_l = False, 0.0, 0
+            while not done:
+                cs.synchronize()               # the action of step k is in pinned memory; the staging block is free again
+                obs, r, d, _infos = henv.step_host(act)
+                st["obs"][:] = obs
+                k += 1
+                rew = float(r[0]); ep_r += rew; ep_l += 1
+                done = bool(d[0])
+                launch(k, int(not (done and ep == n_episodes - 1)))
+            ep_rewards.append(ep_r); lengths.append(ep_l)
+        # the chain as the per-step loop leaves it: the raw observation of the last step (after `done`: the auto-reset one) in the host
+        # env and in every wrapper, the returns zeroed by the last `done`
+        last_raw = out["orig_obs"][k - 1:k]
+        henv.s.copy_(last_raw)
+        nenv.old_obs, nenv.old_reward = last_raw.clone(), torch.full((1,), rew, dtype=torch.float64, device=dev)
+        nenv.ret.zero_()
+        if cw is not None:
+            cw.previous_obs = last_raw.clone()
+            cw.actions = out["actions"][k - 1:k].clone()
+            if cw.cost_function is not None:
+                nenv.cost_ret.zero_()
+        out["ep_rewards"] = torch.as_tensor(np.asarray(ep_rewards, np.float64), device=dev)
+        out["ep_lengths"] = torch.as_tensor(np.asarray(lengths, np.int32), device=dev)
+        self.out, self._keepalive = out, (noise, lo, hi)
+        self.lengths = np.asarray(lengths, np.int64)
+        self.keep = None if k == rows else k
+
+    def rows_of(self, name):
+        x = self.out[name]
+        return x if self.keep is None else x[:self.keep]
+
+
 def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel):
-    if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: the reference's own loop over the device-tensor API
+    if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: one launch per env step, or the reference's own loop
         if env.unwrapped.max_steps is None:
             raise ValueError("sampling / evaluation over a host env needs its episode limit: register it with max_episode_steps "
                              "(or give the env spec.max_episode_steps / _max_episode_steps)")
+        if host_episodes_ok(agent, env):
+            return HostEpisodeRun(agent, env, n_episodes, deterministic, noise)
         return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
     # (policies of the generic-shape path take the same launch: icrl_sample_episodes runs its persistent loop with the table-driven
     # forward, csrc/rollout.hip sample_episodes_generic_kernel; SteppedEpisodeRun is the same loop from the host, kept as the check)

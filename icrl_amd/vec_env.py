@@ -209,7 +209,8 @@ class HostVecEnv(VecEnv):
       device: reset / step_async / step_wait of VecEnv -> float64 obs, float64 rewards, uint8 dones on `device`, HostInfos
 
     so that VecCostWrapper, VecNormalize[WithCost], the per-step rollout and SteppedEpisodeRun run over it unchanged; PPOLagrangian
-    runs its rollout over such a chain as one kernel launch per env step (ppo_lag._collect_rollouts_host).
+    runs its rollout over such a chain as one kernel launch per env step (ppo_lag._collect_rollouts_host), and sampling / evaluation
+    episodes over one such env run the same way (utils.HostEpisodeRun).
 
     Numerics: what the reference's SubprocVecEnv returns, np.stack of what the envs produced — observations and rewards are kept in
     float64, never rounded through float32 / observation-space-dtype buffers as SB3's DummyVecEnv does (the reference never trains
@@ -291,7 +292,8 @@ class HostVecEnv(VecEnv):
         return self.s.clone(), blk[:, O].contiguous(), blk[:, O + 1].to(torch.uint8), HostInfos(infos)
 
     def staging(self):
-        """the host rollout path's transfer buffers (icrl_host_step_t), allocated on first use: a pinned block [obs f64 N x O | rew f64 N |
+        """the transfer buffers of the host rollout path (icrl_host_step_t) and of the host episode loop (icrl_host_episode_t, which
+        copies the observation part only), allocated on first use: a pinned block [obs f64 N x O | rew f64 N |
         done u8 N] copied to its device twin once per env step, and a pinned, device-visible float32 [N, act] the kernel writes the
         clipped actions (Discrete: the index) into — icrl_host_step maps its host address with hipHostGetDevicePointer, which serves
         torch's pinned allocations whether they come from hipHostMalloc or from host registration."""

@@ -296,6 +296,33 @@ int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_c
                    const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
                    const float* action_high, int k, void* stream);
 
+/* Sampling / evaluation episodes over ONE HOST env (utils.HostEpisodeRun): one launch per env step, `rows` + 1 launches at most
+ * (k = 0 .. rows), one workgroup of 256 threads, a plain launch.  Launch k is one pass of icrl_sample_episodes' loop around the env
+ * step, the raw observation coming from the staging block the host copied in before the launch (raw obs f64 [O] first): the reset
+ * observation for k = 0, else what the env returned for step k - 1 (after `done`: the auto-reset observation).  It
+ *   - normalises with the frozen statistics of `nm` (norm_obs, epsilon, clip_obs; nothing of `nm` is written);
+ *   - for k >= 1 writes row k - 1 of orig_obs / obs: the observation after step k - 1;
+ *   - with `act` != 0 runs the policy forward (mode when `deterministic` or noise == NULL, else sampled on noise row k) and writes
+ *     the clipped action (Discrete: the index) to `act_host` and to row k of `actions`.
+ * The launch after the last episode's last step passes act = 0: it only finishes that step.  Episode returns and lengths are the
+ * host's (it has every reward and done flag).
+ * Served: what icrl_host_step serves of the policy (the one-workgroup-per-env image), obs_dim <= 128, num_envs == 1, a frozen
+ * normaliser; anything else is refused with a reason (the host then runs the per-step loop). */
+typedef struct icrl_host_episode_t {
+  int num_envs;          /* 1 */
+  int obs_dim;
+  int rows;              /* rows of `noise` and of the outputs (episodes x the env's step limit) */
+  int deterministic;
+  const void* stage;     /* device copy of the staging block: raw obs f64 [O] | ... */
+  float* act_host;       /* HOST address of page-locked memory (see icrl_host_step_t): [act] float32 clipped action ([1] index when discrete) */
+  double* orig_obs;      /* [rows, O] raw observation AFTER each step */
+  double* obs;           /* same, normalised */
+  float* actions;        /* [rows, act] clipped action that produced it ([rows, 1] index when discrete) */
+} icrl_host_episode_t;
+
+int icrl_host_episode_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_host_episode_t* he, const float* noise,
+                           const float* action_low, const float* action_high, int k, int act, void* stream);
+
 /* ActorTwoCriticsPolicy.evaluate_actions (policies.py:752-767): values, log-prob of the GIVEN actions and the entropy of
  * the action distribution (used by compute_kl, icrl/utils.py:421-437).  actions [N,act_store] float32. */
 int icrl_policy_evaluate(const icrl_policy_t* pol, const double* obs, const float* actions, int N, float* v_r, float* v_c,

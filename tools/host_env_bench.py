@@ -7,6 +7,15 @@
 
 The host env is a do-nothing HC-shaped numpy env (obs 18, act 6), so (a) - (c) is device and transfer overhead.  Each figure is
 one timed rollout of T steps after a warm-up rollout.  usage: python tools/host_env_bench.py [--T 1024] [--N 8 64 128]
+
+--episodes E adds the episode mode: us per env step of utils.sample_from_agent, E fixed-length episodes (1000 steps) of ONE env:
+
+  (a) host path      utils.HostEpisodeRun (one staging copy + one icrl_host_episode_step launch per env step)
+  (b) stepped path   utils.SteppedEpisodeRun over the same host env, forced with ICRL_HOST_EPISODES_STEPPED=1, same process
+  (c) env alone      HostVecEnv.step_host over the same env
+  (d) device env     icrl_sample_episodes over HipSynthVecEnv (HCWithPos-v0), sequential episodes in one launch
+
+printed as one more JSON line after the rollout table (--N with no value skips that table).
 """
 import argparse
 import json
@@ -39,6 +48,22 @@ class NullHC:
         return self._obs, 0.0, False, {}
 
 
+class NullHCEpisodes(NullHC):
+    """NullHC whose episodes end at the 1000-step limit (the episode mode needs `done`)."""
+
+    def __init__(self):
+        super().__init__()
+        self._t = 0
+
+    def reset(self):
+        self._t = 0
+        return self._obs
+
+    def step(self, a):
+        self._t += 1
+        return self._obs, 0.0, self._t >= self._max_episode_steps, {}
+
+
 def _agent(env, T):
     import torch
     from icrl_amd.constraint_net import ConstraintNet
@@ -62,10 +87,46 @@ def _time(fn):
     return time.perf_counter() - t0
 
 
+def episodes(E):
+    """the episode mode: one warm-up and one timed sample_from_agent of E episodes per figure."""
+    import torch
+    from icrl_amd import utils
+    from icrl_amd.ppo_lag import PPOLagrangian
+    from icrl_amd.vec_env import DummyVecEnv, VecNormalizeWithCost
+    steps = 1000 * E
+    denv = utils.make_eval_env("HCWithPos-v0", False, seed=0)
+    agent = PPOLagrangian("TwoCriticsMlpPolicy", utils.make_train_env("HCWithPos-v0", None, True, 0, 1, cost_info_str="cost", reward_gamma=0.99, cost_gamma=0.99), n_steps=64, seed=0)
+    henv = VecNormalizeWithCost(DummyVecEnv([NullHCEpisodes]), training=False, norm_reward=False, norm_cost=False)
+    noise = torch.randn(steps, 6, device="cuda")
+
+    def sample(env, stepped):
+        if stepped:
+            os.environ["ICRL_HOST_EPISODES_STEPPED"] = "1"
+        else:
+            os.environ.pop("ICRL_HOST_EPISODES_STEPPED", None)
+        try:
+            run = utils._run_episodes(agent, env, E, False, noise, False)
+        finally:
+            os.environ.pop("ICRL_HOST_EPISODES_STEPPED", None)
+        assert int(run.lengths.sum()) == steps
+        return run
+    assert isinstance(sample(henv, False), utils.HostEpisodeRun) and isinstance(sample(henv, True), utils.SteppedEpisodeRun)
+    a = _time(lambda: sample(henv, False))
+    b = _time(lambda: sample(henv, True))
+    act = np.zeros((1, 6), np.float32)
+    c = _time(lambda: [henv.unwrapped.step_host(act) for _ in range(steps)])
+    d = _time(lambda: sample(denv, False))
+    row = dict(mode="episodes", episodes=E, steps=steps, host_path_us=1e6 * a / steps, stepped_path_us=1e6 * b / steps,
+               env_alone_us=1e6 * c / steps, device_env_us=1e6 * d / steps)
+    print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=1024)
-    ap.add_argument("--N", type=int, nargs="+", default=[8, 64, 128])
+    ap.add_argument("--N", type=int, nargs="*", default=[8, 64, 128])
+    ap.add_argument("--episodes", type=int, default=0, help="episode mode: this many 1000-step episodes of one env per figure (0: off)")
     args = ap.parse_args()
     import torch
     from icrl_amd import utils
@@ -87,6 +148,8 @@ def main():
         row = dict(N=N, T=T, host_path_us=1e6 * a / T, stepped_path_us=1e6 * b / T, env_alone_us=1e6 * c / T, device_env_us=1e6 * d / T)
         rows.append(row)
         print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+    if args.episodes > 0:
+        rows.append(episodes(args.episodes))
     return rows
 
 
