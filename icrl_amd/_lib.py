@@ -39,6 +39,12 @@ SIGNATURES = {
     "icrl_rollout_collect_ex": [c_void_p] * 9 + [c_double] * 4 + [c_int, c_void_p],
     "icrl_host_step_ws_bytes": [c_int, c_int],
     "icrl_host_step": [c_void_p] * 9 + [c_int, c_void_p],
+    # training-episode statistics (csrc/monitor.hip) and the rollout entry points that feed them: the descriptor sits before the stream
+    "icrl_monitor_ws_bytes": [c_int, c_int],
+    "icrl_monitor_scan": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "icrl_rollout_collect_ex_mon": [c_void_p] * 9 + [c_double] * 4 + [c_int, c_void_p, c_void_p],
+    "icrl_host_step_mon": [c_void_p] * 9 + [c_int, c_void_p, c_void_p],
+    "icrl_rollout_collect_batch_mon": [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_double] * 4 + [c_int, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_host_episode_step": [c_void_p] * 6 + [c_int, c_int, c_void_p],
     "icrl_ppo_lag_train": [c_void_p] * 11,
     "icrl_ppo_generic_row_floats": [c_void_p],
@@ -69,7 +75,7 @@ SIGNATURES = {
     "icrl_ppo_lag_train_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

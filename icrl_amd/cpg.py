@@ -102,7 +102,7 @@ def setup(config, log=print):
                         delta_p_ema_alpha=config.proportional_cost_ema_alpha, delta_d_ema_alpha=config.derivative_cost_ema_alpha),
         policy_kwargs=dict(net_arch=utils.get_net_arch(config)),
         action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-        streams=getattr(config, "streams", None))
+        streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
     if world > 1:      # all ranks hold the same initial networks (same seed); from here on rank r draws its own noise / permutations
         D.decorrelate_streams(config.seed, rank)
     # ref: icrl/cpg.py:160-176
@@ -169,6 +169,7 @@ def build_parser():
     a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
+    a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
     return p
 
 

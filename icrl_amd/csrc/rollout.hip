@@ -423,6 +423,7 @@ struct ActStepArgs {
   const float* alow;
   const float* ahigh;
   int has_cn;
+  double* raw_plane;    // [T,N] float64 or NULL: the raw env reward of every step (icrl_monitor_t.raw_rewards), stored next to ag.raw_rew
 };
 
 template <int OCT, int CIT>
@@ -455,7 +456,10 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
     env_step_wave(a.env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
     float* nob = a.buf.new_orig_observations + tn * O;
     for (int i = lane; i < O; i += WAVE) nob[i] = (float)sh.s_new[i];
-    if (lane == 0) { a.ag.raw_rew[n] = rew; a.ag.dones[n] = (uint8_t)done; }
+    if (lane == 0) {
+      a.ag.raw_rew[n] = rew; a.ag.dones[n] = (uint8_t)done;
+      if (a.raw_plane != nullptr) a.raw_plane[tn] = rew;
+    }
   } else if (w == 3) {
     float cost = 0.f;
     if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
@@ -486,6 +490,7 @@ struct GenStepArgs {
   icrl_buffer_t buf;
   icrl_agent_t ag;
   int has_cn;
+  double* raw_plane;    // see ActStepArgs
 };
 
 __global__ void __launch_bounds__(64) act_step_generic_kernel(GenStepArgs a, int t) {
@@ -513,6 +518,7 @@ __global__ void __launch_bounds__(64) act_step_generic_kernel(GenStepArgs a, int
   for (int i = lane; i < O; i += WAVE) nob[i] = (float)s_new[i];
   if (lane == 0) {
     a.ag.raw_rew[n] = rew; a.ag.dones[n] = (uint8_t)done;
+    if (a.raw_plane != nullptr) a.raw_plane[tn] = rew;
     const float cost = a.has_cn ? a.ag.raw_cost[n] : 0.f;
     a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
     a.buf.dones[tn] = (float)a.ag.last_dones[n];
@@ -1049,7 +1055,9 @@ static inline size_t persist_dyn_lds(int N, int O, int A) { return ((size_t)O * 
 
 // PROF: the diagnostic phase timers (do_gae bit 2) as a compile-time variant: as a run-time flag their seven 64-bit accumulators sat in scalar registers
 // across the step loop of every launch (ppo_train_halves.hip: 2.5 % there)
-template <int OCT, int CIT, bool GRAN, bool PROF = false>
+// MON: store the raw reward of every step into ActStepArgs.raw_plane (icrl_monitor_t.raw_rewards) — a compile-time variant like PROF: the
+// instantiations without it are the kernels as they were, with not one more value in the step loop's registers
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false>
 __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ ActShared sh;
@@ -1070,6 +1078,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   icrl_costnet_t cnet = a.cn; globalize(cnet);
   unsigned long long* const xg_all = as_global(p.xg);
   const float* const noise_g = as_global(a.noise);
+  double* const raw_plane = MON ? as_global(a.raw_plane) : nullptr;
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   load_pol_regs<OCT>(a.pl, a.PT, R);
@@ -1281,6 +1290,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
         buf.costs[tn] = (float)c;
       }
       last_done_s = done_s[n];
+      if (MON) raw_plane[tn] = fin_rew;
     }
     if (PROF) { const unsigned long long tn_ = prof_now(); pc2 += tn_ - tl; tl = tn_; }
   }
@@ -1313,7 +1323,7 @@ struct GenRolloutArgs {
   GenNet net;
   const float* P;      // the policy's parameters in their natural layout (log_std of the Gaussian head)
 };
-template <int OCT, int CIT>
+template <int OCT, int CIT, bool MON>
 __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
   constexpr bool GRAN = true;
   const PersistArgs& p = ga.p;
@@ -1338,6 +1348,7 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
   icrl_costnet_t cnet = a.cn; globalize(cnet);
   unsigned long long* const xg_all = as_global(p.xg);
   const float* const noise_g = as_global(a.noise);
+  double* const raw_plane = MON ? as_global(a.raw_plane) : nullptr;
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   if ((threadIdx.x >> 6) == 3 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
@@ -1557,6 +1568,7 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
         buf.costs[tn] = (float)c;
       }
       last_done_s = done_s[n];
+      if (MON) raw_plane[tn] = fin_rew;
     }
     if (p.prof) { const unsigned long long tn_ = prof_now(); pc2 += tn_ - tl; tl = tn_; }
   }
@@ -1580,21 +1592,21 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
   }
 }
 
-template <int OCT, int CIT>
+template <int OCT, int CIT, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_generic_kernel(GenRolloutArgs ga) {
-  rollout_generic_body<OCT, CIT>(ga);
+  rollout_generic_body<OCT, CIT, MON>(ga);
 }
 
-template <int OCT, int CIT, bool GRAN, bool PROF = false>
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_persistent_kernel(PersistArgs p) {
-  rollout_persistent_body<OCT, CIT, GRAN, PROF>(p);
+  rollout_persistent_body<OCT, CIT, GRAN, PROF, MON>(p);
 }
 
 // several independent runs in ONE launch: grid (N, n_runs), run = blockIdx.y, argument blocks in device memory.  Workgroups are
 // dispatched x-fastest, so a run's N workgroups become resident together and the oldest run of the grid is always complete: runs
 // whose workgroups do not fit yet simply start when earlier runs have finished (the exchange waits are bounded by seconds).
 // MINW: waves per SIMD the register allocation must leave room for (= workgroups per CU: each workgroup has one wave per SIMD)
-template <int OCT, int CIT, bool GRAN, int MINW>
+template <int OCT, int CIT, bool GRAN, int MINW, bool MON = false>
 __global__ void __launch_bounds__(256, MINW) rollout_persistent_batch_kernel(const PersistArgs* __restrict__ runs) {
   __shared__ PersistArgs p;
   {
@@ -1603,7 +1615,7 @@ __global__ void __launch_bounds__(256, MINW) rollout_persistent_batch_kernel(con
     for (unsigned i = threadIdx.x; i < sizeof(PersistArgs) / 4; i += 256) dst[i] = src[i];
   }
   __syncthreads();
-  rollout_persistent_body<OCT, CIT, GRAN>(p);
+  rollout_persistent_body<OCT, CIT, GRAN, false, MON>(p);
 }
 
 // =================================================================================================================
@@ -1632,7 +1644,7 @@ struct WideArgs {
   unsigned long long* xcc;     // multi-env kernel, packed batched launches: G zeroed words (the workgroups' XCD ids), else NULL
 };
 
-template <int OCT, int CIT, bool PROF = false>      // PROF: the phase timers (do_gae bits 2 / 3) as a compile-time variant (rollout_persistent_body)
+template <int OCT, int CIT, bool PROF = false, bool MON = false>      // PROF: the phase timers (do_gae bits 2 / 3) as a compile-time variant, MON: the raw-reward plane (rollout_persistent_body)
 __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
   __shared__ ActShared sh[WIDE_E];
   __shared__ double Bl[MAX_OBS * MAX_ACT];
@@ -1868,7 +1880,7 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
       }
       if (tid == 64) {
         double r = rew_s[e];
-        if (nm.norm_reward) r = fmin(fmax(r / dens_s[0], -nm.clip_reward), nm.clip_reward);
+          if (nm.norm_reward) r = fmin(fmax(r / dens_s[0], -nm.clip_reward), nm.clip_reward);
         a.buf.rewards[tn] = (float)r;
         if (has_cost) {
           double c = (double)cost_s[e];
@@ -1876,6 +1888,7 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
           a.buf.costs[tn] = (float)c;
         }
         last_done_s[e] = done_s[e];
+        if (MON) a.raw_plane[tn] = rew_s[e];
       }
     }
     if (pf) noise_s[par ^ 1][pe][pk] = noise_next;
@@ -2119,7 +2132,7 @@ __device__ __noinline__ void env_step_wave3(int O, int A, int flags, int max_ste
   }
 }
 
-template <int OCT, int CIT, int E>
+template <int OCT, int CIT, int E, bool MON>
 __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int g_arg) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ MultiShared<E, CIT> sh;
@@ -2133,6 +2146,7 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
   unsigned long long* const xg_all = as_global(p.xg);      // granules of every env, both parities
   unsigned long long* const sg_all = as_global(p.sg);      // statistics granules
   const float* const noise_g = as_global(a.noise);
+  double* const raw_plane = MON ? as_global(a.raw_plane) : nullptr;
   TileRegs<OCT, CIT> R;                // waves 0..2: policy / value / cost-value net, wave 3: cost net — as MFMA A operands
   if (threadIdx.x >= 192 && a.has_cn) load_cn_tiles<OCT, CIT>(a.cn, a.cl, R, sh.cst[3]);
   else load_pol_tiles<OCT, CIT>(a.pl, a.PT, R, sh.cst[threadIdx.x >> 6]);
@@ -2635,6 +2649,7 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
         buf.costs[tn] = (float)c;
       }
       sh.last_done[e] = sh.done[e];
+      if (MON) raw_plane[tn] = sh.rew[e];
     }
     if (pf) sh.noise[par ^ 1][pe][pk] = noise_next;
     __syncthreads();
@@ -2663,14 +2678,14 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
   }
 }
 
-template <int OCT, int CIT, int E>
+template <int OCT, int CIT, int E, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_multi_kernel(WideArgs p, int packed) {
   if (packed && (blockIdx.x & 7)) return;      // the G <= 32 workgroups on one XCD: workgroups 0, 8, 16, ... (ppo_common.h, "XCD placement")
-  rollout_multi_body<OCT, CIT, E>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+  rollout_multi_body<OCT, CIT, E, MON>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
 }
 
 // several independent runs in ONE launch: grid (G, n_runs), run = blockIdx.y
-template <int OCT, int CIT, int E>
+template <int OCT, int CIT, int E, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_multi_batch_kernel(const WideArgs* __restrict__ runs, int n_runs, int G, int packed) {
   __shared__ WideArgs p;
   int run = (int)blockIdx.y, g = (int)blockIdx.x;
@@ -2686,7 +2701,7 @@ __global__ void __launch_bounds__(256) rollout_multi_batch_kernel(const WideArgs
     for (unsigned i = threadIdx.x; i < sizeof(WideArgs) / 4; i += 256) dst[i] = src[i];
   }
   __syncthreads();
-  rollout_multi_body<OCT, CIT, E>(p, g);
+  rollout_multi_body<OCT, CIT, E, MON>(p, g);
 }
 
 // VecNormalizeWithCost.reset (vec_normalize.py:148-157, 270-278)
@@ -3178,6 +3193,7 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
       last_done_s = done_s[n];
       a.ag.last_dones[n] = (uint8_t)done_s[n];
       a.ag.raw_rew[n] = rawr_s[n];
+      if (a.raw_plane != nullptr) a.raw_plane[tn] = rawr_s[n];
       a.ag.dones[n] = (uint8_t)done_s[n];
     }
     if (n == 0) {              // the statistics for launch k + 1; after the rollout's last step also the normaliser's own arrays
@@ -3664,49 +3680,66 @@ static bool multi_shape(int N, int n_stats, int* E, int* G) {
   return *G >= gmin;
 }
 
-template <int OCT, int CIT, int E>
+template <int OCT, int CIT, int E, bool MON>
 static int launch_multi_e(const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
   if (one != nullptr) {
-    if (!persistent_fits(rollout_multi_kernel<OCT, CIT, E>, G, dyn)) return -1;
+    if (!persistent_fits(rollout_multi_kernel<OCT, CIT, E, MON>, G, dyn)) return -1;
     WideArgs arg = *one;
     static const bool no_pack = getenv("ICRL_NO_XCD_PACK") != nullptr;
     const int packed = !no_pack && arg.xcc != nullptr && G <= 32;
     void* params[] = {(void*)&arg, (void*)&packed};
-    const hipError_t e = hipLaunchCooperativeKernel((const void*)rollout_multi_kernel<OCT, CIT, E>, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
+    const hipError_t e = hipLaunchCooperativeKernel((const void*)rollout_multi_kernel<OCT, CIT, E, MON>, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
     if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
     return (int)e;
   } else {
-    if (!persistent_fits(rollout_multi_batch_kernel<OCT, CIT, E>, G, dyn)) return -1;
+    if (!persistent_fits(rollout_multi_batch_kernel<OCT, CIT, E, MON>, G, dyn)) return -1;
     // packed layout (a run's G workgroups on ONE XCD: workgroups b, b + 8, ...) when every XCD can hold its share of the grid at once
     // (32 CUs each); otherwise run-major, whose runs become resident oldest first
     int per_cu = 0;
     const int groups = (n_runs + 7) / 8;
     static const bool no_pack_b = getenv("ICRL_NO_XCD_PACK") != nullptr;
-    const bool packed = !no_pack_b && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_multi_batch_kernel<OCT, CIT, E>, 256, dyn) == hipSuccess &&
+    const bool packed = !no_pack_b && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_multi_batch_kernel<OCT, CIT, E, MON>, 256, dyn) == hipSuccess &&
                         groups * G <= 32 * per_cu;
-    if (packed) hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E>), dim3(8 * G * ((n_runs + 7) / 8)), dim3(256), dyn, s, d_args, n_runs, G, 1);
-    else hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E>), dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
+    if (packed) hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E, MON>), dim3(8 * G * ((n_runs + 7) / 8)), dim3(256), dyn, s, d_args, n_runs, G, 1);
+    else hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E, MON>), dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
   }
   return (int)hipGetLastError();
 }
 
 // one: single-run launch (argument block by value) | d_args: n_runs blocks in device memory.  -1: does not fit the device
-static int launch_multi(bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+template <bool MON>
+static int launch_multi_m(bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
   // cn128: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
   if (!small && cn128)
-    return E == 16 ? launch_multi_e<8, 8, 16>(one, d_args, n_runs, G, dyn, s)
-           : (E == 8 ? launch_multi_e<8, 8, 8>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 8, 4>(one, d_args, n_runs, G, dyn, s));
-  if (small) return E == 16 ? launch_multi_e<2, 2, 16>(one, d_args, n_runs, G, dyn, s)
-                    : (E == 8 ? launch_multi_e<2, 2, 8>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<2, 2, 4>(one, d_args, n_runs, G, dyn, s));
-  return E == 16 ? launch_multi_e<8, 10, 16>(one, d_args, n_runs, G, dyn, s)
-         : (E == 8 ? launch_multi_e<8, 10, 8>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 10, 4>(one, d_args, n_runs, G, dyn, s));
+    return E == 16 ? launch_multi_e<8, 8, 16, MON>(one, d_args, n_runs, G, dyn, s)
+           : (E == 8 ? launch_multi_e<8, 8, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 8, 4, MON>(one, d_args, n_runs, G, dyn, s));
+  if (small) return E == 16 ? launch_multi_e<2, 2, 16, MON>(one, d_args, n_runs, G, dyn, s)
+                    : (E == 8 ? launch_multi_e<2, 2, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<2, 2, 4, MON>(one, d_args, n_runs, G, dyn, s));
+  return E == 16 ? launch_multi_e<8, 10, 16, MON>(one, d_args, n_runs, G, dyn, s)
+         : (E == 8 ? launch_multi_e<8, 10, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 10, 4, MON>(one, d_args, n_runs, G, dyn, s));
 }
 
-extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
-                                       const icrl_costnet_t* cn, const icrl_buffer_t* buf, const icrl_agent_t* ag,
-                                       const float* noise, const float* action_low, const float* action_high,
-                                       double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
-                                       int do_gae, void* stream) {
+// mon: the instantiations that store the raw-reward plane (ActStepArgs.raw_plane is set in every argument block)
+static int launch_multi(bool mon, bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+  return mon ? launch_multi_m<true>(small, cn128, E, one, d_args, n_runs, G, dyn, s) : launch_multi_m<false>(small, cn128, E, one, d_args, n_runs, G, dyn, s);
+}
+
+// the raw-reward plane of a monitor descriptor (NULL descriptor: no plane, the kernels then store nothing extra)
+static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane) {
+  *plane = nullptr;
+  if (mon == nullptr) return 0;
+  if (mon->raw_rewards == nullptr) return fail("%s: icrl_monitor_t.raw_rewards is NULL (a [T, N] float64 plane is required)", who);
+  *plane = mon->raw_rewards;
+  return 0;
+}
+
+extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
+                                           const icrl_costnet_t* cn, const icrl_buffer_t* buf, const icrl_agent_t* ag,
+                                           const float* noise, const float* action_low, const float* action_high,
+                                           double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
+                                           int do_gae, const icrl_monitor_t* mon, void* stream) {
+  double* raw_plane = nullptr;
+  if (int e = mon_plane("icrl_rollout_collect_ex_mon", mon, &raw_plane)) return e;
   const int N = env->n_envs, O = env->obs_dim, T = buf->T;
   const bool generic = policy_is_wide(pol) || (cn != nullptr && costnet_is_wide(cn));      // shapes of the generic-shape path: per-step launches
   if (!generic && !dims_ok(pol)) return bad_dims("icrl_rollout_collect", pol);
@@ -3740,7 +3773,7 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
       if (ws != nullptr) {
         PersistArgs& p = ga.p;
         ActStepArgs& a = p.act;
-        a.env = *env; a.buf = *buf; a.ag = *ag;
+        a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
         a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, MAX_H, MAX_H, pol->discrete);      // (only obs / act / discrete are read)
         a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
         a.has_cn = cn != nullptr;
@@ -3768,7 +3801,8 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
           if (e_ == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
           return (int)e_;
         };
-        const int perr = small ? go(rollout_generic_kernel<2, 2>) : go(rollout_generic_kernel<8, 10>);
+        const int perr = raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 2, true>) : go(rollout_generic_kernel<8, 10, true>))
+                                               : (small ? go(rollout_generic_kernel<2, 2>) : go(rollout_generic_kernel<8, 10>));
         if (perr >= 0) {
           const int err = perr != 0 ? perr : (int)hipGetLastError();
           if (err || !(do_gae & 1)) return err;
@@ -3779,7 +3813,7 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
       }
     }
     GenStepArgs g;
-    g.env = *env; g.buf = *buf; g.ag = *ag; g.has_cn = cn != nullptr;
+    g.env = *env; g.buf = *buf; g.ag = *ag; g.has_cn = cn != nullptr; g.raw_plane = raw_plane;
     const int AS = buf->act_store;
     for (int t = 0; t < T; ++t) {
       const size_t row = (size_t)t * N;
@@ -3805,7 +3839,7 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
                             reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws, buf->gae_ws_bytes, stream);
   }
   ActStepArgs a;
-  a.env = *env; a.buf = *buf; a.ag = *ag;
+  a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
   a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
   a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
   a.has_cn = cn != nullptr;
@@ -3827,7 +3861,7 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
       hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS + (p.xcc ? 256 : 0), s);
       if (e != hipSuccess) return (int)e;
       const bool small = a.pl.O <= 32 && (!cn || cn->in_dim <= 32);
-      const int err = launch_multi(small, !cn || cn->in_dim <= 128, E, &p, nullptr, 1, G, multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G), s);
+      const int err = launch_multi(raw_plane != nullptr, small, !cn || cn->in_dim <= 128, E, &p, nullptr, 1, G, multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G), s);
       if (err >= 0) {
         if (err || !(do_gae & 1)) return err;
         return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
@@ -3841,7 +3875,9 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
   // against the replicated-statistics kernel at HC widths: 64 envs 9.6 vs 9.5 us per step, 128 envs 9.9 vs 13.9
   if (!(do_gae & 2) && nm->training && (N > 96 || N * O > NORM_CHUNK || (do_gae & 16)) && N <= WIDE_MAX_N && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1) {
     const bool small = a.pl.O <= 32 && (!cn || cn->in_dim <= 32);
-    const void* kfn = small ? (const void*)rollout_wide_kernel<2, 2> : (const void*)rollout_wide_kernel<8, 10>;
+    const bool monv = raw_plane != nullptr;      // (with the plane: the instantiations without phase timers)
+    const void* kfn = monv ? (small ? (const void*)rollout_wide_kernel<2, 2, false, true> : (const void*)rollout_wide_kernel<8, 10, false, true>)
+                           : (small ? (const void*)rollout_wide_kernel<2, 2> : (const void*)rollout_wide_kernel<8, 10>);
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0) == hipSuccess && per_cu > 0) {
@@ -3861,7 +3897,10 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
         p.xcc = nullptr;
         hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS, s);
         if (e != hipSuccess) return (int)e;
-        int err = p.prof ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, true>, dim3(G), dim3(256), 0, s, p)
+        if (monv) p.prof = 0;
+        int err = monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, false, true>, dim3(G), dim3(256), 0, s, p)
+                                     : launch_coresident(rollout_wide_kernel<8, 10, false, true>, dim3(G), dim3(256), 0, s, p))
+                  : p.prof ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, true>, dim3(G), dim3(256), 0, s, p)
                                        : launch_coresident(rollout_wide_kernel<8, 10, true>, dim3(G), dim3(256), 0, s, p))
                          : (int)(small ? launch_coresident(rollout_wide_kernel<2, 2>, dim3(G), dim3(256), 0, s, p)
                                        : launch_coresident(rollout_wide_kernel<8, 10>, dim3(G), dim3(256), 0, s, p));
@@ -3906,7 +3945,13 @@ extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t*
         return true;
       };
       bool launched;
-      if (p.prof) {      // (tools: the instantiations with the phase timers)
+      if (raw_plane != nullptr) {      // the instantiations that store the raw-reward plane (no phase timers)
+        p.prof = 0;
+        if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true, false, true>);
+        else if (small) launched = go(rollout_persistent_kernel<2, 2, false, false, true>);
+        else if (gran) launched = go(rollout_persistent_kernel<8, 10, true, false, true>);
+        else launched = go(rollout_persistent_kernel<8, 10, false, false, true>);
+      } else if (p.prof) {      // (tools: the instantiations with the phase timers)
         if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true, true>);
         else if (small) launched = go(rollout_persistent_kernel<2, 2, false, true>);
         else if (gran) launched = go(rollout_persistent_kernel<8, 10, true, true>);
@@ -3944,9 +3989,9 @@ per_step:
 // icrl_rollout_collect for n_runs runs: ONE persistent launch of grid (N, n_runs) + ONE batched dual-GAE launch.  Only the
 // one-workgroup-per-env persistent kernel has a batched form (N <= 128 and N x obs <= 4096: BASELINE configs[1]); other shapes
 // are refused (the caller then issues the single-run calls).
-extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* jobs, const float* action_low, const float* action_high,
-                                          double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
-                                          int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
+                                              const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
+                                              double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
   static_assert(sizeof(PersistArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
   if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
@@ -3985,6 +4030,7 @@ extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* 
         WideArgs p;
         ActStepArgs& a = p.act;
         a.env = *j.env; a.buf = *j.buf; a.ag = *j.ag;
+        if (int e_ = mon_plane("icrl_rollout_collect_batch_mon", mons ? mons + r : nullptr, &a.raw_plane)) return e_;
         a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
         a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
         a.has_cn = j.cn != nullptr;
@@ -4001,7 +4047,7 @@ extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* 
       }
       if (ok) {
         const bool small = O <= 32 && (!has_cn || j0.cn->in_dim <= 32);
-        const int err = launch_multi(small, !has_cn || j0.cn->in_dim <= 128, E, nullptr, d_args, n_runs, G, multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G), s);
+        const int err = launch_multi(mons != nullptr, small, !has_cn || j0.cn->in_dim <= 128, E, nullptr, d_args, n_runs, G, multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G), s);
         if (err >= 0) {
           if (err || !(do_gae & 1)) return err;
           if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
@@ -4033,6 +4079,7 @@ extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* 
     PersistArgs p;
     ActStepArgs& a = p.act;
     a.env = *j.env; a.buf = *j.buf; a.ag = *j.ag;
+    if (int e_ = mon_plane("icrl_rollout_collect_batch_mon", mons ? mons + r : nullptr, &a.raw_plane)) return e_;
     a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
     a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
     a.has_cn = j.cn != nullptr;
@@ -4067,16 +4114,39 @@ extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* 
   if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess) cus_ = 256;
   const int minw = minw_env > 0 ? minw_env : ((long long)n_runs * N <= cus_ ? 1 : 2);
   int err;
-  if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2>) : go(rollout_persistent_batch_kernel<2, 2, true, 1>));
-  else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2>);
-  else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1>);
-  else err = go(rollout_persistent_batch_kernel<8, 10, false, 1>);
+  if (mons != nullptr) {
+    if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3, true>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2, true>) : go(rollout_persistent_batch_kernel<2, 2, true, 1, true>));
+    else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2, true>);
+    else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1, true>);
+    else err = go(rollout_persistent_batch_kernel<8, 10, false, 1, true>);
+  } else {
+    if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2>) : go(rollout_persistent_batch_kernel<2, 2, true, 1>));
+    else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2>);
+    else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1>);
+    else err = go(rollout_persistent_batch_kernel<8, 10, false, 1>);
+  }
   if (err || !(do_gae & 1)) return err;
   // dual GAE of every run in one launch; its argument blocks go behind the rollout's in args_ws (both launches are in flight together)
   if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
     return fail("icrl_rollout_collect_batch: args_ws needs 2 x n_runs x ICRL_BATCH_ARGS_BYTES = %lld B when the GAE launch is included", 2ll * n_runs * ICRL_BATCH_ARGS_BYTES);
   return icrl_gae_dual_batch_impl(n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda,
                                   (char*)args_ws + (size_t)n_runs * ICRL_BATCH_ARGS_BYTES, stream);
+}
+
+extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
+                                       const icrl_costnet_t* cn, const icrl_buffer_t* buf, const icrl_agent_t* ag,
+                                       const float* noise, const float* action_low, const float* action_high,
+                                       double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
+                                       int do_gae, void* stream) {
+  return icrl_rollout_collect_ex_mon(env, nm, pol, cn, buf, ag, noise, action_low, action_high, reward_gamma, reward_gae_lambda,
+                                     cost_gamma, cost_gae_lambda, do_gae, nullptr, stream);
+}
+
+extern "C" int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* jobs, const float* action_low, const float* action_high,
+                                          double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
+                                          int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+  return icrl_rollout_collect_batch_mon(n_runs, jobs, nullptr, action_low, action_high, reward_gamma, reward_gae_lambda, cost_gamma,
+                                        cost_gae_lambda, do_gae, args_ws, args_ws_bytes, stream);
 }
 
 extern "C" int icrl_rollout_collect(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
@@ -4093,9 +4163,11 @@ extern "C" size_t icrl_host_step_ws_bytes(int N, int obs_dim) {
   return N < 1 || obs_dim < 1 ? 0 : 2 * host_copy_doubles(N, obs_dim) * sizeof(double);
 }
 
-extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
-                              const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
-                              const float* action_high, int k, void* stream) {
+extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
+                                  const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
+                                  const float* action_high, int k, const icrl_monitor_t* mon, void* stream) {
+  double* raw_plane = nullptr;
+  if (int e = mon_plane("icrl_host_step_mon", mon, &raw_plane)) return e;
   if (nm == nullptr || pol == nullptr || buf == nullptr || ag == nullptr || hs == nullptr) return fail("icrl_host_step: NULL descriptor");
   const int N = buf->N, O = buf->obs_dim, T = hs->T;
   if (policy_is_wide(pol) || !dims_ok(pol)) return bad_dims("icrl_host_step", pol);
@@ -4112,7 +4184,7 @@ extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, c
   HostStepArgs h{};
   ActStepArgs& a = h.act;
   a.env.n_envs = N; a.env.obs_dim = O; a.env.act_dim = pol->discrete ? 1 : pol->act_dim;
-  a.buf = *buf; a.ag = *ag;
+  a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
   a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
   a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
   a.has_cn = cn != nullptr;
@@ -4129,6 +4201,12 @@ extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, c
   if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
   else hipLaunchKernelGGL((host_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, h, k);
   return (int)hipGetLastError();
+}
+
+extern "C" int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
+                              const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
+                              const float* action_high, int k, void* stream) {
+  return icrl_host_step_mon(nm, pol, cn, buf, ag, hs, noise, action_low, action_high, k, nullptr, stream);
 }
 
 // ---- sampling / evaluation episodes over one host env: one launch per env step (host_episode_kernel) ----

@@ -83,7 +83,7 @@ def gail(config, log=print):
                 sde_sample_freq=config.sde_sample_freq, target_kl=config.target_kl, seed=config.seed, device=dev, verbose=config.verbose,
                 policy_kwargs=dict(net_arch=[dict(pi=list(config.policy_layers), vf=list(config.reward_vf_layers), cvf=list(config.reward_vf_layers))]),
                 action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-                streams=getattr(config, "streams", None))
+                streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
     cbs = [gail_update]
     if config.save_dir and rank == 0:
         cbs.append(callbacks.CheckpointCallback(int(config.save_every), os.path.join(config.save_dir, "models"), verbose=0))
@@ -132,6 +132,7 @@ def build_parser():
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
+    a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
     return p
 
 

@@ -80,7 +80,7 @@ def setup(config):
                             delta_p_ema_alpha=config.proportional_cost_ema_alpha, delta_d_ema_alpha=config.derivative_cost_ema_alpha),
             policy_kwargs=dict(net_arch=utils.get_net_arch(config)),
             action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-            streams=getattr(config, "streams", None))
+            streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
         # the constructor seeded every generator with config.seed (common/utils.py:23-39): all ranks now hold the SAME initial
         # networks; from here on rank r draws its own action noise / minibatch permutations
         D.decorrelate_streams(config.seed, rank)
@@ -265,6 +265,7 @@ def build_parser():
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
+    a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
     return p
 
 

@@ -11,6 +11,7 @@ the work is enqueued as kernels of libicrl_hip.so:
   train            -> icrl_ppo_lag_train   (ONE persistent launch for all epochs x minibatches); the dual variable is one
                       float32 scalar updated on the host (dual_variable.py)
 """
+import os
 import time
 
 import numpy as np
@@ -20,7 +21,7 @@ from . import _lib, logger, spaces
 from .buffers import RolloutBufferWithCost
 from .dual_variable import DualVariable, PIDLagrangian
 from .policies import ActorTwoCriticsPolicy
-from .structs import AgentT, HostStepT, PpoHyperT, p
+from .structs import AgentT, HostStepT, MonitorT, PpoHyperT, p
 from .vec_env import HipSynthVecEnv, HostVecEnv, VecCostWrapper, VecEnv, VecNormalize, VecNormalizeWithCost
 
 
@@ -44,7 +45,7 @@ class PPOLagrangian:
                  max_grad_norm=0.5, use_sde=False, sde_sample_freq=-1, target_kl=None, penalty_initial_value=1,
                  penalty_learning_rate=0.01, penalty_min_value=None, update_penalty_after=1, budget=0.,
                  tensorboard_log=None, create_eval_env=False, pid_kwargs=None, policy_kwargs=None, verbose=0, seed=None,
-                 device="cuda", _init_setup_model=True, action_noise="device", permutation="numpy", streams=None):
+                 device="cuda", _init_setup_model=True, action_noise="device", permutation="numpy", streams=None, episode_stats=None):
         if use_sde:
             raise NotImplementedError("gSDE is outside the hot path (no BASELINE config uses it)")
         if policy not in ("TwoCriticsMlpPolicy", ActorTwoCriticsPolicy):
@@ -71,6 +72,10 @@ class PPOLagrangian:
         #   streams:      optional object with rollout_noise(T, N, A), permutation(epoch, n), consumed(executed_epochs): every
         #                 draw of learn() comes from it (teacher forcing against the reference / the CPU oracle in the tests)
         self.action_noise, self.permutation, self.streams = action_noise, permutation, streams
+        #   episode_stats: keep the training envs' episode returns / lengths (the reference's Monitor + ep_info_buffer) and log
+        #                 rollout/ep_rew_mean, rollout/ep_len_mean.  None: the environment switch ICRL_EPISODE_STATS (default off)
+        self.episode_stats = episode_stats
+        self._mon = None
         self.num_timesteps, self._n_updates, self._total_timesteps = 0, 0, 0
         self._current_progress_remaining = 1
         self._last_obs = self._last_original_obs = self._last_dones = None
@@ -118,6 +123,63 @@ class PPOLagrangian:
             self._ahigh = torch.as_tensor(self.action_space.high, device=dev).float().contiguous()
         else:
             self._alow = self._ahigh = None
+        if self.episode_stats is None:
+            self.episode_stats = os.environ.get("ICRL_EPISODE_STATS", "0").strip().lower() not in ("", "0", "false", "no", "off")
+        self._mon = self._monitor_alloc() if self.episode_stats else None
+
+    # ---- training-episode statistics (ref: common/monitor.py:91-122, base_class.py:328-332, 368-389; csrc/monitor.hip) ---------
+    EP_WINDOW = 100      # ep_info_buffer = deque(maxlen=100)
+
+    def _monitor_alloc(self):
+        """the raw-reward plane the rollout kernels fill, the per-env carries of the episodes in progress, the ring of the last 100
+        finished episodes and the scan's scratch — only when episode_stats is on."""
+        T, N, dev = int(self.n_steps), int(self.n_envs), self.device
+        ws_bytes = int(_lib.lib().icrl_monitor_ws_bytes(T, N))
+        m = dict(raw_rewards=torch.zeros((T, N), dtype=torch.float64, device=dev), ep_ret=torch.zeros(N, dtype=torch.float64, device=dev),
+                 ep_len=torch.zeros(N, dtype=torch.int32, device=dev), win_ret=torch.zeros(self.EP_WINDOW, dtype=torch.float64, device=dev),
+                 win_len=torch.zeros(self.EP_WINDOW, dtype=torch.int32, device=dev), win_state=torch.zeros(2, dtype=torch.int32, device=dev),
+                 ws=torch.zeros((ws_bytes + 3) // 4, dtype=torch.int32, device=dev))
+        m["struct"] = MonitorT(p(m["raw_rewards"]), p(m["ep_ret"]), p(m["ep_len"]), p(m["win_ret"]), p(m["win_len"]), p(m["win_state"]), p(m["ws"]),
+                               m["ws"].numel() * 4)
+        return m
+
+    def _monitor_scan(self, rollout_buffer, rows, last_dones=None):
+        """episode records of the first `rows` steps of the rollout just collected (icrl_monitor_scan, on the rollout's stream)."""
+        if self._mon is None or rows < 1:
+            return
+        ld = self._ag["last_dones"] if last_dones is None else last_dones
+        _lib.check(_lib.lib().icrl_monitor_scan(_lib.byref(self._mon["struct"]), p(rollout_buffer.dones), p(ld), rollout_buffer.buffer_size,
+                                                rollout_buffer.n_envs, int(rows), _lib.current_stream()), "icrl_monitor_scan")
+
+    def _monitor_unrecorded_step(self, t, dones):
+        """a rollout a callback ended at step t: the envs have made that step (the reference's Monitor has its reward, and has started a new
+        episode where it was the last), but its episode records never reached ep_info_buffer (on_policy_algorithm.py:400-403)."""
+        m = self._mon
+        d = torch.as_tensor(dones, device=self.device).to(torch.bool).flatten()
+        m["ep_ret"].copy_(torch.where(d, torch.zeros_like(m["ep_ret"]), m["ep_ret"] + m["raw_rewards"][t]))
+        m["ep_len"].copy_(torch.where(d, torch.zeros_like(m["ep_len"]), m["ep_len"] + 1))
+
+    @staticmethod
+    def _window_order(count, size=100):
+        """ring slots of the valid records, oldest first, after `count` appends (record i lies in slot i % size)."""
+        count, size = int(count), int(size)
+        return list(range(count)) if count <= size else [(count + i) % size for i in range(size)]
+
+    @classmethod
+    def _window_records(cls, count, win_ret, win_len):
+        """(returns, lengths) oldest first as the reference keeps them: r = round(sum, 6) (monitor.py:109), l = int."""
+        idx = cls._window_order(count, len(win_ret))
+        return [round(float(win_ret[i]), 6) for i in idx], [int(win_len[i]) for i in idx]
+
+    def episode_window(self):
+        """the last (up to) 100 finished training episodes, oldest first: (returns: list[float], lengths: list[int]) — the `r` and `l` of
+        the reference's ep_info_buffer.  One device-to-host copy of the ring (about 1.2 KB)."""
+        if self._mon is None:
+            raise RuntimeError("episode statistics are off: PPOLagrangian(..., episode_stats=True) or ICRL_EPISODE_STATS=1")
+        m = self._mon
+        host = torch.cat([m["win_state"][:1].double(), m["win_len"].double(), m["win_ret"]]).cpu().numpy()
+        W = self.EP_WINDOW
+        return self._window_records(int(host[0]), host[1 + W:1 + 2 * W], host[1:1 + W])
 
     # ---- env-chain introspection: is this the device-native stack the fused rollout handles? ---------------------------
     def _fused_chain(self):
@@ -209,11 +271,17 @@ class PPOLagrangian:
             rev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             rev[0].record()
         cn = job["cn"]
-        _lib.check(_lib.lib().icrl_rollout_collect_ex(b(job["env"]), b(job["nm"]), b(job["pol"]), b(cn) if cn is not None else None, b(job["buf"]), b(job["ag"]),
-                                                      p(job["noise"]), p(self._alow), p(self._ahigh),
-                                                      float(self.reward_gamma), float(self.reward_gae_lambda), float(self.cost_gamma),
-                                                      float(self.cost_gae_lambda), job["flags"], _lib.current_stream()),
-                   "icrl_rollout_collect")
+        if self._mon is not None:      # the same entry point with the raw-reward plane (episode statistics)
+            _lib.check(_lib.lib().icrl_rollout_collect_ex_mon(b(job["env"]), b(job["nm"]), b(job["pol"]), b(cn) if cn is not None else None, b(job["buf"]),
+                                                              b(job["ag"]), p(job["noise"]), p(self._alow), p(self._ahigh), float(self.reward_gamma),
+                                                              float(self.reward_gae_lambda), float(self.cost_gamma), float(self.cost_gae_lambda),
+                                                              job["flags"], b(self._mon["struct"]), _lib.current_stream()), "icrl_rollout_collect")
+        else:
+            _lib.check(_lib.lib().icrl_rollout_collect_ex(b(job["env"]), b(job["nm"]), b(job["pol"]), b(cn) if cn is not None else None, b(job["buf"]), b(job["ag"]),
+                                                          p(job["noise"]), p(self._alow), p(self._ahigh),
+                                                          float(self.reward_gamma), float(self.reward_gae_lambda), float(self.cost_gamma),
+                                                          float(self.cost_gae_lambda), job["flags"], _lib.current_stream()),
+                       "icrl_rollout_collect")
         if rev is not None:
             rev[1].record()
             self.rollout_events.append(rev)
@@ -227,6 +295,7 @@ class PPOLagrangian:
             e1.record()
             self.gae_events.append((e0, e1))
         self._keepalive = (job["noise"],)
+        self._monitor_scan(rollout_buffer, n_rollout_steps)      # (outside every pair of timing events)
         rollout_buffer.pos, rollout_buffer.full = n_rollout_steps, True
         self.num_timesteps += env.num_envs * n_rollout_steps
         # wrapper-visible "last step" state, as the reference leaves it
@@ -296,7 +365,13 @@ class PPOLagrangian:
         cs = torch.cuda.current_stream()
         act = st["act"].numpy()
 
+        mon = b(self._mon["struct"]) if self._mon is not None else None
+
         def launch(k):
+            if mon is not None:
+                _lib.check(lib.icrl_host_step_mon(b(nm), b(pol), b(cn) if cn is not None else None, b(buf), b(ag), b(hs), p(noise), p(self._alow),
+                                                  p(self._ahigh), k, mon, stream), "icrl_host_step")
+                return
             _lib.check(lib.icrl_host_step(b(nm), b(pol), b(cn) if cn is not None else None, b(buf), b(ag), b(hs), p(noise), p(self._alow),
                                           p(self._ahigh), k, stream), "icrl_host_step")
 
@@ -317,9 +392,14 @@ class PPOLagrangian:
                 # updates its own copies, one step behind the envs)
                 self._host_stats_to_normaliser(k, nenv, cw is not None, N, O)
                 self._host_wrapper_state(nenv, cw, henv)
+                if self._mon is not None:      # step k - 1 was made, but its records never reach the window (see _monitor_unrecorded_step)
+                    if k >= 2:
+                        self._monitor_scan(rollout_buffer, k - 1, last_dones=rollout_buffer.dones[k - 1].to(torch.uint8).contiguous())
+                    self._monitor_unrecorded_step(k - 1, self._ag["last_dones"])
                 return False
         rollout_buffer.compute_returns_and_advantage(self._ag["last_v_r"], self._ag["last_v_c"], self._ag["last_dones"])
         self._keepalive = (noise,)
+        self._monitor_scan(rollout_buffer, T)
         rollout_buffer.pos, rollout_buffer.full = T, True
         self._host_wrapper_state(nenv, cw, henv)
         if callback is not None:
@@ -375,10 +455,17 @@ class PPOLagrangian:
                 costs = np.asarray(cost_function(orig_obs.cpu().numpy().copy(), clipped.cpu().numpy()), dtype=np.float32)
                 orig_costs = costs
             self.num_timesteps += env.num_envs
+            if self._mon is not None:      # the raw reward of the step (what Monitor, innermost in the reference's chain, sees) -> plane row t
+                raw = env.get_original_reward() if isinstance(env, VecNormalize) else rewards
+                self._mon["raw_rewards"][t].copy_(torch.as_tensor(raw, device=self.device).to(torch.float64).flatten())
             if callback is not None and hasattr(callback, "on_step"):
                 if hasattr(callback, "update_locals"):
                     callback.update_locals(locals())
                 if callback.on_step() is False:
+                    if self._mon is not None:      # steps 0 .. t - 1 are in the buffer; step t was made but is not recorded
+                        if t >= 1:
+                            self._monitor_scan(rollout_buffer, t, last_dones=torch.as_tensor(self._last_dones, device=self.device).to(torch.uint8).contiguous())
+                        self._monitor_unrecorded_step(t, dones)
                     return False
             rollout_buffer.add(self._last_obs, self._last_original_obs, new_obs, orig_obs, actions, rewards, costs, orig_costs,
                                self._last_dones, v_r, v_c, log_probs)
@@ -386,6 +473,7 @@ class PPOLagrangian:
         self._ag["last_dones"].copy_(torch.as_tensor(dones, device=self.device).to(torch.uint8))
         self._last_dones = self._ag["last_dones"]
         rollout_buffer.compute_returns_and_advantage(v_r, v_c, dones)
+        self._monitor_scan(rollout_buffer, n_rollout_steps)
         if callback is not None:
             callback.on_rollout_end()
         return True
@@ -398,7 +486,11 @@ class PPOLagrangian:
         else:
             total_timesteps += self.num_timesteps
         self._total_timesteps = total_timesteps
+        if self._mon is not None and reset_num_timesteps:      # ep_info_buffer is re-created (base_class.py:328-332)
+            self._mon["win_state"].zero_()
         if reset_num_timesteps or self._last_obs is None:
+            if self._mon is not None:                          # env.reset(): every Monitor starts a new episode
+                self._mon["ep_ret"].zero_(); self._mon["ep_len"].zero_()
             self._last_obs = self.env.reset().contiguous()
             self._ag["last_dones"].zero_()
             self._last_dones = self._ag["last_dones"]
@@ -406,7 +498,14 @@ class PPOLagrangian:
         return total_timesteps
 
     def _training_infos(self, itr):
-        """ref: on_policy_algorithm.py:452-457 (Monitor's `rollout/ep_*` episode statistics are not kept: the envs are device-resident)."""
+        """ref: on_policy_algorithm.py:452-471.  Monitor's `rollout/ep_rew_mean` / `rollout/ep_len_mean` are recorded when episode_stats is
+        on and at least one training episode has ended since the window was cleared (the reference's `len(ep_info_buffer) > 0` guard):
+        one read of the device-side ring, then safe_mean over the rounded records on the host."""
+        if self._mon is not None:
+            rs, ls = self.episode_window()
+            if rs:
+                logger.record("rollout/ep_rew_mean", np.mean(rs))
+                logger.record("rollout/ep_len_mean", np.mean(ls))
         elapsed = max(time.time() - self.start_time, 1e-9)
         logger.record("time/iterations", itr)
         logger.record("time/fps", int(self.num_timesteps / elapsed))
@@ -426,10 +525,19 @@ class PPOLagrangian:
                 break
             iteration += 1
             self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(total_timesteps)
+            job = None
             if log_interval is not None and iteration % log_interval == 0:
+                # with episode statistics the log line reads the ring back, which waits for the rollout: the host-side part of train() (the
+                # permutation draws) goes first, so that it still runs beside the rollout on the device as it does without the statistics
+                if self._mon is not None and not self._train_is_epochwise():
+                    job = self._train_begin()
                 self._training_infos(iteration)
                 logger.dump(step=self.num_timesteps)
-            self.train()
+            if job is not None:
+                self._train_launch(job)
+                self._train_end(job)
+            else:
+                self.train()
         self._training_infos(iteration + 1)       # (the reference's closing call: what icrl() scrapes holds iterations + 1, on_policy_algorithm.py:488)
         if callback is not None:
             callback.on_training_end()
@@ -599,11 +707,14 @@ class PPOLagrangian:
     # epochs up front — see _train_epochwise.  Below it the draws hide under the asynchronous rollout launch anyway.
     LAZY_PERM_ROWS = 262144
 
+    def _train_is_epochwise(self):
+        rb = self.rollout_buffer
+        return (self.streams is None and not callable(self.permutation) and self.permutation != "device" and self.n_epochs > 1
+                and rb.buffer_size * rb.n_envs >= self.LAZY_PERM_ROWS)
+
     def train(self, perms=None):
         """ref: ppo_lag.py:177-338."""
-        rb = self.rollout_buffer
-        if (perms is None and self.streams is None and not callable(self.permutation) and self.permutation != "device" and self.n_epochs > 1
-                and rb.buffer_size * rb.n_envs >= self.LAZY_PERM_ROWS):
+        if perms is None and self._train_is_epochwise():
             return self._train_epochwise()
         job = self._train_begin(perms)
         self._train_launch(job)

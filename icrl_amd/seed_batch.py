@@ -30,7 +30,7 @@ import torch
 
 from . import _lib, logger, utils
 from .streams import PrivateStreams
-from .structs import CnTrainJobT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
+from .structs import CnTrainJobT, MonitorT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
 from .true_constraint_net import mean_cost
 from .vec_env import ENV_IDS, HostVecEnv, sync_envs_normalization
 
@@ -128,8 +128,16 @@ class SeedBatch:
         arr = _jobs(RolloutJobT, [(addr(j["env"]), addr(j["nm"]), addr(j["pol"]), addr(j["cn"]), addr(j["buf"]), addr(j["ag"]), p(j["noise"])) for j in jobs])
         L = _lib.lib()
         ws, nbytes = self._ws()
-        err = L.icrl_rollout_collect_batch(len(jobs), arr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
-                                           float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, ws, nbytes, _lib.current_stream())
+        mons = [a._mon for a in agents]
+        if any(m is not None for m in mons):      # episode statistics: one icrl_monitor_t per run (all runs or none: the kernels are one grid)
+            if any(m is None for m in mons):
+                raise ValueError("seed batch: episode_stats must be on in every run of a batch or in none")
+            marr = (MonitorT * len(mons))(*[m["struct"] for m in mons])
+            err = L.icrl_rollout_collect_batch_mon(len(jobs), arr, marr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
+                                                   float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, ws, nbytes, _lib.current_stream())
+        else:
+            err = L.icrl_rollout_collect_batch(len(jobs), arr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
+                                               float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, ws, nbytes, _lib.current_stream())
         if err == 1 and b"batched form" in L.icrl_last_error():       # shapes without a batched persistent kernel: one launch per run
             L.icrl_clear_error()
             for a, j in zip(agents, jobs):

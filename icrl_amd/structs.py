@@ -48,6 +48,12 @@ class HostStepT(C.Structure):
     _fields_ = [("T", i32), ("_pad", i32), ("stage", vp), ("s", vp), ("act_host", vp), ("ws", vp), ("ws_bytes", C.c_longlong)]
 
 
+class MonitorT(C.Structure):
+    """icrl_monitor_t: the raw-reward plane of a rollout, the per-env episode carries and the ring of the last 100 finished episodes."""
+    _fields_ = [("raw_rewards", vp), ("ep_ret", vp), ("ep_len", vp), ("win_ret", vp), ("win_len", vp), ("win_state", vp), ("ws", vp),
+                ("ws_bytes", C.c_longlong)]
+
+
 class HostEpisodeT(C.Structure):
     """icrl_host_episode_t: the transfer buffers and outputs of the episode loop over one host env (icrl_host_episode_step)."""
     _fields_ = [("num_envs", i32), ("obs_dim", i32), ("rows", i32), ("deterministic", i32), ("stage", vp), ("act_host", vp),

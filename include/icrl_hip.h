@@ -296,6 +296,49 @@ int icrl_host_step(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_c
                    const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
                    const float* action_high, int k, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training-episode statistics: the reference's Monitor wrapper + ep_info_buffer (rollout/ep_rew_mean, rollout/ep_len_mean)
+ * ------------------------------------------------------------------------------------------------------------------
+ * stable_baselines3/common/monitor.py:91-122 (Monitor.step around every single env), common/base_class.py:328-332, 368-389
+ * (ep_info_buffer = deque(maxlen=100), _update_info_buffer once per env step over the envs in index order).
+ * Optional and additive: the `_mon` forms of the rollout entry points take this descriptor and store the raw (un-normalised) env
+ * reward of every step — the double they store into icrl_agent_t.raw_rew — into raw_rewards[t * N + n] as well; with a NULL
+ * descriptor they ARE the entry points without the suffix (which forward with NULL).  icrl_monitor_scan, called once after a rollout on
+ * the rollout's stream, turns the plane into episode records:
+ *   - per env, ep_ret is the sequential float64 sum in step order of the raw rewards since the episode began (from +0.0), ep_len the
+ *     step count; both carry over from one rollout to the next (the caller zeroes them where it resets the envs);
+ *   - the done flag of step t is dones_plane[(t + 1) * N + n] for t < rows - 1 (the buffer stores the flag ENTERING a step) and
+ *     last_dones[n] for t = rows - 1; a time-limit end counts;
+ *   - when step t of env n is done, (ep_ret, ep_len) is appended and both restart from zero.  Append order: step-major, env index
+ *     ascending within a step.  Record number i (counted from 0 since the caller last zeroed win_state[0]) lies in slot i % 100;
+ *     win_state[0] counts all records: min(win_state[0], 100) slots are valid, the oldest is slot win_state[0] % 100 once the ring is full;
+ *   - rows < T: a rollout a callback ended after `rows` steps.
+ * Returns are stored UNROUNDED (the reference rounds to 6 decimals in Python; so does the host).  Two plain launches, no waiting
+ * between workgroups, no host synchronisation. */
+typedef struct {
+  double* raw_rewards;        /* [T, N] float64, time-major */
+  double* ep_ret;             /* [N] raw return of the episode in progress */
+  int32_t* ep_len;            /* [N] its length so far */
+  double* win_ret;            /* [100] ring of finished episodes: raw return */
+  int32_t* win_len;           /* [100] length */
+  int32_t* win_state;         /* [2] records appended since the last clear | reserved */
+  int32_t* ws;                /* icrl_monitor_ws_bytes(T, N) bytes of device scratch, any contents (only icrl_monitor_scan reads it) */
+  long long ws_bytes;
+} icrl_monitor_t;
+
+size_t icrl_monitor_ws_bytes(int T, int N);
+int icrl_monitor_scan(const icrl_monitor_t* m, const float* dones_plane, const uint8_t* last_dones, int T, int N, int rows, void* stream);
+
+/* icrl_rollout_collect_ex / icrl_host_step with the raw-reward plane of `mon` (NULL: exactly the entry point without the suffix) */
+int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn,
+                                const icrl_buffer_t* buf, const icrl_agent_t* ag, const float* noise,
+                                const float* action_low, const float* action_high,
+                                double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
+                                int do_gae, const icrl_monitor_t* mon, void* stream);
+int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn, const icrl_buffer_t* buf,
+                       const icrl_agent_t* ag, const icrl_host_step_t* hs, const float* noise, const float* action_low,
+                       const float* action_high, int k, const icrl_monitor_t* mon, void* stream);
+
 /* Sampling / evaluation episodes over ONE HOST env (utils.HostEpisodeRun): one launch per env step, `rows` + 1 launches at most
  * (k = 0 .. rows), one workgroup of 256 threads, a plain launch.  Launch k is one pass of icrl_sample_episodes' loop around the env
  * step, the raw observation coming from the staging block the host copied in before the launch (raw obs f64 [O] first): the reset
@@ -450,6 +493,11 @@ typedef struct {
 int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* jobs, const float* action_low, const float* action_high,
                                double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
                                int do_gae, void* args_ws, long long args_ws_bytes, void* stream);
+
+/* the same with one icrl_monitor_t per run (`mons`: n_runs descriptors in host memory, or NULL = icrl_rollout_collect_batch) */
+int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
+                                   const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
+                                   double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream);
 
 /* icrl_gae_dual_ws for n_runs [T,N] rollouts of one shape: ONE launch of the two-level scan, grid (tiles * C, n_runs), every run
  * with its own workspace; shapes the split scan does not serve are issued as n_runs single launches. */
