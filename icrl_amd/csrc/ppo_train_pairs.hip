@@ -27,59 +27,6 @@
 // Built with -ffp-contract=off; FMA is used only where written (fmaf / MFMA).
 #include "ppo_common.h"
 
-// A/B switches (tools/build_variant.sh): the defaults are what ships
-#ifndef ICRL_EARLY_POLL
-#define ICRL_EARLY_POLL 0
-#endif
-#ifndef ICRL_STATIC_LDS
-#define ICRL_STATIC_LDS 1
-#endif
-#ifndef ICRL_BOOK_WAVE
-#define ICRL_BOOK_WAVE 7
-#endif
-#ifndef ICRL_W1_TAIL
-#define ICRL_W1_TAIL 0
-#endif
-// weight-gradient GEMMs: ALL operand tiles of a GEMM fetched before its first MFMA (a scheduling barrier; left alone the compiler fetches
-// one K step at a time and waits for the LDS in front of every group of four dependent MFMAs).  Measured: 8.53 vs 8.53 us — the other
-// wave of the SIMD already covers those waits; off.
-#ifndef ICRL_OPERANDS_FIRST
-#define ICRL_OPERANDS_FIRST 0
-#endif
-#if ICRL_OPERANDS_FIRST
-#define OPERANDS_FIRST() __builtin_amdgcn_sched_barrier(0)
-#else
-#define OPERANDS_FIRST()
-#endif
-#ifndef ICRL_EARLY_COMMIT
-#define ICRL_EARLY_COMMIT 0
-#endif
-#ifndef ICRL_LOW_GATHER
-#define ICRL_LOW_GATHER 0
-#endif
-#ifndef ICRL_HIGH_PRIO
-#define ICRL_HIGH_PRIO 0
-#endif
-#ifndef ICRL_LOW_PRIO
-#define ICRL_LOW_PRIO 0
-#endif
-#ifndef ICRL_W1_TAIL_MOVE_HEAD
-#define ICRL_W1_TAIL_MOVE_HEAD 0
-#endif
-#ifndef ICRL_L1_TAILQ
-#define ICRL_L1_TAILQ 1
-#endif
-// head outputs along the lane groups (see `out_of`): the dH2 GEMM then needs ceil(n_out / 4) of its 4 MFMAs per tile
-#ifndef ICRL_HEAD_PERM
-#define ICRL_HEAD_PERM 1
-#endif
-#ifndef ICRL_STATS_WAVE0
-#define ICRL_STATS_WAVE0 1
-#endif
-#ifndef ICRL_L1_AHEAD
-#define ICRL_L1_AHEAD 0
-#endif
-
 // Timing diagnostics (tools/diag_train.sh; WRONG RESULTS, never the shipped build): -DICRL_DIAG=<bits> removes one component of the
 // step so that its marginal cost on the critical path can be read off the step time:
 //   1 barrier S5 | 2 barrier S6 | 4 barrier S7 | 8 pair hand-offs | 16 tanh | 32 Adam arithmetic | 64 loss tail | 128 row prefetch + staging
@@ -165,45 +112,23 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   using S = SmemP<NT1>;
   constexpr int SX = S::SX;
   constexpr int NW1 = NT1 / 2;          // observation column tiles of dW1 per wave
-  constexpr bool EARLY_COMMIT = ICRL_EARLY_COMMIT && S::XDB;      // needs the second X^T buffer
   constexpr int XR = (S::O16 + 7) / 8; (void)XR;  // floats of an X row each of the 8 threads of a row stages
   static_assert(NT1 % 2 == 0, "the two waves of a pair split the observation tiles");
   static_assert(!S::DZ1A, "wide observations (dz1^T sharing h2^T's storage) stay on the row-owning kernel");
-#if ICRL_STATIC_LDS
   // a STATIC array: its address is the compile-time constant 0, so every image offset folds into an instruction's immediate or one
   // literal move.  With `extern __shared__` the base is a symbol the optimiser cannot fold: it hoisted ~40 "base + offset" sums out of
   // the step loop into scalar registers, spilled them to VGPR lanes and read them back (107 v_readlane + s_nop + v_mov per step)
   __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
-#else
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-#endif
   const int role = role_arg;  // 0 policy, 1 reward critic, 2 cost critic
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Which two waves form a pair, and how they hand data to each other, is a speed choice only (nothing depends on the
-  // placement).  Measured on MI355X, HC shapes, us per optimiser step (the row-owning kernel: 10.5):
-  //   partners w, w + 4 (a workgroup's waves go to the SIMDs round-robin: the partners SHARE a SIMD), LDS flags   9.6
-  //   partners w, w + 4, workgroup barriers instead of flags                                                       9.9
-  //   partners w, w ^ 1 (different SIMDs), workgroup barriers 10.6; flags 10.4
-#ifndef ICRL_OWN_LDS
-#define ICRL_OWN_LDS 1
-#endif
-#ifndef ICRL_PAIR_ADJ
-#define ICRL_PAIR_ADJ 0
-#endif
-#ifndef ICRL_PAIR_FLAGS
-#define ICRL_PAIR_FLAGS 1
-#endif
-#if ICRL_PAIR_ADJ
-  const int rt = w >> 1, fh = w & 1;       // row tile, feature half (= jt, kh in the weight-gradient phase)
-
-  const int partner = w ^ 1;
-#else
+  // Which two waves form a pair, and how they hand data to each other, is a speed choice only (nothing depends on the placement):
+  // partners w, w + 4 (a workgroup's waves go to the SIMDs round-robin: the partners SHARE a SIMD) and LDS flags measured fastest
+  // (workgroup barriers, or partners w, w ^ 1 on different SIMDs: DESIGN 5, PAIR_ADJ / PAIR_FLAGS)
   const int rt = w & 3, fh = w >> 2;
 
   const int partner = w ^ 4;
-#endif
   const int r = lane & 15, q = lane >> 4;
   const int O = a.L.O, A = a.L.A;
   const int n_out = role == 0 ? A : 1;
@@ -214,8 +139,8 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   // 2 of 4; a critic: 1 of 4).  Every head image (WH, WHT, BH, LS, GAU, ACT, DOT, PLS) is indexed by position; only the places
   // that meet a real output index (parameter load / write-back, masks against n_out, the staged action columns) go through
   // out_of / pos_of.
-  auto out_of = [&](int i) { return ICRL_HEAD_PERM ? 4 * i + q : 4 * q + i; };      // output of this lane's C-layout element i
-  auto pos_of = [](int o) { return ICRL_HEAD_PERM ? 4 * (o & 3) + (o >> 2) : o; };   // position of output o (and back)
+  auto out_of = [&](int i) { return 4 * i + q; };                         // output of this lane's C-layout element i
+  auto pos_of = [](int o) { return 4 * (o & 3) + (o >> 2); };   // position of output o (and back)
   const int ro = pos_of(r);                                                          // the output at position r
   const int T = a.buf.T, N = a.buf.N;
   const float nu = as_global(a.nu)[0];
@@ -239,23 +164,11 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   const int jb = 16 * rt + r;
   float mb1 = 0.f, vb1 = 0.f, mb2 = 0.f, vb2 = 0.f, mex = 0.f, vex = 0.f, gb1r = 0.f, gb2r = 0.f, gex = 0.f;
   int ex_g = -1, ex_s = S::MISC + 63;
-  const bool low = fh == 0;     // wave-uniform: owns b1 / b2 (and, without TAILW, the head column block and the extra entries)
-  // TAILW (obs 17 / 18: the second observation tile holds one or two real columns) — MEASURED AND REJECTED, off by default.  That tile is a full
-  // 16 x 16 x 64 GEMM of the high waves (16 MFMAs for <= 2 useful columns) and a full Adam block.  With TAILW the tail columns are per-row
-  // vectors like the biases: d W1[j][16 + c] = sum_rows dz1^T[j][row] x^T[16 + c][row] as 16 FMAs per lane and column + the quad-row sum,
-  // owned (q-replicated, lane q == 0 stores) by the high wave of row block rt: 16 MFMAs less on the SIMD's pipe per step.  8.48 us per
-  // step against 8.42 — the ~45 VALU / LDS instructions cost the late (high) wave more than the 16 MFMAs did.  ICRL_W1_TAIL_MOVE_HEAD
-  // additionally moves the head (dWh GEMM, its Adam block, head bias, log_std) to the high waves so that both waves of a pair carry 48
-  // weight-gradient MFMAs and 4 Adam blocks (64 / 48 and 5 / 3 otherwise): 8.84 us — the high wave of a pair loses the issue arbitration
-  // to the older low wave, so the uneven split IS the balanced one (per-wave timers: the high waves then reach the norm barrier 1.8 k
-  // cycles after the low waves instead of 1 k before them).
-  constexpr bool TAILW = ICRL_W1_TAIL && OBS > 0 && NT1 == 2 && OBS / 16 == 1 && (OBS % 16 == 1 || OBS % 16 == 2);
-  constexpr int NTAIL = TAILW ? OBS % 16 : 0;
-  const bool own_wh = (TAILW && ICRL_W1_TAIL_MOVE_HEAD) ? !low : low;          // head column block, head bias / log_std
-  auto wave_of = [](int rt_, int fh_) { return ICRL_PAIR_ADJ ? 2 * rt_ + fh_ : rt_ + 4 * fh_; };
-  const int W_BH = wave_of(0, (TAILW && ICRL_W1_TAIL_MOVE_HEAD) ? 1 : 0), W_LS = wave_of(1, (TAILW && ICRL_W1_TAIL_MOVE_HEAD) ? 1 : 0);       // the waves that own the head bias / log_std
-  float mt[2] = {0.f, 0.f}, vt[2] = {0.f, 0.f}, gt[2] = {0.f, 0.f};                     // tail columns' moments / gradients (high waves)
-  const bool own_w1_tile = !(TAILW && !low);       // this wave owns an observation tile of W1 (TAILW: the low waves' tile 0 only)
+  const bool low = fh == 0;     // wave-uniform: owns b1 / b2, the head column block and the extra entries (head bias / log_std)
+  // (the uneven split — 64 / 48 weight-gradient MFMAs and 5 / 3 Adam blocks on the low / high wave — IS the balanced one: the high wave of a
+  // pair loses the issue arbitration to the older low wave.  Moving the head to the high waves, or obs 17 / 18's one or two tail columns of
+  // W1 out of the MFMAs, measured slower: DESIGN 5, W1_TAIL / W1_TAIL_MOVE_HEAD)
+  constexpr int W_BH = 0, W_LS = 1;       // the waves that own the head bias / log_std
   auto w1_addr = [&](int cc, int i) { return S::W1 + (16 * rt + 4 * q + i) * SX + 16 * (NW1 * fh + cc) + r; };
   auto w2_addr = [&](int cc, int i) { return S::W2 + (16 * rt + 4 * q + i) * SH + 16 * (2 * fh + cc) + r; };
   auto store_w1 = [&](int cc, const f32x4& v) {
@@ -305,20 +218,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int j = 16 * rt + 4 * q + i, k = 16 * (NW1 * fh + cc) + r;
-        const bool mine = own_w1_tile && k < O;
+        const bool mine = k < O;
         pv[i] = mine ? a.params[gW1 + j * O + k] : 0.f;
         mW1[cc][i] = mine ? a.exp_avg[gW1 + j * O + k] : 0.f;
         vW1[cc][i] = mine ? a.exp_avg_sq[gW1 + j * O + k] : 0.f;
       }
-      if (own_w1_tile) store_w1(cc, pv);
-    }
-    if (TAILW && !low) {
-#pragma unroll
-      for (int c = 0; c < NTAIL; ++c) {
-        const int e = gW1 + jb * O + 16 + c;
-        mt[c] = a.exp_avg[e]; vt[c] = a.exp_avg_sq[e];
-        if (q == 0) sm[S::W1 + jb * SX + 16 + c] = a.params[e];
-      }
+      store_w1(cc, pv);
     }
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
@@ -333,7 +238,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       store_w2(cc, pv);
     }
     mWh = vWh = gWhr = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (own_wh) {
+    if (low) {
       f32x4 pv;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -369,18 +274,13 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   // row stream (see ppo_train_rows.hip): `perms` holds storage offsets; rows of chunk g + 1 are prefetched into registers
   // while chunk g is processed.  The 16 rows of tile rt are staged by the 128 threads of the wave pair (rt, *): 8 per row.
   // ---------------------------------------------------------------------------------------------------------------
-  // ICRL_LOW_GATHER (measured and rejected: 8.60 us per step against 8.49; off): the LOW wave of a pair fetches and stages all 16 rows of
-  // the tile (4 threads per row) and the high wave none — in the forward the high wave is the late one of the pair (the low wave waits
-  // ~1 k cycles for it behind the head partials) and the issue of the row fetches sits on its path; but the low wave then carries all of
-  // the staging at the end of the step, where IT is the late one
-  constexpr bool LOWG = ICRL_LOW_GATHER;
-  constexpr int GP = LOWG ? 4 : 8;       // threads per row
-  const int gb_row = 16 * rt + (lane >> 2), gpart = LOWG ? (lane & 3) : (lane & 3) + 4 * fh;
-  const bool gather = !LOWG || fh == 0;  // wave-uniform
+  // (the LOW wave of a pair staging all 16 rows of the tile, the high wave none, measured slower: DESIGN 5, LOW_GATHER)
+  constexpr int GP = 8;                  // threads per row
+  const int gb_row = 16 * rt + (lane >> 2), gpart = (lane & 3) + 4 * fh;
   // advantage statistics: row stid of the minibatch lives in waves SW0 .. SW0 + 3 (<= 256 rows).  SW0 = 1 (low waves 1, 2 at <= 128 rows):
   // measured 8.40 us per step against 8.45 with the statistics on the high waves 4, 5 — the younger wave of a pair already trails its
   // partner through every phase; extra work belongs on the leading one (wave 0 polls the granules, so the rows start at wave 1).
-  constexpr int SW0 = ICRL_STATS_WAVE0;
+  constexpr int SW0 = 1;
   const int stid = tid - 64 * SW0;
   auto ld_step = [&](int i) -> int4 {
     asm volatile("" : "+v"(i));
@@ -418,7 +318,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   const float* const p_sc = gpart == 0 ? p_s0 : (gpart == 1 ? p_s1 : p_s2);
   const int sc_dst = gpart == 0 ? S::OLP + gb_row : (gpart == 1 ? S::ADR + gb_row : (gpart == 2 ? S::ADC + gb_row : S::MISC + 62));
   auto issue_rows = [&](int idx) {
-    if ((ICRL_DIAG & 128) || !gather) return;
+    if (ICRL_DIAG & 128) return;
     const unsigned off = idx >= 0 ? (unsigned)idx : 0u;
     const unsigned ob = off * (unsigned)O;
 #pragma unroll
@@ -430,7 +330,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
     psc = p_sc[off];
   };
   auto commit_rows = [&](int xbase) {
-    if ((ICRL_DIAG & 128) || !gather) return;
+    if (ICRL_DIAG & 128) return;
 #pragma unroll
     for (int i = 0; i < XRL; ++i) { const int k = gpart + GP * i; if (OBS > 0 ? k < OBS : k < S::O16) sm[xbase + k * ST + gb_row] = px[i]; }
     if (role == 0) {
@@ -492,7 +392,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
 #if ICRL_DIAG & 8
   auto pair_signal = [&]() { (void)pflag; (void)pphase; (void)partner; };
   auto pair_wait = [&]() {};
-#elif ICRL_PAIR_FLAGS
+#else
   auto pair_signal = [&]() {
     ++pphase;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -502,14 +402,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
     while (__hip_atomic_load(pflag + partner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < pphase) __builtin_amdgcn_s_sleep(0);
     asm volatile("" ::: "memory");
   };
-#else
-  auto pair_signal = [&]() { (void)pflag; (void)pphase; (void)partner; lds_barrier(); };
-  auto pair_wait = [&]() {};
 #endif
-  // lane 0 of wave ICRL_BOOK_WAVE keeps the running statistics of the role.  A HIGH wave (fh == 1): those have no head-weight
+  // lane 0 of wave BOOK_WAVE keeps the running statistics of the role.  A HIGH wave (fh == 1): those have no head-weight
   // gradient to form and reach the norm barrier ~1 k cycles before the low waves, which is about what the book-keeping costs
   // (per-wave timers: on wave 3 it made that wave the last one at the barrier by ~750 cycles)
-  const bool book = !(ICRL_DIAG & 1024) && tid == 64 * ICRL_BOOK_WAVE;
+  constexpr int BOOK_WAVE = 7;
+  const bool book = !(ICRL_DIAG & 1024) && tid == 64 * BOOK_WAVE;
   // Its running sums live in LDS (MISC + 56..61) and are advanced with ds_add_f32, which needs no answer: as loop-carried registers of
   // one lane they were spilled to scratch at the 256-register limit (two scratch reloads + three stores per optimiser step on the
   // book-keeping wave; in-loop scratch instructions 12 -> 3; measured 8.91-8.93 against 8.94-8.95 us per step on the same box).  One
@@ -548,7 +446,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   // components along q (k = 16 js + q): same products in the same order (the others are zeros), one MFMA and one operand fetch less
   // per component and tile.
   constexpr int JT = OBS / 16;
-  constexpr bool TAILQ = ICRL_L1_TAILQ && OBS > 0 && OBS % 16 >= 1 && OBS % 16 <= 4 && JT < NT1;
+  constexpr bool TAILQ = OBS > 0 && OBS % 16 >= 1 && OBS % 16 <= 4 && JT < NT1;
   auto l1_forward = [&](int xbase) {
     float bx[NT1][4];                   // x[row b][k = 16 js + 4 q + e]
     const float* pb = sm + xbase + (4 * q) * ST + b;
@@ -584,16 +482,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
 #pragma unroll
       for (int i = 0; i < 4; ++i) pt[S::H1T + (16 * (2 * fh + tt) + i) * ST] = h1c[tt][i];
   };
-#if ICRL_L1_AHEAD
-  l1_forward(xcur);       // layer 1 of the first minibatch; from here on every step ends with layer 1 of the next one
-  lds_barrier();
-#endif
 
-#if ICRL_HIGH_PRIO
-  if (fh == 1) __builtin_amdgcn_s_setprio(ICRL_HIGH_PRIO);      // (A/B: the younger wave of a pair loses the issue arbitration to the older one)
-#elif ICRL_LOW_PRIO
-  if (fh == 0) __builtin_amdgcn_s_setprio(ICRL_LOW_PRIO);
-#endif
   constexpr bool prof = PROF;
   unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #ifdef ICRL_FINE_PROF
@@ -624,19 +513,13 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       const int nrows = (nb - ch * RB) < RB ? (nb - ch * RB) : RB;
       if (ch > 0) {
         if (S::XDB) xcur = xcur == S::XT0 ? S::XT1 : S::XT0;
-        if (!EARLY_COMMIT) {
-          commit_rows(xcur);
-          lds_barrier();                    // a row is staged by threads of both waves of its pair
-        }                                   // (EARLY_COMMIT: staged in front of the previous chunk's dz1 barrier, S5 and the chunk-end barrier passed since)
+        commit_rows(xcur);
+        lds_barrier();                    // a row is staged by threads of both waves of its pair
       }
       const bool valid = b < nrows;
       // ================= forward =================
       f32x4 h2c[2], outc;                   // own feature tiles t = 2 fh + tt
-#if ICRL_L1_AHEAD
-      if (ch > 0) l1_forward(xcur);         // (chunk 0: computed at the end of the previous step, under its Adam)
-#else
       l1_forward(xcur);
-#endif
       FSTAMP(0)   // L1
       // prefetch the next chunk's rows (random 72-byte pieces of the rollout buffer: several microseconds away)
       {
@@ -647,11 +530,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
         issue_rows(idx_now);
       }
       FSTAMP(1)   // row prefetch issue
-#if ICRL_L1_AHEAD
-      if (ch > 0) pair_signal();     // (P1) this wave's columns of h1^T are complete (chunk 0: the S7 barrier said so)
-#else
       pair_signal();                 // (P1) this wave's columns of h1^T are complete
-#endif
       FSTAMP(2)   // S1
       {
         // the own half of K (h1c, registers) needs nobody: its MFMAs run before the wait for the partner's half
@@ -670,11 +549,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
 #pragma unroll
             for (int e = 0; e < 4; ++e) z[tt] = MFMA_F32(awo[jj][e], h1c[jj][e], z[tt]);
         }
-#if ICRL_L1_AHEAD
-        if (ch > 0) pair_wait();     // the partner's columns of h1^T are complete
-#else
         pair_wait();                 // the partner's columns of h1^T are complete
-#endif
         float hpart[2][4];                  // the partner's half of h1 as B operand: features 16 js + 4 q + e, js = 2 (1 - fh) + jj
         const float* ph1 = sm + S::H1T + (4 * q) * ST + b + 32 * (1 - fh) * ST;
 #pragma unroll
@@ -725,7 +600,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       } else {
         float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f;
         if (role == 0) {
-          const int ngp = ICRL_HEAD_PERM ? (A + 3) >> 2 : 4;      // groups of four outputs that hold real ones
+          const int ngp = (A + 3) >> 2;      // groups of four outputs that hold real ones
           float lp = 0.f, ent = 0.f;
           f32x4 g1 = f32x4{0.f, 0.f, 0.f, 0.f}, g2 = f32x4{0.f, 0.f, 0.f, 0.f};
           if (DISC) {
@@ -820,7 +695,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       f32x4 dz2c[2], dz1c[2];
       {  // dH2^T = Wh^T . dOut^T for the own feature tiles: A = WHT[j = 16 t + r][position 4 q + e] (K = 16 head positions);
          // MFMA e covers the outputs 4 e .. 4 e + 3 (out_of): those with 4 e >= n_out would multiply zeros
-        const int ng = ICRL_HEAD_PERM ? (n_out + 3) >> 2 : 4;
+        const int ng = (n_out + 3) >> 2;
         f32x4 aw[2], acc[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -907,20 +782,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
         for (int i = 0; i < 4; ++i) pt[S::DZ1T + (16 * (2 * fh + tt) + i) * ST] = dz1c[tt][i];
       STAMP(2)   // activation backward
       FSTAMP(9)   // dH1 + dz1 store
-      if (EARLY_COMMIT) {
-        // ICRL_EARLY_COMMIT (measured and rejected: 8.81 us per step against 8.46; off — the dz1 barrier waits for the HIGH waves, and the
-        // staging lands on their path).  The prefetched rows (the next chunk's, or the next minibatch's first chunk) are staged HERE, in front of the dz1 barrier, instead of
-        // behind the norm publish: the other X^T buffer is free during the whole chunk, the per-row action / scalar images belong to this
-        // pair alone and its loss tail is over (the partner's dz2 hand-off has been passed).  At the end of the step the low waves are the
-        // critical ones (they carry dWh) and the staging sat on their path; here it sits where they wait for the dz1 barrier.
-        commit_rows(xcur == S::XT0 ? S::XT1 : S::XT0);
-        if (ch + 1 == n_chunks) stats_partials(__builtin_amdgcn_readfirstlane(ps_next.z) & NB_MASK);
-      }
+      // (staging the prefetched rows HERE, in front of the dz1 barrier, instead of behind the norm publish measured slower: DESIGN 5, EARLY_COMMIT)
       if (ch == 0) {   // gradient accumulators start their life here
 #pragma unroll
         for (int cc = 0; cc < NW1; ++cc) gW1r[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
         gW2r[0] = gW2r[1] = gWhr = f32x4{0.f, 0.f, 0.f, 0.f};
-        gb1r = 0.f; gb2r = 0.f; gex = 0.f; gt[0] = gt[1] = 0.f;
+        gb1r = 0.f; gb2r = 0.f; gex = 0.f;
       }
       if (!(ICRL_DIAG & 1)) lds_barrier();  // (S5) every pair's columns of h1^T, h2^T, dz1^T, dz2^T, dOut^T (and the loss partials) are complete
       FSTAMP(12)  // S5
@@ -936,7 +803,6 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
           f32x4 bh[4];
 #pragma unroll
           for (int js = 0; js < 4; ++js) bh[js] = lds128(pb + 16 * js);
-          OPERANDS_FIRST();
 #pragma unroll
           for (int js = 0; js < 4; ++js)
 #pragma unroll
@@ -950,13 +816,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
         }
       }
       FSTAMP(10)  // dW2
-      if (own_wh) {   // dWh columns 16 rt..: A = dOut^T[o = r][rows], B = h2^T[j = 16 rt + r][rows]
+      if (low) {   // dWh columns 16 rt..: A = dOut^T[o = r][rows], B = h2^T[j = 16 rt + r][rows]
         f32x4 ao[4], bh[4];
         const float* pa = sm + S::DOT + r * ST + 4 * q;
         const float* pb = sm + S::H2T + (16 * rt + r) * ST + 4 * q;
 #pragma unroll
         for (int js = 0; js < 4; ++js) { ao[js] = lds128(pa + 16 * js); bh[js] = lds128(pb + 16 * js); }
-        OPERANDS_FIRST();
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int js = 0; js < 4; ++js)
@@ -978,28 +843,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
         const float* pa = sm + S::DZ1T + (16 * rt + r) * ST + 4 * q;
 #pragma unroll
         for (int js = 0; js < 4; ++js) az[js] = lds128(pa + 16 * js);
-        if (TAILW && !low) {      // the tail columns k = 16 + c as dot products over this lane's 16 rows, summed over the lane groups
-#pragma unroll
-          for (int c = 0; c < NTAIL; ++c) {
-            const float* px_ = sm + xcur + (16 + c) * ST + 4 * q;      // x^T[16 + c][rows 16 js + 4 q + e] (the same for every r)
-            float s_ = 0.f;
-#pragma unroll
-            for (int js = 0; js < 4; ++js) {
-              const f32x4 xr = lds128(px_ + 16 * js);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) s_ = fmaf(az[js][e], xr[e], s_);
-            }
-            gt[c] += quad_rows_sum(s_);
-          }
-        }
 #pragma unroll
         for (int cc = 0; cc < NW1; ++cc) {
-          if (!own_w1_tile) break;
           const float* pb = sm + xcur + (16 * (NW1 * fh + cc) + r) * ST + 4 * q;     // x^T[k][rows 16 js + 4 q + e]
           f32x4 bx[4];
 #pragma unroll
           for (int js = 0; js < 4; ++js) bx[js] = lds128(pb + 16 * js);
-          OPERANDS_FIRST();
 #pragma unroll
           for (int js = 0; js < 4; ++js)
 #pragma unroll
@@ -1042,13 +891,12 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       for (int i = 0; i < 4; ++i) ss = fmaf(gW2r[cc][i], gW2r[cc][i], ss);
     {
       float sb = 0.f;      // per-row entries (replicated over the lane groups: counted on q == 0)
-      if (own_wh) {
+      if (low) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) ss = fmaf(gWhr[i], gWhr[i], ss);
         sb = ex_g >= 0 ? gex * gex : 0.f;
       }
       if (low) sb = fmaf(gb1r, gb1r, gb2r * gb2r) + sb;
-      if (TAILW && !low) sb = fmaf(gt[0], gt[0], gt[1] * gt[1]) + sb;
       ss += q == 0 ? sb : 0.f;
     }
     ss = wave_sum_fast(ss);
@@ -1074,10 +922,8 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       // this workgroup reads its OWN eight partials from LDS (same floats, same summation order as everybody else's view of
       // them): the role that publishes last — the policy, the critical path — does not wait for its own stores to come back
       // through the memory system (~870 cycles)
-#if ICRL_OWN_LDS
       sm[S::MISC + 24 + role * 8 + w] = ss;
       if (book && role == 0) sm[S::MISC + 12] = want_stop ? 1.f : 0.f;
-#endif
       if (book) {
         ++steps_done;
         if (role == 0) {
@@ -1101,29 +947,18 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
     // ---- while the granules travel: stage the next minibatch (rows -> the other X^T buffer, advantage statistics)
     const int xnext = S::XDB ? (xcur == S::XT0 ? S::XT1 : S::XT0) : xcur;
     const int nb_next = __builtin_amdgcn_readfirstlane(ps_next.z) & NB_MASK;
-    // granule (role rr, wave ww) = slot 8 rr + ww; a workgroup polls the other two roles' sixteen.  The FIRST look is issued before
-    // the staging and read behind it: the policy workgroup publishes last, so the critics' granules are in memory by now and the
-    // look's trip through the memory system (~0.9 k cycles) runs under the staging instead of behind it.
-    const bool poller = tid < 24 && (!ICRL_OWN_LDS || (tid >> 3) != role);
+    // granule (role rr, wave ww) = slot 8 rr + ww; a workgroup polls the other two roles' sixteen, behind the staging
+    // (a first look issued in front of the staging and read behind it measured no faster: DESIGN 5, EARLY_POLL)
+    const bool poller = tid < 24 && (tid >> 3) != role;
     const u64* const slot = xch + (step & 1) * 32 + (tid < 24 ? tid : 0);
-#if ICRL_EARLY_POLL
-    u64 v_first = 0;
-    if (poller) v_first = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-    if (!EARLY_COMMIT) {
-      commit_rows(xnext);
-      stats_partials(nb_next);
-    }
+    commit_rows(xnext);
+    stats_partials(nb_next);
     xcur = xnext;
     FSTAMP(15)  // staging
     if (poller) {
       u64 v = 0;
       int spins = 0;
       bool ok = false;
-#if ICRL_EARLY_POLL
-      v = v_first;
-      ok = (unsigned)((v >> 32) & 0x7fffffffu) == step;
-#endif
       if (ICRL_DIAG & 256) ok = true;
       while (!ok && spins < (1 << 24)) {
         v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1132,7 +967,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
         ++spins;
       }
       sm[S::MISC + 24 + tid] = __uint_as_float((unsigned)(v & 0xffffffffu));
-      if (tid == ICRL_BOOK_WAVE) sm[S::MISC + 12] = (v >> 63) ? 1.f : 0.f;     // the granule of the policy's book-keeping wave carries the stop flag
+      if (tid == BOOK_WAVE) sm[S::MISC + 12] = (v >> 63) ? 1.f : 0.f;     // the granule of the policy's book-keeping wave carries the stop flag
       if (!ok) sm[S::MISC + 13] = 1.f;
     }
     if (!(ICRL_DIAG & 2)) lds_barrier();   // (S6) norm partials, next minibatch and its statistics visible
@@ -1172,27 +1007,9 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       };
       // pad elements (k >= obs, o >= n_out) have g = m = v = p = 0 and stay 0: no masks needed
       // Part 1: what layer 1 reads (W1, b1; the low waves' bias block carries b2 and the head bias / log_std along)
-      if (own_w1_tile) {
 #pragma unroll
-        for (int cc = 0; cc < NW1; ++cc) { f32x4 p_ = load_own_w1(cc); adam4(gW1r[cc], mW1[cc], vW1[cc], p_); store_w1(cc, p_); }
-      }
-      if (TAILW) {      // per-row entries, lane q == 0 stores — low: {b1, b2}, high: {tail column 0, tail column 1}; the head bias | log_std rides with its owner
-        const bool exo = own_wh && ex_g >= 0;
-        if (low) {
-          f32x4 g_ = f32x4{gb1r, gb2r, exo ? gex : 0.f, 0.f}, p_ = f32x4{sm[S::B1 + jb], sm[S::B2 + jb], own_wh ? sm[ex_s] : 0.f, 0.f};
-          f32x4 m_ = f32x4{mb1, mb2, mex, 0.f}, v_ = f32x4{vb1, vb2, vex, 0.f};
-          adam4(g_, m_, v_, p_);
-          mb1 = m_[0]; mb2 = m_[1]; mex = m_[2]; vb1 = v_[0]; vb2 = v_[1]; vex = v_[2];
-          if (q == 0) { sm[S::B1 + jb] = p_[0]; sm[S::B2 + jb] = p_[1]; if (own_wh) sm[ex_s] = p_[2]; }
-        } else {
-          float* const pw = sm + S::W1 + jb * SX + 16;
-          f32x4 g_ = f32x4{gt[0], gt[1], exo ? gex : 0.f, 0.f}, p_ = f32x4{pw[0], NTAIL > 1 ? pw[1] : 0.f, own_wh ? sm[ex_s] : 0.f, 0.f};
-          f32x4 m_ = f32x4{mt[0], mt[1], mex, 0.f}, v_ = f32x4{vt[0], vt[1], vex, 0.f};
-          adam4(g_, m_, v_, p_);
-          mt[0] = m_[0]; mt[1] = m_[1]; mex = m_[2]; vt[0] = v_[0]; vt[1] = v_[1]; vex = v_[2];
-          if (q == 0) { pw[0] = p_[0]; if (NTAIL > 1) pw[1] = p_[1]; if (own_wh) sm[ex_s] = p_[2]; }
-        }
-      } else if (low) {
+      for (int cc = 0; cc < NW1; ++cc) { f32x4 p_ = load_own_w1(cc); adam4(gW1r[cc], mW1[cc], vW1[cc], p_); store_w1(cc, p_); }
+      if (low) {
         f32x4 g_ = f32x4{gb1r, gb2r, ex_g >= 0 ? gex : 0.f, 0.f}, p_ = f32x4{sm[S::B1 + jb], sm[S::B2 + jb], sm[ex_s], 0.f};
         f32x4 m_ = f32x4{mb1, mb2, mex, 0.f}, v_ = f32x4{vb1, vb2, vex, 0.f};
         adam4(g_, m_, v_, p_);     // identical arithmetic in the four q lanes, lane q == 0 stores
@@ -1203,21 +1020,13 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       auto adam_rest = [&]() {
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) { f32x4 p_ = load_own_w2(cc); adam4(gW2r[cc], mW2[cc], vW2[cc], p_); store_w2(cc, p_); }
-        if (own_wh) {
+        if (low) {
           { f32x4 p_ = load_own_wh(); adam4(gWhr, mWh, vWh, p_); store_wh(p_); }
           __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the log_std store has landed before refresh_gauss re-reads it
           refresh_gauss();
         }
       };
-#if ICRL_L1_AHEAD
-      // Layer 1 of the NEXT minibatch (staged above) needs W1 and b1 only: the two waves of a SIMD run it and the rest of Adam in
-      // opposite orders, so one wave's MFMAs / LDS latencies meet the other's VALU work instead of its twin
-      lds_barrier();   // (S7a) W1, b1 visible
-      FSTAMP(19)
-      if (low) { l1_forward(xcur); adam_rest(); } else { adam_rest(); l1_forward(xcur); }
-#else
       adam_rest();
-#endif
     }
     FSTAMP(17)  // Adam
     if (!(ICRL_DIAG & 4)) lds_barrier();   // (S7) updated weights visible
@@ -1234,21 +1043,13 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
   const PolLayout& L = a.L;
   const int gW1 = L.W1[role], gb1 = L.b1[role], gW2 = L.W2[role], gb2 = L.b2[role];
   const int gWh = role == 0 ? L.Wa : (role == 1 ? L.Wv : L.Wc);
-  if (own_w1_tile) {
 #pragma unroll
-    for (int cc = 0; cc < NW1; ++cc) {
-      const f32x4 pv = load_own_w1(cc);
+  for (int cc = 0; cc < NW1; ++cc) {
+    const f32x4 pv = load_own_w1(cc);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * rt + 4 * q + i, k = 16 * (NW1 * fh + cc) + r;
-        if (k < O) { a.params[gW1 + j * O + k] = pv[i]; a.exp_avg[gW1 + j * O + k] = mW1[cc][i]; a.exp_avg_sq[gW1 + j * O + k] = vW1[cc][i]; }
-      }
-    }
-  } else if (q == 0) {
-#pragma unroll
-    for (int c = 0; c < NTAIL; ++c) {
-      const int e = gW1 + jb * O + 16 + c;
-      a.params[e] = sm[S::W1 + jb * SX + 16 + c]; a.exp_avg[e] = mt[c]; a.exp_avg_sq[e] = vt[c];
+    for (int i = 0; i < 4; ++i) {
+      const int j = 16 * rt + 4 * q + i, k = 16 * (NW1 * fh + cc) + r;
+      if (k < O) { a.params[gW1 + j * O + k] = pv[i]; a.exp_avg[gW1 + j * O + k] = mW1[cc][i]; a.exp_avg_sq[gW1 + j * O + k] = vW1[cc][i]; }
     }
   }
 #pragma unroll
@@ -1262,7 +1063,7 @@ __device__ __forceinline__ void ppo_train_pairs_body(const TrainArgs& a, const T
       a.exp_avg_sq[gW2 + j * HD + k] = vW2[cc][i];
     }
   }
-  if (own_wh) {
+  if (low) {
     const f32x4 pv = load_own_wh();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1328,7 +1129,7 @@ __global__ void __launch_bounds__(TH8) ppo_train_pairs_batch_kernel(const TrainA
 template <int NT1, bool DISC, int OBS, bool PROF>
 static int launch_pairs_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, hipStream_t s) {
   static_assert(SmemP<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
-  const size_t bytes = ICRL_STATIC_LDS ? 0 : (size_t)SmemP<NT1>::TOTAL * sizeof(float);
+  const size_t bytes = 0;      // (the LDS array is static)
   if (one != nullptr) {
     hipError_t e = hipFuncSetAttribute((const void*)ppo_train_pairs_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return (int)e;

@@ -14,7 +14,7 @@
 //   * weight gradients, norm and Adam with the row-owning kernel's ownership (wave w: rows 16 w .. of W1 / W2, columns 16 w .. of the head
 //     weights, b1 / b2 entries 16 w + r, wave 0 the head bias, wave 1 log_std; master weights in LDS, Adam moments in accumulation registers)
 //     and K = 16 rows per chunk: a quarter of the MFMAs of the two-workgroup form.
-//   * the four partial gradients travel as RAW 16-byte stores + one flag per wave (ppo_train_rows.hip, ICRL_ROWS_RAWX) and every part forms
+//   * the four partial gradients travel as RAW 16-byte stores + one flag per wave (ppo_train_rows.hip) and every part forms
 //     (own + partner) + (the other pair) — float addition is commutative bit for bit, so all four hold (q0 + q1) + (q2 + q3), run identical
 //     norm / Adam arithmetic on identical weights and stay replicas; part 0 writes the results back.
 //   * the next minibatch's first chunk is staged inside the exchange hop (ppo_train_halves.hip, STAGE_HOP).
@@ -22,23 +22,6 @@
 //
 // Built with -ffp-contract=off; FMA is used only where written (fmaf / MFMA).
 #include "ppo_common.h"
-
-// the gradient groups leave for the other parts as soon as their GEMM is done (one GEMM late, so that the store does not wait for the MFMA
-// chain that produces it) instead of all behind the last GEMM
-#ifndef ICRL_QW_EARLY_PUBLISH
-#define ICRL_QW_EARLY_PUBLISH 1
-#endif
-// groups of the three peers in flight while one is summed
-#ifndef ICRL_QW_DEP
-#define ICRL_QW_DEP 4
-#endif
-
-#ifndef ICRL_QW_QUAD_BARRIER
-#define ICRL_QW_QUAD_BARRIER 1
-#endif
-#ifndef ICRL_QW_STATIC_LDS
-#define ICRL_QW_STATIC_LDS 0
-#endif
 
 namespace icrl {
 
@@ -77,7 +60,7 @@ struct SmemQ {  // offsets in floats (multiples of 4)
   static constexpr int PST = ADC + 16;         // [8] loss statistics of the row tile
   static constexpr int PLS = PST + 8;          // [16] d log_std partial sums of the row tile
   static constexpr int MISC = PLS + 16;        // [64]: 0..8 advantage-statistics partials, 12 stop, 13 timed out, 14 one XCD, 22 entropy,
-                                               //       24..47 norm partials [role][8], 48..51 quad flags, 62 / 63 scratch words
+                                               //       24..47 norm partials [role][8], 48..51 unused, 62 / 63 scratch words
   static constexpr int TOTAL = MISC + 64;
 };
 
@@ -89,11 +72,7 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
   using S = SmemQ<NT1>;
   constexpr int SX = S::SX;
   static_assert(OBS == 0 || (OBS > 16 * (NT1 - 1) && OBS <= 16 * NT1), "OBS names the observation width of an NT1-tile instantiation");
-#if ICRL_QW_STATIC_LDS
-  __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
-#else
   extern __shared__ __attribute__((aligned(16))) float sm[];      // dynamic: with a static array the folded offsets let the optimiser hoist more addresses than the register file holds (ppo_train_rows.hip)
-#endif
   // fault injection for the tests (hp._pad & 64): the last workgroup of the run leaves at once — every wait of the others is bounded, the launch ENDS
   // with the status word set and the host raises
   if ((a.hp._pad & 64) && slot_j == 11) return;
@@ -102,7 +81,6 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // forward / activation backward: feature tile; weight gradients / Adam: parameter row block
-  const int qp0 = w ^ 1, qp1 = w ^ 2, qp2 = w ^ 3;          // the other three waves of the quad
   const int r = lane & 15, q = lane >> 4;
   const int O = OBS > 0 ? OBS : a.L.O, A = a.L.A;
   const int n_out = role == 0 ? A : 1;
@@ -305,29 +283,9 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
       if (r == 0) sm[S::MISC + 22] = ent;
     }
   };
-  // ---- synchronisation inside the quad: a phase counter per wave in LDS; the producer drains its LDS stores and raises its counter, a
-  // consumer polls the three others' counters, then reads (ppo_train_halves.hip)
-  int* const pflag = reinterpret_cast<int*>(sm + S::MISC + 48);      // [4] one word per wave
-  int pphase = 0;
-  // (ICRL_QW_QUAD_BARRIER: the quad is the whole workgroup here — a workgroup barrier does the hand-off; ppo_train_quarters2.hip: 11.68 -> 11.53 us)
-  auto quad_signal = [&]() {
-    if (ICRL_QW_QUAD_BARRIER) return;
-    ++pphase;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(pflag + w, pphase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
-  auto quad_wait = [&]() {
-    if (ICRL_QW_QUAD_BARRIER) { lds_barrier(); return; }
-    while (true) {
-      const int f0 = __hip_atomic_load(pflag + qp0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f1 = __hip_atomic_load(pflag + qp1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f2 = __hip_atomic_load(pflag + qp2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f = f0 < f1 ? (f0 < f2 ? f0 : f2) : (f1 < f2 ? f1 : f2);
-      if (f >= pphase) break;
-      __builtin_amdgcn_s_sleep(0);
-    }
-    asm volatile("" ::: "memory");
-  };
+  // ---- synchronisation inside the quad: the quad is the whole workgroup here, so a workgroup barrier does the hand-off (per-wave phase
+  // counters in LDS, polled by the consumers as in ppo_train_halves.hip's two-part form: 11.68 against 11.53 us per step in ppo_train_quarters2.hip)
+  auto quad_wait = [&]() { lds_barrier(); };
   // the running statistics live in lane 0 of wave 3 of each role
   const bool book = tid == 192;
   float st_ent = 0.f, st_pg = 0.f, st_vl = 0.f, st_cf = 0.f, last_loss = 0.f, kl_sum = 0.f;
@@ -396,8 +354,10 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
     float mb_s0 = 0.f, mb_s1 = 0.f, mb_s2 = 0.f, mb_s3 = 0.f, mb_s4 = 0.f;  // bookkeeping lane: minibatch sums of the loss statistics
     const int xrole = ((int)(step & 1) * 3 + role) * 4 * XBLK;      // the four blocks of this role and step parity
     const int xmine = xrole + part * XBLK;
+    // a gradient group leaves for the other parts as soon as its GEMM is done (one GEMM late, so that the store does not wait for the MFMA
+    // chain that produces it) instead of all behind the last GEMM
     auto publish4 = [&](bool on, int g, const f32x4& v) {
-      if (ICRL_QW_EARLY_PUBLISH && on) raw_store(xmine + (g * THQ + tid) * 16, v);
+      if (on) raw_store(xmine + (g * THQ + tid) * 16, v);
     };
 
     const int n_chunks = (nb + RB - 1) / RB;
@@ -444,7 +404,6 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
         pc_nx3 = ld_chunk(g_chunk + 4);
         issue_rows(idx_now);
       }
-      quad_signal();               // (P1) this wave's features of h1 are complete
       {  // layer 2: own quarter of K from registers, the other three from the row-major image
         const float* pa = sm + S::W2 + (16 * w + r) * SH + 4 * q;
         const f32x4 awo = lds128(pa + 16 * w);
@@ -476,7 +435,7 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
         for (int e = 0; e < 4; ++e) acc = MFMA_F32(aw[e], h2c[e], acc);
         float* const hpx = sm + S::HPX + lane * 4;
         *reinterpret_cast<f32x4*>(hpx + w * 256) = acc;
-        quad_signal(); quad_wait();  // (P3) all four partial tiles stored
+        quad_wait();               // (P3) all four partial tiles stored
         const f32x4 p0 = lds128(hpx), p1 = lds128(hpx + 256), p2 = lds128(hpx + 512), p3 = lds128(hpx + 768);
 #pragma unroll
         for (int i = 0; i < 4; ++i) outc[i] = (p0[i] + p1[i]) + (p2[i] + p3[i]);
@@ -591,7 +550,6 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
           for (int i = 0; i < 4; ++i) pt[S::DOT + i * STQ] = dout[i];
         }
       }
-      quad_signal();               // (P4) this wave's features of dz2 complete
       {  // dH1^T = W2^T . dz2^T: A = W2T[k = 16 w + r][j = 16 js + 4 q + e]; own quarter of K before the wait for the others
         const float* pa = sm + S::W2T + (16 * w + r) * SH + 4 * q;
         const f32x4 awo = lds128(pa + 16 * w);
@@ -689,7 +647,7 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
       auto grp = [&](int g) -> f32x4& { return g < NT1 ? gW1r[g] : (g < NT1 + 4 ? gW2r[g - NT1] : (g == NT1 + 4 ? gWhr : gsc)); };
 #pragma unroll
       for (int g = 0; g < NGRP; ++g) {
-        if (ICRL_QW_EARLY_PUBLISH && g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
+        if (g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
         raw_store(xmine + (g * THQ + tid) * 16, grp(g));
       }
       f32x4 bks = f32x4{mb_s1, mb_s2, mb_s3, mb_s4};
@@ -719,7 +677,7 @@ __device__ __forceinline__ void ppo_train_quarters_body(const TrainArgs& a, cons
         }
         asm volatile("" ::: "memory");
       }
-      constexpr int DEP = ICRL_QW_DEP;
+      constexpr int DEP = 4;      // groups of the three peers in flight while one is summed
       f32x4 ra[DEP], rb[DEP], rc[DEP];
 #pragma unroll
       for (int k = 0; k < DEP; ++k)
@@ -963,7 +921,7 @@ __global__ void __launch_bounds__(THQ) ppo_train_quarters_kernel(TrainArgs a, in
 template <int NT1, bool DISC, int OBS, bool PROF>
 static int launch_quarters_p(const TrainArgs& a, hipStream_t s) {
   static_assert(SmemQ<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
-  const size_t bytes = ICRL_QW_STATIC_LDS ? 0 : (size_t)SmemQ<NT1>::TOTAL * sizeof(float);
+  const size_t bytes = (size_t)SmemQ<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_quarters_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;

@@ -17,40 +17,7 @@
 // Built with -ffp-contract=off; FMA is used only where written (fmaf / MFMA).
 #include "ppo_common.h"
 
-#ifndef ICRL_QW2_EARLY_PUBLISH
-#define ICRL_QW2_EARLY_PUBLISH 1
-#endif
-#ifndef ICRL_QW2_DEP
-#define ICRL_QW2_DEP 4
-#endif
-
-// the Adam moments as plain values (the register allocator places them) instead of pinned to accumulation registers with explicit moves
-// (ppo_train_rows.hip's scheme): the step loop loses ~150 instructions net — 12.30 -> 12.07 us per step (two alternating rounds), no scratch traffic in the loop
-#ifndef ICRL_QW2_MOMENTS_PLAIN
-#define ICRL_QW2_MOMENTS_PLAIN 1
-#endif
-// the loss tail's per-row operands and dH2's A operand fetched from LDS before the head hand-off (P3) instead of behind it (ppo_train_halves.hip:
-// 6.00 -> 5.98 us there); here 12.30 vs 12.31 — nothing; off
-#ifndef ICRL_QW2_LOSS_PRELOAD
-#define ICRL_QW2_LOSS_PRELOAD 0
-#endif
-// the three hand-offs inside the wave quad as WORKGROUP BARRIERS: here the quad is the whole workgroup (ppo_train_halves.hip needs LDS flags — its waves 4..7
-// are parked at another barrier meanwhile), so `s_waitcnt lgkmcnt(0); s_barrier` replaces a flag store plus a polling loop of three LDS loads per look:
-// 11.68 -> 11.53 us per step (three alternating rounds)
-#ifndef ICRL_QW2_QUAD_BARRIER
-#define ICRL_QW2_QUAD_BARRIER 1
-#endif
-#ifndef ICRL_QW_STATIC_LDS
-#define ICRL_QW_STATIC_LDS 0
-#endif
-
 namespace icrl {
-
-#if ICRL_QW2_MOMENTS_PLAIN
-#define acc_put(slot, v) ((slot) = (v))
-#define acc_set(slot, v) ((slot) = (v))
-#define acc_get(slot) (slot)
-#endif
 
 constexpr int THQ2 = 256;  // 4 waves, one per SIMD
 constexpr int STX = 36;    // row stride of the [feature][row] images (32 rows + 4: conflict-free ds_read_b128 and column stores)
@@ -80,7 +47,7 @@ struct SmemQ2 {  // offsets in floats (multiples of 4)
   static constexpr int PST = ADC + 32;         // [2][8] loss statistics of the row tiles
   static constexpr int PLS = PST + 16;         // [2][16] d log_std partial sums of the row tiles
   static constexpr int MISC = PLS + 32;        // [64]: 0..8 advantage-statistics partials, 12 stop, 13 timed out, 14 one XCD, 22 entropy,
-                                               //       24..47 norm partials [role][8], 48..51 quad flags, 62 / 63 scratch words
+                                               //       24..47 norm partials [role][8], 48..51 unused, 62 / 63 scratch words
   static constexpr int GAU = MISC + 64;        // [3][16] per-action 1/var, 0.5/var, log(sd) + log(sqrt(2 pi))
   static constexpr int B1 = GAU + 48;
   static constexpr int B2 = B1 + HD;
@@ -102,11 +69,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
   using S = SmemQ2<NT1>;
   constexpr int SX = S::SX;
   static_assert(OBS == 0 || (OBS > 16 * (NT1 - 1) && OBS <= 16 * NT1), "OBS names the observation width of an NT1-tile instantiation");
-#if ICRL_QW_STATIC_LDS
-  __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
-#else
   extern __shared__ __attribute__((aligned(16))) float sm[];      // dynamic: with a static array the folded offsets let the optimiser hoist more addresses than the register file holds (ppo_train_rows.hip)
-#endif
   // fault injection for the tests (hp._pad & 64): the last workgroup of the run leaves at once — every wait of the others is bounded, the launch ENDS
   // with the status word set and the host raises
   if ((a.hp._pad & 64) && slot_j == 11) return;
@@ -115,7 +78,6 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // forward / activation backward: feature tile; weight gradients / Adam: parameter row block
-  const int qp0 = w ^ 1, qp1 = w ^ 2, qp2 = w ^ 3;          // the other three waves of the quad
   const int r = lane & 15, q = lane >> 4;
   const int O = OBS > 0 ? OBS : a.L.O, A = a.L.A;
   const int n_out = role == 0 ? A : 1;
@@ -136,7 +98,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
   // 16 w .. (element o = 4 q + i, j = 16 w + r), b1 / b2 entries 16 w + r (replicated over q, lane q == 0 stores); wave 0: head bias r,
   // wave 1: log_std r.  Master weights in LDS (the operand copies ARE the master values), moments in accumulation registers.
   constexpr int E_W2 = 4 * NT1, E_WH = E_W2 + 16, E_B1 = E_WH + 4, E_B2 = E_B1 + 1, E_EX = E_B2 + 1, NEL = E_EX + 1;
-  float mA[NEL], vA[NEL];                      // AGPR-resident (acc_put / acc_get)
+  float mA[NEL], vA[NEL];                      // plain values, placed by the register allocator (pinned to accumulation registers as in ppo_train_rows.hip: ~150 more instructions in the step loop, 12.30 against 12.07 us per step)
   f32x4 gW1r[NT1], gW2r[4], gWhr;
   const int jb = 16 * w + r;
   // per-pattern bases of what lies beyond the first 64 KB of the LDS: opaque to the optimiser, so that every access is base + immediate
@@ -200,8 +162,8 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       for (int i = 0; i < 4; ++i) {
         const int j = 16 * w + 4 * q + i, k = 16 * c + r;
         pv[i] = k < O ? a.params[gW1 + j * O + k] : 0.f;
-        acc_put(mA[4 * c + i], k < O ? a.exp_avg[gW1 + j * O + k] : 0.f);
-        acc_put(vA[4 * c + i], k < O ? a.exp_avg_sq[gW1 + j * O + k] : 0.f);
+        mA[4 * c + i] = k < O ? a.exp_avg[gW1 + j * O + k] : 0.f;
+        vA[4 * c + i] = k < O ? a.exp_avg_sq[gW1 + j * O + k] : 0.f;
       }
       store_w1(c, pv);
     }
@@ -212,8 +174,8 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       for (int i = 0; i < 4; ++i) {
         const int j = 16 * w + 4 * q + i, k = 16 * c + r;
         pv[i] = a.params[gW2 + j * HD + k];
-        acc_put(mA[E_W2 + 4 * c + i], a.exp_avg[gW2 + j * HD + k]);
-        acc_put(vA[E_W2 + 4 * c + i], a.exp_avg_sq[gW2 + j * HD + k]);
+        mA[E_W2 + 4 * c + i] = a.exp_avg[gW2 + j * HD + k];
+        vA[E_W2 + 4 * c + i] = a.exp_avg_sq[gW2 + j * HD + k];
       }
       store_w2(c, pv);
     }
@@ -223,14 +185,14 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       for (int i = 0; i < 4; ++i) {
         const int o = 4 * q + i, j = 16 * w + r;
         pv[i] = o < n_out ? a.params[gWh + o * HD + j] : 0.f;
-        acc_put(mA[E_WH + i], o < n_out ? a.exp_avg[gWh + o * HD + j] : 0.f);
-        acc_put(vA[E_WH + i], o < n_out ? a.exp_avg_sq[gWh + o * HD + j] : 0.f);
+        mA[E_WH + i] = o < n_out ? a.exp_avg[gWh + o * HD + j] : 0.f;
+        vA[E_WH + i] = o < n_out ? a.exp_avg_sq[gWh + o * HD + j] : 0.f;
       }
       store_wh(pv);
     }
-    acc_put(mA[E_B1], a.exp_avg[gb1 + jb]); acc_put(vA[E_B1], a.exp_avg_sq[gb1 + jb]);
-    acc_put(mA[E_B2], a.exp_avg[gb2 + jb]); acc_put(vA[E_B2], a.exp_avg_sq[gb2 + jb]);
-    acc_put(mA[E_EX], ex_g >= 0 ? a.exp_avg[ex_g] : 0.f); acc_put(vA[E_EX], ex_g >= 0 ? a.exp_avg_sq[ex_g] : 0.f);
+    mA[E_B1] = a.exp_avg[gb1 + jb]; vA[E_B1] = a.exp_avg_sq[gb1 + jb];
+    mA[E_B2] = a.exp_avg[gb2 + jb]; vA[E_B2] = a.exp_avg_sq[gb2 + jb];
+    mA[E_EX] = ex_g >= 0 ? a.exp_avg[ex_g] : 0.f; vA[E_EX] = ex_g >= 0 ? a.exp_avg_sq[ex_g] : 0.f;
     if (q == 0) {
       sm[o_bo] = a.params[gb1 + jb]; sm[o_bo + HD] = a.params[gb2 + jb];
       sm[ex_s] = ex_g >= 0 ? a.params[ex_g] : 0.f;          // lanes without an extra entry hit a scratch word
@@ -328,27 +290,11 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       if (r == 0) sm[o_msc + 22] = ent;
     }
   };
-  // ---- synchronisation inside the quad (ppo_train_halves.hip): a phase counter per wave in LDS
-  int* const pflag = reinterpret_cast<int*>(sm + o_msc + 48);      // [4] one word per wave
-  int pphase = 0;
-  auto quad_signal = [&]() {
-    if (ICRL_QW2_QUAD_BARRIER) return;      // (the barrier in quad_wait does both)
-    ++pphase;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_store(pflag + w, pphase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
-  auto quad_wait = [&]() {
-    if (ICRL_QW2_QUAD_BARRIER) { lds_barrier(); return; }
-    while (true) {
-      const int f0 = __hip_atomic_load(pflag + qp0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f1 = __hip_atomic_load(pflag + qp1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f2 = __hip_atomic_load(pflag + qp2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int f = f0 < f1 ? (f0 < f2 ? f0 : f2) : (f1 < f2 ? f1 : f2);
-      if (f >= pphase) break;
-      __builtin_amdgcn_s_sleep(0);
-    }
-    asm volatile("" ::: "memory");
-  };
+  // ---- synchronisation inside the quad: the quad is the whole workgroup here (ppo_train_halves.hip needs LDS flags: its waves 4..7 are parked at
+  // another barrier meanwhile), so `s_waitcnt lgkmcnt(0); s_barrier` does a hand-off instead of a flag store plus a polling loop of three LDS loads
+  // per look: 11.68 -> 11.53 us per step
+  auto quad_wait = [&]() { lds_barrier(); };
+  float* const msc = sm + o_msc;      // the MISC block as a pointer (the loss statistics' stores and reads below)
   // the running statistics live in lane 0 of wave 3 of each role
   const bool book = tid == 192;
   float st_ent = 0.f, st_pg = 0.f, st_vl = 0.f, st_cf = 0.f, last_loss = 0.f, kl_sum = 0.f;
@@ -369,11 +315,8 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
   int sidx_next = stat_idx(ps_nx2);
   if (tid == 0) sm[o_msc + 14] = run_on_one_xcd(xch0, slot_j, 12, true) ? 1.f : 0.f;
   __syncthreads();                      // initial weights visible (refresh_gauss reads log_std)
-#ifdef ICRL_ASSUME_XCD_LOCAL      // (measurement only: what a compile-time store scope would buy — no branch per exchange store: 11.61 -> 11.48 us per step (-1.1 %): not worth a verify-and-relaunch protocol in the ABI)
-  constexpr bool xcd_local = true;
-#else
+  // (a compile-time store scope — no branch per exchange store — measured 11.61 -> 11.48 us per step: not worth a verify-and-relaunch protocol in the ABI)
   const bool xcd_local = __builtin_amdgcn_readfirstlane(__float_as_int(sm[o_msc + 14])) != 0;
-#endif
   refresh_gauss();
   commit_rows();
   stats_partials(__builtin_amdgcn_readfirstlane(ps_next.z) & NB_MASK);
@@ -421,9 +364,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
     float mb_s0 = 0.f, mb_s1 = 0.f, mb_s2 = 0.f, mb_s3 = 0.f, mb_s4 = 0.f;  // bookkeeping lane: minibatch sums of the loss statistics
     const int xrole = ((int)(step & 1) * 3 + role) * 4 * XBLK;      // the four blocks of this role and step parity
     const int xmine = xrole + part * XBLK;
-    auto publish4 = [&](int g, const f32x4& v) {
-      if (ICRL_QW2_EARLY_PUBLISH) raw_store(xmine + (g * THQ2 + tid) * 16, v);
-    };
+    auto publish4 = [&](int g, const f32x4& v) { raw_store(xmine + (g * THQ2 + tid) * 16, v); };
     // row tile t = rows 16 part .. of chunk t: chunk 0 holds min(nb, 64) rows, chunk 1 the rest
     bool valid[2];
     valid[0] = 16 * part + b < (nb < RB ? nb : RB);
@@ -431,9 +372,6 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
 
     // ================= forward: feature tile w of every layer, both row tiles =================
     f32x4 h1c[2], h2c[2], outc[2];
-    float pl_olp[2] = {0.f, 0.f}, pl_adr[2] = {0.f, 0.f}, pl_adc[2] = {0.f, 0.f};      // (ICRL_QW2_LOSS_PRELOAD)
-    f32x4 pl_act[2], pl_iv, pl_hiv, pl_lsd, pl_wht;
-    pl_act[0] = pl_act[1] = pl_iv = pl_hiv = pl_lsd = pl_wht = f32x4{0.f, 0.f, 0.f, 0.f};
     {  // layer 1: the weight operands once, two independent MFMA chains
       const float* pa = sm + o_w1a;
       f32x4 aw[NT1];
@@ -479,7 +417,6 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
         issue_rows(t, idx_now);
       }
     }
-    quad_signal();               // (P1) this wave's features of h1 are complete
     {  // layer 2: own quarter of K from registers, the other three from the row-major image
       const float* pa = sm + o_w2a;
       const f32x4 awo = lds128(pa + 16 * w);
@@ -518,16 +455,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       float* const hpx = sm + o_hpx;
       *reinterpret_cast<f32x4*>(hpx + w * 256) = acc[0];
       *reinterpret_cast<f32x4*>(hpx + 1024 + w * 256) = acc[1];
-      if (ICRL_QW2_LOSS_PRELOAD) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          pl_olp[t] = sm[o_sid + 16 * t]; pl_adr[t] = sm[o_sid + 32 + 16 * t]; pl_adc[t] = sm[o_sid + 64 + 16 * t];
-          if (role == 0 && !DISC) pl_act[t] = lds128(sm + o_act + 16 * t * SAX);
-        }
-        if (role == 0 && !DISC) { pl_iv = lds128(sm + o_gau); pl_hiv = lds128(sm + o_gau + 16); pl_lsd = lds128(sm + o_gau + 32); }
-        pl_wht = lds128(sm + o_wht);
-      }
-      quad_signal(); quad_wait();  // (P3) all four partial tiles of both row tiles stored
+      quad_wait();               // (P3) all four partial tiles of both row tiles stored
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const f32x4 p0 = lds128(hpx + 1024 * t), p1 = lds128(hpx + 1024 * t + 256), p2 = lds128(hpx + 1024 * t + 512), p3 = lds128(hpx + 1024 * t + 768);
@@ -575,9 +503,9 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
             g2[i] = k < A ? pr[i] * (lg[i] + ent) : 0.f;     // d(-H)/dz_k = p_k (log p_k + H)
           }
         } else {
-          const f32x4 actv = ICRL_QW2_LOSS_PRELOAD ? pl_act[t] : lds128(sm + o_act + 16 * t * SAX);
-          const f32x4 iv = ICRL_QW2_LOSS_PRELOAD ? pl_iv : lds128(sm + o_gau), hiv = ICRL_QW2_LOSS_PRELOAD ? pl_hiv : lds128(sm + o_gau + 16),
-                      lsd = ICRL_QW2_LOSS_PRELOAD ? pl_lsd : lds128(sm + o_gau + 32);
+          const f32x4 actv = lds128(sm + o_act + 16 * t * SAX);
+          const f32x4 iv = lds128(sm + o_gau), hiv = lds128(sm + o_gau + 16),
+                      lsd = lds128(sm + o_gau + 32);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float dd = actv[i] - outc[t][i];                 // pad actions / outputs are 0
@@ -587,10 +515,10 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
           }
           lp = quad_rows_sum(lp);
         }
-        const float old_lp = ICRL_QW2_LOSS_PRELOAD ? pl_olp[t] : sm[o_sid + 16 * t];
+        const float old_lp = sm[o_sid + 16 * t];
         const float ratio = __expf(lp - old_lp);
-        const float Ar = ((ICRL_QW2_LOSS_PRELOAD ? pl_adr[t] : sm[o_sid + 32 + 16 * t]) - c_mean_r) * c_istd_r;
-        const float Ac = (ICRL_QW2_LOSS_PRELOAD ? pl_adc[t] : sm[o_sid + 64 + 16 * t]) - c_mean_c;
+        const float Ar = (sm[o_sid + 32 + 16 * t] - c_mean_r) * c_istd_r;
+        const float Ac = sm[o_sid + 64 + 16 * t] - c_mean_c;
         const float s1 = Ar * ratio;
         const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
         const float s2 = Ar * rc;
@@ -611,10 +539,10 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
         v3 = cnt ? old_lp - lp : 0.f; v4 = cnt ? ent : 0.f;
       } else {
         const float v = quad_rows_sum(q == 0 ? outc[t][0] : 0.f);      // lane (r, q = 0) holds output 0 of row b
-        const float R = ICRL_QW2_LOSS_PRELOAD ? pl_adr[t] : sm[o_sid + 32 + 16 * t];
+        const float R = sm[o_sid + 32 + 16 * t];
         float vp = v, pass = 1.f;
         if (vclip >= 0.f) {
-          const float old = ICRL_QW2_LOSS_PRELOAD ? pl_olp[t] : sm[o_sid + 16 * t];
+          const float old = sm[o_sid + 16 * t];
           const float dv = v - old;
           vp = old + fminf(fmaxf(dv, -vclip), vclip);
           pass = (dv >= -vclip && dv <= vclip) ? 1.f : 0.f;
@@ -627,14 +555,14 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       if (w == 0) {     // one wave of the quad reports the tile's statistics
         v0 = row_sum(v0); v1 = row_sum(v1); v2 = row_sum(v2); v3 = row_sum(v3);
         if (DISC) v4 = row_sum(v4);
-        if (lane == 0) { float* pst = sm + o_msc + (S::PST - S::MISC) + 8 * t; pst[0] = v0; pst[1] = v1; pst[2] = v2; pst[3] = v3; pst[4] = v4; }
+        if (lane == 0) { float* pst = msc + (S::PST - S::MISC) + 8 * t; pst[0] = v0; pst[1] = v1; pst[2] = v2; pst[3] = v3; pst[4] = v4; }
       }
     }
     STAMP(1)   // loss
     // ================= backward of the activations =================
     f32x4 dz2c[2], dz1c[2];
     {  // dH2^T = Wh^T . dOut^T for the own feature tile: A = WHT[j = 16 w + r][o = 4 q + e] (K = 16 outputs)
-      const f32x4 aw = ICRL_QW2_LOSS_PRELOAD ? pl_wht : lds128(sm + o_wht);
+      const f32x4 aw = lds128(sm + o_wht);
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int e = 0; e < 4; ++e) { acc[0] = MFMA_F32(aw[e], dout[0][e], acc[0]); acc[1] = MFMA_F32(aw[e], dout[1][e], acc[1]); }
@@ -651,7 +579,6 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
         }
       }
     }
-    quad_signal();               // (P4) this wave's features of dz2 complete
     {  // dH1^T = W2^T . dz2^T: A = W2T[k = 16 w + r][j = 16 js + 4 q + e]; own quarter of K before the wait for the others
       const float* pa = sm + o_w2a + (S::W2T - S::W2);
       const f32x4 awo = lds128(pa + 16 * w);
@@ -752,7 +679,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       publish4(NT1 - 2, gW1r[NT1 - 2]); publish4(NT1 - 1, gW1r[NT1 - 1]);
     }
     if (book) {
-      const float* pst = sm + o_msc + (S::PST - S::MISC);
+      const float* pst = msc + (S::PST - S::MISC);
       mb_s0 = pst[0] + pst[8]; mb_s1 = pst[1] + pst[9]; mb_s2 = pst[2] + pst[10]; mb_s3 = pst[3] + pst[11];
       if (DISC) mb_s4 = pst[4] + pst[12];
     }
@@ -764,7 +691,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       auto grp = [&](int g) -> f32x4& { return g < NT1 ? gW1r[g] : (g < NT1 + 4 ? gW2r[g - NT1] : (g == NT1 + 4 ? gWhr : gsc)); };
 #pragma unroll
       for (int g = 0; g < NGRP; ++g) {
-        if (ICRL_QW2_EARLY_PUBLISH && g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
+        if (g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
         raw_store(xmine + (g * THQ2 + tid) * 16, grp(g));
       }
       f32x4 bks = f32x4{mb_s1, mb_s2, mb_s3, mb_s4};
@@ -792,7 +719,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
         }
         asm volatile("" ::: "memory");
       }
-      constexpr int DEP = ICRL_QW2_DEP;
+      constexpr int DEP = 4;      // groups of the three peers in flight while one is summed
       f32x4 ra[DEP], rb[DEP], rc[DEP];
 #pragma unroll
       for (int k = 0; k < DEP; ++k)
@@ -926,7 +853,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
       auto adam4 = [&](const f32x4& g, float* mA4, float* vA4, f32x4& p) {
         f32x4 m, v, d;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { m[i] = acc_get(mA4[i]); v[i] = acc_get(vA4[i]); }
+        for (int i = 0; i < 4; ++i) { m[i] = mA4[i]; v[i] = vA4[i]; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) { m[i] = fmaf(cw1, g[i], omw1 * m[i]); v[i] = fmaf(c2w2, g[i] * g[i], b2f_ * v[i]); }
 #pragma unroll
@@ -934,7 +861,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
 #pragma unroll
         for (int i = 0; i < 4; ++i) p[i] = fmaf(-step_size, m[i] * __builtin_amdgcn_rcpf(d[i]), p[i]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { acc_set(mA4[i], m[i]); acc_set(vA4[i], v[i]); }
+        for (int i = 0; i < 4; ++i) { mA4[i] = m[i]; vA4[i] = v[i]; }
       };
       // pad elements (k >= obs, o >= n_out) have g = m = v = p = 0 and stay 0: no masks needed
 #pragma unroll
@@ -947,7 +874,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
         float m3[4], v3[4];
 #pragma unroll
         for (int i = 0; i < 3; ++i) { m3[i] = mA[E_B1 + i]; v3[i] = vA[E_B1 + i]; }
-        acc_put(m3[3], 0.f); acc_put(v3[3], 0.f);
+        m3[3] = 0.f; v3[3] = 0.f;
         adam4(g_, m3, v3, p_);
 #pragma unroll
         for (int i = 0; i < 3; ++i) { mA[E_B1 + i] = m3[i]; vA[E_B1 + i] = v3[i]; }
@@ -975,7 +902,7 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int j = 16 * w + 4 * q + i, k = 16 * c + r;
-      if (k < O) { a.params[gW1 + j * O + k] = pv[i]; a.exp_avg[gW1 + j * O + k] = acc_get(mA[4 * c + i]); a.exp_avg_sq[gW1 + j * O + k] = acc_get(vA[4 * c + i]); }
+      if (k < O) { a.params[gW1 + j * O + k] = pv[i]; a.exp_avg[gW1 + j * O + k] = mA[4 * c + i]; a.exp_avg_sq[gW1 + j * O + k] = vA[4 * c + i]; }
     }
   }
 #pragma unroll
@@ -985,8 +912,8 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
     for (int i = 0; i < 4; ++i) {
       const int j = 16 * w + 4 * q + i, k = 16 * c + r;
       a.params[gW2 + j * HD + k] = pv[i];
-      a.exp_avg[gW2 + j * HD + k] = acc_get(mA[E_W2 + 4 * c + i]);
-      a.exp_avg_sq[gW2 + j * HD + k] = acc_get(vA[E_W2 + 4 * c + i]);
+      a.exp_avg[gW2 + j * HD + k] = mA[E_W2 + 4 * c + i];
+      a.exp_avg_sq[gW2 + j * HD + k] = vA[E_W2 + 4 * c + i];
     }
   }
   {
@@ -994,13 +921,13 @@ __device__ __forceinline__ void ppo_train_quarters2_body(const TrainArgs& a, con
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int o = 4 * q + i, j = 16 * w + r;
-      if (o < n_out) { a.params[gWh + o * HD + j] = pv[i]; a.exp_avg[gWh + o * HD + j] = acc_get(mA[E_WH + i]); a.exp_avg_sq[gWh + o * HD + j] = acc_get(vA[E_WH + i]); }
+      if (o < n_out) { a.params[gWh + o * HD + j] = pv[i]; a.exp_avg[gWh + o * HD + j] = mA[E_WH + i]; a.exp_avg_sq[gWh + o * HD + j] = vA[E_WH + i]; }
     }
   }
   if (q == 0) {
-    a.params[gb1 + jb] = sm[o_bo]; a.exp_avg[gb1 + jb] = acc_get(mA[E_B1]); a.exp_avg_sq[gb1 + jb] = acc_get(vA[E_B1]);
-    a.params[gb2 + jb] = sm[o_bo + HD]; a.exp_avg[gb2 + jb] = acc_get(mA[E_B2]); a.exp_avg_sq[gb2 + jb] = acc_get(vA[E_B2]);
-    if (ex_g >= 0) { a.params[ex_g] = sm[ex_s]; a.exp_avg[ex_g] = acc_get(mA[E_EX]); a.exp_avg_sq[ex_g] = acc_get(vA[E_EX]); }
+    a.params[gb1 + jb] = sm[o_bo]; a.exp_avg[gb1 + jb] = mA[E_B1]; a.exp_avg_sq[gb1 + jb] = vA[E_B1];
+    a.params[gb2 + jb] = sm[o_bo + HD]; a.exp_avg[gb2 + jb] = mA[E_B2]; a.exp_avg_sq[gb2 + jb] = vA[E_B2];
+    if (ex_g >= 0) { a.params[ex_g] = sm[ex_s]; a.exp_avg[ex_g] = mA[E_EX]; a.exp_avg_sq[ex_g] = vA[E_EX]; }
   }
   if (tid == 0 && prof) {
     for (int k = 0; k < 7; ++k) {
@@ -1035,7 +962,7 @@ __global__ void __launch_bounds__(THQ2) ppo_train_quarters2_kernel(TrainArgs a, 
 template <int NT1, bool DISC, int OBS, bool PROF>
 static int launch_quarters2_p(const TrainArgs& a, hipStream_t s) {
   static_assert(SmemQ2<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
-  const size_t bytes = ICRL_QW_STATIC_LDS ? 0 : (size_t)SmemQ2<NT1>::TOTAL * sizeof(float);
+  const size_t bytes = (size_t)SmemQ2<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_quarters2_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;

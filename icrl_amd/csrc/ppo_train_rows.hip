@@ -25,9 +25,6 @@
 // Built with -ffp-contract=off; FMA is used only where written (fmaf / MFMA).
 #include "ppo_common.h"
 
-// static LDS array instead of `extern __shared__` (ppo_train_pairs.hip: -1.6 % there).  Measured here: at AntWall widths 30.5 us per
-// step against 24.0 (scratch instructions 336 -> 424: the folded offsets let the optimiser hoist more than the register file holds),
-// at HC widths 10.1-10.3 against 10.2-10.5 — off.
 // granule store: workgroup scope (`sc0`: the line stays in this XCD's L2) when all workgroups of the run share an XCD, else agent
 // scope (ppo_common.h: XCD placement)
 #define GSTORE(ptr, val)                                                                              \
@@ -35,35 +32,6 @@
     if (xcd_local) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  \
     else __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                \
   } while (0)
-// A/B (measured and rejected twice: across the fabric in round 3, 24.0-25.1 vs 23.7-24.1 us per step, and with the XCD-local exchange in
-// round 4, 20.3 vs 19.6): the partial gradients as 16-byte records {step, a, b, step} — two per group of four values — instead of four
-// 8-byte granules; same bytes, half the memory instructions, bit-identical results
-#ifndef ICRL_ROWS_REC16
-#define ICRL_ROWS_REC16 0
-#endif
-// SPLIT exchange as RAW 16-byte stores + ONE flag per wave (round 5): a gradient group is four floats of a lane — one dwordx4 store, no
-// tags — and when a wave has stored all its groups it drains its stores (s_waitcnt vmcnt(0): a store is acknowledged by the L2 it was
-// written through to) and raises a flag word carrying the step; the same wave of the other half polls that flag and then fetches the
-// groups with L1-bypassing loads.  A quarter of the memory instructions of the tagged granules (14 stores + 14 loads per lane and step
-// instead of 55 + 55) and half their bytes; the exchange was request-rate-bound.  What it gives up is the early receive (nothing can be
-// fetched before the flag).  Both halves still form own + partner, so they stay bit-identical replicas, and the sums are the granule
-// path's sums: results are bit-identical to it.
-#ifndef ICRL_ROWS_RAWX
-#define ICRL_ROWS_RAWX 1
-#endif
-#ifndef ICRL_EARLY_PUBLISH
-#define ICRL_EARLY_PUBLISH 1
-#endif
-#ifndef ICRL_EARLY_RECV
-#define ICRL_EARLY_RECV 1
-#endif
-#ifndef ICRL_ROWS_STATIC_LDS
-#define ICRL_ROWS_STATIC_LDS 0
-#endif
-// the first look at the other networks' norm granules issued before the staging of the next minibatch, read behind it (ppo_train_halves.hip)
-#ifndef ICRL_ROWS_EARLY_POLL
-#define ICRL_ROWS_EARLY_POLL 0
-#endif
 
 namespace icrl {
 
@@ -109,44 +77,28 @@ struct SmemR {  // offsets in floats (multiples of 4)
 // that need pointers: keeps ~30 scalar registers out of the loop-carried state (the SGPR file spills otherwise)
 #define KARGS() ([&]() { const TrainArgs* k_ = ka; asm volatile("" : "+s"(k_)); return k_; }())
 
+// the whole update of ONE run (see ppo_train_pairs_body): `ka` = the same argument block in memory
 // SPLIT: TWO workgroups per network (grid 6).  A minibatch of more than 64 rows is two chunks; workgroup (role, half) runs
 // the forward / backward / weight-gradient GEMMs of chunk `half` only, the two halves then exchange their partial gradients
-// (every gradient register as a {step tag | float} granule, same protocol as the norm exchange) and each forms
-// own + partner — float addition is commutative bit for bit, so both halves hold identical gradients, run the identical norm /
-// Adam arithmetic on identical weights and stay replicas of each other.  One more hop per step for half of the GEMM work.
-// the whole update of ONE run (see ppo_train_pairs_body): `ka` = the same argument block in memory
+// and each forms own + partner — float addition is commutative bit for bit, so both halves hold identical gradients, run the
+// identical norm / Adam arithmetic on identical weights and stay replicas of each other.  One more hop per step for half of the
+// GEMM work.  The exchange is RAW 16-byte stores + ONE flag per wave: a gradient group is four floats of a lane — one dwordx4
+// store, no tags — and when a wave has stored all its groups it drains its stores (s_waitcnt vmcnt(0): a store is acknowledged by
+// the L2 it was written through to) and raises a flag word carrying the step; the same wave of the other half polls that flag and
+// then fetches the groups with L1-bypassing loads.  (Every gradient register as a {step tag | float} granule, the norm exchange's
+// protocol, took four times the memory instructions and twice the bytes of a request-rate-bound exchange; 16-byte tagged
+// records measured slower than the granules twice: DESIGN 5, ROWS_RAWX / ROWS_REC16.)
 // BATCH: the argument block was read from memory (batched launch): its pointers are marked as global-memory pointers (common.h:
 // as_global).  The single-run kernel's by-value pointers already are, and at AntWall widths the extra scalar traffic costs it 6 %.
-// SPLIT exchange: which gradient group (0 .. NT1-1: W1 tiles, NT1 .. NT1+3: W2 tiles, NT1+4: head, NT1+5: {b1, b2, extra}) is fetched
-// during dW1 tile c — the W2 tiles and the head first (published before dW1 started), then the W1 tiles published five tiles ago
-__host__ __device__ constexpr int early_group_of(int nt1, int c) { return c < 5 ? nt1 + c : c - 5; }
-template <int NT1>
-struct RemGroups {      // the groups the final pass still has to fetch
-  int v[NT1 + 6];
-  int n;
-  static constexpr RemGroups make(bool early) {
-    RemGroups r{};
-    r.n = 0;
-    for (int g = 0; g < NT1 + 6; ++g) {
-      bool e = false;
-      for (int c = 0; c < NT1; ++c) e = e || (early && early_group_of(NT1, c) == g);
-      if (!e) r.v[r.n++] = g;
-    }
-    return r;
-  }
-};
-
 template <int NT1, bool DISC, bool SPLIT, bool BATCH>
 __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const TrainArgs* const ka, const int slot_j) {
 #define GP(x) (BATCH ? as_global(x) : (x))
   using S = SmemR<NT1>;
   constexpr int SX = S::SX;
   constexpr int XR = (S::O16 + 3) / 4;  // floats of an X row each of the 4 threads of a row stages
-#if ICRL_ROWS_STATIC_LDS
-  __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];   // static: offsets fold into immediates (see ppo_train_pairs.hip)
-#else
+  // dynamic: with a static array the folded offsets let the optimiser hoist more addresses than the register file holds (AntWall widths: 30.5
+  // against 24.0 us per step, scratch instructions 336 -> 424; ppo_train_pairs.hip gains 1.6 % from the static array)
   extern __shared__ __attribute__((aligned(16))) float sm[];
-#endif
   const int role = slot_j % 3;   // 0 policy, 1 reward critic, 2 cost critic
   const int half = slot_j / 3;   // SPLIT: which 64-row chunk of every minibatch this workgroup computes
   const int tid = threadIdx.x;
@@ -448,8 +400,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
     float mb_s0 = 0.f, mb_s1 = 0.f, mb_s2 = 0.f, mb_s3 = 0.f, mb_s4 = 0.f;  // bookkeeping lane: minibatch sums of the loss statistics
 
     const int n_chunks = SPLIT ? 1 : (nb + RB - 1) / RB;
-    unsigned pend = 0; (void)pend;      // SPLIT: gradient groups of the other half that had not arrived when they were looked at
-#if ICRL_ROWS_RAWX
     typedef unsigned int raw_u4 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? GP(KARGS()->gx) : nullptr, 0, (int)ICRL_PPO_SPLIT_BYTES, 0x00020000);
     constexpr int XBLK = (4 * NT1 + 23 + 5) * TH4 * 8;          // bytes of one (parity, role, half) block (the granule layout's size)
@@ -462,23 +412,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
       else __builtin_amdgcn_raw_buffer_store_b128(u, grs, byte_off, 0, 16);               // sc1
     };
     auto raw_load = [&](int byte_off) -> f32x4 { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(grs, byte_off, 0, 16)); };
-#elif ICRL_ROWS_REC16
-    typedef unsigned int rec_u4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(SPLIT ? GP(KARGS()->gx) : nullptr, 0, (int)ICRL_PPO_SPLIT_BYTES, 0x00020000);
-    constexpr int RBLK = (4 * NT1 + 23 + 5) * TH4 * 8;          // bytes of one (parity, role, half) block: (KG + 5) / 2 records per thread
-    const int rmine = (((int)(step & 1) * 3 + role) * 2 + half) * RBLK + tid * 16;
-    const int rtheirs = (((int)(step & 1) * 3 + role) * 2 + (1 - half)) * RBLK + tid * 16;
-    auto rec_store = [&](int byte_off, rec_u4 v) {
-      if (xcd_local) __builtin_amdgcn_raw_buffer_store_b128(v, grs, byte_off, 0, 1);      // sc0
-      else __builtin_amdgcn_raw_buffer_store_b128(v, grs, byte_off, 0, 16);               // sc1
-    };
-    auto rec_load = [&](int byte_off) -> rec_u4 { return __builtin_amdgcn_raw_buffer_load_b128(grs, byte_off, 0, 16); };
-    auto rec_pub = [&](int g, const f32x4& v) {      // group g = records 2 g, 2 g + 1 of this thread
-      rec_store(rmine + (2 * g) * TH4 * 16, rec_u4{step, __float_as_uint(v[0]), __float_as_uint(v[1]), step});
-      rec_store(rmine + (2 * g + 1) * TH4 * 16, rec_u4{step, __float_as_uint(v[2]), __float_as_uint(v[3]), step});
-    };
-    auto rec_ok = [&](const rec_u4& a_, const rec_u4& b_) -> bool { return a_[0] == step && a_[3] == step && b_[0] == step && b_[3] == step; };
-#endif
     for (int ch = 0; ch < n_chunks; ++ch, ++g_chunk) {
       const int first = SPLIT ? half * RB : ch * RB;        // SPLIT: a half without rows (ragged last minibatch) runs on zero rows
       const int nrows = nb - first < 0 ? 0 : ((nb - first) < RB ? (nb - first) : RB);
@@ -740,61 +673,12 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
         gWhr = f32x4{0.f, 0.f, 0.f, 0.f};
         gb1r = 0.f; gb2r = 0.f; gex = 0.f;
       }
-      // SPLIT + ICRL_EARLY_PUBLISH: a gradient register group goes out to the other half as soon as its GEMM is done — one GEMM late, so that
-      // the store does not wait for the MFMA chain that produces it — instead of all 55 granules per thread behind the last GEMM:
-      // the exchange is throughput-bound (~1 granule per cycle and CU), and the memory pipe runs beside the MFMAs of the next tiles.
-      constexpr int KG_ = 4 * NT1 + 23;
-#if !ICRL_ROWS_RAWX
-      u64* const mine_e = SPLIT ? GP(KARGS()->gx) + ((size_t)((step & 1) * 3 + role) * 2 + half) * ((size_t)(KG_ + 5) * TH4) + tid : nullptr;
-#endif
-      (void)KG_;
-#if ICRL_ROWS_RAWX
+      // SPLIT: a gradient register group goes out to the other half as soon as its GEMM is done — one GEMM late, so that
+      // the store does not wait for the MFMA chain that produces it — instead of all groups behind the last GEMM:
+      // the exchange is throughput-bound, and the memory pipe runs beside the MFMAs of the next tiles.
       auto publish4 = [&](int g, const f32x4& v) {
-        if (!(SPLIT && ICRL_EARLY_PUBLISH)) return;
-        raw_store(xmine + (g * TH4 + tid) * 16, v);
+        if (SPLIT) raw_store(xmine + (g * TH4 + tid) * 16, v);
       };
-      auto early_issue = [&](int) {};
-      auto early_take = [&](int, f32x4&) {};
-#elif ICRL_ROWS_REC16
-      auto publish4 = [&](int g, const f32x4& v) {
-        if (!(SPLIT && ICRL_EARLY_PUBLISH)) return;
-        rec_pub(g, v);
-      };
-      rec_u4 eb[2] = {rec_u4{0, 0, 0, 0}, rec_u4{0, 0, 0, 0}};
-      auto early_issue = [&](int g) { eb[0] = rec_load(rtheirs + (2 * g) * TH4 * 16); eb[1] = rec_load(rtheirs + (2 * g + 1) * TH4 * 16); };
-      auto early_take = [&](int g, f32x4& v) {
-        const bool ok = rec_ok(eb[0], eb[1]);
-        v[0] = ok ? v[0] + __uint_as_float(eb[0][1]) : v[0]; v[1] = ok ? v[1] + __uint_as_float(eb[0][2]) : v[1];
-        v[2] = ok ? v[2] + __uint_as_float(eb[1][1]) : v[2]; v[3] = ok ? v[3] + __uint_as_float(eb[1][2]) : v[3];
-        pend |= ok ? 0u : (1u << g);
-      };
-#else
-      auto publish4 = [&](int g, const f32x4& v) {
-        if (!(SPLIT && ICRL_EARLY_PUBLISH)) return;
-        const u64 tg_ = (u64)step << 32;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          GSTORE(mine_e + (size_t)(4 * g + i) * TH4, tg_ | (u64)__float_as_uint(v[i]));
-      };
-      // ICRL_EARLY_RECV (on since the exchange is XCD-local: 19.6 us per step against 20.8 with the early publish alone; with agent-scope
-      // stores across XCDs it was 24.0 against 22.5 — a group that is looked at inside the MFMA stream stalls it when it is late, and
-      // the in-order vmcnt makes every look wait for the stores issued since — which is what a launch whose workgroups do NOT share an
-      // XCD still pays): the partner's groups fetched the same way — during dW1 tile c the granules of group early_group(c) (which
-      // the partner published several tiles ago) are loaded, one tile later they are checked and added to the own (already
-      // published) partial; a group that has not arrived is left to the polling pass below (`pend`).
-      const u64* const theirs_e = SPLIT ? GP(KARGS()->gx) + ((size_t)((step & 1) * 3 + role) * 2 + (1 - half)) * ((size_t)(KG_ + 5) * TH4) + tid : nullptr;
-      u64 eb[4] = {0, 0, 0, 0};
-      auto early_issue = [&](int g) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) eb[i] = __hip_atomic_load(theirs_e + (size_t)(4 * g + i) * TH4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      };
-      auto early_take = [&](int g, f32x4& v) {
-        const bool ok = (unsigned)(eb[0] >> 32) == step && (unsigned)(eb[1] >> 32) == step && (unsigned)(eb[2] >> 32) == step && (unsigned)(eb[3] >> 32) == step;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ok ? v[i] + __uint_as_float((unsigned)eb[i]) : v[i];
-        pend |= ok ? 0u : (1u << g);
-      };
-#endif
       // ================= weight gradients: rows 16w.. of dW2 / dW1, columns 16w.. of dWh; K = the 64 rows =================
       {
         f32x4 az[4];   // dz2^T[j = 16w + r][rows 16 js + 4q + e]
@@ -866,14 +750,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
 #pragma unroll
             for (int e = 0; e < 4; ++e) gW1r[c] = MFMA_F32(az[js][e], bx[js][e], gW1r[c]);
           if (c == 0) publish4(NT1 + 4, gWhr); else publish4(c - 1, gW1r[c - 1]);
-          if (SPLIT && ICRL_EARLY_PUBLISH && ICRL_EARLY_RECV && !ICRL_ROWS_RAWX) {
-            if (c > 0) { const int gp = early_group_of(NT1, c - 1); early_take(gp, gp < NT1 ? gW1r[gp < NT1 ? gp : 0] : (gp < NT1 + 4 ? gW2r[gp - NT1 < 4 && gp >= NT1 ? gp - NT1 : 0] : gWhr)); }
-            early_issue(early_group_of(NT1, c));
-          }
-        }
-        if (SPLIT && ICRL_EARLY_PUBLISH && ICRL_EARLY_RECV && !ICRL_ROWS_RAWX) {
-          const int gp = early_group_of(NT1, NT1 - 1);
-          early_take(gp, gp < NT1 ? gW1r[gp < NT1 ? gp : 0] : (gp < NT1 + 4 ? gW2r[gp - NT1 < 4 && gp >= NT1 ? gp - NT1 : 0] : gWhr));
         }
         float s = 0.f;
 #pragma unroll
@@ -893,23 +769,20 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
     }  // chunks
 
     if (SPLIT) {
-      // ---- partial gradients of this half <-> the other half of the same network.  Slot of element k of thread tid:
-      // gx[parity][role][half][k][tid]; KG gradient elements per thread + 5 loss-statistic sums of the book-keeping thread.
+      // ---- partial gradients of this half <-> the other half of the same network: group g of thread tid at byte (g TH4 + tid) 16 of
+      // the (parity, role, half) block, the book-keeping thread's loss-statistic sums behind the groups.
       // Gradient registers are published and summed in place, four at a time (no staging copy: the kernel has no registers to
-      // spare at AntWall widths), the next group's loads in flight while this one is checked.
-      constexpr int KG = 4 * NT1 + 23, NGRP = NT1 + 6;       // groups: W1 tiles, 4 W2 tiles, head, {b1, b2, extra, -}
-      const size_t blk = (size_t)(KG + 5) * TH4;
-      u64* const mine = GP(KARGS()->gx) + ((size_t)((step & 1) * 3 + role) * 2 + half) * blk + tid;
-      const u64* const theirs = GP(KARGS()->gx) + ((size_t)((step & 1) * 3 + role) * 2 + (1 - half)) * blk + tid;
-      const u64 tg = (u64)step << 32;
+      // spare at AntWall widths), the next groups' loads in flight while this one is summed.
+      constexpr int NGRP = NT1 + 6;       // groups: W1 tiles, 4 W2 tiles, head, {b1, b2, extra, -}
+      // (two unused re-reads of the argument pointer, left over from the granule exchange: each is an opaque asm statement and a scalar
+      // move in the shipped instruction stream; they go with the first change that is allowed to move the ISA)
+      (void)KARGS(); (void)KARGS();
       f32x4 gsc = f32x4{gb1r, gb2r, gex, 0.f};
       auto grp = [&](int g) -> f32x4& { return g < NT1 ? gW1r[g] : (g < NT1 + 4 ? gW2r[g - NT1] : (g == NT1 + 4 ? gWhr : gsc)); };
-#if ICRL_ROWS_RAWX
-      (void)mine; (void)theirs; (void)tg; (void)KG;
       if (book) gsc[3] = mb_s0;                    // (the book-keeping lane's first loss sum rides in the spare slot of the last group)
 #pragma unroll
       for (int g = 0; g < NGRP; ++g) {
-        if (ICRL_EARLY_PUBLISH && g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
+        if (g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
         raw_store(xmine + (g * TH4 + tid) * 16, grp(g));
       }
       if (book) raw_store(xmine + NGRP * TH4 * 16, f32x4{mb_s1, mb_s2, mb_s3, mb_s4});
@@ -950,148 +823,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
         const f32x4 c = raw_load(xtheirs + NGRP * TH4 * 16);
         mb_s1 += c[0]; mb_s2 += c[1]; mb_s3 += c[2]; mb_s4 += c[3];
       }
-#elif ICRL_ROWS_REC16
-      if (book) gsc[3] = mb_s0;                    // (the book-keeping thread's first loss sum rides in the spare slot of the last group)
-#pragma unroll
-      for (int g = 0; g < NGRP; ++g) {
-        if (ICRL_EARLY_PUBLISH && g < NT1 + 5) continue;
-        rec_pub(g, grp(g));
-      }
-      if (book) {
-        rec_store(rmine + (2 * NGRP) * TH4 * 16, rec_u4{step, __float_as_uint(mb_s1), __float_as_uint(mb_s2), step});
-        rec_store(rmine + (2 * NGRP + 1) * TH4 * 16, rec_u4{step, __float_as_uint(mb_s3), __float_as_uint(mb_s4), step});
-      }
-      bool timed_out = false;
-      constexpr int DEP = 4;
-      rec_u4 ring[DEP][2];
-      constexpr RemGroups<NT1> REM = RemGroups<NT1>::make(SPLIT && ICRL_EARLY_PUBLISH && ICRL_EARLY_RECV);
-      auto issue = [&](rec_u4 (&b)[2], int g) { b[0] = rec_load(rtheirs + (2 * g) * TH4 * 16); b[1] = rec_load(rtheirs + (2 * g + 1) * TH4 * 16); };
-      auto add_to = [&](f32x4& v, const rec_u4 (&c)[2], bool ok) {
-        v[0] = ok ? v[0] + __uint_as_float(c[0][1]) : v[0]; v[1] = ok ? v[1] + __uint_as_float(c[0][2]) : v[1];
-        v[2] = ok ? v[2] + __uint_as_float(c[1][1]) : v[2]; v[3] = ok ? v[3] + __uint_as_float(c[1][2]) : v[3];
-      };
-#pragma unroll
-      for (int k = 0; k < DEP; ++k)
-        if (k < REM.n) issue(ring[k], REM.v[k]);
-#pragma unroll
-      for (int k = 0; k < REM.n; ++k) {
-        const int g = REM.v[k];
-        rec_u4 (&c)[2] = ring[k % DEP];
-        const bool ok = rec_ok(c[0], c[1]);
-        add_to(grp(g), c, ok);
-        pend |= ok ? 0u : (1u << g);
-        if (k + DEP < REM.n) issue(c, REM.v[k + DEP]);
-      }
-      if (__any(pend != 0u)) {
-#pragma unroll
-        for (int g = 0; g < NGRP; ++g) {
-          if (!__any((pend >> g) & 1u)) continue;
-          const bool mine_pending = (pend >> g) & 1u;
-          rec_u4 c[2] = {rec_u4{0, 0, 0, 0}, rec_u4{0, 0, 0, 0}};
-          bool ok = !mine_pending;
-          for (int spins = 0; spins < (1 << 22) && !timed_out; ++spins) {
-            if (!ok) { issue(c, g); ok = rec_ok(c[0], c[1]); }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if (spins + 1 == (1 << 22)) timed_out = true;
-          }
-          if (mine_pending && ok) add_to(grp(g), c, true);
-        }
-      }
-      gb1r = gsc[0]; gb2r = gsc[1]; gex = gsc[2];
-      if (book) {
-        mb_s0 = gsc[3];
-        rec_u4 c[2] = {rec_u4{0, 0, 0, 0}, rec_u4{0, 0, 0, 0}};
-        for (int spins = 0; spins < (1 << 22) && !timed_out; ++spins) {
-          issue(c, NGRP);
-          if (rec_ok(c[0], c[1])) break;
-          if (spins + 1 == (1 << 22)) timed_out = true;
-        }
-        mb_s1 += __uint_as_float(c[0][1]); mb_s2 += __uint_as_float(c[0][2]); mb_s3 += __uint_as_float(c[1][1]); mb_s4 += __uint_as_float(c[1][2]);
-      }
-#else
-#pragma unroll
-      for (int g = 0; g < NGRP; ++g) {
-        if (ICRL_EARLY_PUBLISH && g < NT1 + 5) continue;      // (already out, group by group, behind their GEMMs)
-        const f32x4 v = grp(g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (4 * g + i < KG)
-            GSTORE(mine + (size_t)(4 * g + i) * TH4, tg | (u64)__float_as_uint(v[i]));
-      }
-      if (book) {
-        const float ms[5] = {mb_s0, mb_s1, mb_s2, mb_s3, mb_s4};
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-          GSTORE(mine + (size_t)(KG + k) * TH4, tg | (u64)__float_as_uint(ms[k]));
-      }
-      // Fast pass, straight-line on purpose (any loop or branch between a load and its use makes the compiler wait for ALL
-      // outstanding loads): DEP groups in flight, a group is added where all four of its granules carry this step's tag; the
-      // rest is remembered per lane and fetched by the polling loop below.  (Measured: the exchange is throughput-bound, not
-      // latency-bound — ~14 k granules stored and ~14 k loaded per workgroup and step at about one 8-byte granule per cycle and
-      // CU; waiting before the first pass changes nothing.)
-      bool timed_out = false;
-      constexpr int DEP = 4;
-      u64 ring[DEP][4];
-      constexpr RemGroups<NT1> REM = RemGroups<NT1>::make(SPLIT && ICRL_EARLY_PUBLISH && ICRL_EARLY_RECV);
-      auto issue = [&](u64 (&b)[4], int g) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          b[i] = (4 * g + i < KG) ? __hip_atomic_load(theirs + (size_t)(4 * g + i) * TH4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tg;
-      };
-      auto arrived = [&](const u64 (&b)[4]) -> bool {
-        return (unsigned)(b[0] >> 32) == step && (unsigned)(b[1] >> 32) == step && (unsigned)(b[2] >> 32) == step && (unsigned)(b[3] >> 32) == step;
-      };
-#pragma unroll
-      for (int k = 0; k < DEP; ++k)
-        if (k < REM.n) issue(ring[k], REM.v[k]);
-#pragma unroll
-      for (int k = 0; k < REM.n; ++k) {
-        const int g = REM.v[k];
-        u64 (&c)[4] = ring[k % DEP];
-        const bool ok = arrived(c);
-        f32x4& v = grp(g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ok ? v[i] + __uint_as_float((unsigned)c[i]) : v[i];   // own + partner (commutative: both halves agree)
-        pend |= ok ? 0u : (1u << g);
-        if (k + DEP < REM.n) issue(c, REM.v[k + DEP]);
-      }
-      if (__any(pend != 0u)) {
-#pragma unroll
-        for (int g = 0; g < NGRP; ++g) {
-          if (!__any((pend >> g) & 1u)) continue;
-          const bool mine_pending = (pend >> g) & 1u;
-          u64 c[4] = {0, 0, 0, 0};
-          bool ok = !mine_pending;
-          for (int spins = 0; spins < (1 << 22) && !timed_out; ++spins) {
-            if (!ok) { issue(c, g); ok = arrived(c); }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if (spins + 1 == (1 << 22)) timed_out = true;
-          }
-          if (mine_pending && ok) {
-            f32x4& v = grp(g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] += __uint_as_float((unsigned)c[i]);
-          }
-        }
-      }
-      gb1r = gsc[0]; gb2r = gsc[1]; gex = gsc[2];
-      if (book) {
-        float ms[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-          u64 v = 0;
-          for (int spins = 0; spins < (1 << 22) && !timed_out; ++spins) {
-            v = __hip_atomic_load(theirs + (size_t)(KG + k) * TH4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((unsigned)(v >> 32) == step) break;
-            if (spins + 1 == (1 << 22)) timed_out = true;
-          }
-          ms[k] = __uint_as_float((unsigned)v);
-        }
-        mb_s0 += ms[0]; mb_s1 += ms[1]; mb_s2 += ms[2]; mb_s3 += ms[3]; mb_s4 += ms[4];
-      }
-#endif
       if (timed_out) sm[S::MISC + 13] = 1.f;       // reported through the status word like a timed-out norm exchange
     }
 
@@ -1152,10 +883,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
     STAMP(4)   // gradient norm + publish
     // ---- while the granules travel: stage the next minibatch (rows -> the other X^T buffer, advantage statistics)
     const int xnext = S::XDB ? (xcur == S::XT0 ? S::XT1 : S::XT0) : xcur;
-#if ICRL_ROWS_EARLY_POLL
-    u64 v_first = 0;
-    if (tid < 12) v_first = __hip_atomic_load(xch + half * 32 + (step & 1) * 16 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     commit_rows(xnext);
     const int nb_next = __builtin_amdgcn_readfirstlane(ps_next.z) & NB_MASK;
     stats_partials(nb_next);
@@ -1165,10 +892,6 @@ __device__ __forceinline__ void ppo_train_rows_body(const TrainArgs& a, const Tr
       int spins = 0;
       bool ok = false;
       const u64* const slot = xch + half * 32 + (step & 1) * 16 + tid;     // (the three networks of the same half)
-#if ICRL_ROWS_EARLY_POLL
-      v = v_first;
-      if ((unsigned)((v >> 32) & 0x7fffffffu) == step) { ok = true; spins = 1 << 24; }
-#endif
       while (spins < (1 << 24)) {
         v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((unsigned)((v >> 32) & 0x7fffffffu) == step) { ok = true; break; }
@@ -1325,7 +1048,7 @@ __global__ void __launch_bounds__(TH4) ppo_train_rows_batch_kernel(const TrainAr
 
 template <int NT1, bool DISC, bool SPLIT>
 static int launch_rows_batch(const TrainArgs* d_args, int n_runs, hipStream_t s) {
-  const size_t bytes = ICRL_ROWS_STATIC_LDS ? 0 : (size_t)SmemR<NT1>::TOTAL * sizeof(float);
+  const size_t bytes = (size_t)SmemR<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_rows_batch_kernel<NT1, DISC, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   const int pg = packed_grid(SPLIT ? 6 : 3, n_runs);
@@ -1348,7 +1071,7 @@ int launch_train_rows_batch(const TrainArgs* d_args, int n_runs, int nt1, bool d
 template <int NT1, bool DISC, bool SPLIT>
 static int launch_rows(const TrainArgs& a, hipStream_t s) {
   static_assert(SmemR<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
-  const size_t bytes = ICRL_ROWS_STATIC_LDS ? 0 : (size_t)SmemR<NT1>::TOTAL * sizeof(float);
+  const size_t bytes = (size_t)SmemR<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_rows_kernel<NT1, DISC, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;

@@ -2,6 +2,8 @@
 # A/B builds of the update kernels for tools/train_only.py (ICRL_LIB=...): recompiles ppo_train_pairs.hip / ppo_train_rows.hip / ppo_train_halves.hip / ppo_train_quarters*.hip with
 # extra -D flags and links them with the shipped objects of the other files.
 #   bash tools/build_variant.sh fine -DICRL_FINE_PROF          -> icrl_amd/lib/var/libicrl_fine.so
+# The flags the sources know: -DICRL_FINE_PROF (per-wave phase timers) and -DICRL_DIAG=<bits> (tools/diag_train.sh), both in ppo_train_pairs.hip.  The settled
+# experiments of rounds 4-6 are no longer switches; a new experiment brings a -D of its own.
 # The shipped library (icrl_amd/lib/libicrl_hip.so) is never touched.
 set -e
 name=$1; shift
