@@ -20,7 +20,7 @@ import torch
 from . import callbacks, distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import get_true_cost_function, null_cost
+from .true_constraint_net import AnalyticCost, get_true_cost_function, null_cost
 from . import envs, spaces
 
 
@@ -62,9 +62,11 @@ def setup(config, log=print):
     obs_dim = train_env.observation_space.shape[0]
     acs_dim = train_env.action_space.n if is_discrete else train_env.action_space.shape[0]
     if config.use_null_cost:
-        cost_function = null_cost
+        cost_function = AnalyticCost.null()
     elif config.cn_path is None:
         cost_function = get_true_cost_function(config.eval_env_id)
+        if cost_function is null_cost:      # (an id without a ground-truth cost: the null cost, in its device form)
+            cost_function = AnalyticCost.null()
     elif config.load_gail:
         # ref: icrl/cpg.py:54-83 — the cost is the discriminator's output D itself (apply_log=False); numpy in / numpy out like the
         # reference's callable, so it runs through VecCostWrapper's callable branch and the per-step rollout loop
@@ -83,8 +85,9 @@ def setup(config, log=print):
                                             obs_select_dim=config.cn_obs_select_dim, acs_select_dim=config.cn_acs_select_dim,
                                             clip_obs=None, obs_mean=None, obs_var=None)
         cost_function = constraint_net.cost_function
-    # a ConstraintNet cost runs inside the fused rollout launch; null_cost / the analytic true cost (numpy callables) go
-    # through VecCostWrapper's callable branch and the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped)
+    # a ConstraintNet cost and an AnalyticCost (the ground-truth cost, the null cost) run inside the fused rollout launch (device envs:
+    # icrl_rollout_collect_ex, host envs: icrl_host_step); the --load_gail callable goes through VecCostWrapper's callable branch and
+    # the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped), as does an AnalyticCost under ICRL_ANALYTIC_COST_STEPPED=1
     train_env.set_cost_function(cost_function)
     eval_env.set_cost_function(cost_function)
     model = PPOLagrangian(

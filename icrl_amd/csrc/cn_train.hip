@@ -15,6 +15,7 @@
 // broadcast); per-episode products are float32 and may overflow to inf / nan, in which case the comparisons of the
 // early-stop test are false.
 #include "common.h"
+#include "cost_fn.h"
 
 namespace icrl {
 
@@ -574,6 +575,7 @@ __global__ void __launch_bounds__(CN_TH) cn_cost_rows_kernel(icrl_costnet_t cn, 
 // descriptor -> CnDims + dynamic LDS bytes of the 64-row kernels; refuses (fail()) what they do not hold
 static int cn_dims_checked(const icrl_costnet_t* cn, const char* who, CnDims* d, size_t* lds) {
   int H[CN_MAX_LAYERS];
+  if (as_cost_fn(cn)) return refuse_cost_fn(who);      // (an icrl_cost_fn_t has no parameters: nothing to train or to prepare inputs for)
   if (!cn_widths(*cn, H) || cn->in_dim < 1) return fail("%s: %d hidden layers (0..%d), in_dim %d", who, cn->n_hidden, CN_MAX_LAYERS, cn->in_dim);
   for (int l = 0; l < cn->n_hidden; ++l)
     if (H[l] < 1) return fail("%s: hidden layer %d has %d units", who, l, H[l]);
@@ -624,6 +626,7 @@ extern "C" size_t icrl_cn_train_work_floats(int n_params, int Nn, int Ne, int n_
 }
 
 extern "C" int icrl_cn_prepare(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* out, void* stream) {
+  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_prepare");
   if (N <= 0) return fail("icrl_cn_prepare: N = %d rows", N);
   hipLaunchKernelGGL(cn_prepare_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, *cn, obs, acs, N, out);
   return (int)hipGetLastError();
@@ -633,6 +636,7 @@ extern "C" int icrl_cn_prepare(const icrl_costnet_t* cn, const double* obs, cons
 static int make_cn_train_args(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, int32_t* adam_step, const float* nominal,
                               const float* expert, int Nn, int Ne, const int32_t* ep_offsets, const int32_t* row_episode, int n_ep,
                               const icrl_cn_hyper_t* hp, float* work, float* metrics, CnTrainArgs& a, size_t* lds_out) {
+  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_train");
   if (Nn <= 0 || Ne <= 0 || n_ep <= 0 || hp->iterations < 0)
     return fail("icrl_cn_train: needs nominal rows (%d), expert rows (%d), episodes (%d) > 0 and iterations (%d) >= 0", Nn, Ne, n_ep, hp->iterations);
   size_t lds;
@@ -730,6 +734,7 @@ extern "C" int icrl_cn_train_minibatch(const icrl_costnet_t* cn, float* exp_avg,
                                        const int32_t* ep_offsets, const int32_t* row_episode, int n_ep,
                                        const icrl_cn_hyper_t* hp, const int32_t* perms, int batch_size, float* work,
                                        float* metrics, void* stream) {
+  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_train_minibatch");
   if (Nn <= 0 || Ne <= 0 || n_ep <= 0 || hp->iterations < 0 || batch_size <= 0 || perms == nullptr)
     return fail("icrl_cn_train_minibatch: needs nominal rows (%d), expert rows (%d), episodes (%d), batch_size (%d) > 0, iterations (%d) >= 0 "
                 "and a permutation table", Nn, Ne, n_ep, batch_size, hp->iterations);

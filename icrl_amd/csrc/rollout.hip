@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "cost_fn.h"
 #include "generic.h"
 
 namespace icrl {
@@ -413,7 +414,10 @@ __device__ __forceinline__ void env_step_wave(const icrl_env_t& e, int n, const 
 // =================================================================================================================
 struct ActStepArgs {
   icrl_env_t env;
-  icrl_costnet_t cn;
+  union {                 // has_cn: the constraint net, or (the CIT == 0 instantiations) the analytic cost in the same bytes
+    icrl_costnet_t cn;
+    icrl_cost_fn_t cf;
+  };
   icrl_buffer_t buf;
   icrl_agent_t ag;
   PolLayout pl;
@@ -432,7 +436,8 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   load_pol_regs<OCT>(a.pl, a.PT, R);   // every weight load of the step is in flight before anything waits
-  if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);   // wave 3 = cost net
+  if constexpr (CIT > 0) { if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }   // wave 3 = cost net
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost (CIT == 0): kind, index and thresholds are read once, before the step loop
   const int n = blockIdx.x;
   const uint32_t e_key = a.env.key[n];
   uint32_t e_ctr = a.env.step_count[n];
@@ -462,7 +467,8 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
     }
   } else if (w == 3) {
     float cost = 0.f;
-    if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+    if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
     if (lane == 0) { a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost; }
   } else if (w == 2) {
     float* ob = a.buf.observations + tn * O;
@@ -489,8 +495,9 @@ struct GenStepArgs {
   icrl_env_t env;
   icrl_buffer_t buf;
   icrl_agent_t ag;
-  int has_cn;
+  int has_cn;           // 1: ag.raw_cost holds the constraint net's cost of this step; 2: the analytic cost `cf`, evaluated here
   double* raw_plane;    // see ActStepArgs
+  icrl_cost_fn_t cf;
 };
 
 __global__ void __launch_bounds__(64) act_step_generic_kernel(GenStepArgs a, int t) {
@@ -519,7 +526,7 @@ __global__ void __launch_bounds__(64) act_step_generic_kernel(GenStepArgs a, int
   if (lane == 0) {
     a.ag.raw_rew[n] = rew; a.ag.dones[n] = (uint8_t)done;
     if (a.raw_plane != nullptr) a.raw_plane[tn] = rew;
-    const float cost = a.has_cn ? a.ag.raw_cost[n] : 0.f;
+    const float cost = a.has_cn == 2 ? cost_fn_wave(a.cf, s_old, act_clip) : (a.has_cn ? a.ag.raw_cost[n] : 0.f);
     a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
     a.buf.dones[tn] = (float)a.ag.last_dones[n];
     a.ag.last_v_r[n] = a.buf.reward_values[tn];
@@ -1082,7 +1089,8 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   load_pol_regs<OCT>(a.pl, a.PT, R);
-  if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
+  if constexpr (CIT > 0) { if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost (CIT == 0): kind, index and thresholds are read once, before the step loop
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1161,7 +1169,8 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
       }
     } else if (w == 3) {
       float cost = 0.f;
-      if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+      if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
       if (lane == 0) {
         if (GRAN) rstore(((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
         else xstore(as_global(p.xch_cost) + par * N + n, cost);
@@ -1351,7 +1360,8 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
   double* const raw_plane = MON ? as_global(a.raw_plane) : nullptr;
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
-  if ((threadIdx.x >> 6) == 3 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
+  if constexpr (CIT > 0) { if ((threadIdx.x >> 6) == 3 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost (CIT == 0): kind, index and thresholds are read once, before the step loop
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const int ctid = tid < 256 ? tid : (1 << 28);      // (the threads beyond the first 256 only take part in the forward)
@@ -1439,7 +1449,8 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
       }
     } else if (w == 3) {
       float cost = 0.f;
-      if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+      if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
       if (lane == 0) {
         if (GRAN) rstore(((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
         else xstore(as_global(p.xch_cost) + par * N + n, cost);
@@ -1659,7 +1670,8 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   load_pol_regs<OCT>(a.pl, a.PT, R);
-  if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
+  if constexpr (CIT > 0) { if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost (CIT == 0): kind, index and thresholds are read once, before the step loop
   const int g = blockIdx.x, G = p.G;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1743,7 +1755,8 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
         }
       } else if (w == 3) {
         float cost = 0.f;
-        if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh[e].s_old, sh[e].act_clip, sh[e].cx, sh[e].ch);
+        if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh[e].s_old, sh[e].act_clip);
+        else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh[e].s_old, sh[e].act_clip, sh[e].cx, sh[e].ch);
         if (lane == 0) {
           rstore(xrs, xrec + 16 * (O + 1), rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
           a.buf.orig_costs[tn] = cost;
@@ -2148,8 +2161,13 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
   const float* const noise_g = as_global(a.noise);
   double* const raw_plane = MON ? as_global(a.raw_plane) : nullptr;
   TileRegs<OCT, CIT> R;                // waves 0..2: policy / value / cost-value net, wave 3: cost net — as MFMA A operands
-  if (threadIdx.x >= 192 && a.has_cn) load_cn_tiles<OCT, CIT>(a.cn, a.cl, R, sh.cst[3]);
-  else load_pol_tiles<OCT, CIT>(a.pl, a.PT, R, sh.cst[threadIdx.x >> 6]);
+  if constexpr (CIT > 0) {
+    if (threadIdx.x >= 192 && a.has_cn) load_cn_tiles<OCT, CIT>(a.cn, a.cl, R, sh.cst[3]);
+    else load_pol_tiles<OCT, CIT>(a.pl, a.PT, R, sh.cst[threadIdx.x >> 6]);
+  } else {                             // analytic cost (CIT == 0): no cost tiles are loaded or run
+    load_pol_tiles<OCT, CIT>(a.pl, a.PT, R, sh.cst[threadIdx.x >> 6]);
+  }
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost: kind, index and thresholds are read once, before the step loop
   const int g = g_arg, G = p.G;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2415,6 +2433,15 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
           rstore(xrs, xrec + 16 * O, rec_u4{gtag, (unsigned)bits, (unsigned)(bits >> 32), gtag | (done ? 0x80000000u : 0u)});
           sh.ctr[e] = e_ctr; sh.tep[e] = e_tep; sh.rew[e] = rew; sh.done[e] = done;
         }
+      }
+    } else if constexpr (CIT == 0) {
+      // analytic cost (wave 3): one lane per env does the compare on the env's own rows
+      if (lane < Eg) {
+        const int n = g + lane * G;
+        const float cost = cost_fn_wave(cf, sh.s_old[lane], sh.act_clip[lane]);
+        rstore(xrs, ((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
+        buf.orig_costs[(size_t)t * N + n] = cost;
+        sh.cost[lane] = cost;
       }
     } else if (has_cost) {
       // cost net of all E envs at once (wave 3): prepare() per env into cx, then the ReLU layers as MFMA tiles
@@ -2685,6 +2712,15 @@ __global__ void __launch_bounds__(256) rollout_multi_kernel(WideArgs p, int pack
 }
 
 // several independent runs in ONE launch: grid (G, n_runs), run = blockIdx.y
+// the analytic-cost form (CIT == 0: no cost tiles) as a kernel of its own name, single-run launches only.  The name sorts behind
+// every other kernel that calls env_step_wave3: the compiler numbers those kernels in name order and passes the number to the callee
+// (s15), so an instantiation of rollout_multi_kernel itself would renumber — and thereby change one immediate in — the shipped ones
+template <int OCT, int E, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_multi_analytic_kernel(WideArgs p, int packed) {
+  if (packed && (blockIdx.x & 7) != 0) return;
+  rollout_multi_body<OCT, 0, E, MON>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+}
+
 template <int OCT, int CIT, int E, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_multi_batch_kernel(const WideArgs* __restrict__ runs, int n_runs, int G, int packed) {
   __shared__ WideArgs p;
@@ -2904,6 +2940,14 @@ __global__ void __launch_bounds__(64) cost_forward_kernel(icrl_costnet_t cn, CnL
   if (threadIdx.x == 0) cost[n] = c;
 }
 
+// an analytic cost on N rows of the caller's arrays (icrl_cost_fn_rows): one row per thread, grid-stride, no LDS
+__global__ void __launch_bounds__(256) cost_fn_rows_kernel(icrl_cost_fn_t f, const double* __restrict__ obs, const float* __restrict__ acs, int N,
+                                                           float* __restrict__ cost) {
+  const int AS = f.kind == ICRL_COST_ACTION_EQUALS ? 1 : f.acs_dim;      // (the class index when discrete)
+  for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
+    cost[n] = cost_fn_wave(f, obs + (size_t)n * f.obs_dim, acs + (size_t)n * AS);
+}
+
 __global__ void __launch_bounds__(64) env_step_kernel(icrl_env_t e, const float* actions, double* raw_rew, uint8_t* dones) {
   __shared__ double s_old[MAX_OBS];
   const int n = blockIdx.x;
@@ -3094,8 +3138,9 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
   const int T = h.hs.T;
   if (k < T) {
     load_pol_regs<OCT>(a.pl, a.PT, R);
-    if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C);
+    if constexpr (CIT > 0) { if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }
   }
+  const icrl_cost_fn_t cf = a.cf;      // analytic cost (CIT == 0): kind, index and thresholds are read once, before the step loop
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3231,7 +3276,8 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
     if (lane < AH) h.hs.act_host[(size_t)n * AH + lane] = sh.act_clip[lane];
   } else if (w == 3) {
     float cost = 0.f;
-    if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+    if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
     if (lane == 0) {
       a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
       dst.cost[n] = (double)cost;              // read by every workgroup of launch k + 1 (ag.raw_cost[n] is rewritten by launch k + 1)
@@ -3342,6 +3388,7 @@ extern "C" int icrl_policy_prepare(const icrl_policy_t* p, void* stream) {
 }
 
 extern "C" int icrl_costnet_prepare(const icrl_costnet_t* cn, void* stream) {
+  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_costnet_prepare");
   if (cn->n_hidden > 2 || cn->n_hidden == 0) return 0;      // served 64 rows per workgroup from `params` (cn_train.hip): no transposed copy
   if (!costnet_is_wide(cn) && !cn_ok(cn)) return bad_cn("icrl_costnet_prepare", cn);
   CnLayout L = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2);
@@ -3583,8 +3630,21 @@ extern "C" int icrl_sample_episodes_batch(int n_runs, const icrl_sample_job_t* j
   return (int)hipGetLastError();
 }
 
+extern "C" int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, const float* acs, int N, float* cost, void* stream) {
+  if (cf == nullptr || cf->n_hidden != ICRL_COST_FN) return fail("icrl_cost_fn_rows: not an analytic cost descriptor (n_hidden must be ICRL_COST_FN)");
+  if (int e = cost_fn_check("icrl_cost_fn_rows", cf, 0, 0, -1)) return e;
+  if (N <= 0 || cost == nullptr) return fail("icrl_cost_fn_rows: N = %d rows, cost = %p", N, (void*)cost);
+  const bool wall = cf->kind == ICRL_COST_WALL_BEHIND || cf->kind == ICRL_COST_WALL_INFRONT || cf->kind == ICRL_COST_WALL_BOTH;
+  if ((wall && obs == nullptr) || ((cf->kind == ICRL_COST_TORQUE || cf->kind == ICRL_COST_ACTION_EQUALS) && acs == nullptr))
+    return fail("icrl_cost_fn_rows: cost kind %d reads the %s, which is NULL", cf->kind, wall ? "observations" : "actions");
+  const int grid = (N + 255) / 256 < 1024 ? (N + 255) / 256 : 1024;
+  hipLaunchKernelGGL(cost_fn_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *cf, obs, acs, N, cost);
+  return (int)hipGetLastError();
+}
+
 extern "C" int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* cost,
                                      void* stream) {
+  if (const icrl_cost_fn_t* cf = as_cost_fn(cn)) return icrl_cost_fn_rows(cf, obs, acs, N, cost, stream);
   if (N <= 0) return fail("cost forward: N = %d rows", N);
   if (costnet_is_wide(cn)) return launch_cn_cost_rows(cn, obs, acs, N, cost, 0, (hipStream_t)stream);
   if (!cn_ok(cn)) return bad_cn("cost forward", cn);
@@ -3596,6 +3656,7 @@ extern "C" int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs
 
 extern "C" int icrl_disc_reward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* out, int apply_log,
                                 void* stream) {
+  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_disc_reward");
   if (N <= 0) return fail("cost forward: N = %d rows", N);
   if (costnet_is_wide(cn)) return launch_cn_cost_rows(cn, obs, acs, N, out, apply_log ? 2 : 1, (hipStream_t)stream);
   if (!cn_ok(cn)) return bad_cn("cost forward", cn);
@@ -3707,6 +3768,24 @@ static int launch_multi_e(const WideArgs* one, const WideArgs* d_args, int n_run
 }
 
 // one: single-run launch (argument block by value) | d_args: n_runs blocks in device memory.  -1: does not fit the device
+// the analytic-cost kernels (rollout_multi_analytic_kernel), single-run launches only: launch_multi_e's first branch
+template <int OCT, int E, bool MON>
+static int launch_multi_fn_e(const WideArgs* one, int G, size_t dyn, hipStream_t s) {
+  if (!persistent_fits(rollout_multi_analytic_kernel<OCT, E, MON>, G, dyn)) return -1;
+  WideArgs arg = *one;
+  static const bool no_pack = getenv("ICRL_NO_XCD_PACK") != nullptr;
+  const int packed = !no_pack && arg.xcc != nullptr && G <= 32;
+  void* params[] = {(void*)&arg, (void*)&packed};
+  const hipError_t e = hipLaunchCooperativeKernel((const void*)rollout_multi_analytic_kernel<OCT, E, MON>, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
+  if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
+  return (int)e;
+}
+template <bool MON>
+static int launch_multi_fn(bool small, int E, const WideArgs* one, int G, size_t dyn, hipStream_t s) {
+  if (small) return E == 16 ? launch_multi_fn_e<2, 16, MON>(one, G, dyn, s) : (E == 8 ? launch_multi_fn_e<2, 8, MON>(one, G, dyn, s) : launch_multi_fn_e<2, 4, MON>(one, G, dyn, s));
+  return E == 16 ? launch_multi_fn_e<8, 16, MON>(one, G, dyn, s) : (E == 8 ? launch_multi_fn_e<8, 8, MON>(one, G, dyn, s) : launch_multi_fn_e<8, 4, MON>(one, G, dyn, s));
+}
+
 template <bool MON>
 static int launch_multi_m(bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
   // cn128: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
@@ -3734,18 +3813,25 @@ static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane)
 }
 
 extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
-                                           const icrl_costnet_t* cn, const icrl_buffer_t* buf, const icrl_agent_t* ag,
+                                           const icrl_costnet_t* cn_arg, const icrl_buffer_t* buf, const icrl_agent_t* ag,
                                            const float* noise, const float* action_low, const float* action_high,
                                            double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
                                            int do_gae, const icrl_monitor_t* mon, void* stream) {
   double* raw_plane = nullptr;
   if (int e = mon_plane("icrl_rollout_collect_ex_mon", mon, &raw_plane)) return e;
   const int N = env->n_envs, O = env->obs_dim, T = buf->T;
-  const bool generic = policy_is_wide(pol) || (cn != nullptr && costnet_is_wide(cn));      // shapes of the generic-shape path: per-step launches
+  // an analytic cost (icrl_cost_fn_t behind the constraint-net pointer): `cn` stays the "this chain has a cost" flag, `net` is the
+  // constraint net proper (NULL then) — only `net` is ever read as an icrl_costnet_t
+  const icrl_cost_fn_t* const cf = as_cost_fn(cn_arg);
+  if (cf != nullptr)
+    if (int e = cost_fn_check("icrl_rollout_collect", cf, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
+  const icrl_costnet_t* const net = cf != nullptr ? nullptr : cn_arg;
+  const bool cn = cn_arg != nullptr;
+  const bool generic = policy_is_wide(pol) || (net != nullptr && costnet_is_wide(net));      // shapes of the generic-shape path: per-step launches
   if (!generic && !dims_ok(pol)) return bad_dims("icrl_rollout_collect", pol);
   if (pol->obs_dim != O || buf->N != N || buf->obs_dim != O)
     return fail("icrl_rollout_collect: env (%d envs, obs_dim %d) vs policy obs_dim %d vs buffer (%d envs, obs_dim %d)", N, O, pol->obs_dim, buf->N, buf->obs_dim);
-  if (!generic && cn != nullptr && !cn_ok(cn)) return bad_cn("icrl_rollout_collect", cn);
+  if (!generic && net != nullptr && !cn_ok(net)) return bad_cn("icrl_rollout_collect", net);
   if (N > NORM_MAX_N)
     return fail("icrl_rollout_collect: %d envs on one GPU, limit %d (shard the envs over ranks: the float64 normaliser statistics are one "
                 "numpy-ordered chain per column)", N, NORM_MAX_N);
@@ -3761,7 +3847,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                   buf->act_store, env->act_dim, pol->act_dim);
     // ONE persistent launch (rollout_generic_kernel: the loop of rollout_persistent_kernel around the table-driven forward) when the
     // shapes are those of the one-workgroup-per-env kernel and the constraint net fits its register image; do_gae & 2 forces the per-step launches
-    if (policy_is_wide(pol) && (cn == nullptr || (!costnet_is_wide(cn) && cn_ok(cn))) && !(do_gae & 2) && N <= 128 && N * O <= NORM_CHUNK &&
+    if (policy_is_wide(pol) && (net == nullptr || (!costnet_is_wide(net) && cn_ok(net))) && !(do_gae & 2) && N <= 128 && N * O <= NORM_CHUNK &&
         O * env->act_dim <= MAX_OBS * MAX_ACT && (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX && pol->params_t != nullptr) {
       GenRolloutArgs ga;
       if (int e = make_gen_net(pol, &ga.net, "icrl_rollout_collect")) return e;
@@ -3776,8 +3862,9 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
         a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, MAX_H, MAX_H, pol->discrete);      // (only obs / act / discrete are read)
         a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
-        a.has_cn = cn != nullptr;
-        if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
+        a.has_cn = cn;
+        if (net) { a.cn = *net; a.cl = make_cn_layout(net->in_dim, net->n_hidden, net->h1, net->h2); }
+        else if (cf) a.cf = *cf;
         p.nm = *nm; p.T = T; p.prof = (do_gae & 4) != 0;
         char* base = ws;
         p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
@@ -3789,7 +3876,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G2 / 2));
         hipError_t e = hipMemsetAsync(p.counter, 0, 512 + (size_t)16 * N * G2, s);
         if (e != hipSuccess) return (int)e;
-        const bool small = O <= 32 && (!cn || cn->in_dim <= 32);
+        const bool small = O <= 32 && (!net || net->in_dim <= 32);
         const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
         const int threads = 256;
         auto go = [&](auto kernel) -> int {      // -1: the grid is not co-resident
@@ -3801,8 +3888,10 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
           if (e_ == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
           return (int)e_;
         };
-        const int perr = raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 2, true>) : go(rollout_generic_kernel<8, 10, true>))
-                                               : (small ? go(rollout_generic_kernel<2, 2>) : go(rollout_generic_kernel<8, 10>));
+        const int perr = cf != nullptr ? (raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 0, true>) : go(rollout_generic_kernel<8, 0, true>))
+                                                               : (small ? go(rollout_generic_kernel<2, 0>) : go(rollout_generic_kernel<8, 0>)))
+                         : raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 2, true>) : go(rollout_generic_kernel<8, 10, true>))
+                                                : (small ? go(rollout_generic_kernel<2, 2>) : go(rollout_generic_kernel<8, 10>));
         if (perr >= 0) {
           const int err = perr != 0 ? perr : (int)hipGetLastError();
           if (err || !(do_gae & 1)) return err;
@@ -3813,7 +3902,8 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       }
     }
     GenStepArgs g;
-    g.env = *env; g.buf = *buf; g.ag = *ag; g.has_cn = cn != nullptr; g.raw_plane = raw_plane;
+    g.env = *env; g.buf = *buf; g.ag = *ag; g.has_cn = cf != nullptr ? 2 : (cn ? 1 : 0); g.raw_plane = raw_plane;
+    g.cf = cf != nullptr ? *cf : icrl_cost_fn_t{};      // (the analytic cost is evaluated inside act_step_generic_kernel: no cost launch)
     const int AS = buf->act_store;
     for (int t = 0; t < T; ++t) {
       const size_t row = (size_t)t * N;
@@ -3823,8 +3913,8 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
           : icrl_policy_forward(pol, ag->last_obs, noise ? noise + row * AS : nullptr, N, 0, action_low, action_high, buf->actions + row * AS, ag->act_clipped,
                                 buf->reward_values + row, buf->cost_values + row, buf->log_probs + row, stream);
       if (err) return err;
-      if (cn != nullptr) {
-        err = icrl_cost_mlp_forward(cn, env->s, ag->act_clipped, N, ag->raw_cost, stream);
+      if (net != nullptr) {
+        err = icrl_cost_mlp_forward(net, env->s, ag->act_clipped, N, ag->raw_cost, stream);
         if (err) return err;
       }
       hipLaunchKernelGGL(act_step_generic_kernel, dim3(N), dim3(64), 0, s, g, t);
@@ -3842,8 +3932,9 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
   a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
   a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
-  a.has_cn = cn != nullptr;
-  if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
+  a.has_cn = cn;
+  if (net) { a.cn = *net; a.cl = make_cn_layout(net->in_dim, net->n_hidden, net->h1, net->h2); }
+  else if (cf) a.cf = *cf;
   // several environments per workgroup, interleaved (rollout_multi_kernel): do_gae bit 5
   if (((do_gae & 32) || N > WIDE_MAX_N) && !(do_gae & 2) && nm->training && !pol->discrete && N <= NORM_MAX_N && T >= 1) {
     int E = 0, G = 0;
@@ -3860,8 +3951,10 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       p.xcc = G <= 32 ? p.sg + 2 * GS : nullptr;      // (the workgroups' XCD ids: the 256 spare bytes behind the statistics granules)
       hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS + (p.xcc ? 256 : 0), s);
       if (e != hipSuccess) return (int)e;
-      const bool small = a.pl.O <= 32 && (!cn || cn->in_dim <= 32);
-      const int err = launch_multi(raw_plane != nullptr, small, !cn || cn->in_dim <= 128, E, &p, nullptr, 1, G, multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G), s);
+      const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
+      const size_t mdyn = multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G);
+      const int err = cf != nullptr ? (raw_plane != nullptr ? launch_multi_fn<true>(small, E, &p, G, mdyn, s) : launch_multi_fn<false>(small, E, &p, G, mdyn, s))
+                                    : launch_multi(raw_plane != nullptr, small, !net || net->in_dim <= 128, E, &p, nullptr, 1, G, mdyn, s);
       if (err >= 0) {
         if (err || !(do_gae & 1)) return err;
         return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
@@ -3874,9 +3967,11 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   // many environments: persistent launch with the statistics partitioned by observation column (rollout_wide_kernel); measured
   // against the replicated-statistics kernel at HC widths: 64 envs 9.6 vs 9.5 us per step, 128 envs 9.9 vs 13.9
   if (!(do_gae & 2) && nm->training && (N > 96 || N * O > NORM_CHUNK || (do_gae & 16)) && N <= WIDE_MAX_N && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1) {
-    const bool small = a.pl.O <= 32 && (!cn || cn->in_dim <= 32);
+    const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
     const bool monv = raw_plane != nullptr;      // (with the plane: the instantiations without phase timers)
-    const void* kfn = monv ? (small ? (const void*)rollout_wide_kernel<2, 2, false, true> : (const void*)rollout_wide_kernel<8, 10, false, true>)
+    const void* kfn = cf != nullptr ? (monv ? (small ? (const void*)rollout_wide_kernel<2, 0, false, true> : (const void*)rollout_wide_kernel<8, 0, false, true>)
+                                            : (small ? (const void*)rollout_wide_kernel<2, 0> : (const void*)rollout_wide_kernel<8, 0>))
+                      : monv ? (small ? (const void*)rollout_wide_kernel<2, 2, false, true> : (const void*)rollout_wide_kernel<8, 10, false, true>)
                            : (small ? (const void*)rollout_wide_kernel<2, 2> : (const void*)rollout_wide_kernel<8, 10>);
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
@@ -3897,8 +3992,12 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         p.xcc = nullptr;
         hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS, s);
         if (e != hipSuccess) return (int)e;
-        if (monv) p.prof = 0;
-        int err = monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, false, true>, dim3(G), dim3(256), 0, s, p)
+        if (monv || cf != nullptr) p.prof = 0;      // (the analytic-cost instantiations: no phase timers either)
+        int err = cf != nullptr ? (monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 0, false, true>, dim3(G), dim3(256), 0, s, p)
+                                                      : launch_coresident(rollout_wide_kernel<8, 0, false, true>, dim3(G), dim3(256), 0, s, p))
+                                        : (int)(small ? launch_coresident(rollout_wide_kernel<2, 0>, dim3(G), dim3(256), 0, s, p)
+                                                      : launch_coresident(rollout_wide_kernel<8, 0>, dim3(G), dim3(256), 0, s, p)))
+                  : monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, false, true>, dim3(G), dim3(256), 0, s, p)
                                      : launch_coresident(rollout_wide_kernel<8, 10, false, true>, dim3(G), dim3(256), 0, s, p))
                   : p.prof ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, true>, dim3(G), dim3(256), 0, s, p)
                                        : launch_coresident(rollout_wide_kernel<8, 10, true>, dim3(G), dim3(256), 0, s, p))
@@ -3934,7 +4033,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G / 2));      // index split by the records per env (obs + 2)
       hipError_t e = hipMemsetAsync(p.counter, 0, 512 + (gran ? (size_t)16 * N * G : 0), s);
       if (e != hipSuccess) return (int)e;
-      const bool small = a.pl.O <= 32 && (!cn || cn->in_dim <= 32);
+      const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
       const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
       int coop_err = 0;
       auto go = [&](auto kernel) -> bool {
@@ -3945,7 +4044,18 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         return true;
       };
       bool launched;
-      if (raw_plane != nullptr) {      // the instantiations that store the raw-reward plane (no phase timers)
+      if (cf != nullptr) {             // the analytic-cost instantiations (CIT == 0: no cost-net register image; no phase timers)
+        p.prof = 0;
+        if (raw_plane != nullptr) {
+          if (small && gran) launched = go(rollout_persistent_kernel<2, 0, true, false, true>);
+          else if (small) launched = go(rollout_persistent_kernel<2, 0, false, false, true>);
+          else if (gran) launched = go(rollout_persistent_kernel<8, 0, true, false, true>);
+          else launched = go(rollout_persistent_kernel<8, 0, false, false, true>);
+        } else if (small && gran) launched = go(rollout_persistent_kernel<2, 0, true>);
+        else if (small) launched = go(rollout_persistent_kernel<2, 0, false>);
+        else if (gran) launched = go(rollout_persistent_kernel<8, 0, true>);
+        else launched = go(rollout_persistent_kernel<8, 0, false>);
+      } else if (raw_plane != nullptr) {      // the instantiations that store the raw-reward plane (no phase timers)
         p.prof = 0;
         if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true, false, true>);
         else if (small) launched = go(rollout_persistent_kernel<2, 2, false, false, true>);
@@ -3971,7 +4081,10 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   }
 per_step:
   for (int t = 0; t < T; ++t) {
-    if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((act_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, a, t);
+    if (cf != nullptr) {
+      if (a.pl.O <= 32) hipLaunchKernelGGL((act_step_kernel<2, 0>), dim3(N), dim3(256), 0, s, a, t);
+      else hipLaunchKernelGGL((act_step_kernel<8, 0>), dim3(N), dim3(256), 0, s, a, t);
+    } else if (a.pl.O <= 32 && (!net || net->in_dim <= 32)) hipLaunchKernelGGL((act_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, a, t);
     else hipLaunchKernelGGL((act_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, a, t);
     const size_t row = (size_t)t * N;
     NormStepArgs b{*nm, env->s, ag->raw_rew, cn ? ag->raw_cost : nullptr, ag->dones, N, O, ag->last_obs, nullptr, nullptr,
@@ -3994,6 +4107,8 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
                                               double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
   static_assert(sizeof(PersistArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
+  for (int r = 0; r < n_runs; ++r)      // (seed batches are ICRL runs: they carry a constraint net)
+    if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
   if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
     return fail("icrl_rollout_collect_batch: args_ws holds %lld B, %d runs need %lld", args_ws_bytes, n_runs, (long long)n_runs * ICRL_BATCH_ARGS_BYTES);
   hipStream_t s = (hipStream_t)stream;
@@ -4171,7 +4286,10 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   if (nm == nullptr || pol == nullptr || buf == nullptr || ag == nullptr || hs == nullptr) return fail("icrl_host_step: NULL descriptor");
   const int N = buf->N, O = buf->obs_dim, T = hs->T;
   if (policy_is_wide(pol) || !dims_ok(pol)) return bad_dims("icrl_host_step", pol);
-  if (cn != nullptr && (costnet_is_wide(cn) || !cn_ok(cn))) return bad_cn("icrl_host_step", cn);
+  const icrl_cost_fn_t* const cf = as_cost_fn(cn);
+  if (cf != nullptr) {
+    if (int e = cost_fn_check("icrl_host_step", cf, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
+  } else if (cn != nullptr && (costnet_is_wide(cn) || !cn_ok(cn))) return bad_cn("icrl_host_step", cn);
   if (N < 1 || N > 128 || O < 1 || O > MAX_OBS || pol->obs_dim != O)
     return fail("icrl_host_step: %d envs (1..128), obs_dim %d (1..%d), policy obs_dim %d: other shapes take the per-step loop", N, O, MAX_OBS, pol->obs_dim);
   if (!nm->training) return fail("icrl_host_step: the normaliser is not training (statistics frozen): the per-step loop serves that");
@@ -4188,7 +4306,8 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
   a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
   a.has_cn = cn != nullptr;
-  if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
+  if (cf) a.cf = *cf;
+  else if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
   h.nm = *nm; h.hs = *hs; h.N = N;
   // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
   void* act_dev = nullptr;
@@ -4198,7 +4317,10 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   }
   h.hs.act_host = reinterpret_cast<float*>(act_dev);
   hipStream_t s = (hipStream_t)stream;
-  if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
+  if (cf != nullptr) {      // the analytic-cost instantiations (CIT == 0)
+    if (a.pl.O <= 32) hipLaunchKernelGGL((host_step_kernel<2, 0>), dim3(N), dim3(256), 0, s, h, k);
+    else hipLaunchKernelGGL((host_step_kernel<8, 0>), dim3(N), dim3(256), 0, s, h, k);
+  } else if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
   else hipLaunchKernelGGL((host_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, h, k);
   return (int)hipGetLastError();
 }

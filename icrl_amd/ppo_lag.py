@@ -192,12 +192,20 @@ class PPOLagrangian:
         cw = env.venv
         if isinstance(cw, HipSynthVecEnv):           # no cost wrapper in the chain (the GAIL baseline, icrl/gail.py:50-59): costs are 0
             return env, None, cw
-        if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HipSynthVecEnv) or cw.constraint_net() is None:
+        if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HipSynthVecEnv) or not self._fused_cost_ok(cw):
             return None
         return env, cw, cw.venv
 
+    @staticmethod
+    def _fused_cost_ok(cw):
+        """a cost the rollout kernels evaluate themselves: a device ConstraintNet, or an AnalyticCost (true_constraint_net.py; the ground-truth
+        and null costs of cpg) unless ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step loop over the same cost object."""
+        if cw.constraint_net() is not None:
+            return True
+        return cw.analytic_cost() is not None and os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") in ("", "0")
+
     def _host_chain(self):
-        """the counterpart of _fused_chain over host envs: VecNormalizeWithCost -> [VecCostWrapper with a device ConstraintNet] ->
+        """the counterpart of _fused_chain over host envs: VecNormalizeWithCost -> [VecCostWrapper with a device ConstraintNet or an AnalyticCost] ->
         HostVecEnv (without the cost wrapper: the GAIL chain)."""
         env = self.env
         if not isinstance(env, VecNormalizeWithCost):
@@ -205,7 +213,7 @@ class PPOLagrangian:
         cw = env.venv
         if isinstance(cw, HostVecEnv):
             return env, None, cw
-        if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HostVecEnv) or cw.constraint_net() is None:
+        if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HostVecEnv) or not self._fused_cost_ok(cw):
             return None
         return env, cw, cw.venv
 
@@ -256,7 +264,7 @@ class PPOLagrangian:
         if noise is None:
             noise = self._draw_action_noise(n_rollout_steps)
         e, nm, pol, buf = senv.struct(), nenv.struct(), self.policy.struct(), rollout_buffer.struct()
-        cn = cw.constraint_net().struct() if cw is not None else None
+        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, or an analytic cost's)
         ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
                     p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
                     p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
@@ -328,7 +336,7 @@ class PPOLagrangian:
         if chain is None or not isinstance(cost_function, str) or n_rollout_steps != rollout_buffer.buffer_size:
             return False
         nenv, cw, henv = chain
-        cn = cw.constraint_net() if cw is not None else None
+        cn = cw.constraint_net() if cw is not None else None      # (None for an AnalyticCost: it has no shape limits of its own)
         # the limits icrl_host_step checks (csrc/rollout.hip: dims_ok / cn_ok — obs <= MAX_OBS 128, act <= MAX_ACT 16, hidden <= MAX_H 64
         # (`wide`), cost-net inputs <= MAX_CN_IN 160 — and N <= 128); other shapes take the per-step loop
         pol_ok = not self.policy.wide and self.policy.obs_dim <= 128 and self.policy.act_dim <= 16
@@ -357,7 +365,7 @@ class PPOLagrangian:
         self._last_obs = self._last_obs.to(device=self.device, dtype=torch.float64).contiguous()
         hs = HostStepT(T, 0, p(st["dev"]), p(henv.s), st["act"].data_ptr(), p(self._host_ws), self._host_ws.numel() * 8)
         nm, pol, buf = nenv.struct(), self.policy.struct(), rollout_buffer.struct()
-        cn = cw.constraint_net().struct() if cw is not None else None
+        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, or an analytic cost's)
         ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
                     p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
                     p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
@@ -431,8 +439,8 @@ class PPOLagrangian:
     def _collect_rollouts_stepped(self, env, callback, rollout_buffer, n_rollout_steps, cost_function, noise=None):
         """The reference's per-step loop, kept for everything the fused launch does not cover: a callable `cost_function`
         (warm-up with null_cost, icrl/icrl.py:187-193; costs are then evaluated on the observation AFTER the step and are not
-        normalised, on_policy_algorithm.py:392-394), an env cost that is an arbitrary Python function (cpg with the analytic
-        cost), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
+        normalised, on_policy_algorithm.py:392-394), an env cost that is an arbitrary Python function (cpg --load_gail; an
+        AnalyticCost under ICRL_ANALYTIC_COST_STEPPED=1), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
         rollout_buffer.reset()
         if callback is not None:
             callback.on_rollout_start()

@@ -30,6 +30,16 @@ class CostNetT(C.Structure):
                 ("obs_var", vp), ("eps", f64), ("params", vp), ("params_t", vp)]
 
 
+COST_FN = -1      # ICRL_COST_FN: the value of n_hidden that marks an analytic cost
+COST_NULL, COST_WALL_BEHIND, COST_WALL_INFRONT, COST_WALL_BOTH, COST_TORQUE, COST_ACTION_EQUALS = range(6)
+
+
+class CostFnT(C.Structure):
+    """icrl_cost_fn_t: an analytic cost; its first four fields alias CostNetT's and it travels through the same pointer arguments."""
+    _fields_ = [("obs_dim", i32), ("acs_dim", i32), ("in_dim", i32), ("n_hidden", i32), ("kind", i32), ("index", i32),
+                ("lo", f64), ("hi", f64)]
+
+
 class BufferT(C.Structure):
     _fields_ = [("T", i32), ("N", i32), ("obs_dim", i32), ("act_store", i32),
                 ("observations", vp), ("new_observations", vp), ("orig_observations", vp), ("new_orig_observations", vp),

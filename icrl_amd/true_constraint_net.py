@@ -1,8 +1,16 @@
-"""Ground-truth cost functions used for the `true/cost` metric (ref: icrl/true_constraint_net.py:11-55)."""
-from functools import partial
+"""Ground-truth cost functions: what `cpg` trains the expert against and the `true/cost` metric
+(ref: icrl/true_constraint_net.py:11-55, 104-111).
 
+`get_true_cost_function` returns `AnalyticCost` objects: closed forms on (previous raw observation, clipped action) that the library
+evaluates inside the fused rollout launches (icrl_cost_fn_t, csrc/cost_fn.h) and, on device tensors, through icrl_cost_fn_rows.  On numpy
+arrays they compute exactly what the reference's functions compute.  The module-level `wall_behind`, `null_cost` and `lap_grid_world` stay
+plain numpy functions (callables handed to `learn(cost_function=...)` keep the per-step loop and its semantics).
+"""
 import numpy as np
 import torch
+
+from . import _lib
+from .structs import (COST_ACTION_EQUALS, COST_FN, COST_NULL, COST_TORQUE, COST_WALL_BEHIND, COST_WALL_BOTH, COST_WALL_INFRONT, CostFnT, p)
 
 
 def wall_behind(pos, obs, acs):
@@ -19,14 +27,114 @@ def lap_grid_world(obs, acs):
     return a == 1
 
 
+class AnalyticCost:
+    """One of the reference's ground-truth costs (or the null cost) as a description the kernels can evaluate.
+
+    numpy in -> numpy out, the reference's function operation for operation (same dtype: bool for the single walls, torque and
+    action_equals, float32 for the two-wall sum, float64 zeros for the null cost; `acs` may be None where it is not read; leading batch
+    dimensions as the reference's functions take them).  Device tensors in -> a float32 device tensor from icrl_cost_fn_rows.
+    `.struct(obs_dim, acs_dim)` is the descriptor the rollout entry points take in place of a constraint net's."""
+
+    WALLS = (COST_WALL_BEHIND, COST_WALL_INFRONT, COST_WALL_BOTH)
+
+    def __init__(self, kind, index=0, lo=0.0, hi=0.0, name="analytic"):
+        self.kind, self.index, self.lo, self.hi, self.name = int(kind), int(index), lo, hi, name
+
+    # ---- constructors (ref: icrl/true_constraint_net.py:40-54, 104-111) ----
+    @classmethod
+    def null(cls):
+        return cls(COST_NULL, name="null_cost")
+
+    @classmethod
+    def wall_behind(cls, pos, index=0):
+        return cls(COST_WALL_BEHIND, index, lo=pos, name="wall_behind")
+
+    @classmethod
+    def wall_infront(cls, pos, index=0):
+        return cls(COST_WALL_INFRONT, index, hi=pos, name="wall_infront")
+
+    @classmethod
+    def wall_behind_and_infront(cls, back, front, index=0):
+        return cls(COST_WALL_BOTH, index, lo=back, hi=front, name="wall_behind_and_infront")
+
+    @classmethod
+    def torque(cls, threshold):
+        return cls(COST_TORQUE, lo=threshold, name="torque_constraint")
+
+    @classmethod
+    def action_equals(cls, value):
+        return cls(COST_ACTION_EQUALS, index=value, name="action_equals")
+
+    def __repr__(self):
+        return f"AnalyticCost({self.name}, index={self.index}, lo={self.lo}, hi={self.hi})"
+
+    def struct(self, obs_dim, acs_dim):
+        return CostFnT(int(obs_dim), int(acs_dim), 0, COST_FN, self.kind, self.index, float(self.lo), float(self.hi))
+
+    # ---- evaluation ----
+    def __call__(self, obs, acs=None):
+        if torch.is_tensor(obs) or torch.is_tensor(acs):
+            return self._device(obs, acs)
+        k, i = self.kind, self.index
+        if k == COST_NULL:
+            return np.zeros(obs.shape[:1])
+        if k == COST_WALL_BEHIND:
+            return obs[..., i] <= self.lo
+        if k == COST_WALL_INFRONT:
+            return obs[..., i] >= self.hi
+        if k == COST_WALL_BOTH:
+            return (obs[..., i] <= self.lo).astype(np.float32) + (obs[..., i] >= self.hi).astype(np.float32)
+        if k == COST_TORQUE:
+            return np.any(np.abs(acs) > self.lo, axis=-1)
+        a = np.asarray(acs)
+        return a.reshape(a.shape[0], -1)[:, 0] == i
+
+    def _device(self, obs, acs):
+        """icrl_cost_fn_rows over the flattened leading dimensions: float32 costs on the device, no host copies."""
+        ref = obs if torch.is_tensor(obs) else acs
+        dev = ref.device
+        reads_obs, reads_acs = self.kind in self.WALLS, self.kind in (COST_TORQUE, COST_ACTION_EQUALS)
+        if self.kind == COST_ACTION_EQUALS:
+            a = torch.as_tensor(acs, device=dev)
+            lead = a.shape[:1]
+            a = a.reshape(a.shape[0], -1)[:, :1].to(torch.float32).contiguous()
+            o, obs_dim, acs_dim = None, 1, 1
+        else:
+            o = torch.as_tensor(obs, device=dev).to(torch.float64) if (reads_obs or not reads_acs) else None
+            a = torch.as_tensor(acs, device=dev).to(torch.float32) if reads_acs else None
+            lead = o.shape[:-1] if reads_obs else (a.shape[:-1] if reads_acs else o.shape[:1])
+            obs_dim = o.shape[-1] if o is not None and o.dim() > 1 else 1
+            acs_dim = a.shape[-1] if a is not None else 1
+            o = o.reshape(-1, obs_dim).contiguous() if reads_obs else None
+            a = a.reshape(-1, acs_dim).contiguous() if reads_acs else None
+        n = int(np.prod(lead)) if len(lead) else 1
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        if n > 0:
+            cf = self.struct(obs_dim, acs_dim)
+            _lib.check(_lib.lib().icrl_cost_fn_rows(_lib.byref(cf), p(o), p(a), n, p(out), _lib.current_stream()), "icrl_cost_fn_rows")
+        return out.reshape(tuple(lead))
+
+
+TRUE_COSTS = {
+    # ref: icrl/true_constraint_net.py:13-34 (the bridge envs CDD2B / CC2B / CDD3B need the reference's gym env and are not served)
+    **{k: ("wall_behind", -3) for k in ("HCWithPosTest-v0", "WalkerWithPosTest-v0", "SwimmerWithPosTest-v0", "AntWallTest-v0",
+                                        "AntWallBrokenTest-v0", "PointCircleTestBack-v0")},
+    **{k: ("wall_behind_and_infront", -3, +3) for k in ("PointNullRewardTest-v0", "PointCircleTest-v0", "AntCircleTest-v0")},
+    **{k: ("torque", 0.5) for k in ("AntTest-v0", "HalfCheetahTest-v0", "Walker2dTest-v0", "SwimmerTest-v0")},
+    "CLGW-v0": ("action_equals", 1),
+}
+
+
 def get_true_cost_function(env_id):
-    if env_id == "CLGW-v0":
-        return lap_grid_world
-    if env_id in ("HCWithPosTest-v0", "WalkerWithPosTest-v0", "SwimmerWithPosTest-v0", "AntWallTest-v0", "AntWallBrokenTest-v0"):
-        return partial(wall_behind, -3)
-    return null_cost
+    """ref: icrl/true_constraint_net.py:11-34."""
+    entry = TRUE_COSTS.get(env_id)
+    if entry is None:
+        print("Cost function for %s is not implemented yet. Returning null cost function" % env_id)
+        return null_cost
+    return getattr(AnalyticCost, entry[0])(*entry[1:])
 
 
 def mean_cost(fn, obs, acs):
+    """mean of a cost function over rows; an AnalyticCost is evaluated where the rows are (device tensors: on the device)."""
     c = fn(obs, acs)
     return float(c.double().mean().item()) if torch.is_tensor(c) else float(np.mean(c))

@@ -468,6 +468,23 @@ class VecCostWrapper(VecEnvWrapper):
         from .constraint_net import ConstraintNet
         return owner if isinstance(owner, ConstraintNet) and getattr(self.cost_function, "__name__", "") == "cost_function" else None
 
+    def analytic_cost(self):
+        """the AnalyticCost behind cost_function, if that is what it is (true_constraint_net.py: evaluated inside the fused rollout like a
+        ConstraintNet, by closed form)."""
+        from .true_constraint_net import AnalyticCost
+        return self.cost_function if isinstance(self.cost_function, AnalyticCost) else None
+
+    def cost_struct(self):
+        """the descriptor the rollout entry points take for this wrapper's cost (icrl_costnet_t or icrl_cost_fn_t), or None."""
+        cn = self.constraint_net()
+        if cn is not None:
+            return cn.struct()
+        ac = self.analytic_cost()
+        if ac is None:
+            return None
+        disc = isinstance(self.action_space, spaces.Discrete)
+        return ac.struct(self.observation_space.shape[0], self.action_space.n if disc else self.action_space.shape[0])
+
     def reset(self):
         obs = self.venv.reset()
         self.previous_obs = obs
@@ -482,6 +499,8 @@ class VecCostWrapper(VecEnvWrapper):
         cn = self.constraint_net()
         if cn is not None:
             cost = cn.cost_function_device(self.previous_obs, self.actions)
+        elif self.analytic_cost() is not None and torch.is_tensor(self.previous_obs) and torch.is_tensor(self.actions):
+            cost = self.cost_function(self.previous_obs, self.actions)      # icrl_cost_fn_rows on the device tensors: no host copies
         else:  # arbitrary Python callable: numpy in / numpy out, as in the reference
             po = self.previous_obs.cpu().numpy() if torch.is_tensor(self.previous_obs) else self.previous_obs
             ac = self.actions.cpu().numpy() if torch.is_tensor(self.actions) else self.actions

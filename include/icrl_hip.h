@@ -121,6 +121,33 @@ typedef struct {
   float* params_t;           /* [n_params] transposed copy (written by icrl_costnet_prepare) */
 } icrl_costnet_t;
 
+/* Analytic (closed-form) cost: the ground-truth constraints of icrl/true_constraint_net.py:13-55 and the null cost, evaluated on
+ * (previous raw observation float64, clipped action float32) exactly where the constraint net is.  Its first four int32 alias the
+ * first four of icrl_costnet_t; n_hidden == ICRL_COST_FN is the tag: every entry point that takes `const icrl_costnet_t* cn` reads a
+ * descriptor carrying it as an icrl_cost_fn_t (cast the pointer).  Served by icrl_rollout_collect[_ex][_mon], icrl_host_step[_mon],
+ * icrl_cost_mlp_forward (= icrl_cost_fn_rows); refused with a reason by the *_batch rollouts, icrl_cn_train*, icrl_cn_prepare,
+ * icrl_disc_reward and icrl_costnet_prepare.  Operation for operation what numpy computes in the reference's callables:
+ *   NULL           0
+ *   WALL_BEHIND    obs[index] <= lo                      (float64 compare on the raw observation; wall_behind)
+ *   WALL_INFRONT   obs[index] >= hi                      (wall_infront)
+ *   WALL_BOTH      float(obs[index] <= lo) + float(obs[index] >= hi)   (wall_behind_and_infront; 2 when lo >= hi and both hold)
+ *   TORQUE         any_a |acs[a]| > (float)lo, a < acs_dim   (float32 compare on the clipped action; torque_constraint)
+ *   ACTION_EQUALS  discrete action == index              (lap_grid_world: index 1)
+ * The result is a float 0 / 1 / 2. */
+#define ICRL_COST_FN (-1)            /* value of n_hidden that marks an analytic cost */
+#define ICRL_COST_NULL 0
+#define ICRL_COST_WALL_BEHIND 1
+#define ICRL_COST_WALL_INFRONT 2
+#define ICRL_COST_WALL_BOTH 3
+#define ICRL_COST_TORQUE 4
+#define ICRL_COST_ACTION_EQUALS 5
+typedef struct {
+  int32_t obs_dim, acs_dim, in_dim /* 0 */, n_hidden /* ICRL_COST_FN */;
+  int32_t kind;     /* ICRL_COST_* */
+  int32_t index;    /* observation column (wall kinds) / action value (ACTION_EQUALS) */
+  double lo, hi;    /* thresholds */
+} icrl_cost_fn_t;
+
 /* RolloutBufferWithCost arrays (stable_baselines3/common/buffers.py:443-491), time-major [T,N,...] float32. */
 typedef struct {
   int32_t T, N, obs_dim, act_store; /* act_store = act_dim (Box) or 1 (Discrete) */
@@ -391,6 +418,11 @@ int icrl_sample_episodes(const icrl_env_t* env, const icrl_norm_t* nm, const icr
 /* ConstraintNet.cost_function (icrl/constraint_net.py:121-130): cost[n] = 1 - zeta(prepare(obs[n], acs[n])).
  * obs [N,obs] float64, acs [N,acs] float32 (class index in acs[n,0] when discrete). */
 int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* cost, void* stream);
+
+/* An analytic cost on N rows: cost[n] = f(obs[n], acs[n]), one row per thread.  obs [N, obs_dim] float64, acs [N, acs_dim] float32
+ * ([N, 1] class index for ACTION_EQUALS); either may be NULL for a kind that does not read it.  icrl_cost_mlp_forward with an analytic
+ * descriptor forwards here. */
+int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, const float* acs, int N, float* cost, void* stream);
 
 /* GailDiscriminator.reward_function (icrl/gail_utils.py:147-157): the same network read the other way round — the
  * discriminator output D = sigmoid(MLP(prepare(obs, acs))) itself (apply_log = 0) or log(D + eps) (apply_log = 1, the

@@ -1,0 +1,100 @@
+"""Per-env-step cost of a rollout whose env cost is an analytic cost (true_constraint_net.AnalyticCost), one process, one GPU
+(DESIGN.md section 13).  HC-shaped device env (HCWithPos-v0), 64 envs, T = 512, one timed rollout after a warm-up rollout:
+
+  (a) fused     wall_behind(0.0) inside the persistent rollout launch (icrl_rollout_collect_ex with an icrl_cost_fn_t)
+  (b) stepped   the same cost object through the per-step loop (ICRL_ANALYTIC_COST_STEPPED=1: PPOLagrangian._collect_rollouts_stepped,
+                the path `cpg` without --cn_path took before the descriptor existed)
+  (c) net       the persistent rollout with a [20] constraint net, for reference ((a) does strictly less device work)
+
+and (a), (b) for 8 envs over the do-nothing host env of tools/host_env_bench.py (icrl_host_step against the per-step loop).
+One JSON line per figure set, microseconds per env step.  usage: python tools/cost_fn_bench.py [--T 512] [--N 64] [--host_N 8]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def _time(fn):
+    import torch
+    fn()                                   # warm-up rollout
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def _agent(env, T, cost):
+    from icrl_amd.ppo_lag import PPOLagrangian
+    env.set_cost_function(cost)
+    agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0)
+    agent._setup_learn(10 * T * env.num_envs)
+    return agent
+
+
+def _rollout(agent, env, T, stepped):
+    """one rollout through collect_rollouts, the switch deciding the path; returns which path ran."""
+    if stepped:
+        os.environ["ICRL_ANALYTIC_COST_STEPPED"] = "1"
+    else:
+        os.environ.pop("ICRL_ANALYTIC_COST_STEPPED", None)
+    try:
+        fused = agent._fused_rollout_ok("cost", T, agent.rollout_buffer) or agent._host_rollout_ok("cost", T, agent.rollout_buffer)
+        agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost")
+    finally:
+        os.environ.pop("ICRL_ANALYTIC_COST_STEPPED", None)
+    return fused
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=512)
+    ap.add_argument("--N", type=int, default=64)
+    ap.add_argument("--host_N", type=int, default=8)
+    args = ap.parse_args()
+    import torch
+    from host_env_bench import NullHC
+    from icrl_amd import utils
+    from icrl_amd.constraint_net import ConstraintNet
+    from icrl_amd.true_constraint_net import AnalyticCost
+    from icrl_amd.vec_env import DummyVecEnv, VecCostWrapper, VecNormalizeWithCost
+    T, N = args.T, args.N
+
+    def device_env():
+        return utils.make_train_env("HCWithPos-v0", None, True, 0, N, cost_info_str="cost", reward_gamma=0.99, cost_gamma=0.99)
+    env = device_env()
+    agent = _agent(env, T, AnalyticCost.wall_behind(0.0))
+    assert _rollout(agent, env, T, False) and not _rollout(agent, env, T, True)
+    a = _time(lambda: _rollout(agent, env, T, False))
+    b = _time(lambda: _rollout(agent, env, T, True))
+    lo = -np.ones(6, np.float32)
+    torch.manual_seed(0)
+    cn = ConstraintNet(18, 6, [20], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
+    nenv = device_env()
+    nagent = _agent(nenv, T, cn.cost_function)
+    c = _time(lambda: _rollout(nagent, nenv, T, False))
+    row = dict(env="device", N=N, T=T, fused_analytic_us=1e6 * a / T, stepped_analytic_us=1e6 * b / T, fused_net_us=1e6 * c / T)
+    print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+    rows = [row]
+    if args.host_N > 0:
+        H = args.host_N
+        henv = VecNormalizeWithCost(VecCostWrapper(DummyVecEnv([NullHC] * H)))
+        hagent = _agent(henv, T, AnalyticCost.wall_behind(0.0))
+        assert _rollout(hagent, henv, T, False) and not _rollout(hagent, henv, T, True)
+        a = _time(lambda: _rollout(hagent, henv, T, False))
+        b = _time(lambda: _rollout(hagent, henv, T, True))
+        row = dict(env="host", N=H, T=T, fused_analytic_us=1e6 * a / T, stepped_analytic_us=1e6 * b / T)
+        print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+        rows.append(row)
+    return rows
+
+
+if __name__ == "__main__":
+    main()
