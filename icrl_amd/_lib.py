@@ -72,11 +72,13 @@ SIGNATURES = {
     "icrl_rollout_collect_batch": [c_int, c_void_p, c_void_p, c_void_p] + [c_double] * 4 + [c_int, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_gae_dual_batch": [c_int, c_void_p, c_int, c_int] + [c_double] * 4 + [c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_sample_episodes_batch": [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_longlong, c_void_p],
+    "icrl_sample_episodes_chain_ws_bytes": [c_int, c_void_p],
+    "icrl_sample_episodes_chain": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_cn_train_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_ppo_lag_train_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

@@ -2994,13 +2994,38 @@ struct SampleArgs {
   int* ep_lengths;         // [n_streams*episodes_per_stream]
 };
 
-template <int OCT>
-__device__ __forceinline__ void sample_episodes_body(const SampleArgs& a) {
+// The chained form (CHAIN, icrl_sample_episodes_chain): stream k IS episode k of the sequential 1-env loop, and the position it starts
+// from is settled inside the launch.  pos_k (first the guess k * max_steps) fixes the env's random-stream counter base + pos_k, the
+// action-noise row pos_k + i and the reset draw.  One word per stream, next_start[k] = {start row of episode k + 1 : 31 bits | final : 1},
+// written and read with single agent-scope relaxed atomics; nothing is read behind it, so it needs no fence.  A stream publishes
+// pos_k + max_steps when it (re)starts and pos_k + len_k when its episode ends, looks at its predecessor's word every step (the load is
+// issued at the top of the step by an otherwise idle wave and consumed after the env step), and starts over from the start it finds
+// there when that differs from pos_k.  It is validated once that word is final and equals pos_k; validated and finished, it writes its
+// episode sum and length and publishes its own word with the final bit.  While it runs a stream writes rows only to a slot of its own
+// (rows k * max_steps + i of the slot arrays), so that a late store of an abandoned run can never land on validated rows; once final it
+// copies its len_k rows to [pos_k, pos_k + len_k) of the outputs, which are disjoint between streams.  A fixed_len job's guesses are
+// exact: it neither polls nor copies (its slot arrays are the outputs).  
+struct ChainArgs {
+  SampleArgs s;            // outputs: the arrays of the sequential loop; env: per-stream scratch state [n_streams]
+  unsigned* next_start;    // [n_streams] position words, CHAIN_UNSET before the launch
+  unsigned* status;        // [1] set to 1 when a bounded wait ran out
+  int* exec_steps;         // [n_streams] env steps the stream executed, abandoned runs included (or NULL)
+  double* slot_orig;       // [n_streams * max_steps, obs] private rows (the outputs themselves when fixed_len)
+  double* slot_obs;
+  float* slot_act;
+  const int* base_count;   // [1] the env's random-stream counter before episode 0
+  int fixed_len, n_streams;
+};
+constexpr unsigned CHAIN_UNSET = 0xFFFFFFFEu;      // "nothing published yet": no start ever reaches 2^31 - 1 rows
+
+template <int OCT, bool CHAIN = false>
+__device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const ChainArgs* c = nullptr) {
   __shared__ ActShared sh;
   PolRegs<OCT> R;
   load_pol_regs<OCT>(a.pl, a.PT, R);    // once for every step of every episode of this stream
   __shared__ int s_done;
   __shared__ double s_rew;
+  __shared__ unsigned s_word;                  // CHAIN: the predecessor's position word as this step saw it
   __shared__ double Bl[MAX_OBS * MAX_ACT];     // dynamics matrix: read every step, kept out of the global-memory latency
   __shared__ float noise_s[MAX_ACT], alow_s[MAX_ACT], ahigh_s[MAX_ACT];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -3010,9 +3035,9 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a) {
   icrl_env_t env = a.env; globalize(env);
   // what the step loop reads of the argument block, once (a batched launch keeps the block in LDS; pointers: common.h as_global)
   const float* const noise_g = as_global(a.noise);
-  float* const actions_g = as_global(a.actions);
-  double* const orig_obs_g = as_global(a.orig_obs);
-  double* const obs_g = as_global(a.obs);
+  float* const actions_g = as_global(CHAIN ? c->slot_act : a.actions);
+  double* const orig_obs_g = as_global(CHAIN ? c->slot_orig : a.orig_obs);
+  double* const obs_g = as_global(CHAIN ? c->slot_obs : a.obs);
   const int norm_obs = a.nm.norm_obs, deterministic = a.deterministic;
   const double clip_obs = a.nm.clip_obs;
   for (int i = tid; i < O * a.env.act_dim; i += 192) Bl[i] = a.env.B[i];
@@ -3026,20 +3051,39 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a) {
   double n_mean = 0.0, n_den = 1.0;
   if (tid < O && a.nm.norm_obs) { n_mean = a.nm.obs_mean[tid]; n_den = sqrt(a.nm.obs_var[tid] + a.nm.epsilon); }
   for (int i = tid; i < MAX_OBS; i += 192) sh.x[i] = 0.f;
+  // CHAIN: where this stream believes its episode starts, whether that is settled, and what it has executed so far
+  const int max_steps = a.env.max_steps;
+  unsigned* const words = CHAIN ? as_global(c->next_start) : nullptr;
+  const uint32_t base = CHAIN ? (uint32_t)as_global(c->base_count)[0] : 0u;
+  const size_t slot0 = CHAIN ? (size_t)n * max_steps : 0;
+  unsigned pos = CHAIN ? (unsigned)n * (unsigned)max_steps : 0u;
+  bool validated = !CHAIN || n == 0 || c->fixed_len != 0;
+  int executed = 0;
+  bool again;
+  do {
+  again = false;
+  if (CHAIN) {
+    __syncthreads();       // (a restart: every thread has left the step it abandoned)
+    e_ctr = base + pos;    // wraps like the env's own counter
+    if (n > 0 || a.do_reset) e_tep = 0;
+    if (tid == 0 && !c->fixed_len) xstore(words + n, (pos + (unsigned)max_steps) << 1);
+  }
   if (tid < O) {
     double v = a.env.s[(size_t)n * O + tid];
-    if (a.do_reset) v = env_reset_value(a.env, e_key, e_ctr, tid);
+    if (a.do_reset || (CHAIN && n > 0)) v = env_reset_value(a.env, e_key, e_ctr, tid);
     sh.s_new[tid] = v;
   }
-  if (a.do_reset) e_tep = 0;
+  if (!CHAIN && a.do_reset) e_tep = 0;
   __syncthreads();
-  size_t row = a.stream_row0 != nullptr ? (size_t)a.stream_row0[n] : (size_t)n * a.rows_per_stream;
-  const size_t row_end = a.stream_row0 != nullptr ? (size_t)a.total_rows : row + a.rows_per_stream;
+  size_t row = CHAIN ? (size_t)pos : a.stream_row0 != nullptr ? (size_t)a.stream_row0[n] : (size_t)n * a.rows_per_stream;
+  const size_t row_end = (CHAIN || a.stream_row0 != nullptr) ? (size_t)a.total_rows : row + a.rows_per_stream;
   float noise_reg = (noise_g != nullptr && tid < AS) ? noise_g[row * AS + tid] : 0.f;   // noise of the first step
   for (int ep = 0; ep < a.episodes_per_stream; ++ep) {
     double ep_rew = 0.0;
     int ep_len = 0;
     while (true) {
+      unsigned word = CHAIN_UNSET;
+      if (CHAIN && !validated && tid == 128) word = xload(words + n - 1);      // consumed after the env step
       if (tid < O) {
         const double raw = sh.s_new[tid];
         double o = raw;
@@ -3055,30 +3099,77 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a) {
       policy_forward_block<OCT>(a.pl, R, sh, noise_g ? noise_s : nullptr, deterministic || noise_g == nullptr,
                                 has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
       __syncthreads();
-      const bool in_rows = row < row_end;      // (a stream whose speculative start row was too late can run off the arrays)
+      const bool in_rows = CHAIN || row < row_end;      // (a stream whose speculative start row was too late can run off the arrays)
+      const size_t orow = CHAIN ? slot0 + (size_t)ep_len : row;
       if (w == 0) {
         double rew; int done;
         env_step_wave(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
         if (lane == 0) { s_done = done; s_rew = rew; }
-        if (lane < AS && in_rows) actions_g[row * AS + lane] = sh.act_clip[lane];
+        if (lane < AS && in_rows) actions_g[orow * AS + lane] = sh.act_clip[lane];
       }
+      if (CHAIN && tid == 128) s_word = word;
       __syncthreads();
       if (tid < O && in_rows) {
         const double raw = sh.s_new[tid];
         double o = raw;
         if (norm_obs) o = fmin(fmax((raw - n_mean) / n_den, -clip_obs), clip_obs);
-        orig_obs_g[row * O + tid] = raw;
-        obs_g[row * O + tid] = o;
+        orig_obs_g[orow * O + tid] = raw;
+        obs_g[orow * O + tid] = o;
       }
       ep_rew += s_rew;     // episode_reward += reward (un-normalised: norm_reward is False on sampling / eval envs)
       ++ep_len;
       ++row;
       const int done = s_done;
+      if (CHAIN) {
+        ++executed;
+        const unsigned pw = s_word;
+        if (!validated && pw != CHAIN_UNSET) {
+          if ((pw >> 1) != pos) { pos = pw >> 1; again = true; }
+          validated = (pw & 1u) != 0u;
+        }
+      }
       __syncthreads();
+      if (CHAIN && again) break;
       if (done) break;
     }
-    if (tid == 0) { a.ep_rewards[(size_t)n * a.episodes_per_stream + ep] = ep_rew; a.ep_lengths[(size_t)n * a.episodes_per_stream + ep] = ep_len; }
+    if (CHAIN) {
+      if (again) break;
+      // finished: tell the successor where it starts (provisional until this stream is validated), then wait for the predecessor's last word
+      if (tid == 0 && !validated) xstore(words + n, (pos + (unsigned)ep_len) << 1);
+      for (int spins = 0; !validated && !again; ++spins) {
+        if (spins == (1 << 22)) {      // the predecessor never finished (its workgroup was not resident): report and leave
+          if (tid == 0) { atomicOr(as_global(c->status), 1u); a.ep_lengths[n] = -1; }
+          return;
+        }
+        if (tid == 0) s_word = xload(words + n - 1);
+        __syncthreads();
+        const unsigned pw = s_word;
+        if (pw != CHAIN_UNSET) {
+          if ((pw >> 1) != pos) { pos = pw >> 1; again = true; }
+          validated = (pw & 1u) != 0u;
+        }
+        __syncthreads();
+        if (!validated && !again) __builtin_amdgcn_s_sleep(32);
+      }
+      if (again) break;
+      if (tid == 0) {
+        a.ep_rewards[n] = ep_rew; a.ep_lengths[n] = ep_len;
+        if (c->exec_steps != nullptr) c->exec_steps[n] = executed;
+        if (!c->fixed_len) xstore(words + n, ((pos + (unsigned)ep_len) << 1) | 1u);
+      }
+      if (!c->fixed_len) {      // the validated rows, from the slot to their place in the sequential loop's arrays
+        const size_t nd = (size_t)ep_len * O, na = (size_t)ep_len * AS;
+        const double* so = orig_obs_g + slot0 * O; const double* sn = obs_g + slot0 * O; const float* sa = actions_g + slot0 * AS;
+        double* dorig = as_global(a.orig_obs) + (size_t)pos * O; double* dobs = as_global(a.obs) + (size_t)pos * O;
+        float* dact = as_global(a.actions) + (size_t)pos * AS;
+#pragma unroll 4
+        for (size_t i = tid; i < nd; i += 192) { dorig[i] = so[i]; dobs[i] = sn[i]; }
+#pragma unroll 4
+        for (size_t i = tid; i < na; i += 192) dact[i] = sa[i];
+      }
+    } else if (tid == 0) { a.ep_rewards[(size_t)n * a.episodes_per_stream + ep] = ep_rew; a.ep_lengths[(size_t)n * a.episodes_per_stream + ep] = ep_len; }
   }
+  } while (CHAIN && again);
 }
 
 template <int OCT>
@@ -3097,6 +3188,26 @@ __global__ void __launch_bounds__(192) sample_episodes_batch_kernel(const Sample
   }
   __syncthreads();
   sample_episodes_body<OCT>(a);
+}
+
+// the chained sampler: grid (max streams of a job, jobs); jobs may differ in env flags, statistics, policy and stream count
+template <int OCT>
+__global__ void __launch_bounds__(192) sample_episodes_chain_kernel(const ChainArgs* __restrict__ jobs) {
+  __shared__ ChainArgs c;
+  {
+    const unsigned* src = reinterpret_cast<const unsigned*>(jobs + blockIdx.y);
+    unsigned* dst = reinterpret_cast<unsigned*>(&c);
+    for (unsigned i = threadIdx.x; i < sizeof(ChainArgs) / 4; i += 192) dst[i] = src[i];
+  }
+  __syncthreads();
+  if ((int)blockIdx.x >= c.n_streams) return;
+  sample_episodes_body<OCT, true>(c.s, &c);
+}
+
+// before the launch, on the same stream: the job's argument block, its position words unset, the status word cleared
+__global__ void __launch_bounds__(64) chain_prep_kernel(ChainArgs v, ChainArgs* dst, int clear_status) {
+  if (threadIdx.x == 0) { *dst = v; if (clear_status) *v.status = 0u; }
+  for (int i = threadIdx.x; i < v.n_streams; i += 64) v.next_start[i] = CHAIN_UNSET;
 }
 
 // =================================================================================================================
@@ -3627,6 +3738,86 @@ extern "C" int icrl_sample_episodes_batch(int n_runs, const icrl_sample_job_t* j
   }
   if (j0.pol->obs_dim <= 32) hipLaunchKernelGGL(sample_episodes_batch_kernel<2>, dim3(j0.env->n_envs, n_runs), dim3(192), 0, s, d_args);
   else hipLaunchKernelGGL(sample_episodes_batch_kernel<8>, dim3(j0.env->n_envs, n_runs), dim3(192), 0, s, d_args);
+  return (int)hipGetLastError();
+}
+
+// ---- icrl_sample_episodes_chain: workspace = [status word | position words of all jobs | private row slots of the jobs that may end early]
+static size_t chain_align(size_t b) { return (b + 255) / 256 * 256; }
+static size_t chain_slot_bytes(const icrl_chain_job_t& j) {      // orig_obs, obs, actions rows of one job's slots
+  if (j.fixed_len) return 0;
+  const size_t rows = (size_t)j.env->n_envs * j.env->max_steps;
+  const size_t AS = j.pol->discrete ? 1 : j.pol->act_dim;
+  return 2 * chain_align(rows * j.env->obs_dim * sizeof(double)) + chain_align(rows * AS * sizeof(float));
+}
+static int chain_total_streams(int n_jobs, const icrl_chain_job_t* jobs) {
+  long long t = 0;
+  for (int r = 0; r < n_jobs; ++r) t += jobs[r].env->n_envs > 0 ? jobs[r].env->n_envs : 0;
+  return t > (1 << 30) ? (1 << 30) : (int)t;
+}
+
+extern "C" size_t icrl_sample_episodes_chain_ws_bytes(int n_jobs, const icrl_chain_job_t* jobs) {
+  if (n_jobs < 1 || jobs == nullptr) return 0;
+  size_t b = 256 + chain_align((size_t)chain_total_streams(n_jobs, jobs) * sizeof(unsigned));
+  for (int r = 0; r < n_jobs; ++r) b += chain_slot_bytes(jobs[r]);
+  return b;
+}
+
+extern "C" int icrl_sample_episodes_chain(int n_jobs, const icrl_chain_job_t* jobs, const float* action_low, const float* action_high,
+                                          int do_reset, void* ws, long long ws_bytes, void* args_ws, long long args_ws_bytes, void* stream) {
+  static_assert(sizeof(ChainArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  if (n_jobs < 1 || n_jobs > 65535 || jobs == nullptr) return fail("icrl_sample_episodes_chain: n_jobs = %d (1..65535)", n_jobs);
+  // what the chained kernel does not serve (the caller takes the multi-pass path): the reason starts with "refused"
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 0;
+  }
+  const int total = chain_total_streams(n_jobs, jobs);
+  if (total > n_cu)
+    return fail("icrl_sample_episodes_chain: refused: %d streams on %d compute units (every stream must be resident while its successors wait)", total, n_cu);
+  int max_streams = 0;
+  for (int r = 0; r < n_jobs; ++r) {
+    const icrl_chain_job_t& j = jobs[r];
+    if (policy_is_wide(j.pol)) return fail("icrl_sample_episodes_chain: refused: job %d has a generic-shape policy", r);
+    if (j.episodes_per_stream != 1) return fail("icrl_sample_episodes_chain: refused: job %d runs %d episodes per stream (1 only)", r, j.episodes_per_stream);
+    if ((j.pol->obs_dim <= 32) != (jobs[0].pol->obs_dim <= 32)) return fail("icrl_sample_episodes_chain: refused: job %d and job 0 take different kernels (obs %d / %d)", r, j.pol->obs_dim, jobs[0].pol->obs_dim);
+    if (j.env->n_envs < 1 || j.base_count == nullptr) return fail("icrl_sample_episodes_chain: job %d: %d streams, base_count %p", r, j.env->n_envs, (const void*)j.base_count);
+    if ((long long)j.env->n_envs * j.env->max_steps >= (1ll << 31) - 1) return fail("icrl_sample_episodes_chain: job %d: %d streams x %d steps do not fit a 31-bit row", r, j.env->n_envs, j.env->max_steps);
+    if (j.env->n_envs > max_streams) max_streams = j.env->n_envs;
+  }
+  const long long need = (long long)icrl_sample_episodes_chain_ws_bytes(n_jobs, jobs);
+  if (ws == nullptr || ws_bytes < need) return fail("icrl_sample_episodes_chain: ws holds %lld B, the jobs need %lld", ws_bytes, need);
+  if (args_ws == nullptr || args_ws_bytes < (long long)n_jobs * ICRL_BATCH_ARGS_BYTES)
+    return fail("icrl_sample_episodes_chain: args_ws holds %lld B, %d jobs need %lld", args_ws_bytes, n_jobs, (long long)n_jobs * ICRL_BATCH_ARGS_BYTES);
+  hipStream_t s = (hipStream_t)stream;
+  ChainArgs* d_args = (ChainArgs*)args_ws;
+  char* const base = (char*)ws;
+  unsigned* words = (unsigned*)(base + 256);
+  char* slots = base + 256 + chain_align((size_t)total * sizeof(unsigned));
+  for (int r = 0; r < n_jobs; ++r) {
+    const icrl_chain_job_t& j = jobs[r];
+    const int rows = j.env->n_envs * j.env->max_steps;
+    ChainArgs c;
+    const int bad = make_sample_args(j.env, j.nm, j.pol, j.noise, action_low, action_high, 1, j.env->max_steps, j.deterministic, do_reset, nullptr,
+                                     rows, j.orig_obs, j.obs, j.actions, j.ep_rewards, j.ep_lengths, c.s);
+    if (bad) return bad;
+    c.next_start = words; words += j.env->n_envs;
+    c.status = (unsigned*)base;
+    c.exec_steps = j.exec_steps;
+    c.base_count = j.base_count;
+    c.fixed_len = j.fixed_len != 0; c.n_streams = j.env->n_envs;
+    if (c.fixed_len) { c.slot_orig = j.orig_obs; c.slot_obs = j.obs; c.slot_act = j.actions; }
+    else {
+      const size_t AS = j.pol->discrete ? 1 : j.pol->act_dim;
+      const size_t ob = chain_align((size_t)rows * j.env->obs_dim * sizeof(double));
+      c.slot_orig = (double*)slots; c.slot_obs = (double*)(slots + ob); c.slot_act = (float*)(slots + 2 * ob);
+      slots += 2 * ob + chain_align((size_t)rows * AS * sizeof(float));
+    }
+    hipLaunchKernelGGL(chain_prep_kernel, dim3(1), dim3(64), 0, s, c, d_args + r, (int)(r == 0));
+    if (const int e = (int)hipGetLastError()) return e;
+  }
+  if (jobs[0].pol->obs_dim <= 32) hipLaunchKernelGGL(sample_episodes_chain_kernel<2>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
+  else hipLaunchKernelGGL(sample_episodes_chain_kernel<8>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
   return (int)hipGetLastError();
 }
 

@@ -146,9 +146,22 @@ def outer_iteration(st, itr):
     sync_envs_normalization(train_env, sampling_env)
     streams = getattr(config, "streams", None)       # explicit random streams (tests: teacher forcing); None = device RNG
     A = 1 if nominal_agent.policy.discrete else nominal_agent.policy.act_dim
-    orig_observations, observations, actions, rewards, lengths = utils.sample_from_agent(
-        nominal_agent, sampling_env, config.expert_rollouts,
-        noise=None if streams is None else streams.sample_noise(config.expert_rollouts * sampling_env.unwrapped.max_steps, A))
+    # On one rank nothing the evaluation reads changes between the two episode phases (the constraint-net update leaves the policy and
+    # train_env's statistics alone, synchronise() is a no-op), so both run in ONE launch here (utils.sample_and_evaluate).  The random
+    # draws keep their order: sampling noise, then evaluation noise; a constraint net in minibatch mode draws its permutations from the
+    # same streams in between, so that configuration keeps the two phases apart, as do several ranks and ICRL_EPISODE_CHAIN=0.
+    draws_cn_perms = constraint_net.batch_size is not None and streams is not None and hasattr(streams, "cn_permutations")
+    fused = (world <= 1 and not getattr(config, "force_collective", False) and not draws_cn_perms and utils.chain_enabled()
+             and utils.episodes_fusable(sampling_env, eval_env))
+    sample_noise = None if streams is None else streams.sample_noise(config.expert_rollouts * sampling_env.unwrapped.max_steps, A)
+    if fused:
+        sync_envs_normalization(train_env, eval_env)
+        (orig_observations, observations, actions, rewards, lengths), (average_true_reward, std_true_reward) = utils.sample_and_evaluate(
+            nominal_agent, sampling_env, config.expert_rollouts, eval_env, n_eval_episodes=10, deterministic=False, sample_noise=sample_noise,
+            eval_noise=None if streams is None else streams.eval_noise(10 * eval_env.unwrapped.max_steps, A))
+    else:
+        orig_observations, observations, actions, rewards, lengths = utils.sample_from_agent(
+            nominal_agent, sampling_env, config.expert_rollouts, noise=sample_noise)
     # ---- backward step
     mean, var = None, None
     if config.cn_normalize:
@@ -165,10 +178,11 @@ def outer_iteration(st, itr):
     average_true_cost = mean_cost(st["true_cost_function"], orig_observations, actions)
     samples_behind = float((orig_observations[..., 0] < -3).double().mean().item())
     samples_infront = float((orig_observations[..., 0] > 3).double().mean().item())
-    sync_envs_normalization(train_env, eval_env)
-    average_true_reward, std_true_reward = utils.evaluate_policy(
-        nominal_agent, eval_env, n_eval_episodes=10, deterministic=False,
-        noise=None if streams is None else streams.eval_noise(10 * eval_env.unwrapped.max_steps, A))
+    if not fused:
+        sync_envs_normalization(train_env, eval_env)
+        average_true_reward, std_true_reward = utils.evaluate_policy(
+            nominal_agent, eval_env, n_eval_episodes=10, deterministic=False,
+            noise=None if streams is None else streams.eval_noise(10 * eval_env.unwrapped.max_steps, A))
     forward_kl = reverse_kl = float("nan")
     if st["expert_agent"] is not None:
         forward_kl = utils.compute_kl(nominal_agent, st["d_expert_obs"], st["d_expert_acs"], st["expert_agent"])

@@ -99,6 +99,13 @@ class SampleJobT(C.Structure):
                 [(k, vp) for k in ("orig_obs", "obs", "actions", "ep_rewards", "ep_lengths")])
 
 
+class ChainJobT(C.Structure):
+    """icrl_chain_job_t: one sequential episode loop of icrl_sample_episodes_chain."""
+    _fields_ = ([(k, vp) for k in ("env", "nm", "pol", "noise", "base_count")] +
+                [("episodes_per_stream", i32), ("deterministic", i32), ("fixed_len", i32), ("_pad", i32)] +
+                [(k, vp) for k in ("orig_obs", "obs", "actions", "ep_rewards", "ep_lengths", "exec_steps")])
+
+
 class CnTrainJobT(C.Structure):
     _fields_ = [("cn", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("adam_step", vp), ("nominal", vp), ("expert", vp), ("Nn", i32), ("Ne", i32),
                 ("ep_offsets", vp), ("row_episode", vp), ("n_ep", i32), ("_pad", i32), ("hp", vp), ("work", vp), ("metrics", vp)]

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, spaces
 from .policies import ActorTwoCriticsPolicy
-from .structs import EnvT, HostEpisodeT, p
+from .structs import ChainJobT, EnvT, HostEpisodeT, addr, p
 from . import envs
 from .vec_env import ENV_IDS, DummyVecEnv, HipSynthVecEnv, HostVecEnv, SubprocVecEnv, VecCostWrapper, VecNormalize, VecNormalizeWithCost
 
@@ -88,7 +88,11 @@ class EpisodeRun:
 
     In pieces, so that several runs sharing a GPU can put their launches into one grid (icrl_amd/seed_batch.py):
     prepare() builds the descriptors, launch() is the single-run launch, finish(lengths) checks the positions and leaves the env
-    where the sequential loop would have left it (returns False when another pass is needed: prepare() again, launch(), ...)."""
+    where the sequential loop would have left it (returns False when another pass is needed: prepare() again, launch(), ...).
+
+    Where the chained launch serves (chain_ok) the positions are settled INSIDE one launch instead — every stream learns its start
+    from its predecessor while both run (icrl_sample_episodes_chain): prepare_chain(), launch_chain([runs]),
+    finish_chain(); always one pass, and the lengths are read once, with the results.  ICRL_EPISODE_CHAIN=0 keeps the passes."""
 
     MAX_PASSES = 4
 
@@ -187,6 +191,71 @@ class EpisodeRun:
     def rows_of(self, name):
         x = self.out[name]
         return x if self.keep is None else x[:self.keep]
+
+    # ---- the chained launch: one pass, positions fixed in the kernel
+    def chain_ok(self):
+        """what icrl_sample_episodes_chain serves: one episode per stream, more than one stream, a policy of the one-workgroup-per-env
+        kernels (the entry point itself refuses the rest: more streams than compute units)."""
+        return chain_enabled() and self.n_streams > 1 and self.n_streams == self.n_episodes and not self.pol.wide
+
+    def prepare_chain(self):
+        senv, dev, O, A, n = self.senv, self.dev, self.O, self.A, self.n_streams
+        self.eps_per, self.rows_per = 1, self.max_steps
+        # per-stream scratch state; the kernel derives every stream's random-stream position from the env's own counter (base_count)
+        self.st = dict(s=senv.s.repeat(n, 1).contiguous(), t_ep=senv.t_ep.repeat(n).contiguous(),
+                       step_count=torch.zeros(n, dtype=torch.int32, device=dev), key=senv.key.repeat(n).contiguous())
+        st = self.st
+        self.e = EnvT(n, O, senv.act_dim, self.max_steps, senv.reward_form, int(senv.wall_terminate), int(senv.broken), 0,
+                      p(senv.B), p(st["s"]), p(st["t_ep"]), p(st["step_count"]), p(st["key"]))
+        rows = self.rows
+        self.out = dict(orig_obs=torch.empty(rows, O, dtype=torch.float64, device=dev), obs=torch.empty(rows, O, dtype=torch.float64, device=dev),
+                        actions=torch.empty(rows, A, device=dev), ep_rewards=torch.empty(n, dtype=torch.float64, device=dev),
+                        ep_lengths=torch.empty(n, dtype=torch.int32, device=dev), exec_steps=torch.empty(n, dtype=torch.int32, device=dev))
+        out = self.out
+        self.job = ChainJobT(addr(self.e), addr(self.nm), addr(self.ps), p(self.noise), p(senv.step_count), 1, int(self.deterministic),
+                             int(self.fixed_len), 0, p(out["orig_obs"]), p(out["obs"]), p(out["actions"]), p(out["ep_rewards"]),
+                             p(out["ep_lengths"]), p(out["exec_steps"]))
+        self.passes += 1
+        return self
+
+    def finish_chain(self):
+        """the single host read of the launch: the lengths (a negative one: a stream's bounded wait for its predecessor ran out)."""
+        lengths = self.out["ep_lengths"].cpu().numpy().astype(np.int64)
+        if (lengths < 0).any():
+            raise RuntimeError("icrl_sample_episodes_chain: a stream gave up waiting for its predecessor (a workgroup was not resident)")
+        senv, env = self.senv, self.env
+        # leave the env where the sequential loop would have left it: the last stream ended exactly there
+        senv.step_count.copy_(self.st["step_count"][-1:])
+        senv.s.copy_(self.st["s"][-1:]); senv.t_ep.zero_()
+        env.old_obs = senv.s
+        total = int(lengths.sum())
+        self.lengths = lengths
+        self.keep = None if total == self.rows else total
+        return True
+
+
+def chain_enabled():
+    """ICRL_EPISODE_CHAIN=0: episode positions are settled by repeated launches (EpisodeRun.finish), as before the chained kernel."""
+    return os.environ.get("ICRL_EPISODE_CHAIN", "1") not in ("0",)
+
+
+def launch_chain(runs):
+    """ONE launch for the prepared (prepare_chain) runs, which share the action box.  False: the entry point refused the case (its
+    reason starts with "refused"): nothing was launched and the caller takes the multi-pass path."""
+    r0 = runs[0]
+    jobs = (ChainJobT * len(runs))(*[r.job for r in runs])
+    lib = _lib.lib()
+    ws_bytes = int(lib.icrl_sample_episodes_chain_ws_bytes(len(runs), jobs))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=r0.dev)
+    args = torch.empty(len(runs) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=r0.dev)
+    try:
+        _lib.check(lib.icrl_sample_episodes_chain(len(runs), jobs, p(r0.lo), p(r0.hi), 1, p(ws), ws_bytes, p(args), args.numel(),
+                                                  _lib.current_stream()), "icrl_sample_episodes_chain")
+    except ValueError as err:
+        if "icrl_sample_episodes_chain: refused:" in str(err):
+            return False
+        raise
+    return True
 
 
 class SteppedEpisodeRun:
@@ -345,7 +414,9 @@ class HostEpisodeRun:
         return x if self.keep is None else x[:self.keep]
 
 
-def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel):
+def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel, chain=False):
+    """chain: settle early-ending episodes' positions inside ONE launch where it serves (what sample_from_agent and evaluate_policy
+    ask for); the default keeps the pass-by-pass protocol of EpisodeRun.prepare / launch / finish, with run.passes counting launches."""
     if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: one launch per env step, or the reference's own loop
         if env.unwrapped.max_steps is None:
             raise ValueError("sampling / evaluation over a host env needs its episode limit: register it with max_episode_steps "
@@ -355,11 +426,46 @@ def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel):
         return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
     # (policies of the generic-shape path take the same launch: icrl_sample_episodes runs its persistent loop with the table-driven
     # forward, csrc/rollout.hip sample_episodes_generic_kernel; SteppedEpisodeRun is the same loop from the host, kept as the check)
-    run = EpisodeRun(agent, env, n_episodes, deterministic, noise, parallel).prepare()
-    run.launch()
+    return _launch_and_finish(EpisodeRun(agent, env, n_episodes, deterministic, noise, parallel), chain)
+
+
+def _launch_and_finish(run, chain=True):
+    if chain and run.chain_ok() and launch_chain([run.prepare_chain()]):
+        run.finish_chain()
+        return run
+    run.passes = 0
+    run.prepare().launch()
     while not run.finish():
         run.prepare().launch()
     return run
+
+
+def _is_device_env(env):
+    return not isinstance(env.unwrapped, HostVecEnv)
+
+
+def episodes_fusable(sampling_env, eval_env):
+    """two device envs with separate state: what sample_and_evaluate puts into one launch"""
+    return _is_device_env(sampling_env) and _is_device_env(eval_env) and sampling_env.unwrapped is not eval_env.unwrapped
+
+
+def sample_and_evaluate(agent, sampling_env, n_rollouts, eval_env, n_eval_episodes=10, deterministic=True, sample_noise=None,
+                        eval_noise=None, parallel=True, reward_threshold=None, return_episode_rewards=False):
+    """sample_from_agent(agent, sampling_env, n_rollouts, sample_noise, parallel) and evaluate_policy(agent, eval_env, n_eval_episodes,
+    deterministic, noise=eval_noise) as ONE launch of two jobs (icrl_sample_episodes_chain) where both serve, else one after the other;
+    returns the pair of their results.  The caller vouches that nothing the evaluation reads (policy, normaliser statistics of eval_env)
+    changes between the two phases it replaces.  Noise is drawn in the sequential order: sampling first, then evaluation."""
+    if episodes_fusable(sampling_env, eval_env):
+        s_run = EpisodeRun(agent, sampling_env, n_rollouts, False, sample_noise, parallel)
+        e_run = EpisodeRun(agent, eval_env, n_eval_episodes, deterministic, eval_noise, False)
+        if s_run.chain_ok() and e_run.chain_ok() and launch_chain([s_run.prepare_chain(), e_run.prepare_chain()]):
+            s_run.finish_chain(); e_run.finish_chain()
+        else:
+            _launch_and_finish(s_run); _launch_and_finish(e_run)
+        return sample_result(s_run), evaluate_result(e_run, None, reward_threshold, return_episode_rewards)
+    return (sample_from_agent(agent, sampling_env, n_rollouts, sample_noise, parallel),
+            evaluate_policy(agent, eval_env, n_eval_episodes, deterministic, reward_threshold=reward_threshold,
+                            return_episode_rewards=return_episode_rewards, noise=eval_noise))
 
 
 def sample_from_agent(agent, env, rollouts, noise=None, parallel=True):
@@ -367,7 +473,7 @@ def sample_from_agent(agent, env, rollouts, noise=None, parallel=True):
     device tensors [sum(lengths), ...] holding the observation AFTER each step next to the (clipped) action of that step;
     rewards / lengths are numpy arrays per episode.  With parallel=True the `rollouts` fixed-length episodes of the 1-env loop
     run as independent streams whose random-stream counters are offset exactly as the sequential loop would advance them."""
-    return sample_result(_run_episodes(agent, env, rollouts, False, noise, parallel))
+    return sample_result(_run_episodes(agent, env, rollouts, False, noise, parallel, chain=True))
 
 
 def sample_result(run, ep_rewards=None):
@@ -378,7 +484,7 @@ def sample_result(run, ep_rewards=None):
 def evaluate_policy(model, env, n_eval_episodes=10, deterministic=True, render=False, callback=None, reward_threshold=None,
                     return_episode_rewards=False, noise=None):
     """ref: stable_baselines3/common/evaluation.py:10-67 (sequential episodes on one env)."""
-    run = _run_episodes(model, env, n_eval_episodes, deterministic, noise, parallel=False)
+    run = _run_episodes(model, env, n_eval_episodes, deterministic, noise, parallel=False, chain=True)
     return evaluate_result(run, None, reward_threshold, return_episode_rewards)
 
 

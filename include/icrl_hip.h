@@ -561,6 +561,38 @@ int icrl_sample_episodes_batch(int n_runs, const icrl_sample_job_t* jobs, const 
                                int episodes_per_stream, int rows_per_stream, int deterministic, int do_reset,
                                void* args_ws, long long args_ws_bytes, void* stream);
 
+/* The episodes of sequential 1-env loops in ONE launch, their positions settled inside it (csrc/rollout.hip ChainArgs, DESIGN.md
+ * section 11): job j = env->n_envs episodes of one loop, stream k = episode k, one episode per stream; grid (largest stream count, n_jobs).
+ * Computes what icrl_sample_episodes computes with ONE stream running the job's episodes back to back — rows, episode sums and lengths,
+ * and in env->s / t_ep / step_count of the LAST stream the state that loop ends in — also when episodes end early: a stream starts from
+ * the guess k * max_steps, learns its true start row from its predecessor while both run, starts over when the two differ, and copies
+ * its rows to their place once that start is final.  Jobs may differ in env flags, statistics, policy, noise and stream count.
+ *   env: per-stream state arrays [n_streams] (s, t_ep, key as for icrl_sample_episodes; step_count is written, not read);
+ *   base_count: [1] int32 on the device, the loop's env->step_count before episode 0; noise / outputs: [n_streams * max_steps, ..] rows;
+ *   fixed_len: episodes always run max_steps (the guesses are exact: no polling, no copy); exec_steps: [n_streams] env steps every
+ *   stream executed including abandoned runs, or NULL.  do_reset: episode 0 starts from a reset (else from env->s[0], t_ep[0]).
+ *   ws: >= icrl_sample_episodes_chain_ws_bytes(n_jobs, jobs) bytes of device scratch, any contents; its first word is 0 afterwards unless
+ *   a stream gave up waiting for its predecessor (its ep_lengths entry is then -1).  args_ws: n_jobs * ICRL_BATCH_ARGS_BYTES.
+ * Refused (hipErrorInvalidValue, reason starting "icrl_sample_episodes_chain: refused:"; callers take the multi-pass path): more
+ * streams in total than the device has compute units, a generic-shape policy, episodes_per_stream != 1, observation widths on both
+ * sides of 32 in one launch. */
+typedef struct {
+  const icrl_env_t* env;
+  const icrl_norm_t* nm;
+  const icrl_policy_t* pol;
+  const float* noise;           /* or NULL (mode of the distribution) */
+  const int32_t* base_count;
+  int32_t episodes_per_stream, deterministic, fixed_len, _pad;
+  double *orig_obs, *obs;
+  float* actions;
+  double* ep_rewards;
+  int32_t* ep_lengths;
+  int32_t* exec_steps;
+} icrl_chain_job_t;
+size_t icrl_sample_episodes_chain_ws_bytes(int n_jobs, const icrl_chain_job_t* jobs);
+int icrl_sample_episodes_chain(int n_jobs, const icrl_chain_job_t* jobs, const float* action_low, const float* action_high, int do_reset,
+                               void* ws, long long ws_bytes, void* args_ws, long long args_ws_bytes, void* stream);
+
 /* icrl_cn_train (full-batch mode) for n_runs constraint nets of one architecture: the four launches of an iteration carry all runs
  * (grid.y = run; row counts may differ between runs: grids are sized for the largest, iteration counts likewise). */
 typedef struct {
