@@ -70,6 +70,7 @@ SIGNATURES = {
                                 c_void_p, c_void_p],
     # batched forms (several independent runs in one launch, run = blockIdx.y): n_runs, jobs[n_runs], ..., args_ws, bytes, stream
     "icrl_rollout_collect_batch": [c_int, c_void_p, c_void_p, c_void_p] + [c_double] * 4 + [c_int, c_void_p, ctypes.c_longlong, c_void_p],
+    "icrl_rollout_collect_batch_cost": [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_double] * 4 + [c_int, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_gae_dual_batch": [c_int, c_void_p, c_int, c_int] + [c_double] * 4 + [c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_sample_episodes_batch": [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_sample_episodes_chain_ws_bytes": [c_int, c_void_p],

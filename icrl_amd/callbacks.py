@@ -157,13 +157,19 @@ class EvalCallback(BaseCallback):
     1-env eval stack, log eval/*, save the best model and fire callback_on_new_best."""
 
     def __init__(self, eval_env, callback_on_new_best=None, n_eval_episodes=5, eval_freq=10000, best_model_save_path=None,
-                 deterministic=True, verbose=1):
+                 deterministic=True, verbose=1, noise_streams=None):
         super().__init__(verbose)
         assert eval_env.num_envs == 1, "You must pass only one environment for evaluation"
         self.eval_env, self.callback, self.n_eval_episodes, self.eval_freq = eval_env, callback_on_new_best, n_eval_episodes, int(eval_freq)
         self.best_model_save_path, self.deterministic = best_model_save_path, deterministic
         self.best_mean_reward = self.last_mean_reward = -np.inf
         self.evaluations_timesteps, self.evaluations_results, self.evaluations_length = [], [], []
+        # opt-in: the action noise of the evaluation episodes comes from the run's own streams (streams.eval_noise) instead of the
+        # process-wide generator — what makes a run reproducible next to other runs in one process (icrl_amd/seed_batch.py)
+        self.noise_streams = noise_streams
+        # a seed batch sets `deferred` to a list: a trigger is then only noted as (n_calls, num_timesteps); the batch evaluates the
+        # episodes of all runs in one launch and hands each callback its results (record)
+        self.deferred = None
 
     def init_callback(self, model):
         super().init_callback(model)
@@ -177,27 +183,45 @@ class EvalCallback(BaseCallback):
     def _trigger_calls(self, lo, hi):
         return _multiples(self.eval_freq, lo, hi)
 
+    def draw_noise(self):
+        """the evaluation's action noise: None (evaluate_policy draws from the process-wide generator) without the opt-in."""
+        if self.noise_streams is None or self.deterministic:
+            return None
+        pol = self.model.policy
+        return self.noise_streams.eval_noise(self.n_eval_episodes * self.eval_env.unwrapped.max_steps, 1 if pol.discrete else pol.act_dim)
+
+    def evaluate(self):
+        """sync the normalisation statistics and run the episodes: (rewards, lengths) per episode."""
+        from .utils import evaluate_policy
+        from .vec_env import sync_envs_normalization
+        sync_envs_normalization(self.training_env, self.eval_env)
+        return evaluate_policy(self.model, self.eval_env, n_eval_episodes=self.n_eval_episodes, deterministic=self.deterministic,
+                               return_episode_rewards=True, noise=self.draw_noise())
+
+    def record(self, rewards, lengths):
+        """log eval/*, save the best model and fire callback_on_new_best."""
+        self.evaluations_timesteps.append(self.num_timesteps)
+        self.evaluations_results.append(list(rewards)); self.evaluations_length.append(list(lengths))
+        mean_reward = float(np.mean(rewards))
+        self.last_mean_reward = mean_reward
+        logger.record("eval/mean_reward", mean_reward)
+        logger.record("eval/mean_ep_length", float(np.mean(lengths)))
+        logger.record("eval/best_mean_reward", max(self.best_mean_reward, mean_reward))
+        if mean_reward > self.best_mean_reward:
+            if self.best_model_save_path is not None:
+                self.model.save(os.path.join(self.best_model_save_path, "best_model"))
+            self.best_mean_reward = mean_reward
+            if self.callback is not None:
+                self.callback.n_calls, self.callback.num_timesteps = self.n_calls, self.num_timesteps
+                return self.callback._on_step()
+        return True
+
     def _on_step(self):
         if self.eval_freq > 0 and self.n_calls % self.eval_freq == 0:
-            from .utils import evaluate_policy
-            from .vec_env import sync_envs_normalization
-            sync_envs_normalization(self.training_env, self.eval_env)
-            rewards, lengths = evaluate_policy(self.model, self.eval_env, n_eval_episodes=self.n_eval_episodes,
-                                               deterministic=self.deterministic, return_episode_rewards=True)
-            self.evaluations_timesteps.append(self.num_timesteps)
-            self.evaluations_results.append(list(rewards)); self.evaluations_length.append(list(lengths))
-            mean_reward = float(np.mean(rewards))
-            self.last_mean_reward = mean_reward
-            logger.record("eval/mean_reward", mean_reward)
-            logger.record("eval/mean_ep_length", float(np.mean(lengths)))
-            logger.record("eval/best_mean_reward", max(self.best_mean_reward, mean_reward))
-            if mean_reward > self.best_mean_reward:
-                if self.best_model_save_path is not None:
-                    self.model.save(os.path.join(self.best_model_save_path, "best_model"))
-                self.best_mean_reward = mean_reward
-                if self.callback is not None:
-                    self.callback.n_calls, self.callback.num_timesteps = self.n_calls, self.num_timesteps
-                    return self.callback._on_step()
+            if self.deferred is not None:
+                self.deferred.append((self.n_calls, self.num_timesteps))
+                return True
+            return self.record(*self.evaluate())
         return True
 
 

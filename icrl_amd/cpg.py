@@ -113,6 +113,8 @@ def setup(config, log=print):
     eval_every = int(config.eval_every) if not getattr(config, "eval_every_rollouts", 0) else int(config.eval_every_rollouts) * int(config.n_steps)
     cbs = [callbacks.EvalCallback(eval_env, eval_freq=eval_every, best_model_save_path=config.save_dir if rank == 0 else None,
                                   deterministic=False, verbose=0,
+                                  # opt-in (a seed batch sets it): evaluation noise from the run's own streams, not the process-wide generator
+                                  noise_streams=getattr(config, "streams", None) if getattr(config, "eval_noise_from_streams", False) else None,
                                   callback_on_new_best=callbacks.SaveEnvStatsCallback(train_env, config.save_dir if rank == 0 else None)),
            callbacks.AdjustedRewardCallback(get_true_cost_function(config.eval_env_id)), hist]
     if config.save_dir and rank == 0:
@@ -173,12 +175,39 @@ def build_parser():
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
+    a("--seeds", type=int, default=None, nargs="+", help="several seeds: the runs advance in lock-step, all of them in every launch "
+      "(icrl_amd/seed_batch.py); results go to <save_dir>/seed_<s>")
     return p
+
+
+def seed_configs(config):
+    """one config per entry of config["seeds"]: its seed, and <save_dir>/seed_<s> (created, with its config.json) as its save_dir."""
+    out = []
+    for s in config["seeds"]:
+        c = dict(config, seed=int(s))
+        if config["save_dir"]:
+            c["save_dir"] = os.path.join(config["save_dir"], f"seed_{int(s)}")
+            os.makedirs(c["save_dir"], exist_ok=True)
+            with open(os.path.join(c["save_dir"], "config.json"), "w") as fh:
+                json.dump(c, fh, indent=2, default=str)
+        out.append(types.SimpleNamespace(**c))
+    return out
 
 
 def main(argv=None):
     start = time.time()
     config = vars(build_parser().parse_args(argv if argv is not None else sys.argv[1:]))
+    if config["seeds"] is not None and len(config["seeds"]) > 1:      # a seed batch: one process, one rank
+        from .seed_batch import run_cpg_seed_batch
+        if len(set(config["seeds"])) != len(config["seeds"]):
+            raise ValueError(f"--seeds {config['seeds']}: the runs of a batch write to <save_dir>/seed_<s>, so every seed is given once")
+        rank, world = D.init_from_env()
+        config["rank"], config["world_size"] = rank, world
+        run_cpg_seed_batch(seed_configs(config))
+        print("Time taken: %05.2f hours" % ((time.time() - start) / 3600))
+        return
+    if config["seeds"] is not None:
+        config["seed"] = int(config["seeds"][0])
     if config["seed"] is None:
         config["seed"] = int(np.random.randint(0, 100))
     rank, world = D.init_from_env()

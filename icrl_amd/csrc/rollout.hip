@@ -1629,6 +1629,21 @@ __global__ void __launch_bounds__(256, MINW) rollout_persistent_batch_kernel(con
   rollout_persistent_body<OCT, CIT, GRAN, false, MON>(p);
 }
 
+// the batched launch with an analytic cost per run (CIT == 0: no cost-net register image), a kernel of its own name like
+// rollout_multi_analytic_kernel below.  Every run's descriptor (ActStepArgs.cf) sits in its own argument block and is read once,
+// before the step loop: the runs of a grid may differ in kind, index and thresholds.
+template <int OCT, bool GRAN, int MINW, bool MON = false>
+__global__ void __launch_bounds__(256, MINW) rollout_persistent_batch_analytic_kernel(const PersistArgs* __restrict__ runs) {
+  __shared__ PersistArgs p;
+  {
+    const unsigned* src = reinterpret_cast<const unsigned*>(runs + blockIdx.y);
+    unsigned* dst = reinterpret_cast<unsigned*>(&p);
+    for (unsigned i = threadIdx.x; i < sizeof(PersistArgs) / 4; i += 256) dst[i] = src[i];
+  }
+  __syncthreads();
+  rollout_persistent_body<OCT, 0, GRAN, false, MON>(p);
+}
+
 // =================================================================================================================
 // persistent rollout for MANY environments (128 < N <= 1024, or N x obs > 4096): BASELINE configs[2..4] per-GPU shards
 // =================================================================================================================
@@ -2738,6 +2753,27 @@ __global__ void __launch_bounds__(256) rollout_multi_batch_kernel(const WideArgs
   }
   __syncthreads();
   rollout_multi_body<OCT, CIT, E, MON>(p, g);
+}
+
+// rollout_multi_batch_kernel with an analytic cost per run (CIT == 0), under a name that sorts behind rollout_multi_analytic_kernel's
+// for the reason given there: the instantiations that existed before keep their numbers, hence their device code
+template <int OCT, int E, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_multi_batch_analytic_kernel(const WideArgs* __restrict__ runs, int n_runs, int G, int packed) {
+  __shared__ WideArgs p;
+  int run = (int)blockIdx.y, g = (int)blockIdx.x;
+  if (packed) {      // the G workgroups of a run on one XCD: workgroups b, b + 8, ... (rollout_multi_batch_kernel)
+    const int id = (int)blockIdx.x, per = 8 * G;
+    run = (id / per) * 8 + (id & 7);
+    g = (id % per) >> 3;
+    if (run >= n_runs) return;
+  }
+  {
+    const unsigned* src = reinterpret_cast<const unsigned*>(runs + run);
+    unsigned* dst = reinterpret_cast<unsigned*>(&p);
+    for (unsigned i = threadIdx.x; i < sizeof(WideArgs) / 4; i += 256) dst[i] = src[i];
+  }
+  __syncthreads();
+  rollout_multi_body<OCT, 0, E, MON>(p, g);
 }
 
 // VecNormalizeWithCost.reset (vec_normalize.py:148-157, 270-278)
@@ -3977,6 +4013,25 @@ static int launch_multi_fn(bool small, int E, const WideArgs* one, int G, size_t
   return E == 16 ? launch_multi_fn_e<8, 16, MON>(one, G, dyn, s) : (E == 8 ? launch_multi_fn_e<8, 8, MON>(one, G, dyn, s) : launch_multi_fn_e<8, 4, MON>(one, G, dyn, s));
 }
 
+// the batched analytic-cost kernels (rollout_multi_batch_analytic_kernel): launch_multi_e's second branch
+template <int OCT, int E, bool MON>
+static int launch_multi_batch_fn_e(const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+  if (!persistent_fits(rollout_multi_batch_analytic_kernel<OCT, E, MON>, G, dyn)) return -1;
+  int per_cu = 0;
+  const int groups = (n_runs + 7) / 8;
+  static const bool no_pack_b = getenv("ICRL_NO_XCD_PACK") != nullptr;
+  const bool packed = !no_pack_b && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_multi_batch_analytic_kernel<OCT, E, MON>, 256, dyn) == hipSuccess &&
+                      groups * G <= 32 * per_cu;
+  if (packed) hipLaunchKernelGGL((rollout_multi_batch_analytic_kernel<OCT, E, MON>), dim3(8 * G * ((n_runs + 7) / 8)), dim3(256), dyn, s, d_args, n_runs, G, 1);
+  else hipLaunchKernelGGL((rollout_multi_batch_analytic_kernel<OCT, E, MON>), dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
+  return (int)hipGetLastError();
+}
+template <bool MON>
+static int launch_multi_batch_fn(bool small, int E, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+  if (small) return E == 16 ? launch_multi_batch_fn_e<2, 16, MON>(d_args, n_runs, G, dyn, s) : (E == 8 ? launch_multi_batch_fn_e<2, 8, MON>(d_args, n_runs, G, dyn, s) : launch_multi_batch_fn_e<2, 4, MON>(d_args, n_runs, G, dyn, s));
+  return E == 16 ? launch_multi_batch_fn_e<8, 16, MON>(d_args, n_runs, G, dyn, s) : (E == 8 ? launch_multi_batch_fn_e<8, 8, MON>(d_args, n_runs, G, dyn, s) : launch_multi_batch_fn_e<8, 4, MON>(d_args, n_runs, G, dyn, s));
+}
+
 template <bool MON>
 static int launch_multi_m(bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
   // cn128: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
@@ -4293,13 +4348,12 @@ per_step:
 // icrl_rollout_collect for n_runs runs: ONE persistent launch of grid (N, n_runs) + ONE batched dual-GAE launch.  Only the
 // one-workgroup-per-env persistent kernel has a batched form (N <= 128 and N x obs <= 4096: BASELINE configs[1]); other shapes
 // are refused (the caller then issues the single-run calls).
-extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
-                                              const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
-                                              double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+// analytic: every jobs[r].cn is an icrl_cost_fn_t that passed cost_fn_check (icrl_rollout_collect_batch_cost) — the CIT == 0 kernels;
+// otherwise every jobs[r].cn is a constraint net, or NULL in every run
+static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
+                                      const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
+                                      double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream, bool analytic) {
   static_assert(sizeof(PersistArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
-  if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
-  for (int r = 0; r < n_runs; ++r)      // (seed batches are ICRL runs: they carry a constraint net)
-    if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
   if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
     return fail("icrl_rollout_collect_batch: args_ws holds %lld B, %d runs need %lld", args_ws_bytes, n_runs, (long long)n_runs * ICRL_BATCH_ARGS_BYTES);
   hipStream_t s = (hipStream_t)stream;
@@ -4329,7 +4383,7 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
           return fail("icrl_rollout_collect_batch: run %d differs from run 0 in a shape (envs / obs / act / T / discrete / constraint net)", r);
         if (!dims_ok(j.pol)) return bad_dims("icrl_rollout_collect_batch", j.pol);
         if (j.buf->obs_dim != O) return fail("icrl_rollout_collect_batch: run %d: buffer obs_dim %d vs env %d", r, j.buf->obs_dim, O);
-        if (j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
+        if (!analytic && j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
         void* ws = (j.ag->xch_ws != nullptr && (size_t)j.ag->xch_ws_bytes >= need) ? j.ag->xch_ws
                    : ((size_t)T * N * sizeof(float) >= need ? (void*)j.buf->reward_advantages : nullptr);
         if (ws == nullptr) { ok = false; break; }
@@ -4340,7 +4394,8 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
         a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
         a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
         a.has_cn = j.cn != nullptr;
-        if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
+        if (analytic) a.cf = *as_cost_fn(j.cn);
+        else if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
         p.nm = *j.nm; p.T = T; p.G = G; p.prof = 0;
         p.xg = reinterpret_cast<unsigned long long*>(ws);
         p.sg = p.xg + 2 * (size_t)N * GX;
@@ -4353,7 +4408,9 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
       }
       if (ok) {
         const bool small = O <= 32 && (!has_cn || j0.cn->in_dim <= 32);
-        const int err = launch_multi(mons != nullptr, small, !has_cn || j0.cn->in_dim <= 128, E, nullptr, d_args, n_runs, G, multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G), s);
+        const size_t mdyn = multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G);
+        const int err = analytic ? (mons != nullptr ? launch_multi_batch_fn<true>(small, E, d_args, n_runs, G, mdyn, s) : launch_multi_batch_fn<false>(small, E, d_args, n_runs, G, mdyn, s))
+                                 : launch_multi(mons != nullptr, small, !has_cn || j0.cn->in_dim <= 128, E, nullptr, d_args, n_runs, G, mdyn, s);
         if (err >= 0) {
           if (err || !(do_gae & 1)) return err;
           if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
@@ -4378,7 +4435,7 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
       return fail("icrl_rollout_collect_batch: run %d differs from run 0 in a shape (envs / obs / act / T / discrete / constraint net)", r);
     if (!dims_ok(j.pol)) return bad_dims("icrl_rollout_collect_batch", j.pol);
     if (j.buf->obs_dim != O) return fail("icrl_rollout_collect_batch: run %d: buffer obs_dim %d vs env %d", r, j.buf->obs_dim, O);
-    if (j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
+    if (!analytic && j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
     char* ws = (j.ag->xch_ws != nullptr && (size_t)j.ag->xch_ws_bytes >= need) ? reinterpret_cast<char*>(j.ag->xch_ws)
                : ((size_t)T * N * sizeof(float) >= need ? reinterpret_cast<char*>(j.buf->reward_advantages) : nullptr);
     if (ws == nullptr) return fail("icrl_rollout_collect_batch: run %d: exchange workspace of %zu B needed (icrl_agent_t.xch_ws, ICRL_ROLLOUT_WS_BYTES)", r, need);
@@ -4389,7 +4446,8 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
     a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
     a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
     a.has_cn = j.cn != nullptr;
-    if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
+    if (analytic) a.cf = *as_cost_fn(j.cn);
+    else if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
     p.nm = *j.nm; p.T = T; p.prof = 0;
     char* base = ws;
     p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
@@ -4420,7 +4478,19 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
   if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess) cus_ = 256;
   const int minw = minw_env > 0 ? minw_env : ((long long)n_runs * N <= cus_ ? 1 : 2);
   int err;
-  if (mons != nullptr) {
+  if (analytic) {      // the CIT == 0 instantiations, the same allocations
+    if (mons != nullptr) {
+      if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_analytic_kernel<2, true, 3, true>) : (minw == 2 ? go(rollout_persistent_batch_analytic_kernel<2, true, 2, true>) : go(rollout_persistent_batch_analytic_kernel<2, true, 1, true>));
+      else if (small) err = go(rollout_persistent_batch_analytic_kernel<2, false, 2, true>);
+      else if (gran) err = go(rollout_persistent_batch_analytic_kernel<8, true, 1, true>);
+      else err = go(rollout_persistent_batch_analytic_kernel<8, false, 1, true>);
+    } else {
+      if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_analytic_kernel<2, true, 3>) : (minw == 2 ? go(rollout_persistent_batch_analytic_kernel<2, true, 2>) : go(rollout_persistent_batch_analytic_kernel<2, true, 1>));
+      else if (small) err = go(rollout_persistent_batch_analytic_kernel<2, false, 2>);
+      else if (gran) err = go(rollout_persistent_batch_analytic_kernel<8, true, 1>);
+      else err = go(rollout_persistent_batch_analytic_kernel<8, false, 1>);
+    }
+  } else if (mons != nullptr) {
     if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3, true>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2, true>) : go(rollout_persistent_batch_kernel<2, 2, true, 1, true>));
     else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2, true>);
     else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1, true>);
@@ -4437,6 +4507,39 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
     return fail("icrl_rollout_collect_batch: args_ws needs 2 x n_runs x ICRL_BATCH_ARGS_BYTES = %lld B when the GAE launch is included", 2ll * n_runs * ICRL_BATCH_ARGS_BYTES);
   return icrl_gae_dual_batch_impl(n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda,
                                   (char*)args_ws + (size_t)n_runs * ICRL_BATCH_ARGS_BYTES, stream);
+}
+
+extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
+                                              const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
+                                              double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+  if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
+  for (int r = 0; r < n_runs; ++r)      // (the analytic form is icrl_rollout_collect_batch_cost's)
+    if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
+  return rollout_collect_batch_impl(n_runs, jobs, mons, action_low, action_high, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, do_gae,
+                                    args_ws, args_ws_bytes, stream, false);
+}
+
+// icrl_rollout_collect_batch_mon for runs against a FIXED cost (cpg seed batches): behind jobs[r].cn a constraint net in every run, NULL
+// in every run (both: exactly icrl_rollout_collect_batch_mon) or an analytic descriptor in every run (the CIT == 0 batched kernels; the
+// runs may differ in the descriptor's kind and values).  Everything is checked on the host before the first device call.
+extern "C" int icrl_rollout_collect_batch_cost(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
+                                               const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
+                                               double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+  if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch_cost: n_runs = %d (1..65535)", n_runs);
+  int n_fn = 0, n_net = 0;
+  for (int r = 0; r < n_runs; ++r) {
+    if (as_cost_fn(jobs[r].cn)) ++n_fn;
+    else if (jobs[r].cn != nullptr) ++n_net;
+  }
+  if (n_fn != 0 && n_fn != n_runs)
+    return fail("icrl_rollout_collect_batch_cost: %d of %d runs carry an analytic cost, %d a constraint net, %d none: a batch is one kernel, so "
+                "every run carries an analytic descriptor, or none does", n_fn, n_runs, n_net, n_runs - n_fn - n_net);
+  for (int r = 0; r < n_fn; ++r) {
+    const icrl_rollout_job_t& j = jobs[r];
+    if (int e = cost_fn_check("icrl_rollout_collect_batch_cost", as_cost_fn(j.cn), j.env->obs_dim, j.pol->discrete ? 0 : j.pol->act_dim, j.pol->discrete ? 1 : 0)) return e;
+  }
+  return rollout_collect_batch_impl(n_runs, jobs, mons, action_low, action_high, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, do_gae,
+                                    args_ws, args_ws_bytes, stream, n_fn != 0);
 }
 
 extern "C" int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,

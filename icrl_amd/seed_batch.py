@@ -30,7 +30,7 @@ import torch
 
 from . import _lib, logger, utils
 from .streams import PrivateStreams
-from .structs import CnTrainJobT, MonitorT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
+from .structs import CnTrainJobT, CostFnT, MonitorT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
 from .true_constraint_net import mean_cost
 from .vec_env import ENV_IDS, HostVecEnv, sync_envs_normalization
 
@@ -90,6 +90,16 @@ def _jobs(cls, rows):
 TUNE_PLACEMENT_IN_BATCH = os.environ.get("ICRL_SEED_TUNE", "0") == "1"
 
 
+def _eval_callbacks(cb):
+    """the EvalCallbacks inside a callback (a CallbackList is walked), in call order."""
+    from .callbacks import CallbackList, EvalCallback
+    if isinstance(cb, EvalCallback):
+        return [cb]
+    if isinstance(cb, CallbackList):
+        return [e for c in cb.callbacks for e in _eval_callbacks(c)]
+    return []
+
+
 class SeedBatch:
     def __init__(self, configs=None, states=None, on_setup=None):
         self.states = setup_runs(configs, on_setup) if states is None else states
@@ -129,10 +139,15 @@ class SeedBatch:
         L = _lib.lib()
         ws, nbytes = self._ws()
         mons = [a._mon for a in agents]
+        marr = None
         if any(m is not None for m in mons):      # episode statistics: one icrl_monitor_t per run (all runs or none: the kernels are one grid)
             if any(m is None for m in mons):
                 raise ValueError("seed batch: episode_stats must be on in every run of a batch or in none")
             marr = (MonitorT * len(mons))(*[m["struct"] for m in mons])
+        if any(isinstance(j["cn"], CostFnT) for j in jobs):      # analytic costs (cpg against the ground-truth or the null cost): their entry point
+            err = L.icrl_rollout_collect_batch_cost(len(jobs), arr, marr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
+                                                    float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, ws, nbytes, _lib.current_stream())
+        elif marr is not None:
             err = L.icrl_rollout_collect_batch_mon(len(jobs), arr, marr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
                                                    float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, ws, nbytes, _lib.current_stream())
         else:
@@ -192,29 +207,50 @@ class SeedBatch:
                 s_.prefetch_permutations(a.n_epochs, a.rollout_buffer.buffer_size * a.rollout_buffer.n_envs, self._side)
 
     # ---- phases ----------------------------------------------------------------------------------------------------------------
-    def _learn(self, total_timesteps):
-        """PPOLagrangian.learn(total_timesteps, cost_function="cost") of every run (ref: on_policy_algorithm.py:430-492), rollouts
-        and updates in lock-step."""
+    def _learn(self, total_timesteps, callbacks=None, prefetch_across_end=None):
+        """PPOLagrangian.learn(total_timesteps, cost_function="cost", callback=callbacks[i]) of every run (ref: on_policy_algorithm.py:430-492),
+        rollouts and updates in lock-step.  A run's callback gets the calls learn() makes, in its order: init_callback, on_training_start,
+        then per rollout on_rollout_start (before the noise draw), on_steps(n_steps), on_rollout_end (both after the launch, before the log
+        line is dumped), and on_training_end.  EvalCallbacks inside it only note their triggers during on_steps; the episodes of all runs
+        then go through ONE launch per trigger (_evaluations) and every callback records its own results before on_rollout_end."""
         sts = self.states
         agents = [st["agent"] for st in sts]
+        cbs = list(callbacks) if callbacks is not None else [None] * len(sts)
+        evals = [_eval_callbacks(cb) for cb in cbs]
+        if len({len(e) for e in evals}) != 1:
+            raise ValueError("seed batch: every run of a batch carries the same callbacks")
+        if prefetch_across_end is None:      # ICRL: not when the constraint net draws minibatch permutations from the same generator after learn()
+            prefetch_across_end = all("constraint_net" in st and st["constraint_net"].batch_size is None for st in sts)
         totals = []
-        for st, a in zip(sts, agents):
+        for st, a, cb, ev in zip(sts, agents, cbs, evals):
             with _as_run(st):
                 totals.append(a._setup_learn(total_timesteps, True))
                 if not a._fused_rollout_ok("cost", a.n_steps, a.rollout_buffer):
-                    raise ValueError("seed batch: the env chain must be the device-native stack with a ConstraintNet cost (the fused rollout)")
+                    raise ValueError("seed batch: the env chain must be the device-native stack with a ConstraintNet or an AnalyticCost (the fused rollout)")
+                for e in ev:
+                    e.deferred = []
+                if cb is not None:
+                    cb.init_callback(a)
+                    cb.on_training_start({}, {})
         iteration = 0
         while agents[0].num_timesteps < totals[0]:
             jobs = []
-            for st, a in zip(sts, agents):
+            for st, a, cb in zip(sts, agents, cbs):
                 with _as_run(st):
-                    jobs.append(a._rollout_begin(None, a.rollout_buffer, a.n_steps, None, zero_buffer=False))
+                    jobs.append(a._rollout_begin(cb, a.rollout_buffer, a.n_steps, None, zero_buffer=False))      # (calls on_rollout_start)
             self._launch_rollouts(agents, jobs)
             iteration += 1
-            tjobs = []
-            for st, a, j in zip(sts, agents, jobs):
+            for i, (st, a, j, cb) in enumerate(zip(sts, agents, jobs, cbs)):
                 with _as_run(st):
                     a._rollout_end(j, a.env, None, a.rollout_buffer, a.n_steps)
+                    if cb is not None and cb.on_steps(a.n_steps) is False:
+                        raise ValueError(f"seed batch: a callback of run {i} asked to stop training; the runs of a batch stop together, at total_timesteps")
+            self._evaluations(evals)
+            tjobs = []
+            for st, a, j, cb in zip(sts, agents, jobs, cbs):
+                with _as_run(st):
+                    if cb is not None:
+                        cb.on_rollout_end()
                     a._current_progress_remaining = 1.0 - float(a.num_timesteps) / float(totals[0])
                     a._training_infos(iteration)
                     logger.dump(step=a.num_timesteps)
@@ -226,15 +262,43 @@ class SeedBatch:
             # were ~5 ms of device time + ~7 ms of launches per update phase at S = 32, in front of the update launch.  Not across the end
             # of the forward step when the constraint net draws minibatch permutations from the same generator in between.
             more = agents[0].num_timesteps < totals[0]
-            if more or sts[0]["constraint_net"].batch_size is None:
+            if more or prefetch_across_end:
                 self._prefetch_permutations(agents, after=before_update)
             host = self._to_host([a.train_readback() for a in agents])          # waits for the update of every run
             for st, a, j, h in zip(sts, agents, tjobs, host):
                 with _as_run(st):
                     a._train_end(j, host=h)
-        for st, a in zip(sts, agents):
+        for st, a, cb, ev in zip(sts, agents, cbs, evals):
             with _as_run(st):
                 a._training_infos(iteration + 1)
+                if cb is not None:
+                    cb.on_training_end()
+                for e in ev:
+                    e.deferred = None
+
+    def _evaluations(self, evals):
+        """the triggers the runs' EvalCallbacks noted during on_steps: per trigger ONE launch with the evaluation episodes of every run
+        (_episodes), then each callback records its rewards and lengths (logs, best model, callback_on_new_best) as of the triggering
+        call.  evals[i]: the EvalCallbacks of run i, the same number in every run."""
+        sts = self.states
+        for slot in range(len(evals[0])):
+            es = [ev[slot] for ev in evals]
+            if len({(tuple(e.deferred), e.n_eval_episodes, bool(e.deterministic)) for e in es}) != 1:
+                raise ValueError("seed batch: the runs' EvalCallbacks trigger at different calls (eval_freq / n_eval_episodes / deterministic differ)")
+            for call, ts in list(es[0].deferred):
+                noises = []
+                for st, e in zip(sts, es):
+                    sync_envs_normalization(e.training_env, e.eval_env)
+                    noises.append(e.draw_noise())
+                runs, rewards = self._episodes([e.eval_env for e in es], es[0].n_eval_episodes, es[0].deterministic, noises, False)
+                for st, e, r, rw in zip(sts, es, runs, rewards):
+                    with _as_run(st):
+                        end = e.n_calls, e.num_timesteps
+                        e.n_calls, e.num_timesteps = call, ts
+                        e.record(*utils.evaluate_result(r, rw, return_episode_rewards=True))
+                        e.n_calls, e.num_timesteps = end
+            for e in es:
+                e.deferred = []
 
     def _episodes(self, envs, n_episodes, deterministic, noises, parallel):
         """n_episodes of the 1-env loop of every run (utils.EpisodeRun) in one launch; runs whose speculation failed repeat
@@ -400,3 +464,88 @@ def run_seed_batch(configs, n_iters, on_setup=None):
     sb = SeedBatch(configs, on_setup=on_setup)
     out, dt = sb.run(0, n_iters)
     return sb.states, out, dt
+
+
+# ---- cpg: PPO-Lagrangian against a FIXED cost (the ground-truth cost, the null cost, a frozen constraint net), S seeds in lock-step ----
+# everything a batched launch takes from run 0 only (grids, the batched GAE's discounting), plus what decides the sequence of phases
+CPG_SAME = ("train_env_id", "eval_env_id", "num_threads", "n_steps", "batch_size", "n_epochs", "reward_gamma", "reward_gae_lambda", "cost_gamma",
+            "cost_gae_lambda", "timesteps", "eval_every", "eval_every_rollouts", "use_pid", "use_null_cost")
+
+
+class CpgSeedBatch(SeedBatch):
+    """cpg.setup() per config — each run with its own PrivateStreams, scalar log, env stacks and callbacks — then ONE batched
+    learn(timesteps, cost_function="cost"): every rollout (icrl_rollout_collect_batch_cost for analytic costs, icrl_rollout_collect_batch[_mon]
+    for constraint nets), update (icrl_ppo_lag_train_batch) and evaluation (icrl_sample_episodes_batch) is one launch sequence for all runs.
+    The evaluation noise of a batched run comes from its own streams (config.eval_noise_from_streams, set here); a solo run with that
+    attribute and the same PrivateStreams computes the same bits."""
+
+    def __init__(self, configs, log=None):
+        from . import cpg as C
+        configs = list(configs)
+        if not configs:
+            raise ValueError("seed batch: no runs")
+        c0 = configs[0]
+        if os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") not in ("", "0"):
+            raise ValueError("seed batch: ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step rollout loop, which has no batched form")
+        for c in configs:
+            _refuse_host_envs(c.train_env_id, c.eval_env_id)
+            if getattr(c, "env_module", None) or getattr(c, "dummy_vec_env", False):
+                raise ValueError("seed batch: --env_module / --dummy_vec_env select host envs; the batched launches step device envs only")
+            if getattr(c, "world_size", 1) > 1:
+                raise ValueError("seed batch: the runs of a batch live on ONE rank (world_size > 1: launch one batch per GPU)")
+            if c.load_gail:
+                raise ValueError("seed batch: --load_gail hands the rollout a Python callable (the per-step loop); a batch takes a constraint net, "
+                                 "the ground-truth cost or the null cost")
+            if c.cost_info_str is None:
+                raise ValueError("seed batch: -cis None hands learn() the cost as a callable (the per-step loop); a batch needs the cost inside the env chain")
+            diff = [k for k in CPG_SAME if getattr(c, k) != getattr(c0, k)]
+            if (c.cn_path is None) != (c0.cn_path is None):
+                diff.append("cn_path is None")
+            if diff:
+                raise ValueError(f"seed batch: the runs of a batch share every grid and the sequence of phases; they differ in {diff}")
+        self.states = []
+        for i, cfg in enumerate(configs):
+            if getattr(cfg, "streams", None) is None:
+                cfg.streams = PrivateStreams(cfg.seed, discrete=cfg.train_env_id in ("LGW-v0", "CLGW-v0"))
+            if not hasattr(cfg.streams, "eval_noise"):
+                raise ValueError("seed batch: every run needs its own random streams")
+            cfg.eval_noise_from_streams = True
+            model, cb, learn_cost, hist = C.setup(cfg, log)
+            cw = model.env.venv
+            cn = cw.constraint_net() if hasattr(cw, "constraint_net") else None
+            if model.policy.wide or int(model.batch_size) > 256 or getattr(cn, "wide", False):
+                raise ValueError(f"seed batch: run {i}: hidden widths above 64 / batch sizes above 256 run on the generic-shape path, which has no batched form")
+            if isinstance(model.env.unwrapped, HostVecEnv) or not isinstance(learn_cost, str):
+                raise ValueError(f"seed batch: run {i}: the batched launches step device envs with the cost inside the env chain")
+            self.states.append(dict(config=cfg, agent=model, callback=cb, hist=hist, logger=logger.Logger.CURRENT, train_env=model.env))
+        torch.cuda.synchronize()
+        self.dev = self.states[0]["agent"].device
+        self.args_ws = torch.empty(2 * len(self.states) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=self.dev)
+
+    def _launch_trains(self, agents, jobs):
+        # observations of 65..128 (AntWall: 113): a run alone updates with FOUR workgroups per network (csrc/ppo_train_quarters*.hip), the
+        # batched grid has the row-owning kernel only, whose partial sums associate differently — a batched run would no longer compute
+        # what it computes alone.  Here: the single-run launch of every run, back to back on the stream (no host wait in between).
+        if agents[0].policy.obs_dim > 64 and len(agents) > 1:
+            for a, j in zip(agents, jobs):
+                if not a._train_ws["sync_tuned"] and not TUNE_PLACEMENT_IN_BATCH:
+                    a.tune_sync_placement = False
+                a._train_launch(j)
+            return
+        super()._launch_trains(agents, jobs)
+
+    def learn(self):
+        """one batched learn(); returns (model, history) per run like cpg(), final_model_policy.pth saved per run."""
+        self._learn(int(self.states[0]["config"].timesteps), callbacks=[st["callback"] for st in self.states], prefetch_across_end=False)
+        out = []
+        for st in self.states:
+            cfg = st["config"]
+            if cfg.save_dir:
+                torch.save(st["agent"].policy.state_dict(), os.path.join(cfg.save_dir, "final_model_policy.pth"))
+            out.append((st["agent"], st["hist"].history))
+        return out
+
+
+def run_cpg_seed_batch(configs, log=None):
+    """configs: one cpg config (types.SimpleNamespace, see cpg.build_parser / cpg.seed_configs) per run.  Returns (model, history) per run."""
+    return CpgSeedBatch(configs, log).learn()

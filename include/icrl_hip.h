@@ -125,7 +125,8 @@ typedef struct {
  * (previous raw observation float64, clipped action float32) exactly where the constraint net is.  Its first four int32 alias the
  * first four of icrl_costnet_t; n_hidden == ICRL_COST_FN is the tag: every entry point that takes `const icrl_costnet_t* cn` reads a
  * descriptor carrying it as an icrl_cost_fn_t (cast the pointer).  Served by icrl_rollout_collect[_ex][_mon], icrl_host_step[_mon],
- * icrl_cost_mlp_forward (= icrl_cost_fn_rows); refused with a reason by the *_batch rollouts, icrl_cn_train*, icrl_cn_prepare,
+ * icrl_cost_mlp_forward (= icrl_cost_fn_rows) and, for seed batches, icrl_rollout_collect_batch_cost; refused with a reason by
+ * icrl_rollout_collect_batch[_mon], icrl_cn_train*, icrl_cn_prepare,
  * icrl_disc_reward and icrl_costnet_prepare.  Operation for operation what numpy computes in the reference's callables:
  *   NULL           0
  *   WALL_BEHIND    obs[index] <= lo                      (float64 compare on the raw observation; wall_behind)
@@ -530,6 +531,18 @@ int icrl_rollout_collect_batch(int n_runs, const icrl_rollout_job_t* jobs, const
 int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
                                    const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
                                    double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream);
+
+/* the batched rollout of runs against a FIXED cost (cpg seed batches).  Behind jobs[r].cn one of: a constraint net in every run,
+ * NULL in every run (both: exactly icrl_rollout_collect_batch_mon, `mons` may be NULL), or an analytic descriptor (icrl_cost_fn_t,
+ * n_hidden == ICRL_COST_FN) in every run — each run's descriptor travels in its own argument block and is read once before the step
+ * loop, so the runs of a batch may differ in its kind, index and thresholds; grids and shapes are shared.  Every descriptor passes
+ * the checks of icrl_rollout_collect_ex; a batch that mixes analytic runs with constraint-net (or cost-free) runs is refused, all of
+ * it on the host before the first device call.  Kernel forms, shapes and the "no batched form for this shape" refusal are those of
+ * icrl_rollout_collect_batch_mon. */
+int icrl_rollout_collect_batch_cost(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons /* may be NULL */,
+                                    const float* action_low, const float* action_high, double reward_gamma, double reward_gae_lambda,
+                                    double cost_gamma, double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes,
+                                    void* stream);
 
 /* icrl_gae_dual_ws for n_runs [T,N] rollouts of one shape: ONE launch of the two-level scan, grid (tiles * C, n_runs), every run
  * with its own workspace; shapes the split scan does not serve are issued as n_runs single launches. */

@@ -1,9 +1,75 @@
-"""aggregate env-steps/s of S independent ICRL runs (BASELINE configs[1] each) sharing one MI355X inside the launches."""
+"""aggregate env-steps/s of S independent ICRL runs (BASELINE configs[1] each) sharing one MI355X inside the launches; --cpg: of S cpg runs
+(cpg_bench below)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from icrl_amd import seed_batch as SB
+
+
+
+def cpg_config(which, seed):
+    """configs4: BASELINE configs[4]'s 512-env shard with its frozen constraint net (bench.config_cpg); hc64: HCWithPos x 64 envs against the
+    ground-truth wall cost (an AnalyticCost: the batched analytic-cost kernels), default cpg flags otherwise."""
+    import types
+    from icrl_amd.cpg import build_parser
+    if which == "configs4":
+        return bench.config_cpg(seed, 0, 1)
+    cfg = vars(build_parser().parse_args(["cpg", "-tei", "HCWithPos-v0", "-eei", "HCWithPosTest-v0", "-nt", "64", "-s", str(seed), "-v", "0", "-t", "2e6"]))
+    cfg.update(rank=0, world_size=1, save_dir=None)
+    return types.SimpleNamespace(**cfg)
+
+
+def cpg_bench(argv):
+    """python tools/seed_batch_bench.py --cpg [--solo] [--workloads configs4,hc64] [--seeds 1,4,8,32] [--steps K] [--warmup W] [--reps R] [--out FILE]
+    One JSON line per (workload, S): aggregate env-steps/s of S cpg runs advancing in lock-step (CpgSeedBatch), R timed learn() calls of K
+    rollouts + updates each after W warm-up rollouts (median, min, max).  --solo: ONE run through cpg.setup + PPOLagrangian.learn, timed the
+    same way — the sequential aggregate of S seeds is that rate, since the runs then go one after another."""
+    import argparse, json
+    from icrl_amd import cpg as C
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cpg", action="store_true"); ap.add_argument("--solo", action="store_true")
+    ap.add_argument("--workloads", default="configs4,hc64"); ap.add_argument("--seeds", default="1,4,8,32")
+    ap.add_argument("--steps", type=int, default=2); ap.add_argument("--warmup", type=int, default=1); ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    for which in a.workloads.split(","):
+        for S in ([1] if a.solo else [int(x) for x in a.seeds.split(",")]):
+            cfgs = [cpg_config(which, seed) for seed in range(S)]
+            per = cfgs[0].num_threads * cfgs[0].n_steps
+            if a.solo:
+                model, cb, learn_cost, _ = C.setup(cfgs[0], log=None)
+                learn = lambda k: model.learn(total_timesteps=k * per, cost_function=learn_cost, callback=cb)
+            else:
+                sb = SB.CpgSeedBatch(cfgs)
+                cbs = [st["callback"] for st in sb.states]
+                learn = lambda k: sb._learn(k * per, callbacks=cbs, prefetch_across_end=False)
+            learn(a.warmup)
+            rates = []
+            for _ in range(a.reps):
+                torch.cuda.synchronize(); t0 = time.time()
+                learn(a.steps)
+                torch.cuda.synchronize(); rates.append(S * a.steps * per / (time.time() - t0))
+            rates.sort()
+            rec = dict(workload=which, driver="solo" if a.solo else "batch", S=S, envs=cfgs[0].num_threads, n_steps=cfgs[0].n_steps, steps=a.steps, warmup=a.warmup,
+                       reps=a.reps, env_steps_per_s_median=round(rates[len(rates) // 2], 1), env_steps_per_s_min=round(rates[0], 1),
+                       env_steps_per_s_max=round(rates[-1], 1))
+            print(json.dumps(rec), flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "a") as fh:
+                    fh.write(json.dumps(rec) + "\n")
+            if a.solo:
+                del model, cb
+            else:
+                del sb, cbs
+            del learn
+            torch.cuda.empty_cache()
+
+
+if "--cpg" in sys.argv[1:]:
+    cpg_bench(sys.argv[1:])
+    sys.exit(0)
 
 for S in [int(x) for x in os.environ.get("SEEDS", "1,8,32,64").split(",")]:
     sb = SB.SeedBatch([bench.config2(4 + int(os.environ.get('ITERS', '2')), seed, 0, 1) for seed in range(S)])
