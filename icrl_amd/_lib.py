@@ -77,6 +77,10 @@ SIGNATURES = {
     "icrl_sample_episodes_chain": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_cn_train_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_ppo_lag_train_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
+    "icrl_cn_train_minibatch_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
+    # the rollout-end work of the GAIL callback around the discriminator step (one icrl_gail_job_t per run)
+    "icrl_gail_unnormalize_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
+    "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
 RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}

@@ -180,34 +180,19 @@ def build_parser():
     return p
 
 
-def seed_configs(config):
-    """one config per entry of config["seeds"]: its seed, and <save_dir>/seed_<s> (created, with its config.json) as its save_dir."""
-    out = []
-    for s in config["seeds"]:
-        c = dict(config, seed=int(s))
-        if config["save_dir"]:
-            c["save_dir"] = os.path.join(config["save_dir"], f"seed_{int(s)}")
-            os.makedirs(c["save_dir"], exist_ok=True)
-            with open(os.path.join(c["save_dir"], "config.json"), "w") as fh:
-                json.dump(c, fh, indent=2, default=str)
-        out.append(types.SimpleNamespace(**c))
-    return out
+seed_configs = utils.seed_configs      # (its home is utils: icrl and gail take --seeds too)
 
 
 def main(argv=None):
     start = time.time()
     config = vars(build_parser().parse_args(argv if argv is not None else sys.argv[1:]))
-    if config["seeds"] is not None and len(config["seeds"]) > 1:      # a seed batch: one process, one rank
+    if utils.batch_seeds(config) is not None:      # a seed batch: one process, one rank
         from .seed_batch import run_cpg_seed_batch
-        if len(set(config["seeds"])) != len(config["seeds"]):
-            raise ValueError(f"--seeds {config['seeds']}: the runs of a batch write to <save_dir>/seed_<s>, so every seed is given once")
         rank, world = D.init_from_env()
         config["rank"], config["world_size"] = rank, world
         run_cpg_seed_batch(seed_configs(config))
         print("Time taken: %05.2f hours" % ((time.time() - start) / 3600))
         return
-    if config["seeds"] is not None:
-        config["seed"] = int(config["seeds"][0])
     if config["seed"] is None:
         config["seed"] = int(np.random.randint(0, 100))
     rank, world = D.init_from_env()

@@ -298,6 +298,15 @@ __device__ __forceinline__ void cn_finalize_body(const CnTrainArgs& a, int itr) 
 // the iteration (cn_forward_kernel + cn_finalize_kernel over ALL rows, as above), one optimiser step per batch of the
 // permutation; the batch takes the SAME row indices from the nominal and the expert set.
 // =================================================================================================================
+// the rows of ONE optimiser step: a minibatch's index slice (nullptr: all rows, full-batch mode), its length and the block counts of its
+// two sets.  The single-run launches carry it in their argument block (mb_idx, mb_n, nb_n, nb_e); the batched minibatch kernels derive
+// it per run (cn_mb_select) and leave the run's argument block where it is, in device memory.
+struct CnMb {
+  const int* idx;
+  int n, nb_n, nb_e;
+};
+__device__ __forceinline__ CnMb cn_mb_of(const CnTrainArgs& a) { return CnMb{a.mb_idx, a.mb_n, a.nb_n, a.nb_e}; }
+
 // importance weight of nominal row i as fixed at the start of the iteration
 __device__ __forceinline__ float cn_row_weight(const CnTrainArgs& a, int i) {
   if (!a.hp.importance_sampling) return 1.f;
@@ -305,20 +314,20 @@ __device__ __forceinline__ float cn_row_weight(const CnTrainArgs& a, int i) {
   return a.normed[a.row_ep[i]];
 }
 
-__global__ void __launch_bounds__(CN_TH) cn_mb_forward_kernel(CnTrainArgs a) {
+__device__ __forceinline__ void cn_mb_forward_body(const CnTrainArgs& a, const CnMb& mb) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   if (a.scal[SC_STOPPED] != 0.f) return;
   const CnDims& d = a.d;
   const int blk = blockIdx.x;
-  const bool nominal = blk < a.nb_n;
-  const int row0 = (nominal ? blk : blk - a.nb_n) * CN_ROWS;
-  cn_block_forward(d, sm, a.params, nominal ? a.nominal : a.expert, row0, a.mb_n, a.mb_idx);
+  const bool nominal = blk < mb.nb_n;
+  const int row0 = (nominal ? blk : blk - mb.nb_n) * CN_ROWS;
+  cn_block_forward(d, sm, a.params, nominal ? a.nominal : a.expert, row0, mb.n, mb.idx);
   if (threadIdx.x < 64) {
     const int row = threadIdx.x, g = row0 + row;
-    const bool valid = g < a.mb_n;
+    const bool valid = g < mb.n;
     const float z = sm[d.sZ + row], eps = a.hp.eps;
     const float lg = valid ? logf(z + eps) : 0.f;
-    const float w = (valid && nominal) ? cn_row_weight(a, a.mb_idx[g]) : 0.f;
+    const float w = (valid && nominal) ? cn_row_weight(a, mb.idx[g]) : 0.f;
     const float bce = valid ? (nominal ? fmaxf(logf(1.f - z), -100.f) : fmaxf(logf(z), -100.f)) : 0.f;
     const float s_log = wave_sum(lg);
     const float s_om = wave_sum(valid ? 1.f - z : 0.f);
@@ -335,13 +344,13 @@ __global__ void __launch_bounds__(CN_TH) cn_mb_forward_kernel(CnTrainArgs a) {
   }
 }
 
-__global__ void __launch_bounds__(64) cn_mb_finalize_kernel(CnTrainArgs a, int itr) {
+__device__ __forceinline__ void cn_mb_finalize_body(const CnTrainArgs& a, const CnMb& mb, int itr) {
   if (a.scal[SC_STOPPED] != 0.f) return;
   const int lane = threadIdx.x;
   float red[2][9];
   for (int set = 0; set < 2; ++set)
     for (int s = 0; s < 9; ++s) {
-      const int b0 = set == 0 ? 0 : a.nb_n, b1 = set == 0 ? a.nb_n : a.nb_n + a.nb_e;
+      const int b0 = set == 0 ? 0 : mb.nb_n, b1 = set == 0 ? mb.nb_n : mb.nb_n + mb.nb_e;
       const bool is_max = s == 3, is_min = s == 4;
       float acc = is_max ? -INFINITY : (is_min ? INFINITY : 0.f);
       for (int b = b0 + lane; b < b1; b += 64) {
@@ -353,7 +362,7 @@ __global__ void __launch_bounds__(64) cn_mb_finalize_kernel(CnTrainArgs a, int i
       red[set][s] = is_max ? wave_max(acc) : (is_min ? wave_min(acc) : wave_sum(acc));
     }
   if (lane != 0) return;
-  const float n = (float)a.mb_n;
+  const float n = (float)mb.n;
   float* m = a.metrics + (size_t)itr * ICRL_CN_METRICS;
   const float unweighted = red[0][0] / n;
   float nominal_loss, expert_loss, reg, loss;
@@ -377,16 +386,16 @@ __global__ void __launch_bounds__(64) cn_mb_finalize_kernel(CnTrainArgs a, int i
 }
 
 template <bool MB>
-__device__ __forceinline__ void cn_backward_body(const CnTrainArgs& a, int itr) {
+__device__ __forceinline__ void cn_backward_body(const CnTrainArgs& a, const CnMb& mb, int itr) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   if (a.scal[SC_STOPPED] != 0.f) return;
   const CnDims& d = a.d;
   const int blk = blockIdx.x, tid = threadIdx.x;
-  const bool nominal = blk < a.nb_n;
-  const int row0 = (nominal ? blk : blk - a.nb_n) * CN_ROWS;
-  const int n_tot = MB ? a.mb_n : (nominal ? a.Nn : a.Ne);
-  const float cnt_n = (float)(MB ? a.mb_n : a.Nn), cnt_e = (float)(MB ? a.mb_n : a.Ne);
-  cn_block_forward(d, sm, a.params, nominal ? a.nominal : a.expert, row0, n_tot, MB ? a.mb_idx : nullptr);
+  const bool nominal = blk < mb.nb_n;
+  const int row0 = (nominal ? blk : blk - mb.nb_n) * CN_ROWS;
+  const int n_tot = MB ? mb.n : (nominal ? a.Nn : a.Ne);
+  const float cnt_n = (float)(MB ? mb.n : a.Nn), cnt_e = (float)(MB ? mb.n : a.Ne);
+  cn_block_forward(d, sm, a.params, nominal ? a.nominal : a.expert, row0, n_tot, MB ? mb.idx : nullptr);
   const int row = tid & 63, part = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float* W = d.wglobal ? a.params : sm + d.sW;
   // ---- d loss / d logit
@@ -402,7 +411,7 @@ __device__ __forceinline__ void cn_backward_body(const CnTrainArgs& a, int itr) 
         else dzeta = (logf(z) > -100.f) ? -1.f / (cnt_e * z) : 0.f;
       } else if (nominal) {
         float wgt = 1.f;
-        if (a.hp.importance_sampling) wgt = a.hp.per_step ? a.scal[SC_MEAN_W] : a.normed[a.row_ep[MB ? a.mb_idx[g] : g]];
+        if (a.hp.importance_sampling) wgt = a.hp.per_step ? a.scal[SC_MEAN_W] : a.normed[a.row_ep[MB ? mb.idx[g] : g]];
         dzeta = wgt / (cnt_n * (z + eps)) - a.hp.reg_coeff / cnt_n;
       } else {
         dzeta = -1.f / (cnt_e * (z + eps)) - a.hp.reg_coeff / cnt_e;
@@ -457,10 +466,10 @@ __device__ __forceinline__ void cn_backward_body(const CnTrainArgs& a, int itr) 
   }
 }
 
-__device__ __forceinline__ void cn_adam_body(const CnTrainArgs& a, int itr, int upd) {
+__device__ __forceinline__ void cn_adam_body(const CnTrainArgs& a, const CnMb& mb, int itr, int upd) {
   if (a.scal[SC_STOPPED] != 0.f) return;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int nb = a.nb_n + a.nb_e;
+  const int nb = mb.nb_n + mb.nb_e;
   const int t = a.adam_t[0] + upd + 1;   // upd: optimiser steps before this one in the call; adam_t is advanced once at the end
   if (p < a.d.n_params) {
     float g = 0.f;
@@ -483,10 +492,12 @@ __device__ __forceinline__ void cn_adam_body(const CnTrainArgs& a, int itr, int 
 // shape in one launch: run = blockIdx.y, argument blocks in device memory; grids are sized for the largest run, surplus workgroups
 // of smaller runs leave at once)
 __global__ void __launch_bounds__(CN_TH) cn_forward_kernel(CnTrainArgs a, int itr) { cn_forward_body(a, itr); }
+__global__ void __launch_bounds__(CN_TH) cn_mb_forward_kernel(CnTrainArgs a) { cn_mb_forward_body(a, cn_mb_of(a)); }
+__global__ void __launch_bounds__(64) cn_mb_finalize_kernel(CnTrainArgs a, int itr) { cn_mb_finalize_body(a, cn_mb_of(a), itr); }
 __global__ void __launch_bounds__(1024) cn_finalize_kernel(CnTrainArgs a, int itr) { cn_finalize_body(a, itr); }
 template <bool MB>
-__global__ void __launch_bounds__(CN_TH) cn_backward_kernel(CnTrainArgs a, int itr) { cn_backward_body<MB>(a, itr); }
-__global__ void __launch_bounds__(256) cn_adam_kernel(CnTrainArgs a, int itr, int upd) { cn_adam_body(a, itr, upd); }
+__global__ void __launch_bounds__(CN_TH) cn_backward_kernel(CnTrainArgs a, int itr) { cn_backward_body<MB>(a, cn_mb_of(a), itr); }
+__global__ void __launch_bounds__(256) cn_adam_kernel(CnTrainArgs a, int itr, int upd) { cn_adam_body(a, cn_mb_of(a), itr, upd); }
 __global__ void cn_commit_kernel(CnTrainArgs a) {
   // advance the optimiser step counter by the number of executed updates
   if (threadIdx.x == 0 && blockIdx.x == 0) a.adam_t[0] += (int)a.scal[SC_ITER];
@@ -505,16 +516,55 @@ __global__ void __launch_bounds__(1024) cn_finalize_batch_kernel(const CnTrainAr
 __global__ void __launch_bounds__(CN_TH) cn_backward_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr) {
   const CnTrainArgs a = runs[blockIdx.y];
   if ((int)blockIdx.x >= a.nb_n + a.nb_e || itr >= a.hp.iterations) return;
-  cn_backward_body<false>(a, itr);
+  cn_backward_body<false>(a, cn_mb_of(a), itr);
 }
 __global__ void __launch_bounds__(256) cn_adam_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr) {
   const CnTrainArgs a = runs[blockIdx.y];
   if (itr >= a.hp.iterations) return;
-  cn_adam_body(a, itr, itr);
+  cn_adam_body(a, cn_mb_of(a), itr, itr);
 }
 __global__ void cn_commit_batch_kernel(const CnTrainArgs* __restrict__ runs) {
   const CnTrainArgs a = runs[blockIdx.y];
   if (threadIdx.x == 0 && blockIdx.x == 0) a.adam_t[0] += (int)a.scal[SC_ITER];
+}
+
+// minibatch mode, batched: the argument block of a run holds the call's arguments (mb_idx = the run's permutation table, mb_n = 0) and is
+// read where it lies; minibatch k of iteration itr — its index slice, its ragged length and its two block counts — is derived here, as
+// the single-run entry point derives it on the host per launch.  Returns false for a launch the run does not have (iterations and
+// minibatch counts differ between runs: the grids are sized for the largest).
+__device__ __forceinline__ bool cn_mb_select(const CnTrainArgs& a, int itr, int k, int batch_size, CnMb& mb) {
+  if (itr >= a.hp.iterations) return false;
+  const int size = a.Nn < a.Ne ? a.Nn : a.Ne;
+  if (k * batch_size >= size) return false;
+  mb.idx = a.mb_idx + (size_t)itr * size + (size_t)k * batch_size;
+  mb.n = (k + 1) * batch_size <= size ? batch_size : size - k * batch_size;
+  mb.nb_n = mb.nb_e = (mb.n + CN_ROWS - 1) / CN_ROWS;
+  return true;
+}
+__global__ void __launch_bounds__(CN_TH) cn_mb_forward_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr, int k, int batch_size) {
+  const CnTrainArgs& a = runs[blockIdx.y];
+  CnMb mb;
+  if (!cn_mb_select(a, itr, k, batch_size, mb) || (int)blockIdx.x >= mb.nb_n + mb.nb_e) return;
+  cn_mb_forward_body(a, mb);
+}
+__global__ void __launch_bounds__(64) cn_mb_finalize_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr, int k, int batch_size) {
+  const CnTrainArgs& a = runs[blockIdx.y];
+  CnMb mb;
+  if (!cn_mb_select(a, itr, k, batch_size, mb)) return;
+  cn_mb_finalize_body(a, mb, itr);
+}
+__global__ void __launch_bounds__(CN_TH) cn_mb_backward_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr, int k, int batch_size) {
+  const CnTrainArgs& a = runs[blockIdx.y];
+  CnMb mb;
+  if (!cn_mb_select(a, itr, k, batch_size, mb) || (int)blockIdx.x >= mb.nb_n + mb.nb_e) return;
+  cn_backward_body<true>(a, mb, itr);
+}
+__global__ void __launch_bounds__(256) cn_mb_adam_batch_kernel(const CnTrainArgs* __restrict__ runs, int itr, int k, int batch_size) {
+  const CnTrainArgs& a = runs[blockIdx.y];
+  CnMb mb;
+  if (!cn_mb_select(a, itr, k, batch_size, mb)) return;
+  const int size = a.Nn < a.Ne ? a.Nn : a.Ne;
+  cn_adam_body(a, mb, itr, itr * ((size + batch_size - 1) / batch_size) + k);
 }
 
 __global__ void __launch_bounds__(64) cn_prepare_kernel(icrl_costnet_t cn, const double* obs, const float* acs, int N, float* out) {
@@ -542,7 +592,9 @@ __global__ void __launch_bounds__(64) cn_prepare_kernel(icrl_costnet_t cn, const
 // ConstraintNet.cost_function / the GAIL discriminator's reward for nets the one-wave-per-row kernel of rollout.hip does not hold
 // (a hidden layer above 64 units): 64 rows per workgroup, prepare_data (constraint_net.py:258-299) straight into the LDS input image,
 // then the block MLP of the update kernels.  mode 0: cost = 1 - zeta; 1: zeta; 2: log(zeta + eps).
-__global__ void __launch_bounds__(CN_TH) cn_cost_rows_kernel(icrl_costnet_t cn, CnDims d, const double* obs, const float* acs, int N, float* out, int mode) {
+// accumulate (the GAIL relabelling with --learn_cost): out += the value instead of out = the value
+__device__ __forceinline__ void cn_cost_rows_body(const icrl_costnet_t& cn, const CnDims& d, const double* obs, const float* acs, int N, float* out, int mode,
+                                                  bool accumulate) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, row0 = blockIdx.x * CN_ROWS, D = d.D;
   const int AS = cn.is_discrete ? 1 : cn.acs_dim;
@@ -568,8 +620,26 @@ __global__ void __launch_bounds__(CN_TH) cn_cost_rows_kernel(icrl_costnet_t cn, 
   cn_block_mlp(d, sm, cn.params);
   if (tid < CN_ROWS && row0 + tid < N) {
     const float zeta = sm[d.sZ + tid];
-    out[row0 + tid] = mode == 1 ? zeta : (mode == 2 ? logf(zeta + (float)cn.eps) : 1.f - zeta);
+    const float v = mode == 1 ? zeta : (mode == 2 ? logf(zeta + (float)cn.eps) : 1.f - zeta);
+    out[row0 + tid] = accumulate ? out[row0 + tid] + v : v;
   }
+}
+__global__ void __launch_bounds__(CN_TH) cn_cost_rows_kernel(icrl_costnet_t cn, CnDims d, const double* obs, const float* acs, int N, float* out, int mode) {
+  cn_cost_rows_body(cn, d, obs, acs, N, out, mode, false);
+}
+// the GAIL relabelling of several runs (icrl_gail_relabel_batch) for the nets this kernel serves: run = blockIdx.y
+struct CnRowsArgs {
+  icrl_costnet_t cn;
+  CnDims d;
+  const double* obs;
+  const float* acs;
+  float* out;
+  int N, accumulate;
+};
+__global__ void __launch_bounds__(CN_TH) cn_cost_rows_batch_kernel(const CnRowsArgs* __restrict__ runs) {
+  const CnRowsArgs& a = runs[blockIdx.y];      // (read where it lies: the layer loops index its dimension arrays)
+  if ((int)blockIdx.x * CN_ROWS >= a.N) return;
+  cn_cost_rows_body(a.cn, a.d, a.obs, a.acs, a.N, a.out, 2, a.accumulate != 0);
 }
 
 // descriptor -> CnDims + dynamic LDS bytes of the 64-row kernels; refuses (fail()) what they do not hold
@@ -598,6 +668,47 @@ int launch_cn_cost_rows(const icrl_costnet_t* cn, const double* obs, const float
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(cn_cost_rows_kernel, dim3((N + CN_ROWS - 1) / CN_ROWS), dim3(CN_TH), lds, s, *cn, d, obs, acs, N, out, mode);
   return (int)hipGetLastError();
+}
+
+static bool same_cn_shape(const CnDims& a, const CnDims& b) {
+  bool same = a.D == b.D && a.nh == b.nh && a.n_params == b.n_params;
+  for (int l = 0; l < CN_MAX_LAYERS; ++l) same = same && a.H[l] == b.H[l];
+  return same;
+}
+
+// log D of n_runs discriminators of one shape on each run's rows, into (or onto) its rewards: ONE launch, grid (row blocks of the largest
+// run, n_runs).  Every check runs before the first device call.
+int launch_gail_relabel_rows(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, hipStream_t s) {
+  static_assert(sizeof(CnRowsArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  CnRowsArgs stack_args[16];
+  CnRowsArgs* args = n_runs <= 16 ? stack_args : new CnRowsArgs[n_runs];
+  size_t lds0 = 0;
+  int rows_max = 0, bad = 0;
+  for (int r = 0; r < n_runs && !bad; ++r) {
+    const icrl_gail_job_t& j = jobs[r];
+    CnRowsArgs& a = args[r];
+    size_t lds = 0;
+    bad = cn_dims_checked(j.disc, "icrl_gail_relabel_batch", &a.d, &lds);
+    if (bad) break;
+    if (r == 0) lds0 = lds;
+    else if (lds != lds0 || !same_cn_shape(a.d, args[0].d)) {
+      bad = fail("icrl_gail_relabel_batch: run %d's discriminator shape differs from run 0's (the runs of a batch share one grid)", r);
+      break;
+    }
+    a.cn = *j.disc; a.obs = j.raw_obs; a.acs = j.actions; a.out = j.rewards; a.N = j.rows; a.accumulate = j.learn_cost != 0;
+    rows_max = j.rows > rows_max ? j.rows : rows_max;
+  }
+  if (!bad) {
+    hipError_t e = hipFuncSetAttribute((const void*)cn_cost_rows_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0);
+    bad = (int)e;
+    for (int r = 0; r < n_runs && !bad; ++r) bad = put_args(args[r], (CnRowsArgs*)args_ws + r, s);
+    if (!bad) {
+      hipLaunchKernelGGL(cn_cost_rows_batch_kernel, dim3((rows_max + CN_ROWS - 1) / CN_ROWS, n_runs), dim3(CN_TH), lds0, s, (const CnRowsArgs*)args_ws);
+      bad = (int)hipGetLastError();
+    }
+  }
+  if (args != stack_args) delete[] args;
+  return bad;
 }
 
 static void cn_work_layout(int n_params, int Nn, int Ne, int n_ep, size_t* offs /* 9 */, size_t* total) {
@@ -635,12 +746,13 @@ extern "C" int icrl_cn_prepare(const icrl_costnet_t* cn, const double* obs, cons
 // argument checks + argument block of one full-batch train() call; *lds = dynamic LDS bytes of the forward / backward kernels
 static int make_cn_train_args(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, int32_t* adam_step, const float* nominal,
                               const float* expert, int Nn, int Ne, const int32_t* ep_offsets, const int32_t* row_episode, int n_ep,
-                              const icrl_cn_hyper_t* hp, float* work, float* metrics, CnTrainArgs& a, size_t* lds_out) {
-  if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_train");
+                              const icrl_cn_hyper_t* hp, float* work, float* metrics, CnTrainArgs& a, size_t* lds_out,
+                              const char* who = "icrl_cn_train") {
+  if (as_cost_fn(cn)) return refuse_cost_fn(who);
   if (Nn <= 0 || Ne <= 0 || n_ep <= 0 || hp->iterations < 0)
-    return fail("icrl_cn_train: needs nominal rows (%d), expert rows (%d), episodes (%d) > 0 and iterations (%d) >= 0", Nn, Ne, n_ep, hp->iterations);
+    return fail("%s: needs nominal rows (%d), expert rows (%d), episodes (%d) > 0 and iterations (%d) >= 0", who, Nn, Ne, n_ep, hp->iterations);
   size_t lds;
-  if (int e = cn_dims_checked(cn, "icrl_cn_train", &a.d, &lds)) return e;
+  if (int e = cn_dims_checked(cn, who, &a.d, &lds)) return e;
   *lds_out = lds;
   a.params = cn->params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.adam_t = adam_step;
   a.nominal = nominal; a.expert = expert; a.Nn = Nn; a.Ne = Ne; a.n_ep = n_ep;
@@ -781,5 +893,72 @@ extern "C" int icrl_cn_train_minibatch(const icrl_costnet_t* cn, float* exp_avg,
     }
   }
   hipLaunchKernelGGL(cn_commit_kernel, dim3(1), dim3(64), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int icrl_cn_train_minibatch_batch(int n_runs, const icrl_cn_train_mb_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream) {
+  const char* who = "icrl_cn_train_minibatch_batch";
+  if (n_runs < 1 || n_runs > 65535) return fail("%s: n_runs = %d (1..65535)", who, n_runs);
+  if (jobs == nullptr) return fail("%s: jobs = NULL", who);
+  if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
+    return fail("%s: args_ws holds %lld B, %d runs need %lld", who, args_ws_bytes, n_runs, (long long)n_runs * ICRL_BATCH_ARGS_BYTES);
+  // ---- every refusal first: nothing reaches the device for a batch one of whose runs is refused
+  CnTrainArgs stack_args[16];
+  CnTrainArgs* args = n_runs <= 16 ? stack_args : new CnTrainArgs[n_runs];
+  size_t lds0 = 0;
+  int nb_max = 0, iters_max = 0, size_max = 0, bad = 0;
+  const int bs = jobs[0].batch_size;
+  for (int r = 0; r < n_runs && !bad; ++r) {
+    const icrl_cn_train_mb_job_t& j = jobs[r];
+    CnTrainArgs& a = args[r];
+    size_t lds = 0;
+    if (j.cn == nullptr || j.hp == nullptr) { bad = fail("%s: run %d has no network descriptor or no hyper-parameters", who, r); break; }
+    bad = make_cn_train_args(j.cn, j.exp_avg, j.exp_avg_sq, j.adam_step, j.nominal, j.expert, j.Nn, j.Ne, j.ep_offsets, j.row_episode, j.n_ep, j.hp,
+                             j.work, j.metrics, a, &lds, who);
+    if (bad) break;
+    if (j.perms == nullptr) { bad = fail("%s: run %d has no permutation table (perms = NULL)", who, r); break; }
+    if (j.batch_size <= 0) { bad = fail("%s: run %d: batch_size = %d (must be > 0)", who, r, j.batch_size); break; }
+    if (r == 0) lds0 = lds;
+    else if (lds != lds0 || !same_cn_shape(a.d, args[0].d)) {
+      bad = fail("%s: run %d's network shape differs from run 0's (the runs of a batch share one grid)", who, r);
+      break;
+    }
+    if (j.batch_size != bs) { bad = fail("%s: run %d's batch_size %d differs from run 0's %d (the runs of a batch share one grid)", who, r, j.batch_size, bs); break; }
+    a.mb_idx = j.perms;      // (the table's base: cn_mb_select takes minibatch k of iteration itr from it)
+    const int size = j.Nn < j.Ne ? j.Nn : j.Ne;
+    nb_max = a.nb_n + a.nb_e > nb_max ? a.nb_n + a.nb_e : nb_max;
+    iters_max = j.hp->iterations > iters_max ? j.hp->iterations : iters_max;
+    size_max = size > size_max ? size : size_max;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  CnTrainArgs* d_args = (CnTrainArgs*)args_ws;
+  for (int r = 0; r < n_runs && !bad; ++r) {
+    const icrl_cn_train_mb_job_t& j = jobs[r];
+    bad = (int)hipMemsetAsync(args[r].scal, 0, SC_COUNT * sizeof(float), s);
+    if (!bad && j.hp->iterations > 0) bad = (int)hipMemsetAsync(j.metrics, 0, (size_t)j.hp->iterations * ICRL_CN_METRICS * sizeof(float), s);
+    if (!bad) bad = put_args(args[r], d_args + r, s);
+  }
+  const int np0 = args[0].d.n_params;
+  if (args != stack_args) delete[] args;
+  if (bad) return bad;
+  const void* fns[3] = {(const void*)cn_forward_batch_kernel, (const void*)cn_mb_forward_batch_kernel, (const void*)cn_mb_backward_batch_kernel};
+  for (const void* f : fns) {
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0);
+    if (e != hipSuccess) return (int)e;
+  }
+  const int n_batches_max = (size_max + bs - 1) / bs;
+  const int mb_rows = bs < size_max ? bs : size_max;
+  const int nb_mb = 2 * ((mb_rows + CN_ROWS - 1) / CN_ROWS);
+  for (int itr = 0; itr < iters_max; ++itr) {
+    hipLaunchKernelGGL(cn_forward_batch_kernel, dim3(nb_max, n_runs), dim3(CN_TH), lds0, s, d_args, itr);
+    hipLaunchKernelGGL(cn_finalize_batch_kernel, dim3(1, n_runs), dim3(1024), 0, s, d_args, itr);
+    for (int k = 0; k < n_batches_max; ++k) {
+      hipLaunchKernelGGL(cn_mb_forward_batch_kernel, dim3(nb_mb, n_runs), dim3(CN_TH), lds0, s, d_args, itr, k, bs);
+      hipLaunchKernelGGL(cn_mb_finalize_batch_kernel, dim3(1, n_runs), dim3(64), 0, s, d_args, itr, k, bs);
+      hipLaunchKernelGGL(cn_mb_backward_batch_kernel, dim3(nb_mb, n_runs), dim3(CN_TH), lds0, s, d_args, itr, k, bs);
+      hipLaunchKernelGGL(cn_mb_adam_batch_kernel, dim3((np0 + 255) / 256, n_runs), dim3(256), 0, s, d_args, itr, k, bs);
+    }
+  }
+  hipLaunchKernelGGL(cn_commit_batch_kernel, dim3(1, n_runs), dim3(64), 0, s, d_args);
   return (int)hipGetLastError();
 }

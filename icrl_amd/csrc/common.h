@@ -31,6 +31,8 @@ int policy_generic_check(const icrl_policy_t* p, const char* who);      // 0, or
 inline bool policy_is_wide(const icrl_policy_t* p) { return p->arch != nullptr || p->h1 > MAX_H || p->h2 > MAX_H; }
 // cn_train.hip: cost / discriminator forward of a constraint net with a hidden layer above MAX_H units or more than two of them (64 rows per workgroup)
 int launch_cn_cost_rows(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* out, int mode, hipStream_t s);
+// cn_train.hip: log D of n_runs wide discriminators on each run's rows, into (or onto) its rewards (icrl_gail_relabel_batch)
+int launch_gail_relabel_rows(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, hipStream_t s);
 inline bool costnet_is_wide(const icrl_costnet_t* cn) { return cn->n_hidden > 2 || cn->n_hidden == 0 || cn->h1 > MAX_H || (cn->n_hidden == 2 && cn->h2 > MAX_H); }
 
 // argument rejection: formats the reason into the calling thread's icrl_last_error() text, returns hipErrorInvalidValue

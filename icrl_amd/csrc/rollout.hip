@@ -2976,6 +2976,82 @@ __global__ void __launch_bounds__(64) cost_forward_kernel(icrl_costnet_t cn, CnL
   if (threadIdx.x == 0) cost[n] = c;
 }
 
+// ---- the rollout-end work of the GAIL callback around the discriminator step (icrl_gail_unnormalize_batch / icrl_gail_relabel_batch):
+// run = blockIdx.y, argument blocks in device memory, grids sized for the largest run
+struct GailArgs {
+  icrl_costnet_t cn;            // the discriminator
+  CnLayout cl;
+  icrl_cost_fn_t f;             // the ground-truth cost (has_cost)
+  const float* obs;             // [rows, obs_dim] normalised float32
+  const float* acs;             // [rows, AS]
+  const double *mean, *var;     // or NULL
+  double eps;
+  double* raw;                  // [rows, obs_dim]
+  float* rewards;               // [rows]
+  double* cost_mean;            // [1]
+  int rows, obs_dim, has_cost, learn_cost;
+};
+
+// raw = float64(obs) * sqrt(var + eps) + mean: the product and the sum are rounded separately (torch issues a mul and an add)
+__global__ void __launch_bounds__(256) gail_unnormalize_kernel(const GailArgs* __restrict__ runs) {
+  const GailArgs& a = runs[blockIdx.y];
+  const long long total = (long long)a.rows * a.obs_dim;
+  const double *mean = a.mean, *var = a.var;
+  const double eps = a.eps;
+  const float* obs = a.obs;
+  double* raw = a.raw;
+  const int O = a.obs_dim;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    double v = (double)obs[i];
+    if (mean != nullptr) {
+      const int k = (int)(i % O);
+      v = __dadd_rn(__dmul_rn(v, sqrt(__dadd_rn(var[k], eps))), mean[k]);
+    }
+    raw[i] = v;
+  }
+}
+
+// cost_mean = mean of the ground-truth cost over the run's rows: one workgroup per run; the costs are 0, 1 or 2, so they are counted in
+// integers (any order is exact).  The mean is count * (1.0 / rows), two roundings: that is how torch's device reduction finishes a mean
+// (sum times the reciprocal of the row count), so the bits are those of c.double().mean() on the device; count / rows can differ from it
+// in the last place (89 of 132 rows does).  Runs after gail_unnormalize_kernel.
+__global__ void __launch_bounds__(1024) gail_cost_mean_kernel(const GailArgs* __restrict__ runs) {
+  __shared__ long long part[16];
+  const GailArgs& a = runs[blockIdx.y];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  long long cnt = 0;
+  if (a.has_cost) {
+    const icrl_cost_fn_t f = a.f;
+    const int AS = f.kind == ICRL_COST_ACTION_EQUALS ? 1 : f.acs_dim;
+    for (int n = tid; n < a.rows; n += 1024) cnt += (long long)cost_fn_wave(f, a.raw + (size_t)n * a.obs_dim, a.acs + (size_t)n * AS);
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+  if (lane == 0) part[wv] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    long long t = 0;
+    for (int w = 0; w < 16; ++w) t += part[w];
+    a.cost_mean[0] = a.has_cost ? __dmul_rn((double)t, 1.0 / (double)a.rows) : 0.0;
+  }
+}
+
+// rewards (+)= log(D(raw, acs) + eps): cost_forward_kernel's row forward in mode 2, one wave per row — the bits of icrl_disc_reward
+template <int CIT>
+__global__ void __launch_bounds__(64) gail_relabel_kernel(const GailArgs* __restrict__ runs) {
+  __shared__ __attribute__((aligned(16))) float cx[MAX_CN_IN];
+  __shared__ __attribute__((aligned(16))) float ch[2][MAX_H];
+  const int n = blockIdx.x;
+  if (n >= runs[blockIdx.y].rows) return;
+  GailArgs a = runs[blockIdx.y];
+  globalize(a.cn);
+  CnRegs<CIT> C;
+  load_cn_regs<CIT>(a.cn, a.cl, C);
+  const int AS = a.cn.is_discrete ? 1 : a.cn.acs_dim;
+  const float r = cost_forward_wave<CIT>(a.cn, a.cl, C, a.raw + (size_t)n * a.cn.obs_dim, a.acs + (size_t)n * AS, cx, ch, 2);
+  if (threadIdx.x == 0) a.rewards[n] = a.learn_cost ? a.rewards[n] + r : r;
+}
+
 // an analytic cost on N rows of the caller's arrays (icrl_cost_fn_rows): one row per thread, grid-stride, no LDS
 __global__ void __launch_bounds__(256) cost_fn_rows_kernel(icrl_cost_fn_t f, const double* __restrict__ obs, const float* __restrict__ acs, int N,
                                                            float* __restrict__ cost) {
@@ -3891,6 +3967,98 @@ extern "C" int icrl_disc_reward(const icrl_costnet_t* cn, const double* obs, con
   const int mode = apply_log ? 2 : 1;
   if (cn->in_dim <= 32) hipLaunchKernelGGL(cost_forward_kernel<2>, dim3(N), dim3(64), 0, (hipStream_t)stream, *cn, L, obs, acs, N, out, mode);
   else hipLaunchKernelGGL(cost_forward_kernel<10>, dim3(N), dim3(64), 0, (hipStream_t)stream, *cn, L, obs, acs, N, out, mode);
+  return (int)hipGetLastError();
+}
+
+// argument checks of the two GAIL entry points + the runs' argument blocks (host memory: `out`, n_runs entries)
+static int make_gail_args(const char* who, int n_runs, const icrl_gail_job_t* jobs, void* args_ws, long long args_ws_bytes, GailArgs* out, bool relabel) {
+  static_assert(sizeof(GailArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
+    return fail("%s: args_ws holds %lld B, %d runs need %lld", who, args_ws_bytes, n_runs, (long long)n_runs * ICRL_BATCH_ARGS_BYTES);
+  for (int r = 0; r < n_runs; ++r) {
+    const icrl_gail_job_t& j = jobs[r];
+    GailArgs& a = out[r];
+    if (j.disc == nullptr) return fail("%s: run %d has no discriminator descriptor", who, r);
+    if (as_cost_fn(j.disc)) return refuse_cost_fn(who);
+    if (j.rows <= 0) return fail("%s: run %d: rows = %d", who, r, j.rows);
+    if (j.actions == nullptr || j.raw_obs == nullptr) return fail("%s: run %d: actions = %p, raw_obs = %p", who, r, (const void*)j.actions, (void*)j.raw_obs);
+    if (j.disc->obs_dim < 1) return fail("%s: run %d: obs_dim = %d", who, r, j.disc->obs_dim);
+    a.has_cost = 0;
+    if (!relabel) {
+      if (j.observations == nullptr || j.cost_mean == nullptr)
+        return fail("%s: run %d: observations = %p, cost_mean = %p", who, r, (const void*)j.observations, (void*)j.cost_mean);
+      if ((j.obs_mean == nullptr) != (j.obs_var == nullptr)) return fail("%s: run %d: obs_mean and obs_var come together or not at all", who, r);
+      if (j.true_cost != nullptr) {
+        if (j.true_cost->n_hidden != ICRL_COST_FN) return fail("%s: run %d: true_cost is not an analytic cost descriptor (n_hidden must be ICRL_COST_FN)", who, r);
+        if (int e = cost_fn_check(who, j.true_cost, 0, 0, -1)) return e;
+        const bool wall = j.true_cost->kind == ICRL_COST_WALL_BEHIND || j.true_cost->kind == ICRL_COST_WALL_INFRONT || j.true_cost->kind == ICRL_COST_WALL_BOTH;
+        if (wall && j.true_cost->obs_dim != j.disc->obs_dim)
+          return fail("%s: run %d: wall cost built for obs_dim %d, the rows have %d", who, r, j.true_cost->obs_dim, j.disc->obs_dim);
+        const int act_store = j.disc->is_discrete ? 1 : j.disc->acs_dim;
+        if (j.true_cost->kind == ICRL_COST_TORQUE && j.true_cost->acs_dim != act_store)
+          return fail("%s: run %d: torque cost over %d action components, the rows have %d", who, r, j.true_cost->acs_dim, act_store);
+        a.f = *j.true_cost; a.has_cost = 1;
+      }
+    } else {
+      if (j.rewards == nullptr) return fail("%s: run %d: rewards = NULL", who, r);
+      const icrl_costnet_t* c0 = jobs[0].disc;
+      if (j.disc->in_dim != c0->in_dim || j.disc->n_hidden != c0->n_hidden || j.disc->h1 != c0->h1 || j.disc->h2 != c0->h2 || j.disc->h3 != c0->h3 ||
+          j.disc->h4 != c0->h4 || j.disc->n_params != c0->n_params)
+        return fail("%s: run %d's discriminator shape differs from run 0's (the runs of a batch share one grid)", who, r);
+      if (!costnet_is_wide(j.disc)) {
+        if (!cn_ok(j.disc)) return bad_cn(who, j.disc);
+        a.cl = make_cn_layout(j.disc->in_dim, j.disc->n_hidden, j.disc->h1, j.disc->h2);
+      }
+    }
+    a.cn = *j.disc;
+    a.obs = j.observations; a.acs = j.actions; a.mean = j.obs_mean; a.var = j.obs_var; a.eps = j.epsilon; a.raw = j.raw_obs;
+    a.rewards = j.rewards; a.cost_mean = j.cost_mean; a.rows = j.rows; a.obs_dim = j.disc->obs_dim; a.learn_cost = j.learn_cost != 0;
+  }
+  return 0;
+}
+
+extern "C" int icrl_gail_unnormalize_batch(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream) {
+  const char* who = "icrl_gail_unnormalize_batch";
+  if (n_runs < 1 || n_runs > 65535 || jobs == nullptr) return fail("%s: n_runs = %d (1..65535)", who, n_runs);
+  GailArgs stack_args[8];
+  GailArgs* args = n_runs <= 8 ? stack_args : new GailArgs[n_runs];
+  int bad = make_gail_args(who, n_runs, jobs, args_ws, args_ws_bytes, args, false);
+  hipStream_t s = (hipStream_t)stream;
+  long long total_max = 0;
+  for (int r = 0; r < n_runs && !bad; ++r) {
+    const long long t = (long long)args[r].rows * args[r].obs_dim;
+    total_max = t > total_max ? t : total_max;
+    bad = put_args(args[r], (GailArgs*)args_ws + r, s);
+  }
+  if (args != stack_args) delete[] args;
+  if (bad) return bad;
+  const long long blocks = (total_max + 255) / 256;
+  hipLaunchKernelGGL(gail_unnormalize_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048), n_runs), dim3(256), 0, s, (const GailArgs*)args_ws);
+  hipLaunchKernelGGL(gail_cost_mean_kernel, dim3(1, n_runs), dim3(1024), 0, s, (const GailArgs*)args_ws);
+  return (int)hipGetLastError();
+}
+
+extern "C" int icrl_gail_relabel_batch(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream) {
+  const char* who = "icrl_gail_relabel_batch";
+  if (n_runs < 1 || n_runs > 65535 || jobs == nullptr) return fail("%s: n_runs = %d (1..65535)", who, n_runs);
+  GailArgs stack_args[8];
+  GailArgs* args = n_runs <= 8 ? stack_args : new GailArgs[n_runs];
+  int bad = make_gail_args(who, n_runs, jobs, args_ws, args_ws_bytes, args, true);
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = !bad && costnet_is_wide(jobs[0].disc);
+  if (wide) {      // a hidden layer above 64 units, or 0 / 3 / 4 of them: 64 rows per workgroup (cn_train.hip), as icrl_disc_reward does
+    if (args != stack_args) delete[] args;
+    return launch_gail_relabel_rows(n_runs, jobs, args_ws, s);
+  }
+  int rows_max = 0;
+  for (int r = 0; r < n_runs && !bad; ++r) {
+    rows_max = args[r].rows > rows_max ? args[r].rows : rows_max;
+    bad = put_args(args[r], (GailArgs*)args_ws + r, s);
+  }
+  if (args != stack_args) delete[] args;
+  if (bad) return bad;
+  if (jobs[0].disc->in_dim <= 32) hipLaunchKernelGGL(gail_relabel_kernel<2>, dim3(rows_max, n_runs), dim3(64), 0, s, (const GailArgs*)args_ws);
+  else hipLaunchKernelGGL(gail_relabel_kernel<10>, dim3(rows_max, n_runs), dim3(64), 0, s, (const GailArgs*)args_ws);
   return (int)hipGetLastError();
 }
 

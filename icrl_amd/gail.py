@@ -41,7 +41,10 @@ class PPO(PPOLagrangian):
                          policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device, **kw)
 
 
-def gail(config, log=print):
+def setup(config, log=print):
+    """everything of gail() up to the learn() call: (model, callback, discriminator, the GailCallback).  Two opt-ins, which a seed batch
+    sets and which are off by default so that a solo run's draws stay what they were: config.eval_noise_from_streams (evaluation noise
+    from the run's own streams, as in cpg) and config.disc_perms_from_streams (the discriminator's permutation likewise)."""
     logger.configure()
     rank = getattr(config, "rank", 0)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
@@ -87,14 +90,29 @@ def gail(config, log=print):
     cbs = [gail_update]
     if config.save_dir and rank == 0:
         cbs.append(callbacks.CheckpointCallback(int(config.save_every), os.path.join(config.save_dir, "models"), verbose=0))
+    streams = getattr(config, "streams", None)
+    if getattr(config, "disc_perms_from_streams", False) and streams is not None:
+        n_exp = int(np.asarray(expert_obs).shape[0])
+        gail_update.perms = lambda itr: streams.cn_permutations(1, min(int(config.n_steps) * int(config.num_threads), n_exp))
     cbs.append(callbacks.EvalCallback(eval_env, eval_freq=int(config.eval_every), deterministic=False, verbose=0,
                                       best_model_save_path=config.save_dir if rank == 0 else None,
+                                      noise_streams=streams if getattr(config, "eval_noise_from_streams", False) else None,
                                       callback_on_new_best=callbacks.SaveEnvStatsCallback(train_env, config.save_dir if rank == 0 else None)))
-    model.learn(total_timesteps=int(config.timesteps), callback=callbacks.CallbackList(cbs))
-    if config.save_dir and rank == 0:
+    return model, callbacks.CallbackList(cbs), discriminator, gail_update
+
+
+def finish(config, model, discriminator):
+    """what gail() saves after learn()."""
+    if config.save_dir and getattr(config, "rank", 0) == 0:
         if not config.freeze_gail_weights:
             discriminator.save(os.path.join(config.save_dir, "gail_discriminator.pt"))
-        train_env.save(os.path.join(config.save_dir, "train_env_stats.pkl"))
+        model.env.save(os.path.join(config.save_dir, "train_env_stats.pkl"))
+
+
+def gail(config, log=print):
+    model, cb, discriminator, gail_update = setup(config, log)
+    model.learn(total_timesteps=int(config.timesteps), callback=cb)
+    finish(config, model, discriminator)
     return model, discriminator, gail_update.history
 
 
@@ -133,12 +151,21 @@ def build_parser():
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
+    a("--seeds", type=int, default=None, nargs="+", help="several seeds: the runs advance in lock-step, all of them in every launch "
+      "(icrl_amd/seed_batch.py); results go to <save_dir>/seed_<s>")
     return p
 
 
 def main(argv=None):
     start = time.time()
     config = vars(build_parser().parse_args(argv if argv is not None else sys.argv[1:]))
+    if utils.batch_seeds(config) is not None:      # a seed batch: one process, one rank
+        from .seed_batch import run_gail_seed_batch
+        rank, world = D.init_from_env()
+        config["rank"], config["world_size"] = rank, world
+        run_gail_seed_batch(utils.seed_configs(config))
+        print("Time taken: %05.2f hours" % ((time.time() - start) / 3600))
+        return
     rank, world = D.init_from_env()
     if config["seed"] is None and rank == 0:
         config["seed"] = int(np.random.randint(0, 100))

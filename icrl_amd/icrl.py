@@ -280,6 +280,8 @@ def build_parser():
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")
     a("--episode_stats", action="store_true", default=None, help="log rollout/ep_rew_mean and rollout/ep_len_mean of the training envs (default: ICRL_EPISODE_STATS)")
+    a("--seeds", type=int, default=None, nargs="+", help="several seeds: the runs advance in lock-step, all of them in every launch "
+      "(icrl_amd/seed_batch.py); results go to <save_dir>/seed_<s>")
     return p
 
 
@@ -299,6 +301,18 @@ def main(argv=None):
         with open(config["config_file"]) as f:
             file_cfg = json.load(f)
         config.update({k: v for k, v in file_cfg.items() if k not in explicit_dests(parser, argv if argv is not None else sys.argv[1:])})
+    if utils.batch_seeds(config) is not None:      # a seed batch: one process, one rank
+        from .seed_batch import run_seed_batch
+        rank, world = D.init_from_env()
+        config["rank"], config["world_size"] = rank, world
+        log = print if config["verbose"] > 0 else None
+        _, all_metrics, _ = run_seed_batch(utils.seed_configs(config), config["n_iters"])
+        for sd, ms in zip(config["seeds"], all_metrics):
+            for m in ms if log is not None else ():
+                log(json.dumps(dict(seed=int(sd), **{k: (round(float(v), 6) if isinstance(v, (int, float, np.floating, np.integer)) else str(v))
+                                                      for k, v in m.items()})))
+        print("Time taken: %05.2f hours" % ((time.time() - start) / 3600))
+        return all_metrics
     rank, world = D.init_from_env()
     if config["seed"] is None and rank == 0:
         config["seed"] = int(np.random.randint(0, 100))

@@ -8,7 +8,8 @@ every phase of an outer iteration is ONE launch (sequence) whose grid carries al
     rollouts    icrl_rollout_collect_batch   grid (envs, S) persistent workgroups + the dual GAE of all runs, grid (tiles x C, S)
     update      icrl_ppo_lag_train_batch     grid (3, S): 3 S persistent workgroups, each run a chain of dependent optimiser steps
     sampling    icrl_sample_episodes_batch   grid (episodes, S)
-    backward    icrl_cn_train_batch          4 launches per constraint-net iteration, grid.y = S
+    backward    icrl_cn_train_batch          4 launches per constraint-net iteration, grid.y = S (--cn_batch_size: icrl_cn_train_minibatch_batch,
+                                             2 + 4 launches per minibatch)
     evaluation  icrl_sample_episodes_batch, the KL metrics per run (small launches)
 
 The host work between the launches is the per-run bookkeeping of the reference's loop (icrl_amd/icrl.py: the same methods, split
@@ -100,7 +101,24 @@ def _eval_callbacks(cb):
     return []
 
 
+def _gail_callbacks(cb):
+    """the GailCallbacks inside a callback (a CallbackList is walked), in call order."""
+    from .callbacks import CallbackList
+    from .gail_utils import GailCallback
+    if isinstance(cb, GailCallback):
+        return [cb]
+    if isinstance(cb, CallbackList):
+        return [g for c in cb.callbacks for g in _gail_callbacks(c)]
+    return []
+
+
 class SeedBatch:
+    # observations of 65..128 (AntWall: 113): a run alone updates with FOUR workgroups per network (csrc/ppo_train_quarters*.hip), the
+    # batched grid has the row-owning kernel only, whose partial sums associate differently — a batched run would no longer compute
+    # what it computes alone.  The drivers that promise exactly that (cpg, gail) set this: the single-run launch of every run, back to
+    # back on the stream (no host wait in between).
+    per_run_wide_updates = False
+
     def __init__(self, configs=None, states=None, on_setup=None):
         self.states = setup_runs(configs, on_setup) if states is None else states
         if any(isinstance(st["train_env"].unwrapped, HostVecEnv) for st in self.states):
@@ -161,6 +179,12 @@ class SeedBatch:
         _lib.check(err, "icrl_rollout_collect_batch")
 
     def _launch_trains(self, agents, jobs):
+        if self.per_run_wide_updates and agents[0].policy.obs_dim > 64 and len(agents) > 1:
+            for a, j in zip(agents, jobs):
+                if not a._train_ws["sync_tuned"] and not TUNE_PLACEMENT_IN_BATCH:
+                    a.tune_sync_placement = False
+                a._train_launch(j)
+            return
         rows = []
         for a, j in zip(agents, jobs):
             ws = a._train_ws
@@ -207,17 +231,21 @@ class SeedBatch:
                 s_.prefetch_permutations(a.n_epochs, a.rollout_buffer.buffer_size * a.rollout_buffer.n_envs, self._side)
 
     # ---- phases ----------------------------------------------------------------------------------------------------------------
-    def _learn(self, total_timesteps, callbacks=None, prefetch_across_end=None):
+    def _learn(self, total_timesteps, callbacks=None, prefetch_across_end=None, prefetch=True):
         """PPOLagrangian.learn(total_timesteps, cost_function="cost", callback=callbacks[i]) of every run (ref: on_policy_algorithm.py:430-492),
         rollouts and updates in lock-step.  A run's callback gets the calls learn() makes, in its order: init_callback, on_training_start,
         then per rollout on_rollout_start (before the noise draw), on_steps(n_steps), on_rollout_end (both after the launch, before the log
         line is dumped), and on_training_end.  EvalCallbacks inside it only note their triggers during on_steps; the episodes of all runs
-        then go through ONE launch per trigger (_evaluations) and every callback records its own results before on_rollout_end."""
+        then go through ONE launch per trigger (_evaluations) and every callback records its own results before on_rollout_end.
+        GailCallbacks inside it do their rollout-end work in lock-step as well (_gail_rollout_ends), before the other callbacks' on_rollout_end.
+        prefetch=False: no permutations are drawn ahead (a GailCallback draws the discriminator's permutation from the same generator between
+        two updates: the draws must keep the order of the run alone)."""
         sts = self.states
         agents = [st["agent"] for st in sts]
         cbs = list(callbacks) if callbacks is not None else [None] * len(sts)
         evals = [_eval_callbacks(cb) for cb in cbs]
-        if len({len(e) for e in evals}) != 1:
+        gails = [_gail_callbacks(cb) for cb in cbs]
+        if len({len(e) for e in evals}) != 1 or len({len(g) for g in gails}) != 1:
             raise ValueError("seed batch: every run of a batch carries the same callbacks")
         if prefetch_across_end is None:      # ICRL: not when the constraint net draws minibatch permutations from the same generator after learn()
             prefetch_across_end = all("constraint_net" in st and st["constraint_net"].batch_size is None for st in sts)
@@ -246,6 +274,7 @@ class SeedBatch:
                     if cb is not None and cb.on_steps(a.n_steps) is False:
                         raise ValueError(f"seed batch: a callback of run {i} asked to stop training; the runs of a batch stop together, at total_timesteps")
             self._evaluations(evals)
+            self._gail_rollout_ends(gails)
             tjobs = []
             for st, a, j, cb in zip(sts, agents, jobs, cbs):
                 with _as_run(st):
@@ -262,7 +291,7 @@ class SeedBatch:
             # were ~5 ms of device time + ~7 ms of launches per update phase at S = 32, in front of the update launch.  Not across the end
             # of the forward step when the constraint net draws minibatch permutations from the same generator in between.
             more = agents[0].num_timesteps < totals[0]
-            if more or prefetch_across_end:
+            if prefetch and (more or prefetch_across_end):
                 self._prefetch_permutations(agents, after=before_update)
             host = self._to_host([a.train_readback() for a in agents])          # waits for the update of every run
             for st, a, j, h in zip(sts, agents, tjobs, host):
@@ -275,6 +304,31 @@ class SeedBatch:
                     cb.on_training_end()
                 for e in ev:
                     e.deferred = None
+        for gs in gails:
+            for g in gs:
+                g.batched = False
+
+    def _gail_rollout_ends(self, gails):
+        """the rollout ends of the runs' GailCallbacks in lock-step: begin per run (statistics, the permutation draw), the device part of all
+        runs through the batched entry points (gail_utils.launch_rollout_ends: un-normalise, discriminator iteration, relabel, dual GAE), ONE
+        device->host copy with every run's metrics, mean cost and Adam step, end per run (discriminator/*, eval/mean_cost, history).
+        The callbacks' own on_rollout_end is then a no-op (`batched`)."""
+        from .gail_utils import launch_rollout_ends
+        sts = self.states
+        for slot in range(len(gails[0])):
+            gs = [g[slot] for g in gails]
+            jobs = []
+            for st, g in zip(sts, gs):
+                with _as_run(st):
+                    g.batched = True
+                    jobs.append(g._rollout_end_begin())
+            if len({j["update"] for j in jobs}) != 1:
+                raise ValueError("seed batch: the runs' discriminators update at different rollouts (update_freq differs)")
+            launch_rollout_ends(gs, jobs, self.args_ws)
+            host = self._to_host([j["readback"] for j in jobs])
+            for st, g, j, h in zip(sts, gs, jobs, host):
+                with _as_run(st):
+                    g._rollout_end_finish(j, h)
 
     def _evaluations(self, evals):
         """the triggers the runs' EvalCallbacks noted during on_steps: per trigger ONE launch with the evaluation episodes of every run
@@ -379,8 +433,10 @@ class SeedBatch:
         if nets[0].batch_size is None:
             self._launch_cn_trains(nets, cjobs)
         else:
+            from .gail_utils import launch_disc_trains
             for cn, j in zip(nets, cjobs):
-                cn._train_launch(j)
+                j["batch_size"] = int(cn.batch_size)
+            launch_disc_trains(nets, cjobs, self.args_ws)
         host = self._to_host([torch.cat([j["metrics"].reshape(-1).double(), j["t_dev"].double()]) for j in cjobs])
         backward = []
         for st, cn, j, h in zip(sts, nets, cjobs, host):
@@ -479,6 +535,8 @@ class CpgSeedBatch(SeedBatch):
     The evaluation noise of a batched run comes from its own streams (config.eval_noise_from_streams, set here); a solo run with that
     attribute and the same PrivateStreams computes the same bits."""
 
+    per_run_wide_updates = True
+
     def __init__(self, configs, log=None):
         from . import cpg as C
         configs = list(configs)
@@ -522,18 +580,6 @@ class CpgSeedBatch(SeedBatch):
         self.dev = self.states[0]["agent"].device
         self.args_ws = torch.empty(2 * len(self.states) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=self.dev)
 
-    def _launch_trains(self, agents, jobs):
-        # observations of 65..128 (AntWall: 113): a run alone updates with FOUR workgroups per network (csrc/ppo_train_quarters*.hip), the
-        # batched grid has the row-owning kernel only, whose partial sums associate differently — a batched run would no longer compute
-        # what it computes alone.  Here: the single-run launch of every run, back to back on the stream (no host wait in between).
-        if agents[0].policy.obs_dim > 64 and len(agents) > 1:
-            for a, j in zip(agents, jobs):
-                if not a._train_ws["sync_tuned"] and not TUNE_PLACEMENT_IN_BATCH:
-                    a.tune_sync_placement = False
-                a._train_launch(j)
-            return
-        super()._launch_trains(agents, jobs)
-
     def learn(self):
         """one batched learn(); returns (model, history) per run like cpg(), final_model_policy.pth saved per run."""
         self._learn(int(self.states[0]["config"].timesteps), callbacks=[st["callback"] for st in self.states], prefetch_across_end=False)
@@ -549,3 +595,79 @@ class CpgSeedBatch(SeedBatch):
 def run_cpg_seed_batch(configs, log=None):
     """configs: one cpg config (types.SimpleNamespace, see cpg.build_parser / cpg.seed_configs) per run.  Returns (model, history) per run."""
     return CpgSeedBatch(configs, log).learn()
+
+
+# ---- gail: plain PPO + the discriminator's rollout-end work (icrl_amd/gail_utils.py: GailCallback), S seeds in lock-step ----
+GAIL_SAME = ("train_env_id", "eval_env_id", "num_threads", "n_steps", "batch_size", "n_epochs", "reward_gamma", "reward_gae_lambda", "timesteps",
+             "eval_every", "learn_cost", "disc_batch_size", "disc_layers", "policy_layers", "reward_vf_layers", "dont_normalize_obs",
+             "disc_obs_select_dim", "disc_acs_select_dim")
+
+
+class GailSeedBatch(SeedBatch):
+    """gail.setup() per config — each run with its own PrivateStreams, scalar log, env stack, discriminator and callbacks — then ONE batched
+    learn(): rollouts (icrl_rollout_collect_batch[_mon]), evaluations (icrl_sample_episodes_batch), the GailCallbacks' rollout ends
+    (icrl_gail_unnormalize_batch, icrl_cn_train_minibatch_batch, icrl_gail_relabel_batch, icrl_gae_dual_batch) and updates
+    (icrl_ppo_lag_train_batch) are one launch sequence for all runs.  Evaluation noise and the discriminator's permutation of a batched run
+    come from its own streams (config.eval_noise_from_streams, config.disc_perms_from_streams, set here); a solo run with both and the same
+    PrivateStreams computes the same bits."""
+
+    per_run_wide_updates = True
+
+    def __init__(self, configs, log=None):
+        from . import gail as G
+        configs = list(configs)
+        if not configs:
+            raise ValueError("seed batch: no runs")
+        c0 = configs[0]
+        for c in configs:      # ---- refused before anything is set up
+            _refuse_host_envs(c.train_env_id, c.eval_env_id)
+            if getattr(c, "env_module", None) or getattr(c, "dummy_vec_env", False):
+                raise ValueError("seed batch: --env_module / --dummy_vec_env select host envs; the batched launches step device envs only")
+            if getattr(c, "world_size", 1) > 1:
+                raise ValueError("seed batch: the runs of a batch live on ONE rank (world_size > 1: launch one batch per GPU)")
+            if getattr(c, "use_cost_shaping_callback", False):
+                raise NotImplementedError("--use_cost_shaping_callback (a shaping ablation of the reference) is outside the hot path")
+            diff = [k for k in GAIL_SAME if getattr(c, k) != getattr(c0, k)]
+            if (c.gail_path is None) != (c0.gail_path is None):
+                diff.append("gail_path is None")
+            if bool(getattr(c, "episode_stats", None)) != bool(getattr(c0, "episode_stats", None)):
+                diff.append("episode_stats")
+            if diff:
+                raise ValueError(f"seed batch: the runs of a batch share every grid and the sequence of phases; they differ in {diff}")
+        self.states = []
+        for i, cfg in enumerate(configs):
+            if getattr(cfg, "streams", None) is None:
+                cfg.streams = PrivateStreams(cfg.seed, discrete=cfg.train_env_id in ("LGW-v0", "CLGW-v0"))
+            if not hasattr(cfg.streams, "eval_noise") or not hasattr(cfg.streams, "cn_permutations"):
+                raise ValueError("seed batch: every run needs its own random streams")
+            cfg.eval_noise_from_streams = cfg.disc_perms_from_streams = True
+            model, cb, disc, gail_cb = G.setup(cfg, log)
+            if model.policy.wide or int(model.batch_size) > 256 or disc.wide:
+                raise ValueError(f"seed batch: run {i}: hidden widths above 64 / batch sizes above 256 (policy or discriminator) run on the generic-shape "
+                                 "path, which has no batched form")
+            if isinstance(model.env.unwrapped, HostVecEnv):
+                raise ValueError(f"seed batch: run {i}: the batched launches step device envs")
+            self.states.append(dict(config=cfg, agent=model, callback=cb, discriminator=disc, gail=gail_cb, logger=logger.Logger.CURRENT, train_env=model.env))
+        if len({st["agent"]._mon is None for st in self.states}) != 1:
+            raise ValueError("seed batch: episode_stats must be on in every run of a batch or in none")
+        if len({tuple(st["discriminator"].hidden_sizes) + (st["discriminator"].input_dims,) for st in self.states}) != 1:
+            raise ValueError("seed batch: the discriminators of a batch share one shape")
+        torch.cuda.synchronize()
+        self.dev = self.states[0]["agent"].device
+        self.args_ws = torch.empty(2 * len(self.states) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=self.dev)
+
+    def learn(self):
+        """one batched learn(); returns (model, discriminator, history) per run like gail(), gail_discriminator.pt / train_env_stats.pkl saved per run."""
+        from . import gail as G
+        self._learn(int(self.states[0]["config"].timesteps), callbacks=[st["callback"] for st in self.states], prefetch=False)
+        out = []
+        for st in self.states:
+            G.finish(st["config"], st["agent"], st["discriminator"])
+            out.append((st["agent"], st["discriminator"], st["gail"].history))
+        return out
+
+
+def run_gail_seed_batch(configs, log=None):
+    """configs: one gail config (types.SimpleNamespace, see gail.build_parser / utils.seed_configs) per run.  Returns (model, discriminator,
+    history) per run."""
+    return GailSeedBatch(configs, log).learn()

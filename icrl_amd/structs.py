@@ -111,6 +111,17 @@ class CnTrainJobT(C.Structure):
                 ("ep_offsets", vp), ("row_episode", vp), ("n_ep", i32), ("_pad", i32), ("hp", vp), ("work", vp), ("metrics", vp)]
 
 
+class CnTrainMbJobT(C.Structure):
+    """icrl_cn_train_mb_job_t: CnTrainJobT's fields + the permutation table and the batch size (icrl_cn_train_minibatch_batch)."""
+    _fields_ = CnTrainJobT._fields_ + [("perms", vp), ("batch_size", i32), ("_pad2", i32)]
+
+
+class GailJobT(C.Structure):
+    """icrl_gail_job_t: one run's rollout-end work of the GAIL callback (icrl_gail_unnormalize_batch / icrl_gail_relabel_batch)."""
+    _fields_ = [("disc", vp), ("true_cost", vp), ("observations", vp), ("actions", vp), ("obs_mean", vp), ("obs_var", vp), ("epsilon", f64),
+                ("raw_obs", vp), ("rewards", vp), ("cost_mean", vp), ("rows", i32), ("learn_cost", i32)]
+
+
 class PpoTrainJobT(C.Structure):
     _fields_ = [(k, vp) for k in ("pol", "exp_avg", "exp_avg_sq", "adam_step", "buf", "perms", "nu", "hp", "stats", "sync_ws")]
 

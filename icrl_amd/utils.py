@@ -5,6 +5,7 @@ ref: icrl/utils.py:256-303 (make_env / make_train_env / make_eval_env), :323-357
      icrl/icrl.py:25-43 (load_expert_data); stable_baselines3/common/save_util.py:284-418 (agent zip format).
 """
 import io
+import json
 import os
 import pickle
 import types
@@ -18,6 +19,35 @@ from .policies import ActorTwoCriticsPolicy
 from .structs import ChainJobT, EnvT, HostEpisodeT, addr, p
 from . import envs
 from .vec_env import ENV_IDS, DummyVecEnv, HipSynthVecEnv, HostVecEnv, SubprocVecEnv, VecCostWrapper, VecNormalize, VecNormalizeWithCost
+
+
+def seed_configs(config):
+    """one config per entry of config["seeds"] (the --seeds flag of icrl / cpg / gail): its seed, and <save_dir>/seed_<s> (created, with
+    its config.json) as its save_dir."""
+    out = []
+    for s in config["seeds"]:
+        c = dict(config, seed=int(s))
+        if config["save_dir"]:
+            c["save_dir"] = os.path.join(config["save_dir"], f"seed_{int(s)}")
+            os.makedirs(c["save_dir"], exist_ok=True)
+            with open(os.path.join(c["save_dir"], "config.json"), "w") as fh:
+                json.dump(c, fh, indent=2, default=str)
+        out.append(types.SimpleNamespace(**c))
+    return out
+
+
+def batch_seeds(config):
+    """the seeds of a seed batch (--seeds with more than one value), or None for the single-run path: one value is that run's --seed.
+    Duplicates are refused: the runs of a batch write to <save_dir>/seed_<s>."""
+    seeds = config.get("seeds")
+    if seeds is None:
+        return None
+    if len(seeds) == 1:
+        config["seed"] = int(seeds[0])
+        return None
+    if len(set(seeds)) != len(seeds):
+        raise ValueError(f"--seeds {seeds}: the runs of a batch write to <save_dir>/seed_<s>, so every seed is given once")
+    return [int(x) for x in seeds]
 
 
 def make_vec_env(env_id, n_envs, seed, device="cuda", env_index_offset=0, dummy_vec_env=False):

@@ -751,6 +751,63 @@ int icrl_cn_train_minibatch(const icrl_costnet_t* cn, float* exp_avg, float* exp
                             const icrl_cn_hyper_t* hp, const int32_t* perms, int batch_size, float* work,
                             float* metrics, void* stream);
 
+/* icrl_cn_train_minibatch for n_runs constraint nets / discriminators of one architecture and one batch_size: the launch sequence of the
+ * single-run call with all runs in every launch (grid.y = run).  Per iteration: forward + finalize on all rows, then per minibatch k
+ * the minibatch forward, finalize, backward and Adam with step index itr * n_batches + k.  Runs may differ in Nn, Ne and n_ep — hence in
+ * min(Nn, Ne), in their number of minibatches and in the length of the ragged last one — and in hp (iterations, learning rate, loss form,
+ * importance-sampling mode): the grids and the launch sequence are sized for the largest run, and a launch a run does not have is a no-op
+ * for it.  The index slice and length of minibatch (itr, k) are derived in the kernels from the run's argument block.  Per run the call
+ * computes the bits icrl_cn_train_minibatch computes (tests/test_gail_seed_batch_gpu.py).  Refused on the host, before the first device
+ * call: n_runs outside 1..65535, a small args_ws, NULL perms, batch_size <= 0, runs that differ in network shape or batch_size, an
+ * analytic descriptor behind `cn`.
+ * Call sites: ConstraintNet.train in minibatch mode (icrl/constraint_net.py:181-206, 300-316) and GailDiscriminator.train
+ * (icrl/gail_utils.py:163-208), which always trains through it. */
+typedef struct {
+  const icrl_costnet_t* cn;
+  float *exp_avg, *exp_avg_sq;
+  int32_t* adam_step;
+  const float *nominal, *expert;
+  int32_t Nn, Ne;
+  const int32_t *ep_offsets, *row_episode;
+  int32_t n_ep, _pad;
+  const icrl_cn_hyper_t* hp;
+  float *work, *metrics;
+  const int32_t* perms;         /* [iterations][min(Nn, Ne)] on the device */
+  int32_t batch_size, _pad2;
+} icrl_cn_train_mb_job_t;
+int icrl_cn_train_minibatch_batch(int n_runs, const icrl_cn_train_mb_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream);
+
+/* The rollout-end work of the GAIL baseline's callback (icrl/gail_utils.py:500-571) around the discriminator step, for n_runs runs:
+ * one job per run, grid.y = run, rows may differ between runs (grids are sized for the largest).
+ *   disc:         the run's discriminator (never an analytic descriptor);   true_cost: the ground-truth cost, or NULL (no ground truth)
+ *   observations: the buffer's NORMALISED float32 observations [rows, disc->obs_dim];   actions: [rows, act] float32 (act = 1 when discrete)
+ *   obs_mean / obs_var: [obs] float64 running moments, or both NULL (norm_obs off);   epsilon: VecNormalize's epsilon
+ *   raw_obs: [rows, obs] float64, output of the first call and input of the second;   rewards: [rows] float32, in / out
+ *   cost_mean: [1] float64, output;   learn_cost: the --learn_cost flag
+ * icrl_gail_unnormalize_batch: raw_obs = float64(obs) * sqrt(var + eps) + mean, product and sum rounded separately (what
+ *   VecNormalize.unnormalize_obs computes, icrl/gail_utils.py:539-542); cost_mean = mean of true_cost(raw_obs, actions) over the rows — the
+ *   costs are 0, 1 or 2, counted in integers; the mean is count * (1.0 / rows) in float64, the way torch's device mean finishes (the
+ *   bits of c.double().mean(); count / rows can differ in the last place) — or 0 for NULL.
+ * icrl_gail_relabel_batch: r = log(D(raw_obs, actions) + eps) through the row forward of icrl_disc_reward (icrl/gail_utils.py:147-157:
+ *   reward_function with apply_log), then rewards += r with learn_cost and rewards = r without (icrl/gail_utils.py:555-560).  The
+ *   discriminators of a batch share one shape.
+ * Both: refusals (n_runs, args_ws, rows <= 0, NULL arrays, one of obs_mean / obs_var without the other, an analytic `disc`, a bad
+ * true_cost descriptor) are made on the host before the first device call. */
+typedef struct {
+  const icrl_costnet_t* disc;
+  const icrl_cost_fn_t* true_cost;
+  const float* observations;
+  const float* actions;
+  const double *obs_mean, *obs_var;
+  double epsilon;
+  double* raw_obs;
+  float* rewards;
+  double* cost_mean;
+  int32_t rows, learn_cost;
+} icrl_gail_job_t;
+int icrl_gail_unnormalize_batch(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream);
+int icrl_gail_relabel_batch(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, long long args_ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
