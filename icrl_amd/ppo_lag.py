@@ -826,7 +826,8 @@ class PPOLagrangian:
         hp = PpoHyperT(int(self.batch_size), int(self.n_epochs), int(self.target_kl is not None), int(getattr(self, "profile_phases", 0)) | {"tiles": 2, "rows": 4, "rows1": 12, "pairs": 16, "halves": 32}.get(getattr(self, "train_kernel", "auto"), 0), clip_range, float(self.ent_coef),
                        float(self.reward_vf_coef), float(self.cost_vf_coef), float(self.max_grad_norm),
                        float(self.target_kl or 0.0), crv, ccv, lr, 0.9, 0.999, float(pol.optimizer_kwargs.get("eps", 1e-8)))
-        return dict(ps=pol.struct(), bs=rb.struct(), hp=hp, perms=perms, rng_state=rng_state, injected=injected, clip_range=clip_range)
+        return dict(ps=pol.struct(), bs=rb.struct(), hp=hp, perms=perms, rng_state=rng_state, injected=injected, clip_range=clip_range,
+                    clip_range_reward_vf=None if self.clip_range_reward_vf is None else crv, clip_range_cost_vf=None if self.clip_range_cost_vf is None else ccv)
 
     # The three workgroups of an update exchange one granule per optimiser step through the first 512 bytes of the `sync` workspace, and
     # how fast that hop is depends on where those bytes lie in device memory: moving the workspace by 2 MB switches the step between
@@ -973,6 +974,9 @@ class PPOLagrangian:
             logger.record("train/std", float(torch.exp(pol.log_std).mean().item()) if host is None else float(host[ns + 5]))
         logger.record("train/n_updates", self._n_updates)
         logger.record("train/clip_range", clip_range)
+        for key in ("clip_range_reward_vf", "clip_range_cost_vf"):      # ref: ppo_lag.py:335-338 — only when value clipping is on
+            if job.get(key) is not None:
+                logger.record("train/" + key, job[key])
         logger.record("train/learning_rate", float(self.lr_schedule(self._current_progress_remaining)))      # ref: base_class.py:221
         self.epoch_kls = st[32:32 + self.n_epochs].copy()
         self.phase_cycles = st[12:32].copy()

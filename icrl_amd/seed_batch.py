@@ -91,6 +91,22 @@ def _jobs(cls, rows):
 TUNE_PLACEMENT_IN_BATCH = os.environ.get("ICRL_SEED_TUNE", "0") == "1"
 
 
+def launch_trains(agents, jobs, args_ws):
+    """the updates of several runs (jobs: each agent's PPOLagrangian._train_begin) as ONE icrl_ppo_lag_train_batch launch; every run brings its
+    own hyper-parameter block.  args_ws: device bytes, _lib.BATCH_ARGS_BYTES per run."""
+    rows = []
+    for a, j in zip(agents, jobs):
+        ws = a._train_ws
+        if not ws["sync_tuned"]:          # first update of the run: where its exchange workspace is fastest (PPOLagrangian._tune_sync_placement)
+            if not TUNE_PLACEMENT_IN_BATCH and len(jobs) > 1:
+                a.tune_sync_placement = False
+            a._tune_sync_placement(j)
+        rows.append((addr(j["ps"]), p(a.policy.exp_avg), p(a.policy.exp_avg_sq), p(ws["t"]), addr(j["bs"]), p(j["perms"]), p(ws["nu"]), addr(j["hp"]),
+                     p(ws["stats"]), p(ws["sync"])))
+    arr = _jobs(PpoTrainJobT, rows)
+    _lib.check(_lib.lib().icrl_ppo_lag_train_batch(len(jobs), arr, p(args_ws), args_ws.numel(), _lib.current_stream()), "icrl_ppo_lag_train_batch")
+
+
 def _eval_callbacks(cb):
     """the EvalCallbacks inside a callback (a CallbackList is walked), in call order."""
     from .callbacks import CallbackList, EvalCallback
@@ -185,18 +201,7 @@ class SeedBatch:
                     a.tune_sync_placement = False
                 a._train_launch(j)
             return
-        rows = []
-        for a, j in zip(agents, jobs):
-            ws = a._train_ws
-            if not ws["sync_tuned"]:          # first update of the run: where its exchange workspace is fastest (PPOLagrangian._tune_sync_placement)
-                if not TUNE_PLACEMENT_IN_BATCH and len(jobs) > 1:
-                    a.tune_sync_placement = False
-                a._tune_sync_placement(j)
-            rows.append((addr(j["ps"]), p(a.policy.exp_avg), p(a.policy.exp_avg_sq), p(ws["t"]), addr(j["bs"]), p(j["perms"]), p(ws["nu"]), addr(j["hp"]),
-                         p(ws["stats"]), p(ws["sync"])))
-        arr = _jobs(PpoTrainJobT, rows)
-        ws, nbytes = self._ws()
-        _lib.check(_lib.lib().icrl_ppo_lag_train_batch(len(jobs), arr, ws, nbytes, _lib.current_stream()), "icrl_ppo_lag_train_batch")
+        launch_trains(agents, jobs, self.args_ws)
 
     def _launch_episodes(self, runs):
         r0 = runs[0]

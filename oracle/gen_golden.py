@@ -791,6 +791,75 @@ def g9_learn_iteration():
          ret_rms_var=env.ret_rms.var, cost_rms_var=env.cost_rms.var)
 
 
+def g23_ppo_hparams():
+    """The reference's own train() (ppo_lag.py:177-338) with value clipping of both critics, the entropy bonus, separate critic weights and
+    max_grad_norm 0.3 (set A of tests/helpers/ppo_hparam_cases.py) on a buffer whose old log-probs and old values were overwritten IN PLACE
+    with that module's banded construction: one learn() so that the buffer exists and is flattened, the overwrite, then train() once more with
+    np.random.permutation recorded.  Stored: weights and Adam state before, weights after, the buffer planes, the permutations, nu, and every
+    train/* scalar of the reference's logger (incl. train/clip_range_reward_vf and train/clip_range_cost_vf, lines 335-338).
+    The banded construction and the conditions on it are imported from the test tree (tests/helpers/ppo_hparam_cases.py): the golden and the GPU
+    tests must share them, so this generator, unlike the others, needs tests/ beside oracle/."""
+    print("G23 train() with value clipping / entropy bonus / critic weights / max_grad_norm on a banded buffer")
+    import copy
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT)))
+    from helpers import ppo_hparam_cases as H
+    N, T, B, E = 4, 32, 64, 2
+    hp = H.hparams("A")
+    agent, env, cn = _make_ref_agent(N, "hc", 0, [20], n_steps=T, batch_size=B, n_epochs=E, target_kl=None, **hp)
+    agent.learn(total_timesteps=N * T, cost_function="cost")
+    rb, pol = agent.rollout_buffer, agent.policy
+    assert rb.generator_ready and rb.observations.shape == (N * T, 18)
+    sd0 = _sd_np(pol.state_dict())
+    osd0 = copy.deepcopy(pol.optimizer.state_dict())
+    names = list(pol.state_dict())
+    assert [tuple(osd0["state"][i]["exp_avg"].shape) for i in range(len(names))] == [tuple(sd0[k].shape) for k in names]      # (parameter order = state_dict order)
+    rng = np.random.RandomState(23)
+    with th.no_grad():
+        v_r, v_c, lp, _ = pol.evaluate_actions(th.as_tensor(rb.observations), th.as_tensor(rb.actions))
+    old_lp, old_vr, old_vc = H.banded(rng, lp.numpy(), v_r.numpy().ravel(), v_c.numpy().ravel(), hp["clip_range_reward_vf"], hp["clip_range_cost_vf"])
+    planes = dict(log_probs=old_lp, reward_values=old_vr, cost_values=old_vc, reward_advantages=rng.randn(N * T) * 2, cost_advantages=rng.rand(N * T),
+                  reward_returns=rng.randn(N * T), cost_returns=rng.rand(N * T))
+    for k, v in planes.items():       # in place, in the flattened (env-major) layout get() left
+        getattr(rb, k)[...] = np.asarray(v, np.float32).reshape(getattr(rb, k).shape)
+    nu = agent.dual.nu().item()
+    perms, orig_perm = [], np.random.permutation
+
+    def rec_perm(n):
+        p = orig_perm(n); perms.append(p.copy()); return p
+    ref_logger.Logger.CURRENT.name_to_value.clear()
+    np.random.permutation = rec_perm
+    try:
+        agent.train()
+    finally:
+        np.random.permutation = orig_perm
+    logs = {k: float(v) for k, v in ref_logger.Logger.CURRENT.name_to_value.items() if k.startswith("train/")}
+    assert len(perms) == E and logs["train/clip_range_reward_vf"] == hp["clip_range_reward_vf"] and logs["train/clip_range_cost_vf"] == hp["clip_range_cost_vf"]
+    flat = lambda a: a.reshape(N, T, -1).swapaxes(0, 1).reshape(T, N, -1) if a.shape[0] == N * T else a.reshape(T, N, -1)
+    buf = {k: flat(getattr(rb, k)) for k in ("observations", "actions", "log_probs", "reward_values", "cost_values", "reward_advantages", "cost_advantages",
+                                             "reward_returns", "cost_returns", "orig_costs")}
+    # ---- oracle on the same buffer, weights, Adam state and permutations: bit for bit
+    op = o_nets.TwoCriticPolicy(18, 6)
+    op.load_state_dict({k: th.as_tensor(v) for k, v in sd0.items()})
+    oopt = th.optim.Adam(op.parameters(), lr=3e-4, eps=1e-5)
+    oopt.load_state_dict(copy.deepcopy(osd0))      # (load_state_dict keeps the tensors it is given: the steps below would write into osd0)
+    trace = []
+    out = o_ppo.ppo_lag_train(op, oopt, {k: (v[..., 0] if v.shape[-1] == 1 and k not in ("observations", "actions") else v) for k, v in buf.items()},
+                              np.array(perms), nu, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=None, trace=trace, **hp)
+    H.check_trace(trace, hp, n_steps=E * (N * T // B))
+    for k, p in op.params.items():
+        assert maxdiff(p.detach().numpy(), pol.state_dict()[k].numpy()) == 0.0, k
+    for key in ("entropy_loss", "policy_gradient_loss", "reward_value_loss", "cost_value_loss", "approx_kl", "clip_fraction", "loss", "early_stop_epoch"):
+        assert float(out["train/" + key]) == logs["train/" + key], (key, out["train/" + key], logs["train/" + key])
+    print("  oracle == reference bit-for-bit (parameters after", len(trace), "steps, the train/* scalars of the loop); clip_fraction",
+          [round(t["clip_fraction"], 3) for t in trace], "grad norms", [round(t["grad_norm"], 3) for t in trace])
+    save("g23_ppo_hparams", perms=np.array(perms), nu=nu, lr=3e-4, adam_step=int(osd0["state"][0]["step"]),
+         **{f"hp/{k}": v for k, v in hp.items()}, **{f"w0/{k}": v for k, v in sd0.items()},
+         **{f"m0/{k}": osd0["state"][i]["exp_avg"].numpy() for i, k in enumerate(names)},
+         **{f"v0/{k}": osd0["state"][i]["exp_avg_sq"].numpy() for i, k in enumerate(names)},
+         **{f"w1/{k}": v.numpy() for k, v in pol.state_dict().items()}, **{f"buf/{k}": v for k, v in buf.items()},
+         **{"log/" + k.split("/")[1]: v for k, v in logs.items()})
+
+
 def g10_lap_grid():
     """configs[0]: the reference's LapGridWorld / ConstrainedLapGridWorld stepped through gym.make + DummyVecEnv against the
     oracle restatement, then one learn() of the reference with a Categorical policy (actions and permutations recorded)
@@ -948,8 +1017,8 @@ def fixtures_expert():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g9", "g10", "expert", "g8", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g9", "g10", "expert", "g8", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g23"]
     table = dict(g1=g1_gae, g2=g2_cost_function, g3=g3_vecnormalize, g4=g4_ppo_minibatch, g5=g5_dual,
-                 g6=g6_constraint_net_train, g7=g7_constraint_net_minibatch, g8=g8_icrl_lgw, g11=g11_pid, g12=g12_gail, g13=g13_widths, g14=g14_batch256, g15=g15_wide, g16=g16_batch512, g17=g17_trunk, g18=g18_deep, g9=g9_learn_iteration, g10=g10_lap_grid, expert=fixtures_expert)
+                 g6=g6_constraint_net_train, g7=g7_constraint_net_minibatch, g8=g8_icrl_lgw, g11=g11_pid, g12=g12_gail, g13=g13_widths, g14=g14_batch256, g15=g15_wide, g16=g16_batch512, g17=g17_trunk, g18=g18_deep, g9=g9_learn_iteration, g10=g10_lap_grid, expert=fixtures_expert, g23=g23_ppo_hparams)
     for w in which:
         table[w]()

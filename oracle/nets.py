@@ -102,15 +102,15 @@ class TwoCriticPolicy:
         v_c = F.linear(lc, self.params["cost_value_net.weight"], self.params["cost_value_net.bias"])
         return mean, v_r, v_c
 
-    def gaussian_log_prob(self, mean, actions):
+    def gaussian_log_prob(self, mean, actions, std=None):
         """ref: distributions.py:143-161 -> torch.distributions.Normal.log_prob, summed over action dims."""
-        std = th.ones_like(mean) * self.params["log_std"].exp()
+        std = th.ones_like(mean) * self.params["log_std"].exp() if std is None else std
         var = std ** 2
         lp = -((actions - mean) ** 2) / (2 * var) - std.log() - LOG_SQRT_2PI
         return lp.sum(dim=1)
 
-    def gaussian_entropy(self, mean):
-        std = th.ones_like(mean) * self.params["log_std"].exp()
+    def gaussian_entropy(self, mean, std=None):
+        std = th.ones_like(mean) * self.params["log_std"].exp() if std is None else std
         return (0.5 + 0.5 * math.log(2 * math.pi) + th.log(std)).sum(dim=1)
 
     def forward(self, obs, noise=None, deterministic=False):
@@ -147,7 +147,10 @@ class TwoCriticPolicy:
             p = th.softmax(logp_all, dim=-1)        # torch.distributions.Categorical: probs = softmax(normalised logits)
             entropy = -(logp_all * p).sum(-1)
             return v_r, v_c, log_prob, entropy
-        return v_r, v_c, self.gaussian_log_prob(mean, actions), self.gaussian_entropy(mean)
+        # ONE scale tensor under log-prob and entropy, like the reference's Normal(mean, action_std) (distributions.py:127-141): with an
+        # entropy bonus both send a gradient into log_std, and autograd adds them per element before the sum over the rows
+        std = th.ones_like(mean) * self.params["log_std"].exp()
+        return v_r, v_c, self.gaussian_log_prob(mean, actions, std), self.gaussian_entropy(mean, std)
 
 
 class CostNet:

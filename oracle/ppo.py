@@ -59,13 +59,18 @@ def minibatch_loss(policy, obs, actions, old_log_prob, adv_r, adv_c, ret_r, ret_
 
 def ppo_lag_train(policy, optimizer, buf, perms, nu, *, batch_size, n_epochs, clip_range, target_kl=None,
                   max_grad_norm=0.5, ent_coef=0.0, reward_vf_coef=0.5, cost_vf_coef=0.5, discrete=False,
-                  clip_range_reward_vf=None, clip_range_cost_vf=None, max_minibatches=None):
+                  clip_range_reward_vf=None, clip_range_cost_vf=None, max_minibatches=None, trace=None):
     """The epoch loop of ``train()`` (ref: ppo_lag.py:196-299).
 
     buf:   dict of [T, N(, d)] float32 arrays (observations, actions, log_probs, reward_values,
            reward_advantages, reward_returns, cost_values, cost_advantages, cost_returns).
     perms: callable epoch -> permutation of T*N (the reference draws np.random.permutation per epoch),
            or an [n_epochs, T*N] integer array (teacher-forced).
+    trace: optional list; per optimiser step it receives a dict that says which branches of the loss the step's rows took and
+           how far they were from its kinks (tests assert these as conditions on their inputs): clip_fraction, the share of
+           rows with |v - old_v| > clip per critic (vclip_share_r / _c), the pre-clip total gradient norm (grad_norm), the
+           minimum over rows of min(|ratio - (1 - clip)|, |ratio - (1 + clip)|) (ratio_margin) and of ||v - old_v| - clip|
+           per critic (v_margin_r / _c); the per-critic entries are None without value clipping.
     Returns dict of the train/* scalars that depend on the loop."""
     flat = {k: th.as_tensor(env_major(buf[k])) for k in
             ("observations", "actions", "log_probs", "reward_values", "reward_advantages", "reward_returns",
@@ -93,7 +98,16 @@ def ppo_lag_train(policy, optimizer, buf, perms, nu, *, batch_size, n_epochs, cl
                 ent_coef, reward_vf_coef, cost_vf_coef, clip_range_reward_vf, clip_range_cost_vf)
             optimizer.zero_grad()
             loss.backward()
-            th.nn.utils.clip_grad_norm_(policy.parameters(), max_grad_norm)
+            total = th.nn.utils.clip_grad_norm_(policy.parameters(), max_grad_norm)
+            if trace is not None:
+                ratio = th.exp(tr["log_prob"] - flat["log_probs"][b].flatten())
+                row = dict(clip_fraction=tr["clip_fraction"].item(), grad_norm=float(total),
+                           ratio_margin=float(th.minimum((ratio - (1 - clip_range)).abs(), (ratio - (1 + clip_range)).abs()).min()))
+                for c, v, old, tag in ((clip_range_reward_vf, tr["v_r"], "reward_values", "r"), (clip_range_cost_vf, tr["v_c"], "cost_values", "c")):
+                    d = None if c is None else (v - flat[old][b].flatten()).abs()
+                    row["vclip_share_" + tag] = None if c is None else float((d > c).float().mean())
+                    row["v_margin_" + tag] = None if c is None else float((d - c).abs().min())
+                trace.append(row)
             optimizer.step()
             pg.append(tr["policy_loss"].item()); cfr.append(tr["clip_fraction"].item())
             rvl.append(tr["reward_value_loss"].item()); cvl.append(tr["cost_value_loss"].item())

@@ -256,3 +256,117 @@ def test_explained_variance_vs_the_reference_formula(n):
     if n <= 7:
         got = out.cpu().numpy()
         assert np.isnan(got[0]) and got[1] == 7.0
+
+
+class _Outputs:
+    """the networks' outputs as autograd leaves: oracle.ppo.minibatch_loss evaluates policy.evaluate_actions(obs, actions)."""
+
+    def __init__(self, v_r, v_c, lp, ent, dtype):
+        self.leaves = [torch.as_tensor(x, dtype=dtype).clone().requires_grad_(True) for x in (v_r, v_c, lp, ent)]
+
+    def evaluate_actions(self, obs, actions):
+        return tuple(self.leaves)
+
+
+def _hparam_batch(n):
+    """one banded minibatch of n rows (helpers/ppo_hparam_cases.py: no row on a kink of the ratio clip or of a value clip)."""
+    from helpers import ppo_hparam_cases as H
+    rng = np.random.RandomState(100 + n)
+    f = lambda x: np.asarray(x, np.float32)
+    out = dict(lp=f(-8 + 0.3 * rng.randn(n)), v_r=f(rng.randn(n)), v_c=f(rng.rand(n)), ent=f(8.5 + 0.1 * rng.randn(n)), adv_r=f(2 * rng.randn(n)),
+               adv_c=f(rng.rand(n)), ret_r=f(rng.randn(n)), ret_c=f(rng.rand(n)))
+    out["old_lp"], out["old_v_r"], out["old_v_c"] = H.banded(rng, out["lp"], out["v_r"], out["v_c"], H.SET_A["clip_range_reward_vf"], H.SET_A["clip_range_cost_vf"])
+    return out
+
+
+def _loss_and_row_grads(b, hp, nu, dtype):
+    """oracle.ppo.minibatch_loss on the outputs + autograd: (terms in the library's order, d loss / d (lp, v_r, v_c, entropy))."""
+    t = lambda k: torch.as_tensor(b[k], dtype=dtype)
+    pol = _Outputs(b["v_r"], b["v_c"], b["lp"], b["ent"], dtype)
+    loss, tr = o_ppo.minibatch_loss(pol, None, None, t("old_lp"), t("adv_r"), t("adv_c"), t("ret_r"), t("ret_c"), t("old_v_r"), t("old_v_c"), nu, 0.2,
+                                    hp["ent_coef"], hp["reward_vf_coef"], hp["cost_vf_coef"], hp["clip_range_reward_vf"], hp["clip_range_cost_vf"])
+    loss.backward()
+    v_r, v_c, lp, ent = pol.leaves
+    terms = [loss.item()] + [tr[k].item() for k in ("policy_loss", "reward_value_loss", "cost_value_loss", "entropy_loss", "approx_kl", "clip_fraction")]
+    ratio = torch.exp(lp.detach() - t("old_lp"))
+    margins = (float(torch.minimum((ratio - 0.8).abs(), (ratio - 1.2).abs()).min()),
+               float(((v_r.detach() - t("old_v_r")).abs() - hp["clip_range_reward_vf"]).abs().min()),
+               float(((v_c.detach() - t("old_v_c")).abs() - hp["clip_range_cost_vf"]).abs().min()))
+    shares = (tr["clip_fraction"].item(), float(((v_r.detach() - t("old_v_r")).abs() > hp["clip_range_reward_vf"]).double().mean()),
+              float(((v_c.detach() - t("old_v_c")).abs() > hp["clip_range_cost_vf"]).double().mean()))
+    return terms, dict(d_lp=lp.grad.numpy(), d_vr=v_r.grad.numpy(), d_vc=v_c.grad.numpy(), d_en=ent.grad.numpy()), margins, shares
+
+
+# Per-row output gradients: max |float32 oracle - float64 oracle| over the four (set, rows) cases below, measured on the CPU:
+# d_lp 3.5e-9 (of values up to 0.025), d_vr 3.4e-9 (of 0.091), d_vc 5.5e-10 (of 0.0087), d_en 3.5e-12 (of 1.6e-4: float32(ent_coef) / n).
+# The bound is 3 x that: the kernel's reductions (advantage mean and standard deviation) run in another order than torch's.
+ROW_GRAD_F32_DEV = dict(d_lp=3.5e-9, d_vr=3.4e-9, d_vc=5.5e-10, d_en=3.5e-12)
+
+
+@pytest.mark.parametrize("n", [64, 100])
+@pytest.mark.parametrize("hset", ["A", "B"])
+def test_loss_fwd_bwd_with_value_clipping_vs_float64_autograd(hset, n):
+    """icrl_ppo_lag_loss_fwd_bwd with both old-value pointers set (value clipping on for both critics), the entropy bonus, separate critic
+    weights; then icrl_clip_adam_step in the branch of the norm clip the set takes (A: max_grad_norm 0.3 below the norm, B: 50 above it)
+    — against float64 autograd of oracle.ppo.minibatch_loss on the same outputs and the explicit clip / Adam formulas."""
+    from helpers import ppo_hparam_cases as H
+    from icrl_amd import _lib, structs as S
+    L = _lib.lib()
+    hpd, nu_f = H.hparams(hset), 0.731
+    b = _hparam_batch(n)
+    ref_terms, ref_g, margins, shares = _loss_and_row_grads(b, hpd, nu_f, torch.float64)
+    # ---- conditions on the inputs, before the kernel
+    assert margins[0] >= H.RATIO_MARGIN and margins[1] >= H.VALUE_MARGIN and margins[2] >= H.VALUE_MARGIN, margins
+    assert H.CLIP_FRACTION[0] <= shares[0] <= H.CLIP_FRACTION[1] and all(H.VCLIP_SHARE[0] <= s <= H.VCLIP_SHARE[1] for s in shares[1:]), shares
+    hp = S.PpoHyperT(n, 1, 0, 0)
+    hp.clip_range, hp.ent_coef, hp.reward_vf_coef, hp.cost_vf_coef, hp.max_grad_norm = 0.2, hpd["ent_coef"], hpd["reward_vf_coef"], hpd["cost_vf_coef"], hpd["max_grad_norm"]
+    hp.clip_range_reward_vf, hp.clip_range_cost_vf = hpd["clip_range_reward_vf"], hpd["clip_range_cost_vf"]
+    hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps = 3e-4, 0.9, 0.999, 1e-5
+    dev = {k: _dev(v) for k, v in b.items()}
+    nu, terms = _dev(np.float32([nu_f])), torch.zeros(8, device="cuda")
+    got = {k: torch.full((n,), 7.0, device="cuda") for k in ("d_lp", "d_vr", "d_vc", "d_en")}
+    st = _lib.current_stream()
+    _lib.check(L.icrl_ppo_lag_loss_fwd_bwd(*[_lib.ptr(dev[k]) for k in ("lp", "old_lp", "adv_r", "adv_c", "v_r", "v_c", "ret_r", "ret_c", "old_v_r", "old_v_c", "ent")],
+                                           _lib.ptr(nu), ctypes.byref(hp), n, _lib.ptr(terms), *[_lib.ptr(got[k]) for k in ("d_lp", "d_vr", "d_vc", "d_en")], st),
+               "icrl_ppo_lag_loss_fwd_bwd")
+    t = terms.cpu().numpy()
+    for i, key in enumerate(("loss", "policy_loss", "rvl", "cvl", "entropy_loss", "approx_kl", "clip_fraction")):
+        print(f"FINE_HP set {hset} n={n} {key}: {t[i]:.9g} vs {ref_terms[i]:.9g}")
+    for k in got:
+        print(f"FINE_HP set {hset} n={n} {k}: max |kernel - float64| = {np.abs(got[k].cpu().numpy() - ref_g[k]).max():.3g} (bound {3 * ROW_GRAD_F32_DEV[k]:.3g})")
+    for i, key in enumerate(("loss", "policy_loss", "rvl", "cvl", "entropy_loss", "approx_kl", "clip_fraction")):
+        assert abs(t[i] - ref_terms[i]) <= 2e-6 + 2e-5 * abs(ref_terms[i]), (key, t[i], ref_terms[i])
+    for k in got:      # row by row
+        assert np.abs(got[k].cpu().numpy() - ref_g[k]).max() <= 3 * ROW_GRAD_F32_DEV[k], (k, np.abs(got[k].cpu().numpy() - ref_g[k]).max())
+    # ---- clip_grad_norm_ + Adam, two steps on a flat buffer of 20 blocks with a ragged tail
+    rng = np.random.RandomState(n)
+    n_p = 5001
+    p0, grads = rng.randn(n_p).astype(np.float32), [(rng.randn(n_p) / np.sqrt(n_p) * s).astype(np.float32) for s in (1.0, 2.5)]      # norms ~ 1 and ~ 2.5
+    flat, m, v = _dev(p0), torch.zeros(n_p, device="cuda"), torch.zeros(n_p, device="cuda")
+    step, work, out2 = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(256, device="cuda"), torch.zeros(2, device="cuda")
+    rp, rm, rv, qm, qv = (torch.as_tensor(x, dtype=torch.float64) for x in (p0, np.zeros(n_p), np.zeros(n_p), np.zeros(n_p), np.zeros(n_p)))
+    w1 = np.float32(1.0 - float(np.float32(0.9)))
+    for s, g in enumerate(grads):
+        total, coef = o_ppo.clip_coef_explicit([torch.as_tensor(g)], hpd["max_grad_norm"])
+        assert (coef < 1.0) == (hset == "A") and abs(total - hpd["max_grad_norm"]) > 0.1      # the branch the set is about, away from its kink
+        gd = _dev(g)
+        _lib.check(L.icrl_clip_adam_step(_lib.ptr(flat), _lib.ptr(gd), _lib.ptr(m), _lib.ptr(v), _lib.ptr(step), n_p, ctypes.byref(hp), _lib.ptr(work),
+                                         _lib.ptr(out2), st), "icrl_clip_adam_step")
+        o = out2.cpu().numpy()
+        assert abs(o[0] - total) <= 1e-5 * max(1.0, total), (o, total)
+        assert abs(o[1] - coef) <= 1e-5 * coef and (o[1] == 1.0) == (hset == "B"), (o, coef)
+        # what enters the moments is g x coef, rounded once.  After the first step exp_avg is (1 - beta1) x that, bit for bit: with the coefficient
+        # capped at 1 (set B) the first moment is (1 - beta1) g itself, the gradient's direction and scale untouched
+        gi = g * o[1]
+        if s == 0:
+            assert np.array_equal(m.cpu().numpy(), w1 * gi)
+            assert np.array_equal(m.cpu().numpy(), w1 * g) == (hset == "B")
+        gc = torch.as_tensor(g, dtype=torch.float64) * coef
+        rp, rm, rv = o_ppo.adam_step_explicit(rp, gc, rm, rv, s + 1, 3e-4, eps=1e-5)
+        assert np.allclose(flat.cpu().numpy(), rp.numpy(), rtol=1e-5, atol=3e-7), np.abs(flat.cpu().numpy() - rp.numpy()).max()
+        # the moments: the explicit formula with the betas as icrl_ppo_hyper_t carries them (float32: 1 - float32(0.999) is smaller than 0.001 by 1.3e-5 of it,
+        # which the parameter tolerance above and ADAM_DEV_BOUND absorb)
+        b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
+        qm, qv = b1 * qm + (1 - b1) * gc, b2 * qv + (1 - b2) * gc * gc
+        assert np.allclose(m.cpu().numpy(), qm.numpy(), rtol=1e-5, atol=1e-9) and np.allclose(v.cpu().numpy(), qv.numpy(), rtol=1e-5, atol=1e-12)
+    assert int(step.item()) == 2

@@ -99,6 +99,13 @@ def test_learn_matches_reference_golden(golden):
                                                   (18, 5, 8, 32, 64, 3, 0.01, "trunk"), (7, 3, 4, 50, 100, 2, 0.03, "deep")])
 def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     """the Categorical branch of the update kernel at other widths (up to 16 classes) against the oracle epoch loop."""
+    _categorical_case(O, A, N, T, B, E, ent, wide)
+
+
+def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None):
+    """one Categorical update against the oracle's epoch loop; hset: a hyper-parameter set of helpers/ppo_hparam_cases.py on a banded buffer."""
+    from helpers import ppo_hparam_cases as H
+    hp = {} if hset is None else {k: v for k, v in H.hparams(hset).items() if k != "ent_coef"}
     from helpers.arches import ARCHES, oracle_arch_kwargs
     from icrl_amd import logger, spaces
     from icrl_amd.ppo_lag import PPOLagrangian
@@ -110,7 +117,7 @@ def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     env = VecNormalizeWithCost(VecCostWrapper(senv))
     net_arch = ARCHES[wide] if isinstance(wide, str) else [dict(pi=[128, 72], vf=[100, 128], cvf=[128, 128])]
     akw = dict(policy_kwargs=dict(net_arch=net_arch)) if wide else {}
-    agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0, batch_size=B, n_epochs=E, target_kl=None, ent_coef=ent, **akw)
+    agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0, batch_size=B, n_epochs=E, target_kl=None, ent_coef=ent, **hp, **akw)
     sd0 = agent.policy.state_dict()
     assert "log_std" not in sd0 and agent.policy.wide == bool(wide)
     okw = oracle_arch_kwargs(net_arch) if wide else {}
@@ -135,16 +142,22 @@ def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
                reward_advantages=rng.randn(T, N).astype(np.float32) * 2, cost_advantages=rng.rand(T, N).astype(np.float32),
                reward_returns=rng.randn(T, N).astype(np.float32), cost_returns=rng.rand(T, N).astype(np.float32),
                orig_costs=rng.rand(T, N).astype(np.float32))
+    if hset is not None:      # old log-probs and old values in bands around the policy's: every clip of the loss is taken by its share of the rows
+        buf["log_probs"], buf["reward_values"], buf["cost_values"] = H.banded(np.random.RandomState(O * A + T + 1), buf["log_probs"], buf["reward_values"],
+                                                                              buf["cost_values"], hp["clip_range_reward_vf"], hp["clip_range_cost_vf"])
     rb = agent.rollout_buffer
     for k, v in buf.items():
         getattr(rb, k).copy_(torch.as_tensor(np.asarray(v, np.float32)).reshape(getattr(rb, k).shape))
     rb.full = True
     perms = np.stack([rng.permutation(T * N) for _ in range(E)])
     nu = agent.dual.nu().item()
-    agent.train(perms=perms)
     opt = torch.optim.Adam(op.parameters(), lr=3e-4, eps=1e-5)
+    trace = []
     out = o_ppo.ppo_lag_train(op, opt, buf, perms, nu, discrete=True, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=None,
-                              ent_coef=ent)
+                              ent_coef=ent, trace=trace, **hp)
+    if hset is not None:      # conditions on the inputs, from the oracle's trace, before the kernel runs
+        H.check_trace(trace, dict(hp, ent_coef=ent), n_steps=E * (-(-N * T // B)))
+    agent.train(perms=perms)
     lg = logger.Logger.CURRENT.name_to_value
     n_steps = agent.policy.adam_step
     for k, v in agent.policy.state_dict().items():
@@ -155,6 +168,13 @@ def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     for key in ("train/policy_gradient_loss", "train/reward_value_loss", "train/cost_value_loss", "train/approx_kl",
                 "train/clip_fraction", "train/entropy_loss", "train/loss"):
         assert abs(lg[key] - out[key]) < 2e-4 + 2e-3 * abs(out[key]), (key, lg[key], out[key])
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_categorical_update_hparams_vs_oracle(wide):
+    """value clipping of both critics, separate critic weights and max_grad_norm 0.3 (set A of helpers/ppo_hparam_cases.py) beside the Categorical
+    entropy bonus, on a banded buffer: the fast kernels' and the generic-shape path's Categorical branch."""
+    _categorical_case(18, 5, 8, 32, 64, 3, 0.01, wide, hset="A")
 
 
 def test_sampling_and_evaluation_vs_port():

@@ -430,3 +430,31 @@ def test_reference_loads_the_archive_this_build_wrote():
     # and what the reference computed from the archive is what the HIP path computed (oracle/verify_agent_archive.py's bounds)
     assert np.abs(ref["actions"] - exp["actions"]).max() <= 1e-5 and np.abs(ref["log_prob"] - exp["log_prob"]).max() <= 1e-4
     assert np.abs(ref["v_r"] - exp["v_r"]).max() <= 2e-5 and np.abs(ref["v_c"] - exp["v_c"]).max() <= 2e-5
+
+
+def test_g23_ppo_hparams_train(golden):
+    """The reference's own train() with value clipping of both critics, the entropy bonus (incl. its -ent_coef on log_std), separate critic
+    weights and max_grad_norm 0.3, on a buffer overwritten in bands (oracle/gen_golden.py: g23_ppo_hparams; helpers/ppo_hparam_cases.py):
+    the oracle's epoch loop from the same weights, Adam state and permutations — bit for bit; the buffer takes every clip of the loss at
+    every step, away from the kinks."""
+    from helpers import ppo_hparam_cases as H
+    g = golden("g23_ppo_hparams")
+    hp = {k: (None if np.isnan(v) else float(v)) for k, v in ((k, g["hp/" + k].astype(np.float64)) for k in H.DEFAULTS)}
+    assert hp == H.hparams("A")
+    pol = o_nets.TwoCriticPolicy(18, 6)
+    pol.load_state_dict(_sub(g, "w0/"))
+    opt = th.optim.Adam(pol.parameters(), lr=float(g["lr"]), eps=1e-5)
+    names = list(pol.params)
+    opt.load_state_dict(dict(state={i: dict(step=th.tensor(float(g["adam_step"])), exp_avg=th.as_tensor(g["m0/" + k]), exp_avg_sq=th.as_tensor(g["v0/" + k]))
+                                    for i, k in enumerate(names)},
+                             param_groups=[dict(opt.state_dict()["param_groups"][0], params=list(range(len(names))))]))
+    buf = {k: (v[..., 0] if k not in ("observations", "actions") else v) for k, v in _sub(g, "buf/").items()}
+    T, N = buf["log_probs"].shape
+    trace = []
+    out = o_ppo.ppo_lag_train(pol, opt, buf, g["perms"], float(g["nu"]), batch_size=64, n_epochs=2, clip_range=0.2, target_kl=None, trace=trace, **hp)
+    H.check_trace(trace, hp, n_steps=2 * (T * N // 64))
+    for k, p in pol.params.items():
+        assert np.array_equal(p.detach().numpy(), g["w1/" + k]), k
+    for key in ("entropy_loss", "policy_gradient_loss", "reward_value_loss", "cost_value_loss", "approx_kl", "clip_fraction", "loss", "early_stop_epoch"):
+        assert float(out["train/" + key]) == g["log/" + key].item(), key
+    assert g["log/clip_range_reward_vf"].item() == 0.2 and g["log/clip_range_cost_vf"].item() == 0.3      # ref: ppo_lag.py:335-338

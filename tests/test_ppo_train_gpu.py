@@ -96,6 +96,28 @@ def test_three_steps_on_one_batch_golden(golden, name, arch):
 ADAM_DEV_BOUND = 5e-4      # 3 x the largest deviation measured on MI355X (1.7e-4 x lr x steps; absolute: <= 9e-8, ~1 ulp)
 
 
+def _compare_with_oracle(agent, ref_params, out, kind, B, lr):
+    """every parameter, the seven train/* scalars and the per-epoch KLs of an agent after train() against the oracle's."""
+    from icrl_amd import logger
+    lg = logger.Logger.CURRENT.name_to_value
+    assert lg["train/early_stop_epoch"] == out["train/early_stop_epoch"]
+    n_steps = agent.policy.adam_step
+    worst = 0.0
+    for k, v in agent.policy.state_dict().items():
+        ref = ref_params[k]
+        worst = max(worst, float(np.abs(v.numpy() - ref).max()))
+    # measured on MI355X (printed below): after up to 48 dependent Adam steps no parameter is further than 9e-8 (about one
+    # float32 ulp) from the oracle's, at most 1.7e-4 of the distance a parameter can travel (lr per step).  The bound is 3x
+    # that plus one ulp; a wrong bias correction or moment update shifts every step by O(lr) and lands 3 orders above it.
+    print(f"ADAM_DEV {kind} B={B} steps={n_steps}: max |param - oracle| = {worst:.3g} = {worst / (lr * n_steps):.3g} x lr x steps")
+    assert worst <= ADAM_DEV_BOUND * lr * n_steps + 2e-7, (worst, worst / (lr * n_steps))
+    for key in ("train/policy_gradient_loss", "train/reward_value_loss", "train/cost_value_loss", "train/approx_kl",
+                "train/clip_fraction", "train/entropy_loss", "train/loss"):
+        assert abs(lg[key] - out[key]) < 2e-4 + 2e-3 * abs(out[key]), (key, lg[key], out[key])
+    assert np.allclose(agent.epoch_kls[:len(out["epoch_kls"])], out["epoch_kls"], atol=2e-5)
+    return worst / (lr * n_steps)
+
+
 def _oracle_train(agent_sd, buf, perms, kind, nu, okw=None, **h):
     od, ad = (18, 6) if kind == "hc" else (113, 8)
     pol = o_nets.TwoCriticPolicy(od, ad, **(okw or {}))
@@ -164,23 +186,113 @@ def test_train_vs_oracle(kind, N, T, B, E, tk, one_workgroup_per_network=False, 
     nu = agent.dual.nu().item()
     agent.train(perms=perms)
     pol, out = _oracle_train(sd0, buf, perms, kind, nu, lr=lr, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=tk, okw=okw)
+    _compare_with_oracle(agent, {k: p_.detach().numpy() for k, p_ in pol.params.items()}, out, kind, B, lr)
+
+
+def _hp_cases():
+    """(kind, N, T, B, E, hyper-parameter set, train_kernel): every update-kernel family at the smallest shapes that reach its edges."""
+    cases = []
+    def add(shapes, sets, kernel=None):
+        cases.extend((*shape, hset, kernel) for shape in shapes for hset in sets)
+    # default kernels.  obs <= 32: wave quads, four workgroups per network — one chunk, ragged 64 + 64 + 64 + 8 / 64 + 36, a 16-row minibatch
+    add([("hc", 8, 32, 64, 3), ("hc", 5, 60, 200, 2), ("hc", 4, 8, 16, 2)], "ABCDE")
+    # obs 113, minibatches of 65..128 rows: ppo_train_quarters2.hip
+    add([("ant", 24, 16, 128, 2), ("ant", 3, 50, 100, 2)], "ABCDE")
+    # obs 113 chunk by chunk: ppo_train_quarters.hip
+    add([("ant", 6, 32, 64, 2), ("ant", 4, 80, 256, 2)], "A")
+    # the kernels behind the defaults
+    for kernel in ("halves", "pairs"):
+        add([("hc", 8, 32, 64, 3), ("hc", 5, 60, 200, 2)], "A", kernel)
+    add([("ant", 24, 16, 128, 2), ("ant", 6, 32, 64, 2)], "AB", "rows"); add([("ant", 24, 16, 128, 2)], "A", "rows1")
+    # generic-shape path, persistent form (its other forms: test_generic_shape_update_as_one_persistent_launch selects these cases too)
+    add([("hc-wide", 8, 32, 64, 3), ("hc-trunk", 9, 48, 144, 2), ("hc", 8, 128, 512, 3)], "AB")
+    return cases
+
+
+@pytest.mark.parametrize("kind,N,T,B,E,hset,train_kernel", _hp_cases())
+def test_train_hparams_vs_oracle(kind, N, T, B, E, hset, train_kernel):
+    """Value clipping of both critics, the DiagGaussian entropy bonus (with its -ent_coef on log_std), separate weights of the two critics
+    and both branches of the global-norm clip (ref: ppo_lag.py:243-288), plus the ratio clip at clip_fraction ~ 0.6, through every update
+    kernel against the oracle's epoch loop — on a buffer built in bands (helpers/ppo_hparam_cases.py) so that no row sits on a kink of a
+    clamp or min.  The conditions on the inputs are asserted from the oracle's trace before the kernel runs; the comparison and its
+    tolerances are test_train_vs_oracle's."""
+    from helpers import ppo_hparam_cases as H
+    from helpers.arches import ARCHES, oracle_arch_kwargs
+    kind, _, shape = kind.partition("-")
+    net_arch = [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])] if shape == "wide" else ARCHES.get(shape)
+    akw = dict(policy_kwargs=dict(net_arch=net_arch)) if net_arch is not None else {}
+    hp = H.hparams(hset)
+    lr = 3e-4 if kind == "hc" else 3e-5
+    agent = _agent(kind, N, T, batch_size=B, n_epochs=E, target_kl=None, learning_rate=lr, clip_range=0.2, **hp, **akw)
+    if train_kernel is not None:
+        agent.train_kernel = train_kernel
+    case = H.oracle_case(kind, shape, N, T, B, E, hset, agent.policy.state_dict(), oracle_kwargs=oracle_arch_kwargs(net_arch) if net_arch is not None else {},
+                         nu=agent.dual.nu().item())
+    H.check_trace(case["trace"], hp, n_steps=E * (-(-N * T // B)))
+    _fill(agent, case["buf"])
     from icrl_amd import logger
+    logger.configure()                 # (an empty log: keys of an earlier test's agent do not count)
+    agent.train(perms=case["perms"])
+    rel = _compare_with_oracle(agent, case["params"], case["out"], kind, B, lr)
+    print(f"ADAM_DEV_HP {kind}{'-' + shape if shape else ''} {N}x{T} B={B} E={E} set {hset} kernel {train_kernel or 'default'}: {rel:.3g} x lr x steps")
     lg = logger.Logger.CURRENT.name_to_value
-    assert lg["train/early_stop_epoch"] == out["train/early_stop_epoch"]
-    n_steps = agent.policy.adam_step
-    worst = 0.0
-    for k, v in agent.policy.state_dict().items():
-        ref = pol.params[k].detach().numpy()
-        worst = max(worst, float(np.abs(v.numpy() - ref).max()))
-    # measured on MI355X (printed below): after up to 48 dependent Adam steps no parameter is further than 9e-8 (about one
-    # float32 ulp) from the oracle's, at most 1.7e-4 of the distance a parameter can travel (lr per step).  The bound is 3x
-    # that plus one ulp; a wrong bias correction or moment update shifts every step by O(lr) and lands 3 orders above it.
-    print(f"ADAM_DEV {kind} B={B} steps={n_steps}: max |param - oracle| = {worst:.3g} = {worst / (lr * n_steps):.3g} x lr x steps")
-    assert worst <= ADAM_DEV_BOUND * lr * n_steps + 2e-7, (worst, worst / (lr * n_steps))
-    for key in ("train/policy_gradient_loss", "train/reward_value_loss", "train/cost_value_loss", "train/approx_kl",
-                "train/clip_fraction", "train/entropy_loss", "train/loss"):
-        assert abs(lg[key] - out[key]) < 2e-4 + 2e-3 * abs(out[key]), (key, lg[key], out[key])
-    assert np.allclose(agent.epoch_kls[:len(out["epoch_kls"])], out["epoch_kls"], atol=2e-5)
+    for key in ("clip_range_reward_vf", "clip_range_cost_vf"):       # ref: ppo_lag.py:335-338 — logged when set, and only then
+        if hp[key] is None:
+            assert "train/" + key not in lg
+        else:
+            assert lg["train/" + key] == hp[key]
+
+
+def test_ant_chunk_by_chunk_form_at_128_rows_hparams():
+    """test_train_hparams_vs_oracle's 128-row AntWall case through ppo_train_quarters.hip where ppo_train_quarters2.hip would run
+    (ICRL_QUARTERS_PASSES=1; child process: the switch is read once per process)."""
+    import subprocess, sys
+    env = dict(os.environ, ICRL_QUARTERS_PASSES="1")
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", "test_train_hparams_vs_oracle and ant-24-16-128-2-A-None",
+                          "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=300, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert out.returncode == 0 and "1 passed" in out.stdout, out.stdout[-3000:]
+
+
+def test_train_hparams_vs_reference_golden(golden):
+    """tests/golden/g23: the reference's own train() (ppo_lag.py:177-338) with value clipping of both critics, the entropy bonus, critic
+    weights 0.7 / 0.3 and max_grad_norm 0.3 on a buffer overwritten in bands, from weights and an Adam state four steps old — agent.train()
+    on that buffer with the reference's permutations: parameters, the train/* scalars, and the two clip ranges the reference logs when set
+    (lines 335-338) and only then."""
+    from helpers import ppo_hparam_cases as H
+    from icrl_amd import logger
+    g = golden("g23_ppo_hparams")
+    hp, lr = H.hparams("A"), float(g["lr"])
+    buf = _sub(g, "buf/")
+    T, N = buf["log_probs"].shape[:2]
+    agent = _agent("hc", N, T, batch_size=64, n_epochs=2, target_kl=None, learning_rate=lr, clip_range=0.2, **hp)
+    pol = agent.policy
+    pol.load_state_dict(_sub(g, "w0/"))
+    names = list(pol.shapes)
+    pol.load_optimizer_state_dict(dict(state={i: dict(step=float(g["adam_step"]), exp_avg=g["m0/" + k], exp_avg_sq=g["v0/" + k]) for i, k in enumerate(names)},
+                                       param_groups=[dict(params=list(range(len(names))))]))
+    assert pol.adam_step == 4
+    _fill(agent, buf)
+    agent.dual.log_nu = np.float32(np.log(np.exp(float(g["nu"])) - 1))       # softplus^-1(nu)
+    assert abs(agent.dual.nu().item() - float(g["nu"])) < 1e-6
+    logger.configure()
+    agent.train(perms=g["perms"])
+    assert pol.adam_step == 8
+    worst = max(float(np.abs(v.numpy() - g["w1/" + k]).max()) for k, v in pol.state_dict().items())
+    print(f"ADAM_DEV_HP golden g23: max |param - reference| = {worst:.3g} = {worst / (lr * 4):.3g} x lr x steps")
+    assert worst <= ADAM_DEV_BOUND * lr * 4 + 2e-7, worst
+    lg = logger.Logger.CURRENT.name_to_value
+    for key in ("policy_gradient_loss", "reward_value_loss", "cost_value_loss", "approx_kl", "clip_fraction", "entropy_loss", "loss"):
+        ref = g["log/" + key].item()
+        assert abs(lg["train/" + key] - ref) < 2e-4 + 2e-3 * abs(ref), (key, lg["train/" + key], ref)
+    assert lg["train/early_stop_epoch"] == g["log/early_stop_epoch"].item() == 2
+    assert lg["train/clip_range"] == g["log/clip_range"].item()
+    assert lg["train/clip_range_reward_vf"] == g["log/clip_range_reward_vf"].item() and lg["train/clip_range_cost_vf"] == g["log/clip_range_cost_vf"].item()
+    plain = _agent("hc", N, T, batch_size=64, n_epochs=2, target_kl=None, learning_rate=lr, clip_range=0.2)      # no value clipping: the keys are not logged
+    _fill(plain, buf)
+    logger.configure()
+    plain.train(perms=g["perms"])
+    lg = logger.Logger.CURRENT.name_to_value
+    assert "train/clip_range" in lg and "train/clip_range_reward_vf" not in lg and "train/clip_range_cost_vf" not in lg
 
 
 @pytest.mark.parametrize("tk", [None, 1e-6])
@@ -298,13 +410,18 @@ def test_generic_shape_update_as_one_persistent_launch(switch):
     cases of the generic-shape path pass under each of them (child process: the switches are read once per process):
     ICRL_GEN_LAUNCHES=1 three plain launches per optimiser step (the fallback of shapes the persistent form does not hold),
     ICRL_GEN_BRANCH_WGS=1 one workgroup per row tile walking all three branches (batches above 160 rows take it anyway),
-    ICRL_NO_XCD_PACK=1 the dense grid: workgroups on several XCDs, agent-scope stores instead of the L2-local exchange."""
+    ICRL_NO_XCD_PACK=1 the dense grid: workgroups on several XCDs, agent-scope stores instead of the L2-local exchange.
+    The selection includes the six generic-shape cases of test_train_hparams_vs_oracle (hc-wide, hc-trunk, hc 8x128 B512 under sets A and B);
+    that all six ran is asserted from the child's output."""
     import subprocess, sys
     env = dict(os.environ, **{switch: "1"})
+    # (the last three also select the generic-shape cases of test_train_hparams_vs_oracle: value clipping, entropy bonus, critic weights, both norm-clip branches)
     sel = "g15 or g16 or g17 or g18 or hc-wide or hc-trunk or ant-deep or hc-bare or hc-8-128-512 or hc-5-200-300"
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-s", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
                          env=env, capture_output=True, text=True, timeout=300, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0 and " passed" in out.stdout, out.stdout[-3000:]
+    ran = out.stdout.count("ADAM_DEV_HP ")      # (-s: one line per case of test_train_hparams_vs_oracle that ran)
+    assert ran == sum(1 for c in _hp_cases() if c[0] in ("hc-wide", "hc-trunk") or c[:4] == ("hc", 8, 128, 512)) == 6, ran
 
 
 @pytest.mark.parametrize("shape,B", [("wide", 64), ("trunk", 64), ("trunk", 144), ("deep", 320)])

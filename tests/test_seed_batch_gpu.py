@@ -74,3 +74,56 @@ def test_batched_entry_points_refuse_mixed_shapes():
     from icrl_amd.seed_batch import SeedBatch
     with pytest.raises(ValueError, match="num_threads"):
         SeedBatch([_cfg(0), _cfg(1, envs=4)])
+
+
+def test_batched_update_reads_each_runs_own_hyper_parameters():
+    """icrl_ppo_lag_train_batch takes one hyper-parameter block per run.  Three HalfCheetah-shaped runs with the same weights and the same
+    (banded: helpers/ppo_hparam_cases.py) buffer but different loss hyper-parameters — value clipping + entropy bonus + critic weights with the
+    norm clip active, the same with the clip's coefficient at 1, the defaults — in ONE batched launch: each must leave bit for bit what it
+    leaves trained alone (parameters, both Adam moments, stats[0:11]); the three differ from each other, so a run that read a neighbour's
+    block would not."""
+    from helpers import ppo_hparam_cases as H
+    from icrl_amd.ppo_lag import PPOLagrangian
+    from icrl_amd.seed_batch import launch_trains
+    from icrl_amd import _lib
+    from icrl_amd.vec_env import HipSynthVecEnv, VecCostWrapper, VecNormalizeWithCost
+    N, T, B, E = 8, 32, 64, 2
+    sets = ("A", "B", "E")
+
+    def agent(hset):
+        env = VecNormalizeWithCost(VecCostWrapper(HipSynthVecEnv(N, "hc", 0)))
+        a = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0, batch_size=B, n_epochs=E, target_kl=None, learning_rate=3e-4, clip_range=0.2,
+                          **H.hparams(hset))
+        case = H.oracle_case("hc", "", N, T, B, E, hset, a.policy.state_dict(), nu=a.dual.nu().item())
+        H.check_trace(case["trace"], case["hp"], n_steps=E * (N * T // B))
+        rb = a.rollout_buffer
+        for k, v in case["buf"].items():
+            getattr(rb, k).copy_(torch.as_tensor(np.asarray(v, np.float32)).reshape(getattr(rb, k).shape))
+        rb.full = True
+        return a, case
+
+    def snapshot(a):
+        pol = a.policy
+        return [t.cpu().numpy().copy() for t in (pol.params, pol.exp_avg, pol.exp_avg_sq, a._train_ws["stats"][:11])]
+
+    solo = []
+    for hset in sets:
+        a, case = agent(hset)
+        a.train(perms=case["perms"])
+        solo.append(snapshot(a))
+    assert not np.array_equal(solo[0][0], solo[1][0]) and not np.array_equal(solo[0][0], solo[2][0]) and not np.array_equal(solo[1][0], solo[2][0])
+    agents, jobs = [], []
+    for hset in sets:
+        a, case = agent(hset)
+        agents.append(a)
+        jobs.append(a._train_begin(case["perms"]))
+    assert np.array_equal(np.asarray(case["buf"]["log_probs"]), agents[0].rollout_buffer.log_probs.cpu().numpy().reshape(T, N))      # one buffer for all three
+    args_ws = torch.empty(len(agents) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=agents[0].device)
+    launch_trains(agents, jobs, args_ws)             # (what SeedBatch._launch_trains calls: the launch alone, no ICRL loop around the agents)
+    torch.cuda.synchronize()
+    for i, (a, j) in enumerate(zip(agents, jobs)):
+        got = snapshot(a)
+        assert float(a._train_ws["stats"][11]) == 0
+        for name, g_, s_ in zip(("params", "exp_avg", "exp_avg_sq", "stats"), got, solo[i]):
+            assert np.array_equal(g_, s_), (sets[i], name, np.abs(g_ - s_).max())
+        a._train_end(j)
