@@ -274,13 +274,15 @@ def compute_kl(policy_2, observations, actions, policy_1=None):
 
 
 def make_stack(n_envs, kind, seed, *, training=True, norm_reward=True, norm_cost=True, norm_obs=True,
-               cost_fn=None, wall_terminate=False, broken=False, reward_gamma=0.99, cost_gamma=0.99):
+               cost_fn=None, wall_terminate=False, broken=False, reward_gamma=0.99, cost_gamma=0.99,
+               clip_obs=10.0, clip_reward=10.0, clip_cost=10.0, epsilon=1e-8):
     if kind in ("lgw", "clgw"):
         env = LapGridVecEnv(n_envs, constrained=(kind == "clgw"))
     else:
         env = SynthVecEnv(n_envs, kind, seed, wall_terminate=wall_terminate, broken=broken)
     norm = stats.NormState(n_envs, env.obs_dim, training=training, norm_obs=norm_obs, norm_reward=norm_reward,
-                           norm_cost=norm_cost, reward_gamma=reward_gamma, cost_gamma=cost_gamma)
+                           norm_cost=norm_cost, clip_obs=clip_obs, clip_reward=clip_reward, clip_cost=clip_cost,
+                           reward_gamma=reward_gamma, cost_gamma=cost_gamma, epsilon=epsilon)
     return EnvStack(env, norm, cost_fn)
 
 

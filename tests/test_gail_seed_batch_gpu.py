@@ -169,7 +169,7 @@ def _true_cost(name):
             "torque": lambda: AnalyticCost.torque(0.5), "null": AnalyticCost.null, "NULL": lambda: None}[name]()
 
 
-def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost):
+def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost, eps=1e-8):
     """per run: a discriminator, normalised float32 observations [rows, obs], actions, statistics, rewards and the references — the torch
     expressions of the callback (un-normalise, mean cost) and icrl_disc_reward plus a torch add."""
     from icrl_amd import _lib
@@ -188,7 +188,6 @@ def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost):
             acs = torch.as_tensor(rng.uniform(-1.2, 1.2, (_ROWS, act_dim)).astype(np.float32), device="cuda")
         mean = torch.as_tensor(rng.randn(obs_dim) * 0.7, device="cuda") if stats else None
         var = torch.as_tensor(rng.uniform(0.2, 3.0, obs_dim), device="cuda") if stats else None
-        eps = 1e-8
         rewards = torch.as_tensor(rng.randn(_ROWS).astype(np.float32), device="cuda")
         # ---- references
         raw = obs.double()

@@ -19,11 +19,11 @@ _HOST = {"hc": "HostHCWithPos-v0", "hctest": "HostHCWithPosTest-v0", "ant": "Hos
 _EARLY_END = ("clgw", "hctest")      # episodes also end before the time limit (the wall at obs[0] <= -3, the backward action)
 
 
-def _chain(bottom, cost, norm, seed, hid):
+def _chain(bottom, cost, norm, seed, hid, norm_kwargs=None):
     from icrl_amd.constraint_net import ConstraintNet
     from icrl_amd.vec_env import VecCostWrapper, VecNormalizeWithCost
     env = VecCostWrapper(bottom) if cost else bottom
-    env = VecNormalizeWithCost(env, norm_obs=norm, norm_reward=norm, norm_cost=norm)
+    env = VecNormalizeWithCost(env, norm_obs=norm, norm_reward=norm, norm_cost=norm, **(norm_kwargs or {}))
     cn = None
     if cost:
         od, ad = bottom.observation_space.shape[0], bottom.action_space.shape[0]
@@ -34,15 +34,15 @@ def _chain(bottom, cost, norm, seed, hid):
     return env, cn
 
 
-def _agents(kind, N, T, seed=5, cost=True, norm=True, subproc=False, agent_kwargs=None):
+def _agents(kind, N, T, seed=5, cost=True, norm=True, subproc=False, agent_kwargs=None, norm_kwargs=None):
     from icrl_amd import envs
     from icrl_amd.ppo_lag import PPOLagrangian
     from icrl_amd.vec_env import DummyVecEnv, HipSynthVecEnv, SubprocVecEnv
     k, broken = _DEVICE[kind]
     hid = [20] if k in ("hc", "lgw", "clgw") else [40, 40]
-    e_d, cn_d = _chain(HipSynthVecEnv(N, k, seed, broken=broken, wall_terminate=kind in _EARLY_END), cost, norm, seed, hid)
+    e_d, cn_d = _chain(HipSynthVecEnv(N, k, seed, broken=broken, wall_terminate=kind in _EARLY_END), cost, norm, seed, hid, norm_kwargs)
     fns = [envs.spec(_HOST[kind])] * N
-    e_h, cn_h = _chain((SubprocVecEnv if subproc else DummyVecEnv)(fns), cost, norm, seed, hid)
+    e_h, cn_h = _chain((SubprocVecEnv if subproc else DummyVecEnv)(fns), cost, norm, seed, hid, norm_kwargs)
     a_d = PPOLagrangian("TwoCriticsMlpPolicy", e_d, n_steps=T, seed=seed, **(agent_kwargs or {}))
     a_h = PPOLagrangian("TwoCriticsMlpPolicy", e_h, n_steps=T, seed=seed, **(agent_kwargs or {}))
     a_h.policy.load_state_dict(a_d.policy.state_dict())
@@ -86,8 +86,8 @@ def _received_actions(e_h):
     ("hc", 8, 16, False, True, False),                      # no cost wrapper (the GAIL chain)
     ("hc", 4, 16, True, True, True),                        # SubprocVecEnv through the host path
 ])
-def test_host_rollout_equals_device_rollout(kind, N, T, cost, norm, subproc):
-    (a_d, e_d), (a_h, e_h) = _agents(kind, N, T, cost=cost, norm=norm, subproc=subproc)
+def test_host_rollout_equals_device_rollout(kind, N, T, cost, norm, subproc, norm_kwargs=None):
+    (a_d, e_d), (a_h, e_h) = _agents(kind, N, T, cost=cost, norm=norm, subproc=subproc, norm_kwargs=norm_kwargs)
     noise = _noise(kind, N, T)
     a_d._setup_learn(2 * N * T); a_h._setup_learn(2 * N * T)
     limit = e_d.unwrapped.max_steps
