@@ -30,6 +30,15 @@ class ConstraintNet:
         self.clip_obs, self.eps = clip_obs, eps
         self.device = torch.device("cuda" if device in (None, "cpu", "auto") else device)  # HBM-resident regardless
         self.train_gail_lambda = train_gail_lambda
+        # the update kernels are Adam with betas (0.9, 0.999), no weight decay, no amsgrad (csrc/cn_train.hip: cn_adam_body); of
+        # optimizer_kwargs they read "eps" only.  Anything else would train differently from the reference without a word.
+        if optimizer_class is not None and optimizer_class is not torch.optim.Adam:
+            raise NotImplementedError(f"icrl_amd ConstraintNet: optimizer_class {getattr(optimizer_class, '__name__', optimizer_class)} is not "
+                                      "supported (torch.optim.Adam, or None for a net that is not trained)")
+        unsupported = sorted(set(optimizer_kwargs or {}) - {"eps"})
+        if unsupported:
+            raise NotImplementedError(f"icrl_amd ConstraintNet: optimizer_kwargs {unsupported} are not supported (the kernels implement Adam "
+                                      "with betas (0.9, 0.999) and read 'eps' only)")
         if optimizer_kwargs is None:
             optimizer_kwargs = {}
             if optimizer_class == torch.optim.Adam:

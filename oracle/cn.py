@@ -18,9 +18,10 @@ import numpy as np
 import torch as th
 
 
-def is_weights_and_kls(preds_old, preds_new, episode_lengths, eps=1e-5, per_step=False):
+def is_weights_and_kls(preds_old, preds_new, episode_lengths, eps=1e-5, per_step=False, with_prod=False):
     """ref: constraint_net.py:231-256.  preds_*: [N,1] float32 tensors.
-    Returns (weights, kl_old_new, kl_new_old); weights is [N,1] (per-step) or [N] (per-episode)."""
+    Returns (weights, kl_old_new, kl_new_old); weights is [N,1] (per-step) or [N] (per-episode).
+    with_prod: the per-episode products of the ratios as a fourth value (for cn_train's trace)."""
     with th.no_grad():
         n_ep = len(episode_lengths)
         bounds = [0] + list(accumulate(int(l) for l in episode_lengths))
@@ -30,13 +31,12 @@ def is_weights_and_kls(preds_old, preds_new, episode_lengths, eps=1e-5, per_step
         if per_step:
             w = (ratio / th.mean(ratio)).clone()
         else:
-            parts = []
-            for length, weight in zip(episode_lengths, normed):
-                parts += [weight] * int(length)
-            w = th.tensor(parts)
+            w = th.repeat_interleave(normed, th.as_tensor(np.asarray(episode_lengths, np.int64)))      # weight j, length j times
         kl_old_new = th.mean(-th.log(prod + eps))
         pm = th.mean(prod)
         kl_new_old = th.mean((prod - pm) * th.log(prod + eps) / (pm + eps))
+    if with_prod:
+        return w, kl_old_new, kl_new_old, prod
     return w, kl_old_new, kl_new_old
 
 
@@ -64,9 +64,15 @@ def cn_loss(net, nominal_batch, expert_batch, is_batch, reg_coeff, eps=1e-5, gai
 
 def cn_train(net, optimizer, iterations, nominal_data, expert_data, episode_lengths, *, reg_coeff=0.0,
              importance_sampling=True, per_step=False, target_kl_old_new=-1, target_kl_new_old=-1,
-             eps=1e-5, gail=False, batch_size=None, factored=False, rng=np.random):
+             eps=1e-5, gail=False, batch_size=None, factored=False, rng=np.random, trace=None):
     """ref: constraint_net.py:155-229 after prepare_data.  nominal_data / expert_data: [N, d] float32 tensors.
-    Returns the ``backward/*`` metrics dict."""
+    Returns the ``backward/*`` metrics dict.
+
+    trace: a list that receives one dict per iteration ENTERED (the stopping one included): ``itr``, ``stopped``, ``kl_old_new`` /
+    ``kl_new_old`` (None without importance sampling), ``is_min`` / ``is_max`` / ``is_mean`` of the weights, ``prod`` (the per-episode
+    products, a float32 array; None without importance sampling) and ``steps``, one dict per optimiser step of the iteration with
+    ``loss``, ``expert_loss``, ``nominal_loss``, ``unweighted_nominal_loss``, ``reg`` and min / max / mean of both sets' predictions.
+    Nothing else changes when it is given."""
     if importance_sampling:
         with th.no_grad():
             start_preds = net.forward(nominal_data).detach()
@@ -76,13 +82,18 @@ def cn_train(net, optimizer, iterations, nominal_data, expert_data, episode_leng
         if importance_sampling:
             with th.no_grad():
                 cur = net.forward(nominal_data).detach()
-            w, kl_on, kl_no = is_weights_and_kls(start_preds.clone(), cur.clone(), episode_lengths, eps, per_step)
-            if (target_kl_old_new != -1 and kl_on > target_kl_old_new) or \
-               (target_kl_new_old != -1 and kl_no > target_kl_new_old):
-                early_stop_itr = itr
-                break
+            w, kl_on, kl_no, prod = is_weights_and_kls(start_preds.clone(), cur.clone(), episode_lengths, eps, per_step, with_prod=True)
+            stop = bool((target_kl_old_new != -1 and kl_on > target_kl_old_new) or
+                        (target_kl_new_old != -1 and kl_no > target_kl_new_old))
         else:
-            w = th.ones(nominal_data.shape[0])
+            w, kl_on, kl_no, prod, stop = th.ones(nominal_data.shape[0]), None, None, None, False
+        if trace is not None:
+            trace.append(dict(itr=itr, stopped=stop, kl_old_new=None if kl_on is None else kl_on.item(),
+                              kl_new_old=None if kl_no is None else kl_no.item(), is_min=th.min(w).item(), is_max=th.max(w).item(),
+                              is_mean=th.mean(w).item(), prod=None if prod is None else prod.numpy().copy(), steps=[]))
+        if stop:
+            early_stop_itr = itr
+            break
         n_nom, n_exp = nominal_data.shape[0], expert_data.shape[0]
         if batch_size is None:
             batches = [(np.arange(n_nom), np.arange(n_exp))]
@@ -97,6 +108,14 @@ def cn_train(net, optimizer, iterations, nominal_data, expert_data, episode_leng
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if trace is not None:
+                with th.no_grad():
+                    trace[-1]["steps"].append(dict(
+                        loss=loss.item(), expert_loss=expert_loss.item(), nominal_loss=nominal_loss.item(),
+                        unweighted_nominal_loss=th.mean(th.log(nominal_preds + eps)).item(), reg=reg.item(),
+                        nominal_preds_max=th.max(nominal_preds).item(), nominal_preds_min=th.min(nominal_preds).item(),
+                        nominal_preds_mean=th.mean(nominal_preds).item(), expert_preds_max=th.max(expert_preds).item(),
+                        expert_preds_min=th.min(expert_preds).item(), expert_preds_mean=th.mean(expert_preds).item()))
     m = {"backward/cn_loss": loss.item(),
          "backward/expert_loss": expert_loss.item(),
          "backward/unweighted_nominal_loss": th.mean(th.log(nominal_preds + eps)).item(),
