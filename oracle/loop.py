@@ -221,7 +221,7 @@ def sync_normalization(train_norm, other_norm):
     other_norm.ret_rms = train_norm.ret_rms.copy()
 
 
-def sample_from_agent(agent, stack1, rollouts, noise=None):
+def sample_from_agent(agent, stack1, rollouts, noise=None, deterministic=False):
     """ref: icrl/utils.py:323-357.  1-env stack; records the observation *after* each step next to the
     action that produced it.  noise: optional [total_steps, act] standard normals."""
     assert stack1.num_envs == 1
@@ -233,7 +233,7 @@ def sample_from_agent(agent, stack1, rollouts, noise=None):
             obs = stack1.reset()
         done, ep_r, ep_l = False, 0.0, 0
         while not done:
-            a = agent.predict(obs, None if noise is None else noise[k:k + 1])
+            a = agent.predict(obs, None if noise is None else noise[k:k + 1], deterministic)
             k += 1
             obs, r, d, _ = stack1.step(a)
             done = bool(d[0])

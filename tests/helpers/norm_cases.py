@@ -94,16 +94,17 @@ _ROLLOUTS = {}
 WIDE_ARCH = [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])]      # -pl 128 96 -rvl 80 128 -cvl 128 128 (icrl/utils.py:636-655)
 
 
-def oracle_buf(kind, N, T, kw, net_arch=None, seed=7, noise_seed=2, rollouts=None, cross_end=True):
+def oracle_buf(kind, N, T, kw, net_arch=None, seed=7, noise_seed=2, rollouts=None, cross_end=True, policy_state=None):
     """One rollout of the oracle port (oracle.loop.PortAgent.collect_rollouts) under the normaliser keywords kw, computed once per
     argument set and shared by every test that asks for it (nothing of it is modified afterwards): policy and constraint net freshly
     initialised under torch seed `seed` (the constraint net first, as the tests' GPU chains draw them), teacher-forced noise
     RandomState(noise_seed).randn([rollouts,] T, N, act)[0]; cross_end: every env starts at limit - T // 2, so that it crosses its time
-    limit inside the rollout.  Returns a dict: buf, norm (the normaliser state after the rollout), policy_sd, cn_sd, noise, start."""
+    limit inside the rollout; policy_state: a name of helpers/policy_states.py, applied to the fresh policy before the rollout (it lands
+    in policy_sd).  Returns a dict: buf, norm (the normaliser state after the rollout), policy_sd, cn_sd, noise, start."""
     import torch
     from helpers.arches import oracle_arch_kwargs
     from oracle import loop as o_loop, nets as o_nets
-    key = (kind, N, T, tuple(sorted(kw.items())), repr(net_arch), seed, noise_seed, rollouts, cross_end)
+    key = (kind, N, T, tuple(sorted(kw.items())), repr(net_arch), seed, noise_seed, rollouts, cross_end, policy_state)
     if key in _ROLLOUTS:
         return _ROLLOUTS[key]
     broken = kind == "antbroken"
@@ -119,6 +120,9 @@ def oracle_buf(kind, N, T, kw, net_arch=None, seed=7, noise_seed=2, rollouts=Non
     stack = o_loop.make_stack(N, ekind, seed, broken=broken, **kw)
     stack.cost_fn = ocn.cost_function
     port = o_loop.PortAgent(stack, n_steps=T, seed=seed, **(oracle_arch_kwargs(net_arch) if net_arch else {}))
+    if policy_state is not None:
+        from helpers import policy_states
+        port.policy.load_state_dict(policy_states.state(policy_state, port.policy.state_dict(), ad))
     out = dict(cn_sd=ocn.state_dict(), policy_sd=port.policy.state_dict(), noise=noise, start=start, port=port)
     port.num_timesteps = 0
     port._last_obs = stack.reset(); port._last_dones = np.zeros(N, bool); port._last_original_obs = stack.old_obs.copy()

@@ -76,21 +76,27 @@ _CASES = {}
 # the stream of the bands is seeded per shape (the same buffer under every hyper-parameter set); a shape whose default seed misses one
 # of the conditions above under one of its sets gets another seed here — never another condition
 BAND_SEEDS = {("hc", "wide", 8, 32, 64, 3): 4}      # (the default seed: ratio margin 4e-4 at step 10 of set B)
+# ... and per (shape, policy state of helpers/policy_states.py, set), found on the CPU (tests/test_policy_state_cpu.py runs check_trace on each)
+STATE_BAND_SEEDS = {("hc", "", 8, 32, 64, 3, "shaped", "B"): 2, ("hc", "", 8, 32, 64, 3, "shaped", "E"): 5, ("hc", "wide", 8, 32, 64, 3, "shaped", "B"): 3,
+                    ("hc", "", 8, 128, 512, 3, "shaped", "A"): 1, ("hc", "", 8, 128, 512, 3, "shaped", "B"): 4,
+                    ("hc", "", 8, 32, 64, 2, "ref", "A"): 1}      # (the default seeds: a ratio margin below 1e-3 at one step)
 
 
-def oracle_case(kind, shape, N, T, B, E, hset, sd0, oracle_kwargs=None, nu=None):
+def oracle_case(kind, shape, N, T, B, E, hset, sd0, oracle_kwargs=None, nu=None, state=None):
     """The banded buffer of one case, the permutations, and the oracle's float32 update on them — computed once per case and shared by
-    every kernel family that runs it (nothing of it is modified afterwards).  sd0: the agent's initial state dict (the same for every agent
+    every kernel family that runs it (nothing of it is modified afterwards).  state: the name of the policy state sd0 is in (part of the cache
+    key and of the band seed's).  sd0: the agent's initial state dict (the same for every agent
     of a case: seed 0); returns a dict with buf, perms, hp, lr, out (the train/* scalars), params (after the update), trace."""
-    key = (kind, shape, N, T, B, E, hset)
+    key = (kind, shape, N, T, B, E, hset, state)
     hit = _CASES.get(key)
-    if hit is not None and all(np.array_equal(hit["sd0"][k], _np(v)) for k, v in sd0.items()):
+    if hit is not None and hit["nu"] == nu and all(np.array_equal(hit["sd0"][k], _np(v)) for k, v in sd0.items()):
         return hit
     hp = hparams(hset)
     od, ad = {"hc": (18, 6), "ant": (113, 8)}[kind]
     lr = 3e-4 if kind == "hc" else 3e-5
     rng = np.random.RandomState(N * T)                  # observations, advantages, returns, permutations: as test_train_vs_oracle draws them
-    brng = np.random.RandomState(BAND_SEEDS.get((kind, shape, N, T, B, E), 7919 + N * T + B))      # the bands
+    seed = BAND_SEEDS.get((kind, shape, N, T, B, E), 7919 + N * T + B)
+    brng = np.random.RandomState(seed if state is None else STATE_BAND_SEEDS.get((kind, shape, N, T, B, E, state, hset), seed))      # the bands
     op = o_nets.TwoCriticPolicy(od, ad, **(oracle_kwargs or {}))
     op.load_state_dict(sd0)
     obs = rng.randn(T, N, od).astype(np.float32)
@@ -108,7 +114,7 @@ def oracle_case(kind, shape, N, T, B, E, hset, sd0, oracle_kwargs=None, nu=None)
     opt = torch.optim.Adam(op.parameters(), lr=lr, eps=1e-5)
     trace = []
     out = o_ppo.ppo_lag_train(op, opt, buf, perms, nu, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=None, trace=trace, **hp)
-    case = dict(sd0={k: _np(v).copy() for k, v in sd0.items()}, buf=buf, perms=perms, hp=hp, lr=lr, out=out, trace=trace,
+    case = dict(sd0={k: _np(v).copy() for k, v in sd0.items()}, buf=buf, perms=perms, hp=hp, lr=lr, nu=nu, out=out, trace=trace,
                 params={k: p.detach().numpy().copy() for k, p in op.params.items()})
     _CASES[key] = case
     return case

@@ -86,8 +86,12 @@ def _received_actions(e_h):
     ("hc", 8, 16, False, True, False),                      # no cost wrapper (the GAIL chain)
     ("hc", 4, 16, True, True, True),                        # SubprocVecEnv through the host path
 ])
-def test_host_rollout_equals_device_rollout(kind, N, T, cost, norm, subproc, norm_kwargs=None):
+def test_host_rollout_equals_device_rollout(kind, N, T, cost, norm, subproc, norm_kwargs=None, policy_state=None):
     (a_d, e_d), (a_h, e_h) = _agents(kind, N, T, cost=cost, norm=norm, subproc=subproc, norm_kwargs=norm_kwargs)
+    if policy_state is not None:      # a named state of helpers/policy_states.py on top of the fresh policy, in both chains
+        from helpers import policy_states
+        sd = policy_states.state(policy_state, a_d.policy.state_dict(), a_d.policy.act_dim)
+        a_d.policy.load_state_dict(sd); a_h.policy.load_state_dict(sd)
     noise = _noise(kind, N, T)
     a_d._setup_learn(2 * N * T); a_h._setup_learn(2 * N * T)
     limit = e_d.unwrapped.max_steps

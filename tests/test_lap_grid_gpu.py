@@ -102,7 +102,7 @@ def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     _categorical_case(O, A, N, T, B, E, ent, wide)
 
 
-def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None):
+def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None):
     """one Categorical update against the oracle's epoch loop; hset: a hyper-parameter set of helpers/ppo_hparam_cases.py on a banded buffer."""
     from helpers import ppo_hparam_cases as H
     hp = {} if hset is None else {k: v for k, v in H.hparams(hset).items() if k != "ent_coef"}
@@ -120,10 +120,17 @@ def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None):
     agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0, batch_size=B, n_epochs=E, target_kl=None, ent_coef=ent, **hp, **akw)
     sd0 = agent.policy.state_dict()
     assert "log_std" not in sd0 and agent.policy.wide == bool(wide)
+    if head_scale is not None:      # a peaked categorical head (helpers/policy_states.py: LGW_K)
+        sd0["action_net.weight"] = sd0["action_net.weight"] * head_scale
+        agent.policy.load_state_dict(sd0)
     okw = oracle_arch_kwargs(net_arch) if wide else {}
     op = o_nets.TwoCriticPolicy(O, A, discrete=True, **okw)
     op.load_state_dict(sd0)
     obs = rng.randn(T, N, O).astype(np.float32)
+    if head_scale is not None:      # the condition on the inputs, from the oracle: rows with a near-certain class and rows without a favourite
+        from helpers import policy_states
+        hi, lo = policy_states.lgw_shares(op, obs.reshape(-1, O))
+        assert hi >= policy_states.LGW_SHARE and lo >= policy_states.LGW_SHARE, (hi, lo)
     with torch.no_grad():
         a, vr, vc, lp = op.forward(torch.as_tensor(obs.reshape(-1, O)), noise=torch.as_tensor(rng.rand(T * N).astype(np.float32)))
     assert len(np.unique(a.numpy())) == A or A > 8

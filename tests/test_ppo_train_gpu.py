@@ -210,7 +210,7 @@ def _hp_cases():
 
 
 @pytest.mark.parametrize("kind,N,T,B,E,hset,train_kernel", _hp_cases())
-def test_train_hparams_vs_oracle(kind, N, T, B, E, hset, train_kernel):
+def test_train_hparams_vs_oracle(kind, N, T, B, E, hset, train_kernel, policy_state=None):
     """Value clipping of both critics, the DiagGaussian entropy bonus (with its -ent_coef on log_std), separate weights of the two critics
     and both branches of the global-norm clip (ref: ppo_lag.py:243-288), plus the ratio clip at clip_fraction ~ 0.6, through every update
     kernel against the oracle's epoch loop — on a buffer built in bands (helpers/ppo_hparam_cases.py) so that no row sits on a kink of a
@@ -226,15 +226,19 @@ def test_train_hparams_vs_oracle(kind, N, T, B, E, hset, train_kernel):
     agent = _agent(kind, N, T, batch_size=B, n_epochs=E, target_kl=None, learning_rate=lr, clip_range=0.2, **hp, **akw)
     if train_kernel is not None:
         agent.train_kernel = train_kernel
+    if policy_state is not None:      # a named state of helpers/policy_states.py on top of the fresh policy
+        from helpers import policy_states
+        agent.policy.load_state_dict(policy_states.state(policy_state, agent.policy.state_dict(), agent.policy.act_dim))
     case = H.oracle_case(kind, shape, N, T, B, E, hset, agent.policy.state_dict(), oracle_kwargs=oracle_arch_kwargs(net_arch) if net_arch is not None else {},
-                         nu=agent.dual.nu().item())
+                         nu=agent.dual.nu().item(), state=policy_state)
     H.check_trace(case["trace"], hp, n_steps=E * (-(-N * T // B)))
     _fill(agent, case["buf"])
     from icrl_amd import logger
     logger.configure()                 # (an empty log: keys of an earlier test's agent do not count)
     agent.train(perms=case["perms"])
     rel = _compare_with_oracle(agent, case["params"], case["out"], kind, B, lr)
-    print(f"ADAM_DEV_HP {kind}{'-' + shape if shape else ''} {N}x{T} B={B} E={E} set {hset} kernel {train_kernel or 'default'}: {rel:.3g} x lr x steps")
+    print(f"ADAM_DEV_HP {kind}{'-' + shape if shape else ''} {N}x{T} B={B} E={E} set {hset} kernel {train_kernel or 'default'} state {policy_state or 'fresh'}: "
+          f"{rel:.3g} x lr x steps = {rel / ADAM_DEV_BOUND:.3f} of the bound")
     lg = logger.Logger.CURRENT.name_to_value
     for key in ("clip_range_reward_vf", "clip_range_cost_vf"):       # ref: ppo_lag.py:335-338 — logged when set, and only then
         if hp[key] is None:

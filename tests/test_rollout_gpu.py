@@ -250,7 +250,7 @@ def test_fused_rollout_vs_port(kind, N, T, kernel):
     assert env.obs_rms.count == stack.norm.obs_rms.count
 
 
-def _pair_of_agents(N, T, seed, kind="hc", broken=False, cn_kwargs=None, hid=None, agent_kwargs=None, norm_kwargs=None):
+def _pair_of_agents(N, T, seed, kind="hc", broken=False, cn_kwargs=None, hid=None, agent_kwargs=None, norm_kwargs=None, policy_state=None):
     from icrl_amd.ppo_lag import PPOLagrangian
     from icrl_amd.vec_env import HipSynthVecEnv, VecCostWrapper, VecNormalizeWithCost
     from icrl_amd.constraint_net import ConstraintNet
@@ -266,6 +266,9 @@ def _pair_of_agents(N, T, seed, kind="hc", broken=False, cn_kwargs=None, hid=Non
         env.set_cost_function(cn.cost_function)
         out.append((PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=seed, **(agent_kwargs or {})), env, cn))
     out[1][2].load_state_dict(out[0][2].state_dict())
+    if policy_state is not None:      # a named state of helpers/policy_states.py on top of the fresh policy
+        from helpers import policy_states
+        out[0][0].policy.load_state_dict(policy_states.state(policy_state, out[0][0].policy.state_dict(), ad))
     out[1][0].policy.load_state_dict(out[0][0].policy.state_dict())
     return out
 
@@ -294,7 +297,7 @@ def test_stepped_rollout_equals_fused_rollout():
 
 @pytest.mark.parametrize("kind,shape,N", [("hc", "wide", 12), ("hc", "trunk", 12), ("ant", "deep", 12), ("hc", "wide-cn", 12), ("ant", "deep-cn", 12), ("hc", "both", 12),
                                           ("hc", "trunk", 64), ("ant", "deep", 33)])
-def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=None):
+def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=None, policy_state=None):
     """policies / constraint nets of the generic-shape path (layers above 64 units, shared trunk, other depths): icrl_rollout_collect runs the
     whole rollout as ONE persistent launch (rollout_generic_kernel: the one-workgroup-per-env loop around the table-driven forward with four
     units per lane) — or, for a constraint net beyond the register image, the reference's per-step loop as four launches per step —
@@ -305,7 +308,7 @@ def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=No
     net_arch = {"wide": [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])], "both": [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])]}.get(shape, ARCHES.get(shape))
     hid = {"wide-cn": [128, 100], "deep-cn": [48, 32, 24], "both": [64, 64, 64]}.get(shape)
     akw = dict(policy_kwargs=dict(net_arch=net_arch)) if net_arch else None
-    (a_f, e_f, c_f), (a_s, e_s, _) = _pair_of_agents(N, T, 11, kind=kind, hid=hid, agent_kwargs=akw, norm_kwargs=norm_kwargs)
+    (a_f, e_f, c_f), (a_s, e_s, _) = _pair_of_agents(N, T, 11, kind=kind, hid=hid, agent_kwargs=akw, norm_kwargs=norm_kwargs, policy_state=policy_state)
     assert a_f.policy.wide == (net_arch is not None) and c_f.wide == (hid is not None) and a_f._fused_chain() is not None
     ad = 6 if kind == "hc" else 8
     noise = torch.as_tensor(np.random.RandomState(3).randn(2, T, N, ad).astype(np.float32), device="cuda")
@@ -382,14 +385,14 @@ def test_analytic_env_cost_through_cost_wrapper():
 # shards of BASELINE configs[3], [2] and [4].
 @pytest.mark.parametrize("kind,N,T", [("hc", 64, 300), ("hc", 7, 33), ("hc", 128, 20), ("hc", 256, 40), ("hc", 130, 24), ("ant", 256, 12),
                                       ("antbroken", 512, 10), ("hc", 1000, 6)])
-def test_persistent_rollout_equals_per_step_launches(kind, N, T, kernel="auto", cn_kwargs=None, norm_kwargs=None):
+def test_persistent_rollout_equals_per_step_launches(kind, N, T, kernel="auto", cn_kwargs=None, norm_kwargs=None, policy_state=None):
     """the one-launch rollout (device-wide exchange per step inside the kernel) against the launch pair per
     step: every buffer plane, the normaliser state and the agent's carry-over state are bit-identical, across two
     consecutive rollouts and across episode ends."""
     ekind = "ant" if kind == "antbroken" else kind
     ad = 6 if ekind == "hc" else 8
     limit = 1000 if ekind == "hc" else 500
-    (a_p, e_p, _), (a_s, e_s, _) = _pair_of_agents(N, T, 13, ekind, broken=kind == "antbroken", cn_kwargs=cn_kwargs, norm_kwargs=norm_kwargs)
+    (a_p, e_p, _), (a_s, e_s, _) = _pair_of_agents(N, T, 13, ekind, broken=kind == "antbroken", cn_kwargs=cn_kwargs, norm_kwargs=norm_kwargs, policy_state=policy_state)
     a_s.rollout_kernel = "steps"
     a_p.rollout_kernel = kernel
     noise = torch.as_tensor(np.random.RandomState(8).randn(2, T, N, ad).astype(np.float32), device="cuda")
