@@ -4108,6 +4108,10 @@ extern "C" int icrl_debug_rollout_profile(unsigned long long* out4) {
   return (int)hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_rollout_prof), sizeof(unsigned long long) * 8);
 }
 
+// =================================================================================================================
+// launch layer of the fused rollouts: kernel choice, exchange workspaces, argument builder, launchers, GAE tails
+// =================================================================================================================
+
 // all N workgroups of the persistent rollout must be co-resident (they wait for each other every step): ask the runtime
 // how many blocks of this kernel one CU takes.  The answer is advisory (MI355X_MICROARCH.md: it can read one high for
 // SGPR-heavy kernels), hence the bounded spins + status word as the backstop.
@@ -4136,85 +4140,217 @@ static bool multi_shape(int N, int n_stats, int* E, int* G) {
   return *G >= gmin;
 }
 
-template <int OCT, int CIT, int E, bool MON>
-static int launch_multi_e(const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
-  if (one != nullptr) {
-    if (!persistent_fits(rollout_multi_kernel<OCT, CIT, E, MON>, G, dyn)) return -1;
-    WideArgs arg = *one;
-    static const bool no_pack = getenv("ICRL_NO_XCD_PACK") != nullptr;
-    const int packed = !no_pack && arg.xcc != nullptr && G <= 32;
-    void* params[] = {(void*)&arg, (void*)&packed};
-    const hipError_t e = hipLaunchCooperativeKernel((const void*)rollout_multi_kernel<OCT, CIT, E, MON>, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
-    if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
-    return (int)e;
-  } else {
-    if (!persistent_fits(rollout_multi_batch_kernel<OCT, CIT, E, MON>, G, dyn)) return -1;
-    // packed layout (a run's G workgroups on ONE XCD: workgroups b, b + 8, ...) when every XCD can hold its share of the grid at once
-    // (32 CUs each); otherwise run-major, whose runs become resident oldest first
-    int per_cu = 0;
-    const int groups = (n_runs + 7) / 8;
-    static const bool no_pack_b = getenv("ICRL_NO_XCD_PACK") != nullptr;
-    const bool packed = !no_pack_b && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_multi_batch_kernel<OCT, CIT, E, MON>, 256, dyn) == hipSuccess &&
-                        groups * G <= 32 * per_cu;
-    if (packed) hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E, MON>), dim3(8 * G * ((n_runs + 7) / 8)), dim3(256), dyn, s, d_args, n_runs, G, 1);
-    else hipLaunchKernelGGL((rollout_multi_batch_kernel<OCT, CIT, E, MON>), dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
+// ---- which instantiation serves a shape.  One function per kernel family, used for the occupancy query and for the launch alike:
+// each hands the chosen kernel to `f` and returns what `f` returns.  Together they name exactly the instantiations the library
+// ships.  What is not listed (phase timers with a monitor plane or an analytic cost, MINW 2 / 3 outside small + granules, <8, 8>
+// outside the multi kernels) does not exist, and the `if constexpr`s keep it that way: every instantiation costs compile time.
+struct KernelPick {
+  bool small = false;      // small_shape(): the <2, .> register images, else <8, .>
+  bool analytic = false;   // an icrl_cost_fn_t behind the cost pointer: CIT == 0 (no cost-net register image), no phase timers
+  bool mon = false;        // the instantiations that store the raw-reward plane (ActStepArgs.raw_plane); no phase timers
+  bool cn128 = false;      // multi kernels: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
+  bool gran = false;       // one-workgroup-per-env kernels: granule mode (N (2 obs + 4) <= 256 GRAN_MAX)
+  bool prof = false;       // tools: the instantiations with the phase timers (do_gae bits 2 / 3)
+  int E = 0;               // multi kernels: envs per workgroup (multi_shape)
+  int minw = 1;            // batched one-workgroup-per-env kernels: workgroups per CU the register allocation leaves room for
+};
+template <int OCT, int CIT> struct Image { static constexpr int oct = OCT, cit = CIT; };
+template <int V> struct Int { static constexpr int value = V; };
+template <bool V> struct Flag { static constexpr bool value = V; };
+template <class F> static int with_flag(bool b, F&& f) { return b ? f(Flag<true>{}) : f(Flag<false>{}); }
+
+// observations of <= 32 columns beside a cost net of <= 32 inputs.  `net` is the constraint net proper: NULL without a cost and NULL
+// for an analytic cost, which has no inputs to count
+static bool small_shape(int O, const icrl_costnet_t* net) { return O <= 32 && (net == nullptr || net->in_dim <= 32); }
+
+// the register images <OCT, CIT> (k steps of the policy / cost-net first layers held in registers); CN128: the family has the <8, 8> image
+template <bool CN128 = false, class F>
+static int with_image(const KernelPick& k, F&& f) {
+  if (k.analytic) return k.small ? f(Image<2, 0>{}) : f(Image<8, 0>{});
+  if (k.small) return f(Image<2, 2>{});
+  if constexpr (CN128) {
+    if (k.cn128) return f(Image<8, 8>{});
   }
-  return (int)hipGetLastError();
+  return f(Image<8, 10>{});
 }
 
-// one: single-run launch (argument block by value) | d_args: n_runs blocks in device memory.  -1: does not fit the device
-// the analytic-cost kernels (rollout_multi_analytic_kernel), single-run launches only: launch_multi_e's first branch
-template <int OCT, int E, bool MON>
-static int launch_multi_fn_e(const WideArgs* one, int G, size_t dyn, hipStream_t s) {
-  if (!persistent_fits(rollout_multi_analytic_kernel<OCT, E, MON>, G, dyn)) return -1;
-  WideArgs arg = *one;
+template <class F> static int with_act_step_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return f(act_step_kernel<decltype(im)::oct, decltype(im)::cit>); });
+}
+template <class F> static int with_host_step_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return f(host_step_kernel<decltype(im)::oct, decltype(im)::cit>); });
+}
+template <class F> static int with_generic_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    return k.mon ? f(rollout_generic_kernel<OCT, CIT, true>) : f(rollout_generic_kernel<OCT, CIT>);
+  });
+}
+template <class F> static int with_persistent_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return with_flag(k.gran, [&](auto gran) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    constexpr bool GRAN = decltype(gran)::value;
+    if (k.mon) return f(rollout_persistent_kernel<OCT, CIT, GRAN, false, true>);
+    if constexpr (CIT != 0) {
+      if (k.prof) return f(rollout_persistent_kernel<OCT, CIT, GRAN, true>);
+    }
+    return f(rollout_persistent_kernel<OCT, CIT, GRAN>);
+  }); });
+}
+template <class F> static int with_wide_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    if (k.mon) return f(rollout_wide_kernel<OCT, CIT, false, true>);
+    if constexpr (CIT != 0) {
+      if (k.prof) return f(rollout_wide_kernel<OCT, CIT, true>);
+    }
+    return f(rollout_wide_kernel<OCT, CIT>);
+  });
+}
+// registers: the narrow (HC-width) kernel leaves room for several workgroups per CU, so that several runs of the grid are resident
+// together: MINW 1 | 2 | 3 with small + granules, 2 with small alone, 1 at the wide widths
+template <class F> static int with_persistent_batch_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return with_flag(k.mon, [&](auto mon) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    constexpr bool MON = decltype(mon)::value;
+    auto kernel = [&](auto gran, auto minw) {      // (the analytic cost: a kernel of its own name, see there)
+      constexpr bool GRAN = decltype(gran)::value;
+      constexpr int MINW = decltype(minw)::value;
+      if constexpr (CIT == 0) return f(rollout_persistent_batch_analytic_kernel<OCT, GRAN, MINW, MON>);
+      else return f(rollout_persistent_batch_kernel<OCT, CIT, GRAN, MINW, MON>);
+    };
+    if constexpr (OCT == 2) {
+      if (!k.gran) return kernel(Flag<false>{}, Int<2>{});
+      return k.minw >= 3 ? kernel(Flag<true>{}, Int<3>{}) : (k.minw == 2 ? kernel(Flag<true>{}, Int<2>{}) : kernel(Flag<true>{}, Int<1>{}));
+    } else {
+      return k.gran ? kernel(Flag<true>{}, Int<1>{}) : kernel(Flag<false>{}, Int<1>{});
+    }
+  }); });
+}
+// BATCH: the kernels that read n_runs argument blocks from device memory
+template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k, F&& f) {
+  return with_image<true>(k, [&](auto im) { return with_flag(k.mon, [&](auto mon) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    constexpr bool MON = decltype(mon)::value;
+    auto kernel = [&](auto e) {      // (the analytic cost: kernels of their own names, see there)
+      constexpr int E = decltype(e)::value;
+      if constexpr (BATCH && CIT == 0) return f(rollout_multi_batch_analytic_kernel<OCT, E, MON>);
+      else if constexpr (BATCH) return f(rollout_multi_batch_kernel<OCT, CIT, E, MON>);
+      else if constexpr (CIT == 0) return f(rollout_multi_analytic_kernel<OCT, E, MON>);
+      else return f(rollout_multi_kernel<OCT, CIT, E, MON>);
+    };
+    return k.E == 16 ? kernel(Int<16>{}) : (k.E == 8 ? kernel(Int<8>{}) : kernel(Int<4>{}));
+  }); });
+}
+
+// ---- exchange workspaces.  A run's workspace is the agent's xch_ws when that holds `need` bytes, else the not yet computed
+// reward_advantages plane of the buffer (GAE fills it afterwards), else NULL: the route is then not taken.
+static char* exchange_ws(const icrl_agent_t* ag, const icrl_buffer_t* buf, size_t need) {
+  if (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) return reinterpret_cast<char*>(ag->xch_ws);
+  return (size_t)buf->T * buf->N * sizeof(float) >= need ? reinterpret_cast<char*>(buf->reward_advantages) : nullptr;
+}
+
+// one-workgroup-per-env kernels (PersistArgs):  xch_obs | xch_rew | xch_cost | xch_done (to 256 B) | counter (512 B) | xg (granule mode)
+// = 48 N O + 96 N + 1024 bytes at most.  persist_ws_carve returns the bytes to clear from p.counter on.
+static size_t persist_ws_bytes(int N, int O, bool gran) {
+  return (size_t)16 * N * O + (size_t)16 * N + (size_t)8 * N + (size_t)8 * N + 1024 + (gran ? (size_t)16 * N * (2 * O + 4) : 0);
+}
+static size_t persist_ws_carve(char* ws, int N, int O, bool gran, PersistArgs& p) {
+  const int G = 2 * O + 4;
+  char* base = ws;
+  p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
+  p.xch_rew = reinterpret_cast<double*>(base); base += (size_t)16 * N;
+  p.xch_cost = reinterpret_cast<float*>(base); base += (size_t)8 * N;
+  p.xch_done = reinterpret_cast<unsigned*>(base); base += ((size_t)8 * N + 255) / 256 * 256;
+  p.counter = reinterpret_cast<unsigned*>(base); base += 512;
+  p.xg = reinterpret_cast<unsigned long long*>(base);
+  p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G / 2));      // index split by the records per env (obs + 2)
+  return 512 + (gran ? (size_t)16 * N * G : 0);
+}
+
+// statistics partitioned by column (WideArgs: the wide and the multi kernels):  xg [2][N][2 O + 4] | sg [2][4 O + 4] | 256 spare bytes
+// = 32 N O + 64 N + 64 O + 320 bytes.  with_xcc: the multi kernels' XCD ids (G <= 32 words) in the spare bytes.  wide_ws_carve
+// returns the bytes to clear from p.xg on.
+// Both layouts stay below ICRL_ROLLOUT_WS_BYTES(N, obs) = 48 N O + 96 N + 64 O + 2048, which the header promises for either.
+static size_t wide_ws_bytes(int N, int O) { return 16 * (size_t)N * (2 * (size_t)O + 4) + 16 * (4 * (size_t)O + 4) + 256; }
+static size_t wide_ws_carve(char* ws, int N, int O, bool with_xcc, WideArgs& p) {
+  const size_t GX = 2 * (size_t)O + 4, GS = 4 * (size_t)O + 4;
+  p.xg = reinterpret_cast<unsigned long long*>(ws);
+  p.sg = p.xg + 2 * (size_t)N * GX;
+  p.xcc = with_xcc ? p.sg + 2 * GS : nullptr;
+  return 16 * (size_t)N * GX + 16 * GS + (p.xcc ? 256 : 0);
+}
+
+// ---- the argument block every rollout kernel starts from.  env NULL: the caller fills a.env (host envs).  net | cf: the constraint net
+// or the analytic cost, at most one of them.  table_forward: the generic-shape kernel, which reads only obs / act / discrete of the layout.
+static void fill_act_args(ActStepArgs& a, const icrl_env_t* env, const icrl_buffer_t* buf, const icrl_agent_t* ag, const icrl_policy_t* pol,
+                          bool table_forward, const icrl_costnet_t* net, const icrl_cost_fn_t* cf, const float* noise, const float* action_low,
+                          const float* action_high, double* raw_plane) {
+  if (env != nullptr) a.env = *env;
+  a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
+  a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, table_forward ? MAX_H : pol->h1, table_forward ? MAX_H : pol->h2, pol->discrete);
+  a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
+  a.has_cn = net != nullptr || cf != nullptr;
+  if (net) { a.cn = *net; a.cl = make_cn_layout(net->in_dim, net->n_hidden, net->h1, net->h2); }
+  else if (cf) a.cf = *cf;
+}
+
+// ---- launchers.  -1: the grid cannot be co-resident on this device (the caller tries its next route)
+static bool xcd_pack() {
   static const bool no_pack = getenv("ICRL_NO_XCD_PACK") != nullptr;
-  const int packed = !no_pack && arg.xcc != nullptr && G <= 32;
-  void* params[] = {(void*)&arg, (void*)&packed};
-  const hipError_t e = hipLaunchCooperativeKernel((const void*)rollout_multi_analytic_kernel<OCT, E, MON>, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
+  return !no_pack;
+}
+
+// single run, one workgroup per env
+template <class K, class A>
+static int launch_per_env(K kernel, int N, size_t dyn, hipStream_t s, A& args) {
+  if (!persistent_fits(kernel, N, dyn)) return -1;
+  const hipError_t e = launch_coresident(kernel, dim3(N), dim3(256), dyn, s, args);
   if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
   return (int)e;
 }
-template <bool MON>
-static int launch_multi_fn(bool small, int E, const WideArgs* one, int G, size_t dyn, hipStream_t s) {
-  if (small) return E == 16 ? launch_multi_fn_e<2, 16, MON>(one, G, dyn, s) : (E == 8 ? launch_multi_fn_e<2, 8, MON>(one, G, dyn, s) : launch_multi_fn_e<2, 4, MON>(one, G, dyn, s));
-  return E == 16 ? launch_multi_fn_e<8, 16, MON>(one, G, dyn, s) : (E == 8 ? launch_multi_fn_e<8, 8, MON>(one, G, dyn, s) : launch_multi_fn_e<8, 4, MON>(one, G, dyn, s));
+
+// single run of a multi kernel: G workgroups, or (packed) workgroups 0, 8, 16, ... of 8 (G - 1) + 1 so that all G sit on one XCD
+template <class K>
+static int launch_multi_run(K kernel, WideArgs& p, int G, size_t dyn, hipStream_t s) {
+  if (!persistent_fits(kernel, G, dyn)) return -1;
+  const int packed = xcd_pack() && p.xcc != nullptr && G <= 32;
+  void* params[] = {(void*)&p, (void*)&packed};
+  const hipError_t e = hipLaunchCooperativeKernel((const void*)kernel, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
+  if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
+  return (int)e;
 }
 
-// the batched analytic-cost kernels (rollout_multi_batch_analytic_kernel): launch_multi_e's second branch
-template <int OCT, int E, bool MON>
-static int launch_multi_batch_fn_e(const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
-  if (!persistent_fits(rollout_multi_batch_analytic_kernel<OCT, E, MON>, G, dyn)) return -1;
+// n_runs runs of a multi kernel, argument blocks in device memory
+template <class K>
+static int launch_multi_runs(K kernel, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+  if (!persistent_fits(kernel, G, dyn)) return -1;
+  // packed layout (a run's G workgroups on ONE XCD: workgroups b, b + 8, ...) when every XCD can hold its share of the grid at once
+  // (32 CUs each); otherwise run-major, whose runs become resident oldest first
   int per_cu = 0;
   const int groups = (n_runs + 7) / 8;
-  static const bool no_pack_b = getenv("ICRL_NO_XCD_PACK") != nullptr;
-  const bool packed = !no_pack_b && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rollout_multi_batch_analytic_kernel<OCT, E, MON>, 256, dyn) == hipSuccess &&
-                      groups * G <= 32 * per_cu;
-  if (packed) hipLaunchKernelGGL((rollout_multi_batch_analytic_kernel<OCT, E, MON>), dim3(8 * G * ((n_runs + 7) / 8)), dim3(256), dyn, s, d_args, n_runs, G, 1);
-  else hipLaunchKernelGGL((rollout_multi_batch_analytic_kernel<OCT, E, MON>), dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
+  const bool packed = xcd_pack() && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, dyn) == hipSuccess && groups * G <= 32 * per_cu;
+  if (packed) hipLaunchKernelGGL(kernel, dim3(8 * G * groups), dim3(256), dyn, s, d_args, n_runs, G, 1);
+  else hipLaunchKernelGGL(kernel, dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
   return (int)hipGetLastError();
 }
-template <bool MON>
-static int launch_multi_batch_fn(bool small, int E, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
-  if (small) return E == 16 ? launch_multi_batch_fn_e<2, 16, MON>(d_args, n_runs, G, dyn, s) : (E == 8 ? launch_multi_batch_fn_e<2, 8, MON>(d_args, n_runs, G, dyn, s) : launch_multi_batch_fn_e<2, 4, MON>(d_args, n_runs, G, dyn, s));
-  return E == 16 ? launch_multi_batch_fn_e<8, 16, MON>(d_args, n_runs, G, dyn, s) : (E == 8 ? launch_multi_batch_fn_e<8, 8, MON>(d_args, n_runs, G, dyn, s) : launch_multi_batch_fn_e<8, 4, MON>(d_args, n_runs, G, dyn, s));
-}
 
-template <bool MON>
-static int launch_multi_m(bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
-  // cn128: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
-  if (!small && cn128)
-    return E == 16 ? launch_multi_e<8, 8, 16, MON>(one, d_args, n_runs, G, dyn, s)
-           : (E == 8 ? launch_multi_e<8, 8, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 8, 4, MON>(one, d_args, n_runs, G, dyn, s));
-  if (small) return E == 16 ? launch_multi_e<2, 2, 16, MON>(one, d_args, n_runs, G, dyn, s)
-                    : (E == 8 ? launch_multi_e<2, 2, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<2, 2, 4, MON>(one, d_args, n_runs, G, dyn, s));
-  return E == 16 ? launch_multi_e<8, 10, 16, MON>(one, d_args, n_runs, G, dyn, s)
-         : (E == 8 ? launch_multi_e<8, 10, 8, MON>(one, d_args, n_runs, G, dyn, s) : launch_multi_e<8, 10, 4, MON>(one, d_args, n_runs, G, dyn, s));
+// ---- tails: the dual GAE behind a rollout (do_gae bit 0), or the rollout's error
+static int finish_with_gae(int err, int do_gae, const icrl_buffer_t* buf, const icrl_agent_t* ag, double reward_gamma, double reward_gae_lambda,
+                           double cost_gamma, double cost_gae_lambda, void* stream) {
+  if (err || !(do_gae & 1)) return err;
+  return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r, ag->last_v_c,
+                          ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns, buf->cost_returns, buf->T, buf->N,
+                          reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws, buf->gae_ws_bytes, stream);
 }
-
-// mon: the instantiations that store the raw-reward plane (ActStepArgs.raw_plane is set in every argument block)
-static int launch_multi(bool mon, bool small, bool cn128, int E, const WideArgs* one, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
-  return mon ? launch_multi_m<true>(small, cn128, E, one, d_args, n_runs, G, dyn, s) : launch_multi_m<false>(small, cn128, E, one, d_args, n_runs, G, dyn, s);
+// dual GAE of every run in one launch; its argument blocks go behind the rollout's in args_ws (both launches are in flight together)
+static int finish_batch_with_gae(int err, int do_gae, int n_runs, const icrl_rollout_job_t* jobs, double reward_gamma, double reward_gae_lambda,
+                                 double cost_gamma, double cost_gae_lambda, void* args_ws, long long args_ws_bytes, void* stream) {
+  if (err || !(do_gae & 1)) return err;
+  if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
+    return fail("icrl_rollout_collect_batch: args_ws needs 2 x n_runs x ICRL_BATCH_ARGS_BYTES = %lld B when the GAE launch is included", 2ll * n_runs * ICRL_BATCH_ARGS_BYTES);
+  return icrl_gae_dual_batch_impl(n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda,
+                                  (char*)args_ws + (size_t)n_runs * ICRL_BATCH_ARGS_BYTES, stream);
 }
 
 // the raw-reward plane of a monitor descriptor (NULL descriptor: no plane, the kernels then store nothing extra)
@@ -4226,6 +4362,18 @@ static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane)
   return 0;
 }
 
+// Routes of a single run, in the order they are tried (-1 from a launcher, a refused cooperative launch or a missing workspace: the next one):
+//   generic persistent   layers above 64 units / `arch`, cost net within the register image, !(do_gae & 2), N <= 128, N obs <= 4096,
+//                        granule mode, transposed weights                                      rollout_generic_kernel
+//   generic per-step     every other generic shape: four launches per step                      policy_generic | cn_cost_rows | act_step_generic | norm_step
+//   multi                do_gae & 32 or N > 1024; !(do_gae & 2), training, Box actions, multi_shape, workspace      rollout_multi[_analytic]_kernel
+//   wide                 !(do_gae & 2), training, N > 96 or N obs > 4096 or do_gae & 16, N <= 1024, <= WIDE_E envs per workgroup,
+//                        grid >= obs + 2, workspace                                             rollout_wide_kernel
+//   persistent           !(do_gae & 2), N <= 128, N obs <= 4096, workspace                      rollout_persistent_kernel
+//   per-step             everything else: two launches per step                                 act_step_kernel | norm_step
+// Routes of a batch (rollout_collect_batch_impl):
+//   multi                !ICRL_BATCH_NO_MULTI, not `few`, Box actions, training, multi_shape, every run has a workspace      rollout_multi_batch[_analytic]_kernel
+//   persistent           N <= 128, N obs <= 4096 (else refused)                                 rollout_persistent_batch[_analytic]_kernel
 extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol,
                                            const icrl_costnet_t* cn_arg, const icrl_buffer_t* buf, const icrl_agent_t* ag,
                                            const float* noise, const float* action_low, const float* action_high,
@@ -4250,6 +4398,9 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
     return fail("icrl_rollout_collect: %d envs on one GPU, limit %d (shard the envs over ranks: the float64 normaliser statistics are one "
                 "numpy-ordered chain per column)", N, NORM_MAX_N);
   hipStream_t s = (hipStream_t)stream;
+  KernelPick k;
+  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.mon = raw_plane != nullptr;
+  auto finish = [&](int err) { return finish_with_gae(err, do_gae, buf, ag, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, stream); };
   if (generic) {
     // a policy with layers above 64 units / an `arch` descriptor, or a constraint net above 64 units / two layers: the reference's
     // per-step loop as four launches per step on this stream — policy_generic_kernel (generic.hip), cn_cost_rows_kernel (cn_train.hip),
@@ -4266,53 +4417,17 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       GenRolloutArgs ga;
       if (int e = make_gen_net(pol, &ga.net, "icrl_rollout_collect")) return e;
       ga.P = pol->params;
-      const int G2 = 2 * O + 4;
-      const size_t need = (size_t)16 * N * O + (size_t)16 * N + (size_t)8 * N + (size_t)8 * N + 1024 + (size_t)16 * N * G2;
-      char* ws = (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) ? reinterpret_cast<char*>(ag->xch_ws)
-                 : ((size_t)T * N * sizeof(float) >= need ? reinterpret_cast<char*>(buf->reward_advantages) : nullptr);
+      char* ws = exchange_ws(ag, buf, persist_ws_bytes(N, O, true));      // (granule mode: the condition above)
       if (ws != nullptr) {
         PersistArgs& p = ga.p;
-        ActStepArgs& a = p.act;
-        a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
-        a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, MAX_H, MAX_H, pol->discrete);      // (only obs / act / discrete are read)
-        a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
-        a.has_cn = cn;
-        if (net) { a.cn = *net; a.cl = make_cn_layout(net->in_dim, net->n_hidden, net->h1, net->h2); }
-        else if (cf) a.cf = *cf;
+        fill_act_args(p.act, env, buf, ag, pol, true, net, cf, noise, action_low, action_high, raw_plane);
         p.nm = *nm; p.T = T; p.prof = (do_gae & 4) != 0;
-        char* base = ws;
-        p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
-        p.xch_rew = reinterpret_cast<double*>(base); base += (size_t)16 * N;
-        p.xch_cost = reinterpret_cast<float*>(base); base += (size_t)8 * N;
-        p.xch_done = reinterpret_cast<unsigned*>(base); base += ((size_t)8 * N + 255) / 256 * 256;
-        p.counter = reinterpret_cast<unsigned*>(base); base += 512;
-        p.xg = reinterpret_cast<unsigned long long*>(base);
-        p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G2 / 2));
-        hipError_t e = hipMemsetAsync(p.counter, 0, 512 + (size_t)16 * N * G2, s);
+        const size_t clear = persist_ws_carve(ws, N, O, true, p);
+        hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
         if (e != hipSuccess) return (int)e;
-        const bool small = O <= 32 && (!net || net->in_dim <= 32);
         const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
-        const int threads = 256;
-        auto go = [&](auto kernel) -> int {      // -1: the grid is not co-resident
-          int dev = 0, cus = 0, per_cu = 0;
-          if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-          if (dyn > 48 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return -1;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn) != hipSuccess || (long long)per_cu * cus < N) return -1;
-          const hipError_t e_ = launch_coresident(kernel, dim3(N), dim3(threads), dyn, s, ga);
-          if (e_ == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
-          return (int)e_;
-        };
-        const int perr = cf != nullptr ? (raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 0, true>) : go(rollout_generic_kernel<8, 0, true>))
-                                                               : (small ? go(rollout_generic_kernel<2, 0>) : go(rollout_generic_kernel<8, 0>)))
-                         : raw_plane != nullptr ? (small ? go(rollout_generic_kernel<2, 2, true>) : go(rollout_generic_kernel<8, 10, true>))
-                                                : (small ? go(rollout_generic_kernel<2, 2>) : go(rollout_generic_kernel<8, 10>));
-        if (perr >= 0) {
-          const int err = perr != 0 ? perr : (int)hipGetLastError();
-          if (err || !(do_gae & 1)) return err;
-          return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r, ag->last_v_c,
-                                  ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns, buf->cost_returns, T, N,
-                                  reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws, buf->gae_ws_bytes, stream);
-        }
+        const int perr = with_generic_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, ga); });
+        if (perr >= 0) return finish(perr != 0 ? perr : (int)hipGetLastError());
       }
     }
     GenStepArgs g;
@@ -4336,345 +4451,195 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                      buf->new_observations + row * O, buf->rewards + row, buf->costs + row, ag->last_dones};
       launch_norm_step(b, s);
     }
-    const int err = (int)hipGetLastError();
-    if (err || !(do_gae & 1)) return err;
-    return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r, ag->last_v_c,
-                            ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns, buf->cost_returns, T, N,
-                            reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws, buf->gae_ws_bytes, stream);
+    return finish((int)hipGetLastError());
   }
   ActStepArgs a;
-  a.env = *env; a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
-  a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
-  a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
-  a.has_cn = cn;
-  if (net) { a.cn = *net; a.cl = make_cn_layout(net->in_dim, net->n_hidden, net->h1, net->h2); }
-  else if (cf) a.cf = *cf;
+  fill_act_args(a, env, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
   // several environments per workgroup, interleaved (rollout_multi_kernel): do_gae bit 5
   if (((do_gae & 32) || N > WIDE_MAX_N) && !(do_gae & 2) && nm->training && !pol->discrete && N <= NORM_MAX_N && T >= 1) {
     int E = 0, G = 0;
     const int n_stats = O + (cn ? 2 : 1);
-    const size_t GX = 2 * (size_t)O + 4, GS = 4 * (size_t)O + 4;
-    const size_t need = 16 * (size_t)N * GX + 16 * GS + 256;
-    void* ws = (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) ? ag->xch_ws
-               : ((size_t)T * N * sizeof(float) >= need ? (void*)buf->reward_advantages : nullptr);
+    char* ws = exchange_ws(ag, buf, wide_ws_bytes(N, O));
     if (multi_shape(N, n_stats, &E, &G) && ws != nullptr) {
       WideArgs p;
       p.act = a; p.nm = *nm; p.T = T; p.G = G; p.prof = (do_gae & 4) ? 1 : ((do_gae & 8) ? G : 0);
-      p.xg = reinterpret_cast<unsigned long long*>(ws);
-      p.sg = p.xg + 2 * (size_t)N * GX;
-      p.xcc = G <= 32 ? p.sg + 2 * GS : nullptr;      // (the workgroups' XCD ids: the 256 spare bytes behind the statistics granules)
-      hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS + (p.xcc ? 256 : 0), s);
+      const size_t clear = wide_ws_carve(ws, N, O, G <= 32, p);
+      hipError_t e = hipMemsetAsync(p.xg, 0, clear, s);
       if (e != hipSuccess) return (int)e;
-      const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
+      k.cn128 = !net || net->in_dim <= 128; k.E = E;
       const size_t mdyn = multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G);
-      const int err = cf != nullptr ? (raw_plane != nullptr ? launch_multi_fn<true>(small, E, &p, G, mdyn, s) : launch_multi_fn<false>(small, E, &p, G, mdyn, s))
-                                    : launch_multi(raw_plane != nullptr, small, !net || net->in_dim <= 128, E, &p, nullptr, 1, G, mdyn, s);
-      if (err >= 0) {
-        if (err || !(do_gae & 1)) return err;
-        return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
-                                ag->last_v_c, ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns,
-                                buf->cost_returns, T, N, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws,
-                                buf->gae_ws_bytes, stream);
-      }
+      const int err = with_multi_kernel<false>(k, [&](auto kernel) { return launch_multi_run(kernel, p, G, mdyn, s); });
+      if (err >= 0) return finish(err);
     }
   }
   // many environments: persistent launch with the statistics partitioned by observation column (rollout_wide_kernel); measured
   // against the replicated-statistics kernel at HC widths: 64 envs 9.6 vs 9.5 us per step, 128 envs 9.9 vs 13.9
   if (!(do_gae & 2) && nm->training && (N > 96 || N * O > NORM_CHUNK || (do_gae & 16)) && N <= WIDE_MAX_N && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1) {
-    const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
-    const bool monv = raw_plane != nullptr;      // (with the plane: the instantiations without phase timers)
-    const void* kfn = cf != nullptr ? (monv ? (small ? (const void*)rollout_wide_kernel<2, 0, false, true> : (const void*)rollout_wide_kernel<8, 0, false, true>)
-                                            : (small ? (const void*)rollout_wide_kernel<2, 0> : (const void*)rollout_wide_kernel<8, 0>))
-                      : monv ? (small ? (const void*)rollout_wide_kernel<2, 2, false, true> : (const void*)rollout_wide_kernel<8, 10, false, true>)
-                           : (small ? (const void*)rollout_wide_kernel<2, 2> : (const void*)rollout_wide_kernel<8, 10>);
     int dev = 0, cus = 0, per_cu = 0;
+    k.prof = false;      // (the occupancy has always been asked of the instantiation without phase timers)
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0) == hipSuccess && per_cu > 0) {
+        with_wide_kernel(k, [&](auto kernel) { return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, 256, 0); }) == (int)hipSuccess &&
+        per_cu > 0) {
       const int max_g = per_cu * cus;
       const int E = (N + max_g - 1) / max_g;                 // envs per workgroup
       const int G = (N + E - 1) / E;                         // balanced grid
-      const size_t GX = 2 * (size_t)O + 4, GS = 4 * (size_t)O + 4;
-      const size_t need = 16 * (size_t)N * GX + 16 * GS + 256;
-      void* ws = (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) ? ag->xch_ws
-                 : ((size_t)T * N * sizeof(float) >= need ? (void*)buf->reward_advantages : nullptr);
+      char* ws = exchange_ws(ag, buf, wide_ws_bytes(N, O));
       if (getenv("ICRL_DEBUG")) fprintf(stderr, "icrl_rollout_collect: wide persistent kernel N=%d obs=%d: %d workgroup(s) per CU x %d CUs -> E=%d envs per workgroup, grid %d\n", N, O, per_cu, cus, E, G);
       if (E <= WIDE_E && G >= O + 2 && ws != nullptr) {
         WideArgs p;
         p.act = a; p.nm = *nm; p.T = T; p.G = G; p.prof = (do_gae & 4) ? 1 : ((do_gae & 8) ? G : 0);
-        p.xg = reinterpret_cast<unsigned long long*>(ws);
-        p.sg = p.xg + 2 * (size_t)N * GX;
-        p.xcc = nullptr;
-        hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS, s);
+        const size_t clear = wide_ws_carve(ws, N, O, false, p);
+        hipError_t e = hipMemsetAsync(p.xg, 0, clear, s);
         if (e != hipSuccess) return (int)e;
-        if (monv || cf != nullptr) p.prof = 0;      // (the analytic-cost instantiations: no phase timers either)
-        int err = cf != nullptr ? (monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 0, false, true>, dim3(G), dim3(256), 0, s, p)
-                                                      : launch_coresident(rollout_wide_kernel<8, 0, false, true>, dim3(G), dim3(256), 0, s, p))
-                                        : (int)(small ? launch_coresident(rollout_wide_kernel<2, 0>, dim3(G), dim3(256), 0, s, p)
-                                                      : launch_coresident(rollout_wide_kernel<8, 0>, dim3(G), dim3(256), 0, s, p)))
-                  : monv ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, false, true>, dim3(G), dim3(256), 0, s, p)
-                                     : launch_coresident(rollout_wide_kernel<8, 10, false, true>, dim3(G), dim3(256), 0, s, p))
-                  : p.prof ? (int)(small ? launch_coresident(rollout_wide_kernel<2, 2, true>, dim3(G), dim3(256), 0, s, p)
-                                       : launch_coresident(rollout_wide_kernel<8, 10, true>, dim3(G), dim3(256), 0, s, p))
-                         : (int)(small ? launch_coresident(rollout_wide_kernel<2, 2>, dim3(G), dim3(256), 0, s, p)
-                                       : launch_coresident(rollout_wide_kernel<8, 10>, dim3(G), dim3(256), 0, s, p));
+        if (k.mon || k.analytic) p.prof = 0;      // (with the plane or an analytic cost: the instantiations without phase timers)
+        k.prof = p.prof != 0;
+        const int err = with_wide_kernel(k, [&](auto kernel) { return (int)launch_coresident(kernel, dim3(G), dim3(256), 0, s, p); });
         if (err == (int)hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); goto per_step; }
-        if (err || !(do_gae & 1)) return err;
-        return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
-                             ag->last_v_c, ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns,
-                             buf->cost_returns, T, N, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws,
-                          buf->gae_ws_bytes, stream);
+        return finish(err);
       }
     }
   }
-  // persistent path: one launch for all T steps (see rollout_persistent_kernel).  Its exchange arrays live in the not yet
-  // computed reward_advantages plane of the buffer (GAE fills that afterwards).  do_gae & 2 forces the per-step launches.
+  // persistent path: one launch for all T steps (see rollout_persistent_kernel).  do_gae & 2 forces the per-step launches.
   {
-    const int G = 2 * O + 4;
-    const bool gran = (size_t)N * G <= (size_t)256 * GRAN_MAX;
-    const size_t need = (size_t)16 * N * O + (size_t)16 * N + (size_t)8 * N + (size_t)8 * N + 1024 + (gran ? (size_t)16 * N * G : 0);
-    char* ws = (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) ? reinterpret_cast<char*>(ag->xch_ws)
-               : ((size_t)T * N * sizeof(float) >= need ? reinterpret_cast<char*>(buf->reward_advantages) : nullptr);
+    const bool gran = (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX;
+    char* ws = exchange_ws(ag, buf, persist_ws_bytes(N, O, gran));
     if (!(do_gae & 2) && N <= 128 && N * O <= NORM_CHUNK && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1 && ws != nullptr) {
       PersistArgs p;
       p.act = a; p.nm = *nm; p.T = T; p.prof = (do_gae & 4) != 0;
-      char* base = ws;
-      p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
-      p.xch_rew = reinterpret_cast<double*>(base); base += (size_t)16 * N;
-      p.xch_cost = reinterpret_cast<float*>(base); base += (size_t)8 * N;
-      p.xch_done = reinterpret_cast<unsigned*>(base); base += ((size_t)8 * N + 255) / 256 * 256;
-      p.counter = reinterpret_cast<unsigned*>(base); base += 512;
-      p.xg = reinterpret_cast<unsigned long long*>(base);
-      p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G / 2));      // index split by the records per env (obs + 2)
-      hipError_t e = hipMemsetAsync(p.counter, 0, 512 + (gran ? (size_t)16 * N * G : 0), s);
+      const size_t clear = persist_ws_carve(ws, N, O, gran, p);
+      hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
       if (e != hipSuccess) return (int)e;
-      const bool small = a.pl.O <= 32 && (!net || net->in_dim <= 32);
+      if (k.mon || k.analytic) p.prof = 0;      // (with the plane or an analytic cost: the instantiations without phase timers)
+      k.gran = gran; k.prof = p.prof != 0;
       const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
-      int coop_err = 0;
-      auto go = [&](auto kernel) -> bool {
-        if (!persistent_fits(kernel, N, dyn)) return false;
-        const hipError_t e_ = launch_coresident(kernel, dim3(N), dim3(256), dyn, s, p);
-        if (e_ == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return false; }
-        coop_err = (int)e_;
-        return true;
-      };
-      bool launched;
-      if (cf != nullptr) {             // the analytic-cost instantiations (CIT == 0: no cost-net register image; no phase timers)
-        p.prof = 0;
-        if (raw_plane != nullptr) {
-          if (small && gran) launched = go(rollout_persistent_kernel<2, 0, true, false, true>);
-          else if (small) launched = go(rollout_persistent_kernel<2, 0, false, false, true>);
-          else if (gran) launched = go(rollout_persistent_kernel<8, 0, true, false, true>);
-          else launched = go(rollout_persistent_kernel<8, 0, false, false, true>);
-        } else if (small && gran) launched = go(rollout_persistent_kernel<2, 0, true>);
-        else if (small) launched = go(rollout_persistent_kernel<2, 0, false>);
-        else if (gran) launched = go(rollout_persistent_kernel<8, 0, true>);
-        else launched = go(rollout_persistent_kernel<8, 0, false>);
-      } else if (raw_plane != nullptr) {      // the instantiations that store the raw-reward plane (no phase timers)
-        p.prof = 0;
-        if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true, false, true>);
-        else if (small) launched = go(rollout_persistent_kernel<2, 2, false, false, true>);
-        else if (gran) launched = go(rollout_persistent_kernel<8, 10, true, false, true>);
-        else launched = go(rollout_persistent_kernel<8, 10, false, false, true>);
-      } else if (p.prof) {      // (tools: the instantiations with the phase timers)
-        if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true, true>);
-        else if (small) launched = go(rollout_persistent_kernel<2, 2, false, true>);
-        else if (gran) launched = go(rollout_persistent_kernel<8, 10, true, true>);
-        else launched = go(rollout_persistent_kernel<8, 10, false, true>);
-      } else if (small && gran) launched = go(rollout_persistent_kernel<2, 2, true>);
-      else if (small) launched = go(rollout_persistent_kernel<2, 2, false>);
-      else if (gran) launched = go(rollout_persistent_kernel<8, 10, true>);
-      else launched = go(rollout_persistent_kernel<8, 10, false>);
-      int err = coop_err != 0 ? coop_err : (int)hipGetLastError();
-      if (!launched) goto per_step;
-      if (err || !(do_gae & 1)) return err;
-      return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
-                           ag->last_v_c, ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns,
-                           buf->cost_returns, T, N, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws,
-                          buf->gae_ws_bytes, stream);
+      const int perr = with_persistent_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, p); });
+      const int err = perr > 0 ? perr : (int)hipGetLastError();
+      if (perr < 0) goto per_step;
+      return finish(err);
     }
   }
 per_step:
   for (int t = 0; t < T; ++t) {
-    if (cf != nullptr) {
-      if (a.pl.O <= 32) hipLaunchKernelGGL((act_step_kernel<2, 0>), dim3(N), dim3(256), 0, s, a, t);
-      else hipLaunchKernelGGL((act_step_kernel<8, 0>), dim3(N), dim3(256), 0, s, a, t);
-    } else if (a.pl.O <= 32 && (!net || net->in_dim <= 32)) hipLaunchKernelGGL((act_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, a, t);
-    else hipLaunchKernelGGL((act_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, a, t);
+    with_act_step_kernel(k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, s, a, t); return 0; });
     const size_t row = (size_t)t * N;
     NormStepArgs b{*nm, env->s, ag->raw_rew, cn ? ag->raw_cost : nullptr, ag->dones, N, O, ag->last_obs, nullptr, nullptr,
                    buf->new_observations + row * O, buf->rewards + row, buf->costs + row, ag->last_dones};
     launch_norm_step(b, s);
   }
-  int err = (int)hipGetLastError();
-  if (err || !(do_gae & 1)) return err;
-  return icrl_gae_dual_ws(buf->rewards, buf->costs, buf->reward_values, buf->cost_values, buf->dones, ag->last_v_r,
-                       ag->last_v_c, ag->last_dones, buf->reward_advantages, buf->cost_advantages, buf->reward_returns,
-                       buf->cost_returns, T, N, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, 0, buf->gae_ws,
-                          buf->gae_ws_bytes, stream);
+  return finish((int)hipGetLastError());
 }
 
-// icrl_rollout_collect for n_runs runs: ONE persistent launch of grid (N, n_runs) + ONE batched dual-GAE launch.  Only the
-// one-workgroup-per-env persistent kernel has a batched form (N <= 128 and N x obs <= 4096: BASELINE configs[1]); other shapes
-// are refused (the caller then issues the single-run calls).
+// what one run of a batch must share with run 0 and satisfy by itself.  same_training is inherited, not designed: the multi route also
+// compares nm->training between the runs, the one-workgroup-per-env route does not
+static int batch_run_check(int r, const icrl_rollout_job_t& j, const icrl_rollout_job_t& j0, bool analytic, bool same_training) {
+  const int N = j0.env->n_envs, O = j0.env->obs_dim;
+  const bool has_cn = j0.cn != nullptr;
+  if (j.env->n_envs != N || j.env->obs_dim != O || j.env->act_dim != j0.env->act_dim || j.buf->T != j0.buf->T || j.buf->N != N ||
+      j.pol->obs_dim != O || j.pol->act_dim != j0.pol->act_dim || j.pol->discrete != j0.pol->discrete || (j.cn != nullptr) != has_cn ||
+      (has_cn && (j.cn->in_dim != j0.cn->in_dim || j.cn->n_hidden != j0.cn->n_hidden)) || (same_training && j.nm->training != j0.nm->training))
+    return fail("icrl_rollout_collect_batch: run %d differs from run 0 in a shape (envs / obs / act / T / discrete / constraint net)", r);
+  if (!dims_ok(j.pol)) return bad_dims("icrl_rollout_collect_batch", j.pol);
+  if (j.buf->obs_dim != O) return fail("icrl_rollout_collect_batch: run %d: buffer obs_dim %d vs env %d", r, j.buf->obs_dim, O);
+  if (!analytic && j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
+  return 0;
+}
+
+// fill_act_args for run r of a batch (its monitor plane from mons[r])
+static int batch_act_args(ActStepArgs& a, int r, const icrl_rollout_job_t& j, const icrl_monitor_t* mons, bool analytic, const float* action_low,
+                          const float* action_high) {
+  double* raw_plane = nullptr;
+  if (int e = mon_plane("icrl_rollout_collect_batch_mon", mons ? mons + r : nullptr, &raw_plane)) return e;
+  fill_act_args(a, j.env, j.buf, j.ag, j.pol, false, analytic ? nullptr : j.cn, analytic ? as_cost_fn(j.cn) : nullptr, j.noise, action_low, action_high,
+                raw_plane);
+  return 0;
+}
+
+// icrl_rollout_collect for n_runs runs: ONE persistent launch + ONE batched dual-GAE launch.  Shapes that neither batched kernel
+// serves are refused (the caller then issues the single-run calls).
 // analytic: every jobs[r].cn is an icrl_cost_fn_t that passed cost_fn_check (icrl_rollout_collect_batch_cost) — the CIT == 0 kernels;
 // otherwise every jobs[r].cn is a constraint net, or NULL in every run
 static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
                                       const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
                                       double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream, bool analytic) {
   static_assert(sizeof(PersistArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  static_assert(sizeof(WideArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
   if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * ICRL_BATCH_ARGS_BYTES)
     return fail("icrl_rollout_collect_batch: args_ws holds %lld B, %d runs need %lld", args_ws_bytes, n_runs, (long long)n_runs * ICRL_BATCH_ARGS_BYTES);
   hipStream_t s = (hipStream_t)stream;
   const icrl_rollout_job_t& j0 = jobs[0];
   const int N = j0.env->n_envs, O = j0.env->obs_dim, T = j0.buf->T;
   const bool has_cn = j0.cn != nullptr;
+  const icrl_costnet_t* const net0 = analytic ? nullptr : j0.cn;
+  KernelPick k;
+  k.small = small_shape(O, net0); k.analytic = analytic; k.mon = mons != nullptr;
+  auto finish = [&](int err) {
+    return finish_batch_with_gae(err, do_gae, n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, args_ws, args_ws_bytes, stream);
+  };
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   // ---- preferred: several envs per workgroup, interleaved (G = N / E workgroups per run: all runs resident together)
   {
     int E = 0, G = 0;
     const int n_stats = O + (has_cn ? 2 : 1);
     static const bool no_multi = getenv("ICRL_BATCH_NO_MULTI") != nullptr;      // tools: the one-workgroup-per-env kernel instead
     // (few small runs: one workgroup per env keeps every env's step at its latency floor and all of them fit the chip at once)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const bool few = (long long)n_runs * N <= cus && N <= 128 && N * O <= NORM_CHUNK;
     if (!no_multi && !few && !j0.pol->discrete && j0.nm->training && N <= NORM_MAX_N && T >= 1 && multi_shape(N, n_stats, &E, &G)) {
-      static_assert(sizeof(WideArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
-      const size_t GX = 2 * (size_t)O + 4, GS = 4 * (size_t)O + 4;
-      const size_t need = 16 * (size_t)N * GX + 16 * GS + 256;
       WideArgs* d_args = (WideArgs*)args_ws;
       bool ok = true;
       for (int r = 0; r < n_runs && ok; ++r) {
         const icrl_rollout_job_t& j = jobs[r];
-        if (j.env->n_envs != N || j.env->obs_dim != O || j.env->act_dim != j0.env->act_dim || j.buf->T != T || j.buf->N != N ||
-            j.pol->obs_dim != O || j.pol->act_dim != j0.pol->act_dim || j.pol->discrete != j0.pol->discrete || (j.cn != nullptr) != has_cn ||
-            (has_cn && (j.cn->in_dim != j0.cn->in_dim || j.cn->n_hidden != j0.cn->n_hidden)) || j.nm->training != j0.nm->training)
-          return fail("icrl_rollout_collect_batch: run %d differs from run 0 in a shape (envs / obs / act / T / discrete / constraint net)", r);
-        if (!dims_ok(j.pol)) return bad_dims("icrl_rollout_collect_batch", j.pol);
-        if (j.buf->obs_dim != O) return fail("icrl_rollout_collect_batch: run %d: buffer obs_dim %d vs env %d", r, j.buf->obs_dim, O);
-        if (!analytic && j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
-        void* ws = (j.ag->xch_ws != nullptr && (size_t)j.ag->xch_ws_bytes >= need) ? j.ag->xch_ws
-                   : ((size_t)T * N * sizeof(float) >= need ? (void*)j.buf->reward_advantages : nullptr);
+        if (int e_ = batch_run_check(r, j, j0, analytic, true)) return e_;
+        char* ws = exchange_ws(j.ag, j.buf, wide_ws_bytes(N, O));
         if (ws == nullptr) { ok = false; break; }
         WideArgs p;
-        ActStepArgs& a = p.act;
-        a.env = *j.env; a.buf = *j.buf; a.ag = *j.ag;
-        if (int e_ = mon_plane("icrl_rollout_collect_batch_mon", mons ? mons + r : nullptr, &a.raw_plane)) return e_;
-        a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
-        a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
-        a.has_cn = j.cn != nullptr;
-        if (analytic) a.cf = *as_cost_fn(j.cn);
-        else if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
+        if (int e_ = batch_act_args(p.act, r, j, mons, analytic, action_low, action_high)) return e_;
         p.nm = *j.nm; p.T = T; p.G = G; p.prof = 0;
-        p.xg = reinterpret_cast<unsigned long long*>(ws);
-        p.sg = p.xg + 2 * (size_t)N * GX;
-        // the workgroups' XCD ids: G words in the 256 spare bytes behind the statistics granules (`need` above)
-        p.xcc = G <= 32 ? p.sg + 2 * GS : nullptr;
-        hipError_t e = hipMemsetAsync(p.xg, 0, 16 * (size_t)N * GX + 16 * GS + (p.xcc ? 256 : 0), s);
+        const size_t clear = wide_ws_carve(ws, N, O, G <= 32, p);
+        hipError_t e = hipMemsetAsync(p.xg, 0, clear, s);
         if (e != hipSuccess) return (int)e;
         const int pe = put_args(p, d_args + r, s);
         if (pe) return pe;
       }
       if (ok) {
-        const bool small = O <= 32 && (!has_cn || j0.cn->in_dim <= 32);
+        k.cn128 = net0 == nullptr || net0->in_dim <= 128; k.E = E;
         const size_t mdyn = multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G);
-        const int err = analytic ? (mons != nullptr ? launch_multi_batch_fn<true>(small, E, d_args, n_runs, G, mdyn, s) : launch_multi_batch_fn<false>(small, E, d_args, n_runs, G, mdyn, s))
-                                 : launch_multi(mons != nullptr, small, !has_cn || j0.cn->in_dim <= 128, E, nullptr, d_args, n_runs, G, mdyn, s);
-        if (err >= 0) {
-          if (err || !(do_gae & 1)) return err;
-          if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
-            return fail("icrl_rollout_collect_batch: args_ws needs 2 x n_runs x ICRL_BATCH_ARGS_BYTES = %lld B when the GAE launch is included", 2ll * n_runs * ICRL_BATCH_ARGS_BYTES);
-          return icrl_gae_dual_batch_impl(n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda,
-                                          (char*)args_ws + (size_t)n_runs * ICRL_BATCH_ARGS_BYTES, stream);
-        }
+        const int err = with_multi_kernel<true>(k, [&](auto kernel) { return launch_multi_runs(kernel, d_args, n_runs, G, mdyn, s); });
+        if (err >= 0) return finish(err);
       }
     }
   }
+  // ---- one workgroup per env: grid (N, n_runs), run = blockIdx.y (N <= 128 and N x obs <= 4096: BASELINE configs[1])
   if (!(N <= 128 && N * O <= NORM_CHUNK && O * j0.env->act_dim <= MAX_OBS * MAX_ACT && T >= 1))
     return fail("icrl_rollout_collect_batch: %d envs x obs %d: no batched form for this shape (multi-env kernel: continuous actions, training statistics, >= 4 envs per statistics-owner group; one workgroup per env: <= 128 envs, envs x obs <= %d)", N, O, NORM_CHUNK);
-  const int G = 2 * O + 4;
-  const bool gran = (size_t)N * G <= (size_t)256 * GRAN_MAX;
-  const size_t need = (size_t)16 * N * O + (size_t)16 * N + (size_t)8 * N + (size_t)8 * N + 1024 + (gran ? (size_t)16 * N * G : 0);
+  const bool gran = (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX;
+  const size_t need = persist_ws_bytes(N, O, gran);
   PersistArgs* d_args = (PersistArgs*)args_ws;
   for (int r = 0; r < n_runs; ++r) {
     const icrl_rollout_job_t& j = jobs[r];
-    if (j.env->n_envs != N || j.env->obs_dim != O || j.env->act_dim != j0.env->act_dim || j.buf->T != T || j.buf->N != N ||
-        j.pol->obs_dim != O || j.pol->act_dim != j0.pol->act_dim || j.pol->discrete != j0.pol->discrete || (j.cn != nullptr) != has_cn ||
-        (has_cn && (j.cn->in_dim != j0.cn->in_dim || j.cn->n_hidden != j0.cn->n_hidden)))
-      return fail("icrl_rollout_collect_batch: run %d differs from run 0 in a shape (envs / obs / act / T / discrete / constraint net)", r);
-    if (!dims_ok(j.pol)) return bad_dims("icrl_rollout_collect_batch", j.pol);
-    if (j.buf->obs_dim != O) return fail("icrl_rollout_collect_batch: run %d: buffer obs_dim %d vs env %d", r, j.buf->obs_dim, O);
-    if (!analytic && j.cn != nullptr && !cn_ok(j.cn)) return bad_cn("icrl_rollout_collect_batch", j.cn);
-    char* ws = (j.ag->xch_ws != nullptr && (size_t)j.ag->xch_ws_bytes >= need) ? reinterpret_cast<char*>(j.ag->xch_ws)
-               : ((size_t)T * N * sizeof(float) >= need ? reinterpret_cast<char*>(j.buf->reward_advantages) : nullptr);
+    if (int e_ = batch_run_check(r, j, j0, analytic, false)) return e_;
+    char* ws = exchange_ws(j.ag, j.buf, need);
     if (ws == nullptr) return fail("icrl_rollout_collect_batch: run %d: exchange workspace of %zu B needed (icrl_agent_t.xch_ws, ICRL_ROLLOUT_WS_BYTES)", r, need);
     PersistArgs p;
-    ActStepArgs& a = p.act;
-    a.env = *j.env; a.buf = *j.buf; a.ag = *j.ag;
-    if (int e_ = mon_plane("icrl_rollout_collect_batch_mon", mons ? mons + r : nullptr, &a.raw_plane)) return e_;
-    a.pl = make_pol_layout(j.pol->obs_dim, j.pol->act_dim, j.pol->h1, j.pol->h2, j.pol->discrete);
-    a.PT = j.pol->params_t; a.noise = j.noise; a.alow = action_low; a.ahigh = action_high;
-    a.has_cn = j.cn != nullptr;
-    if (analytic) a.cf = *as_cost_fn(j.cn);
-    else if (j.cn) { a.cn = *j.cn; a.cl = make_cn_layout(j.cn->in_dim, j.cn->n_hidden, j.cn->h1, j.cn->h2); }
+    if (int e_ = batch_act_args(p.act, r, j, mons, analytic, action_low, action_high)) return e_;
     p.nm = *j.nm; p.T = T; p.prof = 0;
-    char* base = ws;
-    p.xch_obs = reinterpret_cast<double*>(base); base += (size_t)16 * N * O;
-    p.xch_rew = reinterpret_cast<double*>(base); base += (size_t)16 * N;
-    p.xch_cost = reinterpret_cast<float*>(base); base += (size_t)8 * N;
-    p.xch_done = reinterpret_cast<unsigned*>(base); base += ((size_t)8 * N + 255) / 256 * 256;
-    p.counter = reinterpret_cast<unsigned*>(base); base += 512;
-    p.xg = reinterpret_cast<unsigned long long*>(base);
-    p.g_magic = (unsigned)((1ull << 32) / (unsigned long long)(G / 2));      // records per env
-    hipError_t e = hipMemsetAsync(p.counter, 0, 512 + (gran ? (size_t)16 * N * G : 0), s);
+    const size_t clear = persist_ws_carve(ws, N, O, gran, p);
+    hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
     if (e != hipSuccess) return (int)e;
     const int pe = put_args(p, d_args + r, s);
     if (pe) return pe;
   }
-  const bool small = O <= 32 && (!has_cn || j0.cn->in_dim <= 32);
+  // ICRL_ROLLOUT_MINW (tools) picks the register allocation; otherwise the full register file per workgroup when all workgroups of
+  // the grid fit one per CU — up to 4 runs of 64 envs: 17 ms per 2048-step rollout against 29.6 with the two-per-CU allocation,
+  // measured at S = 1 and 4
+  static const int minw_env = getenv("ICRL_ROLLOUT_MINW") ? atoi(getenv("ICRL_ROLLOUT_MINW")) : 0;
+  k.gran = gran; k.minw = minw_env > 0 ? minw_env : ((long long)n_runs * N <= cus ? 1 : 2);
   const size_t dyn = persist_dyn_lds(N, O, j0.env->act_dim);
-  auto go = [&](auto kernel) -> int {
+  return finish(with_persistent_batch_kernel(k, [&](auto kernel) -> int {
     if (!persistent_fits(kernel, N, dyn)) return fail("icrl_rollout_collect_batch: the %d workgroups of one run do not fit the device", N);
     hipLaunchKernelGGL(kernel, dim3(N, n_runs), dim3(256), dyn, s, d_args);
     return (int)hipGetLastError();
-  };
-  // registers: the narrow (HC-width) kernel leaves room for several workgroups per CU, so that several runs of the grid are resident
-  // together; ICRL_ROLLOUT_MINW (tools) picks the allocation
-  // (all workgroups of the grid fit one per CU — up to 4 runs of 64 envs: the full register file per workgroup, 17 ms per 2048-step
-  // rollout against 29.6 with the two-per-CU allocation, measured at S = 1 and 4)
-  static const int minw_env = getenv("ICRL_ROLLOUT_MINW") ? atoi(getenv("ICRL_ROLLOUT_MINW")) : 0;
-  int dev_ = 0, cus_ = 256;
-  if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess) cus_ = 256;
-  const int minw = minw_env > 0 ? minw_env : ((long long)n_runs * N <= cus_ ? 1 : 2);
-  int err;
-  if (analytic) {      // the CIT == 0 instantiations, the same allocations
-    if (mons != nullptr) {
-      if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_analytic_kernel<2, true, 3, true>) : (minw == 2 ? go(rollout_persistent_batch_analytic_kernel<2, true, 2, true>) : go(rollout_persistent_batch_analytic_kernel<2, true, 1, true>));
-      else if (small) err = go(rollout_persistent_batch_analytic_kernel<2, false, 2, true>);
-      else if (gran) err = go(rollout_persistent_batch_analytic_kernel<8, true, 1, true>);
-      else err = go(rollout_persistent_batch_analytic_kernel<8, false, 1, true>);
-    } else {
-      if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_analytic_kernel<2, true, 3>) : (minw == 2 ? go(rollout_persistent_batch_analytic_kernel<2, true, 2>) : go(rollout_persistent_batch_analytic_kernel<2, true, 1>));
-      else if (small) err = go(rollout_persistent_batch_analytic_kernel<2, false, 2>);
-      else if (gran) err = go(rollout_persistent_batch_analytic_kernel<8, true, 1>);
-      else err = go(rollout_persistent_batch_analytic_kernel<8, false, 1>);
-    }
-  } else if (mons != nullptr) {
-    if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3, true>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2, true>) : go(rollout_persistent_batch_kernel<2, 2, true, 1, true>));
-    else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2, true>);
-    else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1, true>);
-    else err = go(rollout_persistent_batch_kernel<8, 10, false, 1, true>);
-  } else {
-    if (small && gran) err = minw >= 3 ? go(rollout_persistent_batch_kernel<2, 2, true, 3>) : (minw == 2 ? go(rollout_persistent_batch_kernel<2, 2, true, 2>) : go(rollout_persistent_batch_kernel<2, 2, true, 1>));
-    else if (small) err = go(rollout_persistent_batch_kernel<2, 2, false, 2>);
-    else if (gran) err = go(rollout_persistent_batch_kernel<8, 10, true, 1>);
-    else err = go(rollout_persistent_batch_kernel<8, 10, false, 1>);
-  }
-  if (err || !(do_gae & 1)) return err;
-  // dual GAE of every run in one launch; its argument blocks go behind the rollout's in args_ws (both launches are in flight together)
-  if (args_ws_bytes < 2ll * n_runs * ICRL_BATCH_ARGS_BYTES)
-    return fail("icrl_rollout_collect_batch: args_ws needs 2 x n_runs x ICRL_BATCH_ARGS_BYTES = %lld B when the GAE launch is included", 2ll * n_runs * ICRL_BATCH_ARGS_BYTES);
-  return icrl_gae_dual_batch_impl(n_runs, jobs, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda,
-                                  (char*)args_ws + (size_t)n_runs * ICRL_BATCH_ARGS_BYTES, stream);
+  }));
 }
 
 extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
@@ -4764,12 +4729,8 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   HostStepArgs h{};
   ActStepArgs& a = h.act;
   a.env.n_envs = N; a.env.obs_dim = O; a.env.act_dim = pol->discrete ? 1 : pol->act_dim;
-  a.buf = *buf; a.ag = *ag; a.raw_plane = raw_plane;
-  a.pl = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
-  a.PT = pol->params_t; a.noise = noise; a.alow = action_low; a.ahigh = action_high;
-  a.has_cn = cn != nullptr;
-  if (cf) a.cf = *cf;
-  else if (cn) { a.cn = *cn; a.cl = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2); }
+  const icrl_costnet_t* const net = cf != nullptr ? nullptr : cn;
+  fill_act_args(a, nullptr, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
   h.nm = *nm; h.hs = *hs; h.N = N;
   // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
   void* act_dev = nullptr;
@@ -4779,11 +4740,9 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   }
   h.hs.act_host = reinterpret_cast<float*>(act_dev);
   hipStream_t s = (hipStream_t)stream;
-  if (cf != nullptr) {      // the analytic-cost instantiations (CIT == 0)
-    if (a.pl.O <= 32) hipLaunchKernelGGL((host_step_kernel<2, 0>), dim3(N), dim3(256), 0, s, h, k);
-    else hipLaunchKernelGGL((host_step_kernel<8, 0>), dim3(N), dim3(256), 0, s, h, k);
-  } else if (a.pl.O <= 32 && (!cn || cn->in_dim <= 32)) hipLaunchKernelGGL((host_step_kernel<2, 2>), dim3(N), dim3(256), 0, s, h, k);
-  else hipLaunchKernelGGL((host_step_kernel<8, 10>), dim3(N), dim3(256), 0, s, h, k);
+  KernelPick pick;
+  pick.small = small_shape(O, net); pick.analytic = cf != nullptr;
+  with_host_step_kernel(pick, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, s, h, k); return 0; });
   return (int)hipGetLastError();
 }
 
