@@ -150,7 +150,14 @@ __global__ void __launch_bounds__(256) clip_adam_kernel(float* p, const float* _
 }
 
 // common/utils.py:43-59 explained_variance(y_pred, y_true) = 1 - Var[y_true - y_pred] / Var[y_true] (nan when Var[y_true] == 0) for up to two
-// (y_pred, y_true) pairs of n floats in one pass: float64 sums of y, y^2, d, d^2 per block -> part[block][8], then one block folds them.
+// (y_pred, y_true) pairs of n floats, MEAN FIRST like np.var.  (Var = E[y^2] - E[y]^2 from one pass of float64 sums cancels where the critic
+// is nearly constant: 14 % off at 1000 + {0, 1} float32 ulps, and a constant critic gives -6.6e17 or NaN depending on how its squares round.)
+//   pass 1: each block's float64 sums of y and d = y - y_pred                          -> part[block][0..3]
+//   pass 2: every block folds those into the four means (the same fixed tree in every block: the same bits), then its sums of
+//           (y - mean)^2 and (d - mean)^2                                              -> part[block][4..7]
+//   fold:   one block adds them up; Var = sum / n
+// The sum of n equal float32 values is exact in float64 (n < 2^29: include/icrl_hip.h states the bound) and so is its division by n: a constant y_true has the mean y, every
+// deviation 0 and the variance exactly 0 -> NaN, as in the reference.  The arrays are a few MB and L2-resident for the second pass.
 __device__ __forceinline__ double block_sum_256d(double v, double* red) {
   const int tid = threadIdx.x;
   red[tid] = v;
@@ -164,39 +171,63 @@ __device__ __forceinline__ double block_sum_256d(double v, double* red) {
   return r;
 }
 
-__global__ void __launch_bounds__(256) ev_partials_kernel(const float* __restrict__ pa, const float* __restrict__ ta, const float* __restrict__ pb,
-                                                          const float* __restrict__ tb, long long n, double* part) {
+__global__ void __launch_bounds__(256) ev_sums_kernel(const float* __restrict__ pa, const float* __restrict__ ta, const float* __restrict__ pb,
+                                                      const float* __restrict__ tb, long long n, double* part) {
   __shared__ double red[256];
-  double q[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+  double q[4] = {0., 0., 0., 0.};
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double ya = (double)ta[i], da = ya - (double)pa[i];
-    q[0] += ya; q[1] += ya * ya; q[2] += da; q[3] += da * da;
+    const double ya = (double)ta[i];
+    q[0] += ya; q[1] += ya - (double)pa[i];
     if (pb != nullptr) {
-      const double yb = (double)tb[i], db = yb - (double)pb[i];
-      q[4] += yb; q[5] += yb * yb; q[6] += db; q[7] += db * db;
+      const double yb = (double)tb[i];
+      q[2] += yb; q[3] += yb - (double)pb[i];
     }
   }
-  for (int k = 0; k < 8; ++k) {
+  for (int k = 0; k < 4; ++k) {
     const double r = block_sum_256d(q[k], red);
     if (threadIdx.x == 0) part[(size_t)blockIdx.x * 8 + k] = r;
   }
 }
 
+__global__ void __launch_bounds__(256) ev_devs_kernel(const float* __restrict__ pa, const float* __restrict__ ta, const float* __restrict__ pb,
+                                                      const float* __restrict__ tb, long long n, double* part) {
+  __shared__ double red[256];
+  __shared__ double mean[4];
+  for (int k = 0; k < 4; ++k) {
+    double s = 0.;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) s += part[(size_t)i * 8 + k];
+    const double r = block_sum_256d(s, red);
+    if (threadIdx.x == 0) mean[k] = r / (double)n;      // a division: n * y / n == y exactly
+  }
+  __syncthreads();
+  double q[4] = {0., 0., 0., 0.};
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const double ya = (double)ta[i], ea = ya - mean[0], fa = (ya - (double)pa[i]) - mean[1];
+    q[0] += ea * ea; q[1] += fa * fa;
+    if (pb != nullptr) {
+      const double yb = (double)tb[i], eb = yb - mean[2], fb = (yb - (double)pb[i]) - mean[3];
+      q[2] += eb * eb; q[3] += fb * fb;
+    }
+  }
+  for (int k = 0; k < 4; ++k) {
+    const double r = block_sum_256d(q[k], red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * 8 + 4 + k] = r;
+  }
+}
+
 __global__ void __launch_bounds__(256) ev_final_kernel(const double* __restrict__ part, int n_part, long long n, int pairs, float* out) {
   __shared__ double red[256];
-  __shared__ double tot[8];
-  for (int k = 0; k < 8; ++k) {
+  __shared__ double tot[4];
+  for (int k = 0; k < 4; ++k) {
     double s = 0.;
-    for (int i = threadIdx.x; i < n_part; i += 256) s += part[(size_t)i * 8 + k];
+    for (int i = threadIdx.x; i < n_part; i += 256) s += part[(size_t)i * 8 + 4 + k];
     const double r = block_sum_256d(s, red);
     if (threadIdx.x == 0) tot[k] = r;
   }
   __syncthreads();
   if (threadIdx.x < pairs) {
-    const double* t = tot + 4 * threadIdx.x;
-    const double inv = 1.0 / (double)n, my = t[0] * inv, md = t[2] * inv;
-    const double var_y = t[1] * inv - my * my, var_d = t[3] * inv - md * md;
-    out[threadIdx.x] = var_y > 0.0 ? (float)(1.0 - var_d / var_y) : __builtin_nanf("");
+    const double var_y = tot[2 * threadIdx.x] / (double)n, var_d = tot[2 * threadIdx.x + 1] / (double)n;
+    out[threadIdx.x] = var_y == 0.0 ? __builtin_nanf("") : (float)(1.0 - var_d / var_y);
   }
 }
 
@@ -387,7 +418,8 @@ extern "C" int icrl_explained_variance(const float* y_pred_a, const float* y_tru
     return fail("icrl_explained_variance: n = %lld, NULL argument (the second pair may be NULL as a whole; work: 8 x 256 doubles)", n);
   const int blocks = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ev_partials_kernel, dim3(blocks), dim3(256), 0, s, y_pred_a, y_true_a, y_pred_b, y_true_b, n, work);
+  hipLaunchKernelGGL(ev_sums_kernel, dim3(blocks), dim3(256), 0, s, y_pred_a, y_true_a, y_pred_b, y_true_b, n, work);
+  hipLaunchKernelGGL(ev_devs_kernel, dim3(blocks), dim3(256), 0, s, y_pred_a, y_true_a, y_pred_b, y_true_b, n, work);
   hipLaunchKernelGGL(ev_final_kernel, dim3(1), dim3(256), 0, s, work, blocks, n, y_pred_b != nullptr ? 2 : 1, out2);
   return (int)hipGetLastError();
 }

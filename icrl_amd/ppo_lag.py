@@ -903,7 +903,7 @@ class PPOLagrangian:
     def _explained_variance(self):
         """device float32 [2]: `explained_variance(returns.flatten(), values.flatten())` of the reward and of the cost critic as the
         reference logs them (ref: ppo_lag.py:311-312 -> common/utils.py:43-59; NB its argument order: y_pred = returns, y_true = values,
-        so the figure is 1 - Var[values - returns] / Var[values]) — one pass over the four [T, N] planes (icrl_explained_variance)."""
+        so the figure is 1 - Var[values - returns] / Var[values]) — one call over the four [T, N] planes (icrl_explained_variance: means first, then squared deviations)."""
         rb, ws = self.rollout_buffer, self._train_ws
         if "ev_work" not in ws:
             ws["ev_work"] = torch.zeros(8 * 256, dtype=torch.float64, device=self.device)

@@ -688,7 +688,8 @@ int icrl_minibatch_gather(const icrl_buffer_t* buf, const int32_t* flat_idx, int
 /* out4 = {mean(adv_r), 1 / (std(adv_r) + 1e-8) with torch's unbiased std, mean(adv_c), std(adv_r)}; n >= 2. */
 int icrl_adv_stats(const float* adv_r, const float* adv_c, int n, float* out4, void* stream);
 /* common/utils.py:43-59 `explained_variance(y_pred, y_true)` = 1 - Var[y_true - y_pred] / Var[y_true] (NaN when Var[y_true] == 0), float64
- * sums over n float32 values, for one or two pairs in one pass (the second pair may be NULL as a whole; then out2[1] is not written).
+ * over n float32 values, the mean subtracted first as np.var does (a nearly constant critic does not cancel; NaN exactly when y_true is
+ * constant, for n < 2^29: up to there the sum of n equal float32 values is exact in float64), for one or two pairs in one call (the second pair may be NULL as a whole; then out2[1] is not written).
  * Call site replaced: ppo_lag/ppo_lag.py:311-312 — NB the reference passes (returns, values), i.e. y_pred = returns, y_true = values.
  * work: 8 x 256 doubles of device scratch; out2: device float32. */
 int icrl_explained_variance(const float* y_pred_a, const float* y_true_a, const float* y_pred_b, const float* y_true_b, long long n,

@@ -258,6 +258,86 @@ def test_explained_variance_vs_the_reference_formula(n):
         assert np.isnan(got[0]) and got[1] == 7.0
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# explained variance where the critic is NEARLY CONSTANT (LapGridWorld, early training): y_true = base + a few float32 ulps.  The reference
+# (np.var) subtracts the mean first.  Single-pass float64 sums of y and y^2 (Var = E[y^2] - E[y]^2, the single-pass form this kernel replaced)
+# cancel there: emulated in numpy in the kernel's summation order (thread-strided partial sums, a 256-leaf tree per block, a tree over the
+# blocks) that form gives -3.28e8 against -2.87e8 at 1000 + {0, 1} ulp x 300, -7.46e13 against -6.99e13 at 1 + {0, 1} ulp x 4096, -6.6e17
+# instead of NaN for a constant float32(0.05) x 300, and reaches NaN for a constant 1000 only because its variance comes out at -1.2e-10:
+# it fails the cases below.  The reference of these tests is the mean-first float64 evaluation on the float32 inputs cast to float64
+# (numpy's own float32 evaluation is itself ill-conditioned here and is not used); the bound is the existing 1e-6 max(1, |want|): the
+# output is one float32 (6e-8 relative) and a mean-first float64 evaluation is exact far below that.
+# ---------------------------------------------------------------------------------------------------------------------
+def _ev_launch(pairs, n):
+    """icrl_explained_variance on one or two (y_pred, y_true) pairs of float32 arrays -> out2 on the host (7.0 where not written)."""
+    from icrl_amd import _lib
+    d = [_dev(x) for pair in pairs for x in pair] + [None, None] * (2 - len(pairs))
+    work, out = torch.zeros(8 * 256, dtype=torch.float64, device="cuda"), torch.full((2,), 7.0, device="cuda")
+    _lib.check(_lib.lib().icrl_explained_variance(*(_lib.ptr(x) for x in d), n, _lib.ptr(work), _lib.ptr(out), _lib.current_stream()),
+               "icrl_explained_variance")
+    return out.cpu().numpy()
+
+
+def _ev_want(y_pred, y_true):
+    from oracle.loop import explained_variance
+    yt = y_true.astype(np.float64)
+    assert np.var(yt) > 0, "the case must have a varying y_true in float64"
+    return explained_variance(y_pred.astype(np.float64), yt)
+
+
+def _near_constant(rng, base, k, n):
+    b = np.float32(base)
+    return (b + np.spacing(b) * rng.randint(0, k + 1, n).astype(np.float32)).astype(np.float32)
+
+
+@pytest.mark.parametrize("n", [300, 4096, 2048 * 64])
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("base", [0.05, 1.0, 100.0, 1000.0])
+def test_explained_variance_of_a_nearly_constant_critic(base, k, n):
+    """pair a: the denominator's variance is the ill-conditioned one (y_pred = base + 0.5 randn); pair b: the numerator's too
+    (y_pred = y_true + 1000 + 0.01 randn: y_true - y_pred is -1000 with a spread of 0.01)."""
+    rng = np.random.RandomState(int(base * 100) + 7 * k + n)
+    yt_a, yt_b = _near_constant(rng, base, k, n), _near_constant(rng, base, k, n)
+    yp_a = (np.float32(base) + 0.5 * rng.randn(n)).astype(np.float32)
+    yp_b = (yt_b + 1000 + 0.01 * rng.randn(n)).astype(np.float32)
+    want = [_ev_want(yp_a, yt_a), _ev_want(yp_b, yt_b)]
+    got = _ev_launch([(yp_a, yt_a), (yp_b, yt_b)], n)
+    print(f"explained variance base {base} k {k} n {n}: got {got.tolist()} want {want}")
+    for g_, w_ in zip(got, want):
+        assert abs(g_ - w_) <= 1e-6 * max(1.0, abs(w_)), (g_, w_)
+
+
+def test_explained_variance_does_not_lean_on_its_first_element():
+    """y_true[0] = 0, the rest 1000 + {0, 1} ulp: a first-element pivot would be no better than no pivot."""
+    n = 4096
+    rng = np.random.RandomState(11)
+    yt_a, yt_b = _near_constant(rng, 1000.0, 1, n), _near_constant(rng, 1000.0, 1, n)
+    yt_a[0] = yt_b[0] = 0.0
+    yp_a = (np.float32(1000.0) + 0.5 * rng.randn(n)).astype(np.float32)
+    yp_b = (yt_b + 1000 + 0.01 * rng.randn(n)).astype(np.float32)
+    want = [_ev_want(yp_a, yt_a), _ev_want(yp_b, yt_b)]
+    got = _ev_launch([(yp_a, yt_a), (yp_b, yt_b)], n)
+    print(f"explained variance, first element 0: got {got.tolist()} want {want}")
+    for g_, w_ in zip(got, want):
+        assert abs(g_ - w_) <= 1e-6 * max(1.0, abs(w_)), (g_, w_)
+
+
+@pytest.mark.parametrize("value,n", [(0.05, 300), (0.1, 2048 * 64 + 3), (1000.0, 300)])
+def test_explained_variance_of_a_constant_critic_is_nan(value, n):
+    """np.var of a constant array is exactly 0 (its mean is the constant), so the reference returns NaN — for every constant, not only those whose
+    squares happen to cancel."""
+    from oracle.loop import explained_variance
+    rng = np.random.RandomState(n)
+    yt = np.full(n, value, np.float32)
+    yp_a, yp_b = (value + rng.randn(n)).astype(np.float32), yt.copy()
+    assert np.isnan(explained_variance(yp_a.astype(np.float64), yt.astype(np.float64)))
+    got = _ev_launch([(yp_a, yt), (yp_b, yt)], n)
+    print(f"explained variance of constant {value} x {n}: got {got.tolist()}")
+    assert np.isnan(got[0]) and np.isnan(got[1]), got
+    got = _ev_launch([(yp_a, yt)], n)
+    assert np.isnan(got[0]) and got[1] == 7.0, got
+
+
 class _Outputs:
     """the networks' outputs as autograd leaves: oracle.ppo.minibatch_loss evaluates policy.evaluate_actions(obs, actions)."""
 
