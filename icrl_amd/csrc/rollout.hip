@@ -302,7 +302,10 @@ __device__ __forceinline__ float cost_forward_wave(const icrl_costnet_t& cn, con
 // synthetic env step for env n; called by ONE wave.  act: float32 clipped actions (LDS or global).
 // Returns reward / done in every lane; writes env.s, t_ep, step_count.  s_old: float64 previous state (LDS copy).
 // observation an env (re)starts from: the synthetic envs draw it from their stream, LapGridWorld always starts in cell 0
+// POINT = false: the kernels that do not serve the Point envs (see env_step_wave)
+template <bool POINT = true>
 __device__ __forceinline__ double env_reset_value(const icrl_env_t& e, uint32_t key, uint32_t ctr, int i) {
+  if (POINT && e.reward_form >= 4) return 0.0;    // the Point envs: init_qpos = init_qvel = 0, reset noise scale 0 (point.py:147-160)
   if (e.reward_form >= 2) return -1.0;   // ((0 - 0) * 2) / 40 - 1
   return (unit_uniform(key, ctr, (uint32_t)(e.obs_dim + i)) - 0.5) * 0.2;
 }
@@ -344,9 +347,67 @@ __device__ __forceinline__ void lap_grid_step_wave(const icrl_env_t& e, int n, c
   done = d;
 }
 
+// The Point envs (ref: custom_envs/custom_envs/envs/point.py:22-276; reward_form 4 PointCircle, 5 PointCircleTest,
+// 6 PointCircleTestBack, 7 PointNullReward, 8 PointNullRewardTest; obs 9 = qpos (x, y, ori), qvel (0, 0, 0), torso position
+// (x, y, 0)): closed-form kinematics in float64, one rounding per operation, the reference's operation order.
+// Every lane computes the env's whole step; lane i < 9 stores component i.  Not inlined: the double-precision sincos is a long
+// sequence that would otherwise enter the register allocation of every rollout kernel; so the env's scalars and arrays come in
+// by value, as for env_step_wave3, and the reward / done pair comes back in registers.
+struct PointStep { double rew; int done; };
+__device__ __noinline__ PointStep point_step_wave(int form, int max_steps, double* s_all, int32_t* t_ep_all, uint32_t* step_count_all,
+                                                  int n, double x0, double y0, double ori0, float act0, float act1, uint32_t ctr_new,
+                                                  int tep, double* s_new_lds) {
+  const int lane = threadIdx.x & 63;
+  const double a0 = fmin(fmax((double)act0, -0.25), 0.25);         // point.py:167
+  const double a1 = fmin(fmax((double)act1, -0.25), 0.25);
+  const double ori = ori0 + a1;                                    // :169-170
+  double sn, cs;
+  sincos(ori, &sn, &cs);
+  const double dx = cs * a0, dy = sn * a0;                         // :173-174
+  const double x = fmin(fmax(x0 + dx, -40.0), 40.0);               // :177-178
+  const double y = fmin(fmax(y0 + dy, -40.0), 40.0);
+  double rew = 1.0;                                                // the null reward (:82)
+  if (form <= 6) {                                                 // the circle reward (:185-186)
+    const double num = y * dx - x * dy;
+    rew = num / (1.0 + fabs(sqrt(x * x + y * y) - 10.0));
+  }
+  int d = 0;
+  // STRICT inequalities (:98, :230, :266): x == -3 does not end the episode
+  if ((form == 5 || form == 8) && (x > 3.0 || x < -3.0)) { d = 1; if (form == 5) rew = 0.0; }
+  if (form == 6 && x < -3.0) { d = 1; rew = 0.0; }
+  if (tep >= max_steps) d = 1;                                     // gym's TimeLimit: the reward is kept
+  if (lane < 9) {
+    double v = 0.0;                                                // on done: reset to all zeros (:147-160, noise scale 0)
+    if (!d) v = (lane == 0 || lane == 6) ? x : (lane == 1 || lane == 7) ? y : lane == 2 ? ori : 0.0;
+    as_global(s_all)[(size_t)n * 9 + lane] = v;
+    if (s_new_lds != nullptr) s_new_lds[lane] = v;
+  }
+  if (lane == 0) {
+    as_global(t_ep_all)[n] = d ? 0 : tep;
+    as_global(step_count_all)[n] = ctr_new;
+  }
+  return PointStep{rew, d};
+}
+
+// POINT = false: without the branch to the Point step.  Even a never-taken call constrains the register allocation of its caller
+// (values that live across it must avoid what the callee clobbers): rollout_persistent_kernel, whose step loop is tuned at HC shapes
+// with every register in use, measured 8.2 instead of 8.0 us per step with it, and the chained episode kernel is part of the same
+// headline; both are built without it, and the host routes the Point envs past them (icrl_rollout_collect: the multi-env kernel or
+// the per-step launches; icrl_sample_episodes_chain refuses, the caller then settles the positions pass by pass).
+template <bool POINT = true>
 __device__ __forceinline__ void env_step_wave(const icrl_env_t& e, int n, const double* s_old, const float* act,
                                               uint32_t key, uint32_t& ctr_io, int& tep_io, double* s_new_lds,
                                               double& reward, int& done) {
+  if (POINT && e.reward_form >= 4) {
+    const int tep = tep_io + 1;
+    ctr_io = ctr_io + 1u;
+    const PointStep r = point_step_wave(e.reward_form, e.max_steps, e.s, e.t_ep, e.step_count, n, s_old[0], s_old[1], s_old[2],
+                                        act[0], act[1], ctr_io, tep, s_new_lds);
+    tep_io = r.done ? 0 : tep;
+    reward = r.rew;
+    done = r.done;
+    return;
+  }
   if (e.reward_form >= 2) {
     lap_grid_step_wave(e, n, s_old, act, ctr_io, tep_io, s_new_lds, reward, done);
     return;
@@ -394,7 +455,7 @@ __device__ __forceinline__ void env_step_wave(const icrl_env_t& e, int n, const 
     const int i = lane + r * WAVE;
     if (i < O) {
       double v = ns[r];
-      if (d) v = env_reset_value(e, key, ctr + 1u, i);   // auto-reset draw
+      if (d) v = env_reset_value<false>(e, key, ctr + 1u, i);   // auto-reset draw (the Point envs returned above)
       e.s[(size_t)n * O + i] = v;
       if (s_new_lds != nullptr) s_new_lds[i] = v;
     }
@@ -1064,7 +1125,7 @@ static inline size_t persist_dyn_lds(int N, int O, int A) { return ((size_t)O * 
 // across the step loop of every launch (ppo_train_halves.hip: 2.5 % there)
 // MON: store the raw reward of every step into ActStepArgs.raw_plane (icrl_monitor_t.raw_rewards) — a compile-time variant like PROF: the
 // instantiations without it are the kernels as they were, with not one more value in the step loop's registers
-template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false>
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true>
 __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ ActShared sh;
@@ -1148,7 +1209,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
     __syncthreads();
     if (w == 0) {
       double rew; int done;
-      env_step_wave(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
+      env_step_wave<POINT>(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
       float* nob = buf.new_orig_observations + tn * O;
       if (GRAN) {
         const int rec0 = ((par * N + n) * R16) * 16;       // byte offset of this env's records of this parity
@@ -1610,7 +1671,7 @@ __global__ void __launch_bounds__(256) rollout_generic_kernel(GenRolloutArgs ga)
 
 template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_persistent_kernel(PersistArgs p) {
-  rollout_persistent_body<OCT, CIT, GRAN, PROF, MON>(p);
+  rollout_persistent_body<OCT, CIT, GRAN, PROF, MON, false>(p);      // (without the Point step: env_step_wave)
 }
 
 // several independent runs in ONE launch: grid (N, n_runs), run = blockIdx.y, argument blocks in device memory.  Workgroups are
@@ -3182,7 +3243,7 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const 
   }
   if (tid < O) {
     double v = a.env.s[(size_t)n * O + tid];
-    if (a.do_reset || (CHAIN && n > 0)) v = env_reset_value(a.env, e_key, e_ctr, tid);
+    if (a.do_reset || (CHAIN && n > 0)) v = env_reset_value<!CHAIN>(a.env, e_key, e_ctr, tid);
     sh.s_new[tid] = v;
   }
   if (!CHAIN && a.do_reset) e_tep = 0;
@@ -3215,7 +3276,7 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const 
       const size_t orow = CHAIN ? slot0 + (size_t)ep_len : row;
       if (w == 0) {
         double rew; int done;
-        env_step_wave(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
+        env_step_wave<!CHAIN>(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
         if (lane == 0) { s_done = done; s_rew = rew; }
         if (lane < AS && in_rows) actions_g[orow * AS + lane] = sh.act_clip[lane];
       }
@@ -3891,6 +3952,7 @@ extern "C" int icrl_sample_episodes_chain(int n_jobs, const icrl_chain_job_t* jo
   for (int r = 0; r < n_jobs; ++r) {
     const icrl_chain_job_t& j = jobs[r];
     if (policy_is_wide(j.pol)) return fail("icrl_sample_episodes_chain: refused: job %d has a generic-shape policy", r);
+    if (j.env->reward_form >= 4) return fail("icrl_sample_episodes_chain: refused: job %d steps a Point env (reward_form %d): the chained kernel is built without its step", r, j.env->reward_form);
     if (j.episodes_per_stream != 1) return fail("icrl_sample_episodes_chain: refused: job %d runs %d episodes per stream (1 only)", r, j.episodes_per_stream);
     if ((j.pol->obs_dim <= 32) != (jobs[0].pol->obs_dim <= 32)) return fail("icrl_sample_episodes_chain: refused: job %d and job 0 take different kernels (obs %d / %d)", r, j.pol->obs_dim, jobs[0].pol->obs_dim);
     if (j.env->n_envs < 1 || j.base_count == nullptr) return fail("icrl_sample_episodes_chain: job %d: %d streams, base_count %p", r, j.env->n_envs, (const void*)j.base_count);
@@ -4366,10 +4428,10 @@ static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane)
 //   generic persistent   layers above 64 units / `arch`, cost net within the register image, !(do_gae & 2), N <= 128, N obs <= 4096,
 //                        granule mode, transposed weights                                      rollout_generic_kernel
 //   generic per-step     every other generic shape: four launches per step                      policy_generic | cn_cost_rows | act_step_generic | norm_step
-//   multi                do_gae & 32 or N > 1024; !(do_gae & 2), training, Box actions, multi_shape, workspace      rollout_multi[_analytic]_kernel
+//   multi                do_gae & 32 or N > 1024 or a Point env at N <= 96; !(do_gae & 2), training, Box actions, multi_shape, workspace      rollout_multi[_analytic]_kernel
 //   wide                 !(do_gae & 2), training, N > 96 or N obs > 4096 or do_gae & 16, N <= 1024, <= WIDE_E envs per workgroup,
 //                        grid >= obs + 2, workspace                                             rollout_wide_kernel
-//   persistent           !(do_gae & 2), N <= 128, N obs <= 4096, workspace                      rollout_persistent_kernel
+//   persistent           !(do_gae & 2), not a Point env, N <= 128, N obs <= 4096, workspace       rollout_persistent_kernel
 //   per-step             everything else: two launches per step                                 act_step_kernel | norm_step
 // Routes of a batch (rollout_collect_batch_impl):
 //   multi                !ICRL_BATCH_NO_MULTI, not `few`, Box actions, training, multi_shape, every run has a workspace      rollout_multi_batch[_analytic]_kernel
@@ -4456,7 +4518,9 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   ActStepArgs a;
   fill_act_args(a, env, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
   // several environments per workgroup, interleaved (rollout_multi_kernel): do_gae bit 5
-  if (((do_gae & 32) || N > WIDE_MAX_N) && !(do_gae & 2) && nm->training && !pol->discrete && N <= NORM_MAX_N && T >= 1) {
+  // (the Point envs at the sizes of the one-workgroup-per-env kernel come here too: that kernel is built without their step, env_step_wave)
+  const bool point = env->reward_form >= 4;
+  if (((do_gae & 32) || N > WIDE_MAX_N || (point && N <= 96 && !(do_gae & 16))) && !(do_gae & 2) && nm->training && !pol->discrete && N <= NORM_MAX_N && T >= 1) {
     int E = 0, G = 0;
     const int n_stats = O + (cn ? 2 : 1);
     char* ws = exchange_ws(ag, buf, wide_ws_bytes(N, O));
@@ -4503,7 +4567,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   {
     const bool gran = (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX;
     char* ws = exchange_ws(ag, buf, persist_ws_bytes(N, O, gran));
-    if (!(do_gae & 2) && N <= 128 && N * O <= NORM_CHUNK && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1 && ws != nullptr) {
+    if (!(do_gae & 2) && !point && N <= 128 && N * O <= NORM_CHUNK && O * env->act_dim <= MAX_OBS * MAX_ACT && T >= 1 && ws != nullptr) {
       PersistArgs p;
       p.act = a; p.nm = *nm; p.T = T; p.prof = (do_gae & 4) != 0;
       const size_t clear = persist_ws_carve(ws, N, O, gran, p);

@@ -12,13 +12,17 @@ load torch or the HIP library.
 """
 import importlib
 
-# reference gym ids (custom_envs/__init__.py:43-57,194-224,357-370) -> (kind, early termination, broken): the device-resident
+# reference gym ids (custom_envs/__init__.py:43-57,123-163,194-224,357-370) -> (kind, early termination, broken): the device-resident
 # synthetic envs of vec_env.HipSynthVecEnv (vec_env.ENV_IDS is this dict)
 ENV_IDS = {
     "HCWithPos-v0": ("hc", False, False), "HCWithPosTest-v0": ("hc", True, False),
     "AntWall-v0": ("ant", False, False), "AntWallTest-v0": ("ant", True, False),
     "AntWallBroken-v0": ("ant", False, True), "AntWallBrokenTest-v0": ("ant", True, True),
     "LGW-v0": ("lgw", False, False), "CLGW-v0": ("clgw", True, False),
+    # custom_envs/__init__.py:123-163 — the Point envs, stepped exactly; the three Test ids end an episode at the wall
+    "PointCircle-v0": ("point_circle", False, False), "PointCircleTest-v0": ("point_circle_test", True, False),
+    "PointCircleTestBack-v0": ("point_circle_test_back", True, False),
+    "PointNullReward-v0": ("point_null", False, False), "PointNullRewardTest-v0": ("point_null_test", True, False),
 }
 
 _REGISTRY = {}

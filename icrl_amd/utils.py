@@ -226,7 +226,9 @@ class EpisodeRun:
     def chain_ok(self):
         """what icrl_sample_episodes_chain serves: one episode per stream, more than one stream, a policy of the one-workgroup-per-env
         kernels (the entry point itself refuses the rest: more streams than compute units)."""
-        return chain_enabled() and self.n_streams > 1 and self.n_streams == self.n_episodes and not self.pol.wide
+        # (the Point envs, reward_form >= 4: the chained kernel is built without their step — csrc/rollout.hip env_step_wave — and the entry
+        # point refuses them; their positions are settled pass by pass)
+        return chain_enabled() and self.n_streams > 1 and self.n_streams == self.n_episodes and not self.pol.wide and self.senv.reward_form < 4
 
     def prepare_chain(self):
         senv, dev, O, A, n = self.senv, self.dev, self.O, self.A, self.n_streams

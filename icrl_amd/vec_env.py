@@ -27,16 +27,22 @@ from .structs import EnvT, NormT, p
 # kind -> obs, act (width of the action vector handed to the env), max_episode_steps, reward form (icrl_env_t.reward_form)
 KINDS = {"hc": (18, 6, 1000, 0), "ant": (113, 8, 500, 1),
          # LapGridWorld / ConstrainedLapGridWorld restated exactly (custom_envs/envs/lap_grid_world.py:29-240): Discrete(2)
-         "lgw": (1, 1, 200, 2), "clgw": (1, 1, 200, 3)}
+         "lgw": (1, 1, 200, 2), "clgw": (1, 1, 200, 3),
+         # the Point envs restated exactly (custom_envs/envs/point.py:22-276, custom_envs/__init__.py:123-163):
+         # obs = qpos (x, y, ori), qvel (0, 0, 0), torso position (x, y, 0)
+         "point_circle": (9, 2, 150, 4), "point_circle_test": (9, 2, 150, 5), "point_circle_test_back": (9, 2, 150, 6),
+         "point_null": (9, 2, 150, 7), "point_null_test": (9, 2, 150, 8)}
 DISCRETE_ACTIONS = {"lgw": 2, "clgw": 2}
+POINT_KINDS = ("point_circle", "point_circle_test", "point_circle_test_back", "point_null", "point_null_test")
+POINT_CTRL = 0.25        # the actuators' ctrlrange (xmls/point_circle.xml); the env clips to it again (point.py:167)
 ENV_IDS = _ENV_IDS   # reference gym ids -> (kind, early termination, broken); defined in envs.py (no torch there)
 
 
 def dynamics_matrix(kind):
     """B ~ N(0, 0.05^2) drawn once from RandomState(1234)."""
     o, a, _, _ = KINDS[kind]
-    if kind in DISCRETE_ACTIONS:
-        return np.zeros((o, a), np.float64)      # no linear dynamics: the grid world is stepped exactly
+    if kind in DISCRETE_ACTIONS or kind in POINT_KINDS:
+        return np.zeros((o, a), np.float64)      # no linear dynamics: the grid world and the Point envs are stepped exactly
     return (np.random.RandomState(1234).randn(o, a) * 0.05).astype(np.float64)
 
 
@@ -120,7 +126,7 @@ def _as_device_f32(x, device):
 
 
 class HipSynthVecEnv(VecEnv):
-    """N synthetic HCWithPos-/AntWall-shaped envs (or exact LapGridWorlds) stepped by one kernel launch; float64 state in HBM."""
+    """N synthetic HCWithPos-/AntWall-shaped envs (or exact LapGridWorlds / Point envs) stepped by one kernel launch; float64 state in HBM."""
 
     def __init__(self, n_envs, kind="hc", seed=0, env_index_offset=0, wall_terminate=False, broken=False, device="cuda"):
         self.kind, self.device = kind, torch.device(device)
@@ -130,6 +136,8 @@ class HipSynthVecEnv(VecEnv):
         if kind in DISCRETE_ACTIONS:
             # ref: lap_grid_world.py:50-53 — Box(0, 40) float32 observation space (the env itself emits 2 pos / 40 - 1)
             super().__init__(n_envs, spaces.Box(0.0, 40.0, (o,), np.float32), spaces.Discrete(DISCRETE_ACTIONS[kind]))
+        elif kind in POINT_KINDS:
+            super().__init__(n_envs, spaces.Box(-np.inf, np.inf, (o,), np.float64), spaces.Box(-POINT_CTRL, POINT_CTRL, (a,), np.float32))
         else:
             super().__init__(n_envs, spaces.Box(-np.inf, np.inf, (o,), np.float64), spaces.Box(-1.0, 1.0, (a,), np.float32))
         dev = self.device

@@ -55,7 +55,11 @@ typedef struct {
   int32_t n_envs, obs_dim, act_dim, max_steps;
   int32_t reward_form;    /* 0: |dx|/dt - 0.1|a|^2 (HC)   1: |xy| + 1 - 0.5|a|^2 (Ant)
                            * 2: LapGridWorld, 3: ConstrainedLapGridWorld (custom_envs/envs/lap_grid_world.py:62-240;
-                           *    obs_dim 1, act_dim 1 = the Discrete(2) action index as a float; B / key unused) */
+                           *    obs_dim 1, act_dim 1 = the Discrete(2) action index as a float; B / key unused)
+                           * 4: PointCircle, 5: PointCircleTest (ends at |x| > 3), 6: PointCircleTestBack (ends at x < -3),
+                           * 7: PointNullReward, 8: PointNullRewardTest (custom_envs/envs/point.py:22-276 stepped exactly;
+                           *    obs_dim 9, act_dim 2, max_steps 150; B / key unused; the variant decides how an episode
+                           *    ends, wall_terminate is not read) */
   int32_t wall_terminate; /* "Test" variants: done & reward 0 when obs[0] <= -3 */
   int32_t broken;         /* AntWallBroken: action[4:] = 0 */
   int32_t _pad;

@@ -1,4 +1,5 @@
-"""rollout timing: persistent launch vs the per-step launch pairs, at HC x 64 / HC x 256 / AntWall x 256 / AntWallBroken x 512."""
+"""rollout timing: persistent launch vs the per-step launch pairs, at HC x 64 / HC x 256 / AntWall x 256 / AntWallBroken x 512
+(CFGS=point64: PointCircle x 64 with the reference's Point transfer constraint net)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -7,10 +8,14 @@ from icrl_amd.vec_env import HipSynthVecEnv, VecCostWrapper, VecNormalizeWithCos
 from icrl_amd.constraint_net import ConstraintNet
 
 def run(kind, N, T, broken=False):
-    od, ad = (18, 6) if kind == "hc" else (113, 8)
     env = VecNormalizeWithCost(VecCostWrapper(HipSynthVecEnv(N, kind, 0, broken=broken)))
-    lo = -np.ones(ad, np.float32)
-    cn = ConstraintNet(od, ad, [20] if kind == "hc" else [40, 40], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
+    od, ad = env.unwrapped.obs_dim, env.unwrapped.act_dim
+    if kind.startswith("point"):      # the reference's AntWall -> Point transfer net on (x, y), as `cpg -cosd 0 1 -casd -1` loads it
+        cn = ConstraintNet.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests/golden/ref_artifacts/point_best_cn_model.pt"),
+                                obs_dim=od, acs_dim=ad, obs_select_dim=[0, 1], acs_select_dim=[-1])
+    else:
+        lo = -np.ones(ad, np.float32)
+        cn = ConstraintNet(od, ad, [20] if kind == "hc" else [40, 40], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
     env.set_cost_function(cn.cost_function)
     agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, batch_size=64, seed=0)
     agent._setup_learn(N * T)
@@ -82,6 +87,7 @@ def run(kind, N, T, broken=False):
               f"(latest: workgroups {np.argsort(-tr[:, 2])[:4].tolist()}, {np.sort(us(tr[:, 2]))[-4:][::-1].round(1).tolist()}); statistics read {us(tr[:, 3]).min():.1f}..{us(tr[:, 3]).max():.1f}")
         agent.profile_phases = 0
 
-CFGS = dict(hc64=("hc", 64, 2048), hc256=("hc", 256, 1024), ant256=("ant", 256, 512), antb512=("ant", 512, 256, True), hc128=("hc", 128, 1024), hc16=("hc", 16, 2048))
+CFGS = dict(hc64=("hc", 64, 2048), hc256=("hc", 256, 1024), ant256=("ant", 256, 512), antb512=("ant", 512, 256, True), hc128=("hc", 128, 1024), hc16=("hc", 16, 2048),
+            ant256x2048=("ant", 256, 2048), point64=("point_circle", 64, 2048))
 for name in os.environ.get("CFGS", "hc64,hc256,ant256,antb512").split(","):
     run(*CFGS[name])
