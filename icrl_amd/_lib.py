@@ -52,6 +52,7 @@ SIGNATURES = {
     "icrl_cn_prepare": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "icrl_cn_train_work_floats": [c_int, c_int, c_int, c_int],
     "icrl_cn_train": [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "icrl_debug_last_route": [c_int, c_void_p],
     "icrl_debug_rollout_profile": [c_void_p],
     "icrl_debug_rollout_profile_wide": [c_void_p],
     "icrl_debug_rollout_trace_wide": [c_void_p, c_int],
@@ -120,6 +121,23 @@ def check(err, what):
             lib().icrl_clear_error()
             raise ValueError(f"{what}: {reason}")
         raise RuntimeError(f"{what} failed with hipError_t {err}")
+
+
+# icrl_debug_last_route: families, and the codes of word 0 by family (include/icrl_hip.h)
+FAMILY_ROLLOUT, FAMILY_UPDATE, FAMILY_GAE = 0, 1, 2
+ROUTE = {"none": 0, "per-step": 1, "persistent": 2, "wide": 3, "multi": 4, "generic-persistent": 5, "generic-per-step": 6,
+         "persistent-batch": 7, "multi-batch": 8}
+WS_NONE, WS_XCH, WS_PLANE = 0, 1, 2
+PICK_SMALL, PICK_ANALYTIC, PICK_MON, PICK_GRAN, PICK_CN128, PICK_MINW_SHIFT = 1, 2, 4, 8, 16, 8
+UPDATE_GENERIC_PERSISTENT, UPDATE_GENERIC_LAUNCHES = 8, 9
+GAE_ROUTE = {"none": 0, "sequential": 1, "split": 2, "regsplit": 3, "batch-split": 4, "batch-regsplit": 5, "batch-singles": 6}
+
+
+def last_route(family):
+    """The eight words icrl_debug_last_route keeps for `family`: what this host thread's last call of that family launched."""
+    out = (ctypes.c_int32 * 8)()
+    check(lib().icrl_debug_last_route(int(family), out), "icrl_debug_last_route")
+    return list(out)
 
 
 def ptr(t):

@@ -37,6 +37,9 @@ inline bool costnet_is_wide(const icrl_costnet_t* cn) { return cn->n_hidden > 2 
 
 // argument rejection: formats the reason into the calling thread's icrl_last_error() text, returns hipErrorInvalidValue
 int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// what a fused call launched, for icrl_debug_last_route (errors.hip; the words per family: include/icrl_hip.h).  An entry point clears its
+// family's record on entry (note_route(family)) and writes it where its ladder returns after a launch, never where a route is only considered
+void note_route(int family, int w0 = 0, int w1 = 0, int w2 = 0, int w3 = 0, int w4 = 0, int w5 = 0, int w6 = 0, int w7 = 0);
 
 // ---------------------------------------------------------------------------------------------------------------
 // argument blocks of a BATCHED launch (several independent runs in one grid, run = blockIdx.y): the kernels read block

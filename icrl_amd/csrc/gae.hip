@@ -606,6 +606,7 @@ extern "C" int icrl_gae_dual_ws(const float* rewards, const float* costs, const 
                                 float* ret_r, float* ret_c, int T, int N, double reward_gamma, double reward_gae_lambda,
                                 double cost_gamma, double cost_gae_lambda, int waves_per_tile, void* ws, long long ws_bytes,
                                 void* stream) {
+  icrl::note_route(ICRL_FAMILY_GAE);
   if (T <= 0 || N <= 0) return fail("icrl_gae_dual: T = %d, N = %d", T, N);
   GaeArgs a{rewards, costs, reward_values, cost_values, dones, last_v_r, last_v_c, last_dones,
             adv_r, adv_c, ret_r, ret_c, T, N,
@@ -619,6 +620,12 @@ extern "C" int icrl_gae_dual_ws(const float* rewards, const float* costs, const 
     while (W > 1 && T / W < 2 * U_DEFAULT) W /= 4;
   }
   hipStream_t s = (hipStream_t)stream;
+  // the route record (shape code or C | tiles | one run), written behind the launch that ran
+  auto routed = [&](int route, int code) {
+    const int err = (int)hipGetLastError();
+    if (err == 0) icrl::note_route(ICRL_FAMILY_GAE, route, code, tiles, 1);
+    return err;
+  };
   // the last word of the workspace is the launch's STATUS word (0; 1: a bounded wait for another workgroup's map expired — the outputs are
   // then invalid; icrl_amd/buffers.py reads it next to the update's statistics)
   unsigned* status = ws != nullptr && ws_bytes >= 16 ? reinterpret_cast<unsigned*>((char*)ws + (ws_bytes & ~7ll) - 4) : nullptr;
@@ -641,7 +648,7 @@ extern "C" int icrl_gae_dual_ws(const float* rewards, const float* costs, const 
       // non-temporal loads / stores once the arrays are beyond what the caches hold (> 128 tiles x 2048 rows x 36 B = 600 MB)
       if ((long long)tiles * T > 128ll * 2048) hipLaunchKernelGGL((gae_dual_regsplit_kernel<true>), dim3(tiles * C), dim3(64 * RS_W), 0, s, a, C, tag, maps, flags, status, spin_limit, fault, tile_major);
       else hipLaunchKernelGGL((gae_dual_regsplit_kernel<false>), dim3(tiles * C), dim3(64 * RS_W), 0, s, a, C, tag, maps, flags, status, spin_limit, fault, tile_major);
-      return (int)hipGetLastError();
+      return routed(ICRL_GAE_REGSPLIT, C);
     }
     if (waves_per_tile != 0) return fail("icrl_gae_dual_ws: the register-resident split scan needs T <= %d and %lld B of workspace + 8 (T = %d, %lld given)", RS_TC * RS_CMAX, need, T, ws_bytes);
   }
@@ -660,7 +667,7 @@ extern "C" int icrl_gae_dual_ws(const float* rewards, const float* costs, const 
       double* maps = (double*)ws;
       unsigned* flags = (unsigned*)(maps + (size_t)tiles * C * 256);
       hipLaunchKernelGGL(gae_dual_split_kernel, dim3(tiles * C), dim3(64 * SPLIT_W), 0, s, a, C, tag, maps, flags, status, spin_limit, fault);
-      return (int)hipGetLastError();
+      return routed(ICRL_GAE_SPLIT, C);
     }
     if (waves_per_tile >= 200) return fail("icrl_gae_dual_ws: split %d needs 2..%d workgroups per tile and %lld B of workspace + 8 (%lld given)", waves_per_tile - 200, SPLIT_CMAX, need, ws_bytes);
   }
@@ -687,7 +694,7 @@ extern "C" int icrl_gae_dual_ws(const float* rewards, const float* costs, const 
   else if (shape == 4) hipLaunchKernelGGL((gae_dual_kernel<4, 8, false>), dim3(tiles), dim3(256), 0, s, a);
   else if (shape == 16) hipLaunchKernelGGL((gae_dual_kernel<16, 8, false>), dim3(tiles), dim3(1024), 0, s, a);
   else return fail("icrl_gae_dual_ex: waves_per_tile = %d (0 = automatic, 1, 4, 16 or a shape code 101 / 105 / 106, 107..112 with N %% 4 == 0)", waves_per_tile);
-  return (int)hipGetLastError();
+  return routed(ICRL_GAE_SEQUENTIAL, shape);
 }
 
 extern "C" size_t icrl_gae_dual_ws_bytes(int T, int N) {
@@ -735,7 +742,7 @@ extern "C" int icrl_debug_stream_ref(const float* in0, const float* in1, const f
   return (int)hipGetLastError();
 }
 
-extern "C" int icrl_abi_version(void) { return 106; }
+extern "C" int icrl_abi_version(void) { return 107; }
 
 // icrl_gae_dual_ws for n_runs rollouts of one shape in ONE launch (the loop-size launches of several runs sharing a GPU): the
 // two-level scan over workgroups, every run with its own workspace.  Shapes the split scan does not serve (> 128 column tiles, T too
@@ -743,6 +750,7 @@ extern "C" int icrl_abi_version(void) { return 106; }
 extern "C" int icrl_gae_dual_batch(int n_runs, const icrl_gae_job_t* jobs, int T, int N, double reward_gamma, double reward_gae_lambda,
                                    double cost_gamma, double cost_gae_lambda, void* args_ws, long long args_ws_bytes, void* stream) {
   static_assert(sizeof(GaeRun) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  icrl::note_route(ICRL_FAMILY_GAE);
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_gae_dual_batch: n_runs = %d (1..65535)", n_runs);
   if (T <= 0 || N <= 0) return fail("icrl_gae_dual_batch: T = %d, N = %d", T, N);
   hipStream_t s = (hipStream_t)stream;
@@ -767,6 +775,10 @@ extern "C" int icrl_gae_dual_batch(int n_runs, const icrl_gae_job_t* jobs, int T
                                      j.ws, j.ws_bytes, stream);
       if (e) return e;
     }
+    // (every single launch wrote its own record: the batch's replaces the last one, with that launch's shape code or C)
+    int32_t last[8];
+    icrl_debug_last_route(ICRL_FAMILY_GAE, last);
+    icrl::note_route(ICRL_FAMILY_GAE, ICRL_GAE_BATCH_SINGLES, last[1], tiles, n_runs);
     return 0;
   }
   GaeRun* d_runs = (GaeRun*)args_ws;
@@ -785,7 +797,9 @@ extern "C" int icrl_gae_dual_batch(int n_runs, const icrl_gae_job_t* jobs, int T
   if (!regs) hipLaunchKernelGGL(gae_dual_split_batch_kernel, dim3(tiles * C, n_runs), dim3(64 * SPLIT_W), 0, s, d_runs, C, next_split_tag());
   else if ((long long)tiles * T > 128ll * 2048) hipLaunchKernelGGL((gae_dual_regsplit_batch_kernel<true>), dim3(tiles * C, n_runs), dim3(64 * RS_W), 0, s, d_runs, C, next_split_tag());
   else hipLaunchKernelGGL((gae_dual_regsplit_batch_kernel<false>), dim3(tiles * C, n_runs), dim3(64 * RS_W), 0, s, d_runs, C, next_split_tag());
-  return (int)hipGetLastError();
+  const int err = (int)hipGetLastError();
+  if (err == 0) icrl::note_route(ICRL_FAMILY_GAE, regs ? ICRL_GAE_BATCH_REGSPLIT : ICRL_GAE_BATCH_SPLIT, C, tiles, n_runs);
+  return err;
 }
 
 namespace icrl {

@@ -1442,7 +1442,9 @@ static int launch_train_generic_persistent(const GenNet& net, GenArgs& a, const 
   }
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(gen_transpose_kernel, dim3((n + 255) / 256), dim3(256), 0, s, net, a.params, a.params_t);      // the forward / sampling kernels read params_t
-  return (int)hipGetLastError();
+  e = hipGetLastError();
+  if (e == hipSuccess) note_route(ICRL_FAMILY_UPDATE, ICRL_UPDATE_GENERIC_PERSISTENT, H, 1, packed);      // (no per-network workgroups: H in all)
+  return (int)e;
 }
 
 // perm_off: the permutations already mapped to storage offsets (prepare in ppo_train.hip); scratch: ICRL_PPO_GENERIC_BYTES
@@ -1487,7 +1489,9 @@ int launch_train_generic(const icrl_policy_t* pol, float* exp_avg, float* exp_av
       hipLaunchKernelGGL(gen_adam_kernel, dim3(nblk), dim3(256), 0, s, net, a, tiled ? n_tiles : nblk, step, ep, mb, nb, last ? 0 : nep * a.n_total + np0, next_nb);
     }
   hipLaunchKernelGGL(gen_finish_kernel, dim3(1), dim3(1), 0, s, a, adam_step);
-  return (int)hipGetLastError();
+  const int err = (int)hipGetLastError();
+  if (err == 0) note_route(ICRL_FAMILY_UPDATE, ICRL_UPDATE_GENERIC_LAUNCHES, 0, 1, 0);
+  return err;
 }
 
 // floats one row's activation record takes (the `row_floats` argument of ICRL_PPO_GENERIC_BYTES), or -1 (reason in icrl_last_error)

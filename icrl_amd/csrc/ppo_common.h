@@ -149,15 +149,17 @@ inline int packed_grid(int M, int n_runs) {
   if (off || groups * M > cus_per_xcd - 2) return 0;
   return n_runs >= XCD_STRIDE ? groups * XCD_STRIDE * M : XCD_STRIDE * (M - 1) + n_runs;
 }
-// a single-run update launch: the packed 1-D grid as a cooperative launch; a device or partition that refuses it
+// a single-run update launch (*packed: the layout it ran in, for the route record): the packed 1-D grid as a cooperative launch; a device or partition that refuses it
 // (hipErrorCooperativeLaunchTooLarge: 8 (M - 1) + 1 workgroups of which M work) gets the plain M-workgroup grid
 template <class K>
-inline int launch_update_single(K kernel, int M, dim3 block, size_t dyn_lds, hipStream_t s, TrainArgs& arg) {
+inline int launch_update_single(K kernel, int M, dim3 block, size_t dyn_lds, hipStream_t s, TrainArgs& arg, int* packed) {
   const int pg = packed_grid(M, 1);
   hipError_t e = launch_coresident(kernel, dim3(pg ? pg : M), block, dyn_lds, s, arg, pg ? 1 : 0);
+  *packed = pg != 0;
   if (e == hipErrorCooperativeLaunchTooLarge && pg) {
     (void)hipGetLastError();
     e = launch_coresident(kernel, dim3(M), block, dyn_lds, s, arg, 0);
+    *packed = 0;
   }
   return (int)e;
 }
@@ -169,22 +171,22 @@ inline int launch_update_single(K kernel, int M, dim3 block, size_t dyn_lds, hip
 #endif
 
 // ppo_train_rows.hip: row-owning-wave kernel (nt1 = ceil(obs / 16) <= 8), one wave per SIMD
-int launch_train_rows(const TrainArgs& a, int nt1, bool discrete, bool split, hipStream_t s);
+int launch_train_rows(const TrainArgs& a, int nt1, bool discrete, bool split, hipStream_t s, int* packed);
 // ppo_train_pairs.hip: wave-pair kernel, two waves per SIMD (nt1 rounded up to an even tile count)
-int launch_train_pairs(const TrainArgs& a, int nt1, bool discrete, hipStream_t s);
+int launch_train_pairs(const TrainArgs& a, int nt1, bool discrete, hipStream_t s, int* packed);
 // ppo_train_halves.hip: two workgroups per network, wave quads (nt1 <= 2; single-run launches; a.gx set)
 // parts = 2 | 4 workgroups per network (round 6: four — 16 rows of every chunk each)
-int launch_train_halves(const TrainArgs& a, bool discrete, int parts, hipStream_t s);
-int launch_train_halves_batch(const TrainArgs* d_args, int n_runs, int obs, bool discrete, int parts, bool prof, hipStream_t s);      // prof: hp._pad & 1 (the runs of a batch share it)
+int launch_train_halves(const TrainArgs& a, bool discrete, int parts, hipStream_t s, int* packed);
+int launch_train_halves_batch(const TrainArgs* d_args, int n_runs, int obs, bool discrete, int parts, bool prof, hipStream_t s, int* packed);      // prof: hp._pad & 1 (the runs of a batch share it)
 // ppo_train_quarters.hip: four workgroups per network at obs 65..128 (wave quads, the row-owning kernel's parameter ownership); single-run launches
-int launch_train_quarters_wide(const TrainArgs& a, bool discrete, hipStream_t s);
+int launch_train_quarters_wide(const TrainArgs& a, bool discrete, hipStream_t s, int* packed);
 // ppo_train_quarters2.hip: the same for minibatches of 65..128 rows: both chunks in one pass, two row tiles per wave (chunk plan with two entries per step)
-int launch_train_quarters_wide2(const TrainArgs& a, bool discrete, hipStream_t s);
+int launch_train_quarters_wide2(const TrainArgs& a, bool discrete, hipStream_t s, int* packed);
 constexpr int HALVES_MAX_RUNS = 40;      // batched launches: 6 workgroups per run, 5 groups of 8 runs = 30 workgroups per XCD (packed_grid)
 constexpr int QUARTERS_MAX_RUNS = 16;    // 12 workgroups per run, 2 groups of 8 runs = 24 workgroups per XCD
 // batched forms: n_runs argument blocks in DEVICE memory, grid.y = run
-int launch_train_rows_batch(const TrainArgs* d_args, int n_runs, int nt1, bool discrete, bool split, hipStream_t s);
-int launch_train_pairs_batch(const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s);
+int launch_train_rows_batch(const TrainArgs* d_args, int n_runs, int nt1, bool discrete, bool split, hipStream_t s, int* packed);
+int launch_train_pairs_batch(const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s, int* packed);
 
 
 }  // namespace icrl

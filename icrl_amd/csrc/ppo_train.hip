@@ -904,7 +904,8 @@ __global__ void ppo_plan_kernel(const int* adam_t, int n_steps, int n_mb, int n_
 using namespace icrl;
 
 template <int NT1, bool DISC>
-static int launch_train(const TrainArgs& a, hipStream_t s) {
+static int launch_train(const TrainArgs& a, hipStream_t s, int* packed) {
+  *packed = 0;      // (three workgroups, no packed form)
   static_assert(Smem<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   const size_t bytes = (size_t)Smem<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_kernel<NT1, DISC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -1032,6 +1033,14 @@ static int train_generic(const icrl_policy_t* pol, float* exp_avg, float* exp_av
   return err;
 }
 
+// the route record of a launched update, its one writer (the generic-shape path has its own in generic.hip): workgroups per network
+// of `kind` (prepare_train) and the grid layout the launcher reported, behind the launcher's error
+static int routed_update(int err, int kind, int n_runs, int packed) {
+  static const int wgs[8] = {1, 1, 2, 1, 2, 4, 4, 4};
+  if (err == 0) note_route(ICRL_FAMILY_UPDATE, kind, wgs[kind], n_runs, packed);
+  return err;
+}
+
 extern "C" int icrl_ppo_generic_row_floats(const icrl_policy_t* pol) { return generic_row_floats(pol); }
 
 extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
@@ -1039,29 +1048,33 @@ extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, floa
                                   const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream) {
   TrainArgs a;
   hipStream_t s = (hipStream_t)stream;
-  if (policy_is_wide(pol) || hp->batch_size > MAXB)
+  note_route(ICRL_FAMILY_UPDATE);
+  if (policy_is_wide(pol) || hp->batch_size > MAXB)      // (kinds 8 / 9: written by launch_train_generic)
     return train_generic(pol, exp_avg, exp_avg_sq, adam_step, buf, perms, nu, hp, stats, sync_ws, s);
   int err = 0;
   const int kind = prepare_train(pol, exp_avg, exp_avg_sq, adam_step, buf, perms, nu, hp, stats, sync_ws, s, a, &err, 1);
   if (kind < 0) return err;
   const int nt1 = (pol->obs_dim + 15) / 16;
-  if (kind == 4 || kind == 5) return launch_train_halves(a, pol->discrete != 0, kind == 5 ? 4 : 2, s);
-  if (kind == 6) return launch_train_quarters_wide(a, pol->discrete != 0, s);
-  if (kind == 7) return launch_train_quarters_wide2(a, pol->discrete != 0, s);
-  if (kind == 0) return launch_train_pairs(a, nt1, pol->discrete != 0, s);
-  if (kind <= 2) return launch_train_rows(a, nt1, pol->discrete != 0, kind == 2, s);
+  int packed = 0;
+  auto routed = [&](int e) { return routed_update(e, kind, 1, packed); };
+  if (kind == 4 || kind == 5) return routed(launch_train_halves(a, pol->discrete != 0, kind == 5 ? 4 : 2, s, &packed));
+  if (kind == 6) return routed(launch_train_quarters_wide(a, pol->discrete != 0, s, &packed));
+  if (kind == 7) return routed(launch_train_quarters_wide2(a, pol->discrete != 0, s, &packed));
+  if (kind == 0) return routed(launch_train_pairs(a, nt1, pol->discrete != 0, s, &packed));
+  if (kind <= 2) return routed(launch_train_rows(a, nt1, pol->discrete != 0, kind == 2, s, &packed));
   if (pol->discrete) {
-    if (nt1 <= 2) return launch_train<2, true>(a, s);
-    if (nt1 <= 4) return launch_train<4, true>(a, s);
-    return launch_train<8, true>(a, s);
+    if (nt1 <= 2) return routed(launch_train<2, true>(a, s, &packed));
+    if (nt1 <= 4) return routed(launch_train<4, true>(a, s, &packed));
+    return routed(launch_train<8, true>(a, s, &packed));
   }
-  if (nt1 <= 2) return launch_train<2, false>(a, s);
-  if (nt1 <= 4) return launch_train<4, false>(a, s);
-  return launch_train<8, false>(a, s);
+  if (nt1 <= 2) return routed(launch_train<2, false>(a, s, &packed));
+  if (nt1 <= 4) return routed(launch_train<4, false>(a, s, &packed));
+  return routed(launch_train<8, false>(a, s, &packed));
 }
 
 extern "C" int icrl_ppo_lag_train_batch(int n_runs, const icrl_ppo_train_job_t* jobs, void* args_ws, long long args_ws_bytes,
                                         void* stream) {
+  note_route(ICRL_FAMILY_UPDATE);
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_ppo_lag_train_batch: n_runs = %d (1..65535)", n_runs);
   if (args_ws == nullptr || args_ws_bytes < (long long)n_runs * (long long)sizeof(TrainArgs))
     return fail("icrl_ppo_lag_train_batch: args_ws holds %lld B, %d runs need %lld (ICRL_BATCH_ARGS_BYTES each)", args_ws_bytes, n_runs,
@@ -1069,7 +1082,7 @@ extern "C" int icrl_ppo_lag_train_batch(int n_runs, const icrl_ppo_train_job_t* 
   static_assert(sizeof(TrainArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
   hipStream_t s = (hipStream_t)stream;
   TrainArgs* d_args = (TrainArgs*)args_ws;
-  int kind0 = -1;
+  int kind0 = -1, packed = 0;
   const icrl_ppo_train_job_t& j0 = jobs[0];
   for (int r = 0; r < n_runs; ++r) {
     const icrl_ppo_train_job_t& j = jobs[r];
@@ -1083,13 +1096,15 @@ extern "C" int icrl_ppo_lag_train_batch(int n_runs, const icrl_ppo_train_job_t* 
     if (kind < 0) return err;
     if (kind == 3) return fail("icrl_ppo_lag_train_batch: the column-split tiles kernel (hp->_pad & 2) has no batched form");
     if (r == 0) kind0 = kind;
-    if (kind == 6) return launch_train_quarters_wide(a, j.pol->discrete != 0, s);      // (a one-run batch at obs 65..128: the single-run launch)
-    if (kind == 7) return launch_train_quarters_wide2(a, j.pol->discrete != 0, s);
+    if (kind == 6) { const int e = launch_train_quarters_wide(a, j.pol->discrete != 0, s, &packed); return routed_update(e, kind, 1, packed); }      // (a one-run batch at obs 65..128: the single-run launch)
+    if (kind == 7) { const int e = launch_train_quarters_wide2(a, j.pol->discrete != 0, s, &packed); return routed_update(e, kind, 1, packed); }
     const int e = put_args(a, d_args + r, s);
     if (e != 0) return e;
   }
   const int nt1 = (j0.pol->obs_dim + 15) / 16;
-  if (kind0 == 4 || kind0 == 5) return launch_train_halves_batch(d_args, n_runs, j0.pol->obs_dim, j0.pol->discrete != 0, kind0 == 5 ? 4 : 2, (j0.hp->_pad & 1) != 0, s);
-  if (kind0 == 0) return launch_train_pairs_batch(d_args, n_runs, j0.pol->obs_dim, nt1, j0.pol->discrete != 0, (j0.hp->_pad & 1) != 0, s);
-  return launch_train_rows_batch(d_args, n_runs, nt1, j0.pol->discrete != 0, kind0 == 2, s);
+  int err;
+  if (kind0 == 4 || kind0 == 5) err = launch_train_halves_batch(d_args, n_runs, j0.pol->obs_dim, j0.pol->discrete != 0, kind0 == 5 ? 4 : 2, (j0.hp->_pad & 1) != 0, s, &packed);
+  else if (kind0 == 0) err = launch_train_pairs_batch(d_args, n_runs, j0.pol->obs_dim, nt1, j0.pol->discrete != 0, (j0.hp->_pad & 1) != 0, s, &packed);
+  else err = launch_train_rows_batch(d_args, n_runs, nt1, j0.pol->discrete != 0, kind0 == 2, s, &packed);
+  return routed_update(err, kind0, n_runs, packed);
 }

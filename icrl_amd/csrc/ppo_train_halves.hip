@@ -1071,36 +1071,37 @@ __global__ void __launch_bounds__(THH) ppo_train_halves_batch_kernel(const Train
 }
 
 template <int NT1, bool DISC, int OBS, int NQ, bool PROF>
-static int launch_halves(const TrainArgs* one, const TrainArgs* d_args, int n_runs, hipStream_t s) {
+static int launch_halves(const TrainArgs* one, const TrainArgs* d_args, int n_runs, hipStream_t s, int* packed) {
   static_assert(SmemH<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   if (one != nullptr) {
     TrainArgs arg = *one;
-    return launch_update_single(ppo_train_halves_kernel<NT1, DISC, OBS, NQ, PROF>, 3 * NQ, dim3(THH), 0, s, arg);
+    return launch_update_single(ppo_train_halves_kernel<NT1, DISC, OBS, NQ, PROF>, 3 * NQ, dim3(THH), 0, s, arg, packed);
   }
   const int pg = packed_grid(3 * NQ, n_runs);
   hipLaunchKernelGGL((ppo_train_halves_batch_kernel<NT1, DISC, OBS, NQ, PROF>), pg ? dim3(pg) : dim3(3 * NQ, n_runs), dim3(THH), 0, s, d_args, n_runs, pg ? 1 : 0);
+  *packed = pg != 0;
   return (int)hipGetLastError();
 }
 
 template <int NQ, bool PROF>
-static int dispatch_halves_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, bool discrete, hipStream_t s) {
-  if (!discrete && obs == 18) return launch_halves<2, false, 18, NQ, PROF>(one, d_args, n_runs, s);      // HCWithPos (BASELINE configs[1], [3])
-  if (discrete && obs == 1) return launch_halves<2, true, 1, NQ, PROF>(one, d_args, n_runs, s);          // LapGridWorld (configs[0])
-  return discrete ? launch_halves<2, true, 0, NQ, PROF>(one, d_args, n_runs, s) : launch_halves<2, false, 0, NQ, PROF>(one, d_args, n_runs, s);
+static int dispatch_halves_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, bool discrete, hipStream_t s, int* packed) {
+  if (!discrete && obs == 18) return launch_halves<2, false, 18, NQ, PROF>(one, d_args, n_runs, s, packed);      // HCWithPos (BASELINE configs[1], [3])
+  if (discrete && obs == 1) return launch_halves<2, true, 1, NQ, PROF>(one, d_args, n_runs, s, packed);          // LapGridWorld (configs[0])
+  return discrete ? launch_halves<2, true, 0, NQ, PROF>(one, d_args, n_runs, s, packed) : launch_halves<2, false, 0, NQ, PROF>(one, d_args, n_runs, s, packed);
 }
 // prof: hp._pad & 1 of the run(s) — the instantiation with the phase timers (tools only)
 template <int NQ>
-static int dispatch_halves(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, bool discrete, bool prof, hipStream_t s) {
-  return prof ? dispatch_halves_p<NQ, true>(one, d_args, n_runs, obs, discrete, s) : dispatch_halves_p<NQ, false>(one, d_args, n_runs, obs, discrete, s);
+static int dispatch_halves(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, bool discrete, bool prof, hipStream_t s, int* packed) {
+  return prof ? dispatch_halves_p<NQ, true>(one, d_args, n_runs, obs, discrete, s, packed) : dispatch_halves_p<NQ, false>(one, d_args, n_runs, obs, discrete, s, packed);
 }
 
 // obs <= 32 (nt1 <= 2), a.gx set and zeroed (prepare_train); parts = 2 | 4 workgroups per network
-int launch_train_halves(const TrainArgs& a, bool discrete, int parts, hipStream_t s) {
+int launch_train_halves(const TrainArgs& a, bool discrete, int parts, hipStream_t s, int* packed) {
   const bool prof = (a.hp._pad & 1) != 0;
-  return parts == 4 ? dispatch_halves<4>(&a, nullptr, 1, a.L.O, discrete, prof, s) : dispatch_halves<2>(&a, nullptr, 1, a.L.O, discrete, prof, s);
+  return parts == 4 ? dispatch_halves<4>(&a, nullptr, 1, a.L.O, discrete, prof, s, packed) : dispatch_halves<2>(&a, nullptr, 1, a.L.O, discrete, prof, s, packed);
 }
-int launch_train_halves_batch(const TrainArgs* d_args, int n_runs, int obs, bool discrete, int parts, bool prof, hipStream_t s) {
-  return parts == 4 ? dispatch_halves<4>(nullptr, d_args, n_runs, obs, discrete, prof, s) : dispatch_halves<2>(nullptr, d_args, n_runs, obs, discrete, prof, s);
+int launch_train_halves_batch(const TrainArgs* d_args, int n_runs, int obs, bool discrete, int parts, bool prof, hipStream_t s, int* packed) {
+  return parts == 4 ? dispatch_halves<4>(nullptr, d_args, n_runs, obs, discrete, prof, s, packed) : dispatch_halves<2>(nullptr, d_args, n_runs, obs, discrete, prof, s, packed);
 }
 
 }  // namespace icrl

@@ -1127,43 +1127,44 @@ __global__ void __launch_bounds__(TH8) ppo_train_pairs_batch_kernel(const TrainA
 
 // one: single-run launch (argument block by value) | d_args: n_runs blocks in device memory
 template <int NT1, bool DISC, int OBS, bool PROF>
-static int launch_pairs_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, hipStream_t s) {
+static int launch_pairs_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, hipStream_t s, int* packed) {
   static_assert(SmemP<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   const size_t bytes = 0;      // (the LDS array is static)
   if (one != nullptr) {
     hipError_t e = hipFuncSetAttribute((const void*)ppo_train_pairs_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return (int)e;
     TrainArgs arg = *one;
-    return launch_update_single(ppo_train_pairs_kernel<NT1, DISC, OBS, PROF>, 3, dim3(TH8), bytes, s, arg);
+    return launch_update_single(ppo_train_pairs_kernel<NT1, DISC, OBS, PROF>, 3, dim3(TH8), bytes, s, arg, packed);
   } else {
     hipError_t e = hipFuncSetAttribute((const void*)ppo_train_pairs_batch_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return (int)e;
     const int pg = packed_grid(3, n_runs);      // the runs' workgroups on one XCD each (ppo_common.h) when the whole grid is resident at once
     hipLaunchKernelGGL((ppo_train_pairs_batch_kernel<NT1, DISC, OBS, PROF>), pg ? dim3(pg) : dim3(3, n_runs), dim3(TH8), bytes, s, d_args, n_runs, pg ? 1 : 0);
+    *packed = pg != 0;
   }
   return (int)hipGetLastError();
 }
 
 template <bool PROF>
-static int dispatch_pairs_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, hipStream_t s) {
+static int dispatch_pairs_p(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, hipStream_t s, int* packed) {
   if (nt1 <= 2) {
-    if (!discrete && obs == 18) return launch_pairs_p<2, false, 18, PROF>(one, d_args, n_runs, s);      // HCWithPos (BASELINE configs[1], [3])
-    if (discrete && obs == 1) return launch_pairs_p<2, true, 1, PROF>(one, d_args, n_runs, s);          // LapGridWorld (configs[0])
-    return discrete ? launch_pairs_p<2, true, 0, PROF>(one, d_args, n_runs, s) : launch_pairs_p<2, false, 0, PROF>(one, d_args, n_runs, s);
+    if (!discrete && obs == 18) return launch_pairs_p<2, false, 18, PROF>(one, d_args, n_runs, s, packed);      // HCWithPos (BASELINE configs[1], [3])
+    if (discrete && obs == 1) return launch_pairs_p<2, true, 1, PROF>(one, d_args, n_runs, s, packed);          // LapGridWorld (configs[0])
+    return discrete ? launch_pairs_p<2, true, 0, PROF>(one, d_args, n_runs, s, packed) : launch_pairs_p<2, false, 0, PROF>(one, d_args, n_runs, s, packed);
   }
-  if (nt1 <= 4) return discrete ? launch_pairs_p<4, true, 0, PROF>(one, d_args, n_runs, s) : launch_pairs_p<4, false, 0, PROF>(one, d_args, n_runs, s);
+  if (nt1 <= 4) return discrete ? launch_pairs_p<4, true, 0, PROF>(one, d_args, n_runs, s, packed) : launch_pairs_p<4, false, 0, PROF>(one, d_args, n_runs, s, packed);
   return fail("update (wave pairs): obs_dim tiles %d > 4", nt1);
 }
-static int dispatch_pairs(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s) {
-  return prof ? dispatch_pairs_p<true>(one, d_args, n_runs, obs, nt1, discrete, s) : dispatch_pairs_p<false>(one, d_args, n_runs, obs, nt1, discrete, s);
+static int dispatch_pairs(const TrainArgs* one, const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s, int* packed) {
+  return prof ? dispatch_pairs_p<true>(one, d_args, n_runs, obs, nt1, discrete, s, packed) : dispatch_pairs_p<false>(one, d_args, n_runs, obs, nt1, discrete, s, packed);
 }
 
-int launch_train_pairs_batch(const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s) {
-  return dispatch_pairs(nullptr, d_args, n_runs, obs, nt1, discrete, prof, s);
+int launch_train_pairs_batch(const TrainArgs* d_args, int n_runs, int obs, int nt1, bool discrete, bool prof, hipStream_t s, int* packed) {
+  return dispatch_pairs(nullptr, d_args, n_runs, obs, nt1, discrete, prof, s, packed);
 }
 
-int launch_train_pairs(const TrainArgs& a, int nt1, bool discrete, hipStream_t s) {
-  return dispatch_pairs(&a, nullptr, 1, a.L.O, nt1, discrete, (a.hp._pad & 1) != 0, s);
+int launch_train_pairs(const TrainArgs& a, int nt1, bool discrete, hipStream_t s, int* packed) {
+  return dispatch_pairs(&a, nullptr, 1, a.L.O, nt1, discrete, (a.hp._pad & 1) != 0, s, packed);
 }
 
 }  // namespace icrl

@@ -919,25 +919,25 @@ __global__ void __launch_bounds__(THQ) ppo_train_quarters_kernel(TrainArgs a, in
 }
 
 template <int NT1, bool DISC, int OBS, bool PROF>
-static int launch_quarters_p(const TrainArgs& a, hipStream_t s) {
+static int launch_quarters_p(const TrainArgs& a, hipStream_t s, int* packed) {
   static_assert(SmemQ<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   const size_t bytes = (size_t)SmemQ<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_quarters_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;
-  return launch_update_single(ppo_train_quarters_kernel<NT1, DISC, OBS, PROF>, 12, dim3(THQ), bytes, s, arg);
+  return launch_update_single(ppo_train_quarters_kernel<NT1, DISC, OBS, PROF>, 12, dim3(THQ), bytes, s, arg, packed);
 }
 template <int NT1, bool DISC, int OBS>
-static int launch_quarters(const TrainArgs& a, hipStream_t s) {
-  return (a.hp._pad & 1) ? launch_quarters_p<NT1, DISC, OBS, true>(a, s) : launch_quarters_p<NT1, DISC, OBS, false>(a, s);
+static int launch_quarters(const TrainArgs& a, hipStream_t s, int* packed) {
+  return (a.hp._pad & 1) ? launch_quarters_p<NT1, DISC, OBS, true>(a, s, packed) : launch_quarters_p<NT1, DISC, OBS, false>(a, s, packed);
 }
 
 // obs 65..128 (nt1 5..8: run on the eight-tile instantiation, pad columns zero), a.gx set and zeroed (prepare_train), the chunk plan with one
 // entry per 64-row chunk; single-run launches
-int launch_train_quarters_wide(const TrainArgs& a, bool discrete, hipStream_t s) {
+int launch_train_quarters_wide(const TrainArgs& a, bool discrete, hipStream_t s, int* packed) {
   if (a.L.O <= 64 || a.L.O > 128) return fail("update (four workgroups per network, wide observations): obs_dim %d outside 65..128", a.L.O);
-  if (!discrete && a.L.O == 113) return launch_quarters<8, false, 113>(a, s);      // AntWall / AntWallBroken (BASELINE configs[2], [4])
-  return discrete ? launch_quarters<8, true, 0>(a, s) : launch_quarters<8, false, 0>(a, s);
+  if (!discrete && a.L.O == 113) return launch_quarters<8, false, 113>(a, s, packed);      // AntWall / AntWallBroken (BASELINE configs[2], [4])
+  return discrete ? launch_quarters<8, true, 0>(a, s, packed) : launch_quarters<8, false, 0>(a, s, packed);
 }
 
 }  // namespace icrl

@@ -960,25 +960,25 @@ __global__ void __launch_bounds__(THQ2) ppo_train_quarters2_kernel(TrainArgs a, 
 }
 
 template <int NT1, bool DISC, int OBS, bool PROF>
-static int launch_quarters2_p(const TrainArgs& a, hipStream_t s) {
+static int launch_quarters2_p(const TrainArgs& a, hipStream_t s, int* packed) {
   static_assert(SmemQ2<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   const size_t bytes = (size_t)SmemQ2<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_quarters2_kernel<NT1, DISC, OBS, PROF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;
-  return launch_update_single(ppo_train_quarters2_kernel<NT1, DISC, OBS, PROF>, 12, dim3(THQ2), bytes, s, arg);
+  return launch_update_single(ppo_train_quarters2_kernel<NT1, DISC, OBS, PROF>, 12, dim3(THQ2), bytes, s, arg, packed);
 }
 template <int NT1, bool DISC, int OBS>
-static int launch_quarters2(const TrainArgs& a, hipStream_t s) {
-  return (a.hp._pad & 1) ? launch_quarters2_p<NT1, DISC, OBS, true>(a, s) : launch_quarters2_p<NT1, DISC, OBS, false>(a, s);
+static int launch_quarters2(const TrainArgs& a, hipStream_t s, int* packed) {
+  return (a.hp._pad & 1) ? launch_quarters2_p<NT1, DISC, OBS, true>(a, s, packed) : launch_quarters2_p<NT1, DISC, OBS, false>(a, s, packed);
 }
 
 // obs 65..128, minibatches of 65..128 rows, a.gx set and zeroed (prepare_train), the chunk plan with TWO entries per step; single-run launches
-int launch_train_quarters_wide2(const TrainArgs& a, bool discrete, hipStream_t s) {
+int launch_train_quarters_wide2(const TrainArgs& a, bool discrete, hipStream_t s, int* packed) {
   if (a.L.O <= 64 || a.L.O > 128) return fail("update (four workgroups per network, two row tiles per wave): obs_dim %d outside 65..128", a.L.O);
   if (a.hp.batch_size <= RB || a.hp.batch_size > 2 * RB) return fail("update (four workgroups per network, two row tiles per wave): batch_size %d outside 65..128", a.hp.batch_size);
-  if (!discrete && a.L.O == 113) return launch_quarters2<8, false, 113>(a, s);      // AntWall / AntWallBroken (BASELINE configs[2], [4])
-  return discrete ? launch_quarters2<8, true, 0>(a, s) : launch_quarters2<8, false, 0>(a, s);
+  if (!discrete && a.L.O == 113) return launch_quarters2<8, false, 113>(a, s, packed);      // AntWall / AntWallBroken (BASELINE configs[2], [4])
+  return discrete ? launch_quarters2<8, true, 0>(a, s, packed) : launch_quarters2<8, false, 0>(a, s, packed);
 }
 
 }  // namespace icrl

@@ -1047,46 +1047,47 @@ __global__ void __launch_bounds__(TH4) ppo_train_rows_batch_kernel(const TrainAr
 }
 
 template <int NT1, bool DISC, bool SPLIT>
-static int launch_rows_batch(const TrainArgs* d_args, int n_runs, hipStream_t s) {
+static int launch_rows_batch(const TrainArgs* d_args, int n_runs, hipStream_t s, int* packed) {
   const size_t bytes = (size_t)SmemR<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_rows_batch_kernel<NT1, DISC, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   const int pg = packed_grid(SPLIT ? 6 : 3, n_runs);
   hipLaunchKernelGGL((ppo_train_rows_batch_kernel<NT1, DISC, SPLIT>), pg ? dim3(pg) : dim3(SPLIT ? 6 : 3, n_runs), dim3(TH4), bytes, s, d_args, n_runs, pg ? 1 : 0);
+  *packed = pg != 0;
   return (int)hipGetLastError();
 }
 
-int launch_train_rows_batch(const TrainArgs* d_args, int n_runs, int nt1, bool discrete, bool split, hipStream_t s) {
+int launch_train_rows_batch(const TrainArgs* d_args, int n_runs, int nt1, bool discrete, bool split, hipStream_t s, int* packed) {
   if (split) {
-    if (nt1 <= 4) return discrete ? launch_rows_batch<4, true, true>(d_args, n_runs, s) : launch_rows_batch<4, false, true>(d_args, n_runs, s);
-    if (nt1 <= 8) return discrete ? launch_rows_batch<8, true, true>(d_args, n_runs, s) : launch_rows_batch<8, false, true>(d_args, n_runs, s);
+    if (nt1 <= 4) return discrete ? launch_rows_batch<4, true, true>(d_args, n_runs, s, packed) : launch_rows_batch<4, false, true>(d_args, n_runs, s, packed);
+    if (nt1 <= 8) return discrete ? launch_rows_batch<8, true, true>(d_args, n_runs, s, packed) : launch_rows_batch<8, false, true>(d_args, n_runs, s, packed);
     return fail("update (row-owning waves): obs_dim tiles %d > 8", nt1);
   }
-  if (nt1 <= 2) return discrete ? launch_rows_batch<2, true, false>(d_args, n_runs, s) : launch_rows_batch<2, false, false>(d_args, n_runs, s);
-  if (nt1 <= 4) return discrete ? launch_rows_batch<4, true, false>(d_args, n_runs, s) : launch_rows_batch<4, false, false>(d_args, n_runs, s);
-  if (nt1 <= 8) return discrete ? launch_rows_batch<8, true, false>(d_args, n_runs, s) : launch_rows_batch<8, false, false>(d_args, n_runs, s);
+  if (nt1 <= 2) return discrete ? launch_rows_batch<2, true, false>(d_args, n_runs, s, packed) : launch_rows_batch<2, false, false>(d_args, n_runs, s, packed);
+  if (nt1 <= 4) return discrete ? launch_rows_batch<4, true, false>(d_args, n_runs, s, packed) : launch_rows_batch<4, false, false>(d_args, n_runs, s, packed);
+  if (nt1 <= 8) return discrete ? launch_rows_batch<8, true, false>(d_args, n_runs, s, packed) : launch_rows_batch<8, false, false>(d_args, n_runs, s, packed);
   return fail("update (row-owning waves): obs_dim tiles %d > 8", nt1);
 }
 
 template <int NT1, bool DISC, bool SPLIT>
-static int launch_rows(const TrainArgs& a, hipStream_t s) {
+static int launch_rows(const TrainArgs& a, hipStream_t s, int* packed) {
   static_assert(SmemR<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   const size_t bytes = (size_t)SmemR<NT1>::TOTAL * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)ppo_train_rows_kernel<NT1, DISC, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   TrainArgs arg = a;
-  return launch_update_single(ppo_train_rows_kernel<NT1, DISC, SPLIT>, SPLIT ? 6 : 3, dim3(TH4), bytes, s, arg);
+  return launch_update_single(ppo_train_rows_kernel<NT1, DISC, SPLIT>, SPLIT ? 6 : 3, dim3(TH4), bytes, s, arg, packed);
 }
 
-int launch_train_rows(const TrainArgs& a, int nt1, bool discrete, bool split, hipStream_t s) {
+int launch_train_rows(const TrainArgs& a, int nt1, bool discrete, bool split, hipStream_t s, int* packed) {
   if (split) {       // two workgroups per network (a.gx set, the chunk plan holds two entries per step)
-    if (nt1 <= 4) return discrete ? launch_rows<4, true, true>(a, s) : launch_rows<4, false, true>(a, s);
-    if (nt1 <= 8) return discrete ? launch_rows<8, true, true>(a, s) : launch_rows<8, false, true>(a, s);
+    if (nt1 <= 4) return discrete ? launch_rows<4, true, true>(a, s, packed) : launch_rows<4, false, true>(a, s, packed);
+    if (nt1 <= 8) return discrete ? launch_rows<8, true, true>(a, s, packed) : launch_rows<8, false, true>(a, s, packed);
     return fail("update (row-owning waves): obs_dim tiles %d > 8", nt1);
   }
-  if (nt1 <= 2) return discrete ? launch_rows<2, true, false>(a, s) : launch_rows<2, false, false>(a, s);
-  if (nt1 <= 4) return discrete ? launch_rows<4, true, false>(a, s) : launch_rows<4, false, false>(a, s);
-  if (nt1 <= 8) return discrete ? launch_rows<8, true, false>(a, s) : launch_rows<8, false, false>(a, s);
+  if (nt1 <= 2) return discrete ? launch_rows<2, true, false>(a, s, packed) : launch_rows<2, false, false>(a, s, packed);
+  if (nt1 <= 4) return discrete ? launch_rows<4, true, false>(a, s, packed) : launch_rows<4, false, false>(a, s, packed);
+  if (nt1 <= 8) return discrete ? launch_rows<8, true, false>(a, s, packed) : launch_rows<8, false, false>(a, s, packed);
   return fail("update (row-owning waves): obs_dim tiles %d > 8", nt1);
 }
 

@@ -4215,6 +4215,10 @@ struct KernelPick {
   bool prof = false;       // tools: the instantiations with the phase timers (do_gae bits 2 / 3)
   int E = 0;               // multi kernels: envs per workgroup (multi_shape)
   int minw = 1;            // batched one-workgroup-per-env kernels: workgroups per CU the register allocation leaves room for
+  // what the dispatch below instantiated, written by it for the route record (pick_bits): the MINW of with_persistent_batch_kernel,
+  // whether with_image took the <8, 8> image
+  mutable int used_minw = 0;
+  mutable bool used_cn128 = false;
 };
 template <int OCT, int CIT> struct Image { static constexpr int oct = OCT, cit = CIT; };
 template <int V> struct Int { static constexpr int value = V; };
@@ -4228,10 +4232,11 @@ static bool small_shape(int O, const icrl_costnet_t* net) { return O <= 32 && (n
 // the register images <OCT, CIT> (k steps of the policy / cost-net first layers held in registers); CN128: the family has the <8, 8> image
 template <bool CN128 = false, class F>
 static int with_image(const KernelPick& k, F&& f) {
+  k.used_cn128 = false;
   if (k.analytic) return k.small ? f(Image<2, 0>{}) : f(Image<8, 0>{});
   if (k.small) return f(Image<2, 2>{});
   if constexpr (CN128) {
-    if (k.cn128) return f(Image<8, 8>{});
+    if (k.cn128) { k.used_cn128 = true; return f(Image<8, 8>{}); }
   }
   return f(Image<8, 10>{});
 }
@@ -4278,6 +4283,7 @@ template <class F> static int with_persistent_batch_kernel(const KernelPick& k, 
     auto kernel = [&](auto gran, auto minw) {      // (the analytic cost: a kernel of its own name, see there)
       constexpr bool GRAN = decltype(gran)::value;
       constexpr int MINW = decltype(minw)::value;
+      k.used_minw = MINW;
       if constexpr (CIT == 0) return f(rollout_persistent_batch_analytic_kernel<OCT, GRAN, MINW, MON>);
       else return f(rollout_persistent_batch_kernel<OCT, CIT, GRAN, MINW, MON>);
     };
@@ -4305,11 +4311,27 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
   }); });
 }
 
+// the route record's word 4: the KernelPick fields that chose the instantiation of `route` (ICRL_PICK_*), nothing that it ignores;
+// the <8, 8> image and MINW as the dispatch that launched it wrote them down (call this after the launch)
+static int pick_bits(const KernelPick& k, int route) {
+  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0);
+  if (route == ICRL_ROUTE_PER_STEP || route == ICRL_ROUTE_GENERIC_PER_STEP) return b;
+  b |= k.mon ? ICRL_PICK_MON : 0;
+  if (route == ICRL_ROUTE_PERSISTENT || route == ICRL_ROUTE_PERSISTENT_BATCH) b |= k.gran ? ICRL_PICK_GRAN : 0;
+  if ((route == ICRL_ROUTE_MULTI || route == ICRL_ROUTE_MULTI_BATCH) && k.used_cn128) b |= ICRL_PICK_CN128;
+  if (route == ICRL_ROUTE_PERSISTENT_BATCH) b |= k.used_minw << ICRL_PICK_MINW_SHIFT;
+  return b;
+}
+
 // ---- exchange workspaces.  A run's workspace is the agent's xch_ws when that holds `need` bytes, else the not yet computed
 // reward_advantages plane of the buffer (GAE fills it afterwards), else NULL: the route is then not taken.
 static char* exchange_ws(const icrl_agent_t* ag, const icrl_buffer_t* buf, size_t need) {
   if (ag->xch_ws != nullptr && (size_t)ag->xch_ws_bytes >= need) return reinterpret_cast<char*>(ag->xch_ws);
   return (size_t)buf->T * buf->N * sizeof(float) >= need ? reinterpret_cast<char*>(buf->reward_advantages) : nullptr;
+}
+// where exchange_ws took `ws` from, for the route record (ICRL_WS_*)
+static int ws_source(const icrl_agent_t* ag, const char* ws) {
+  return ws == nullptr ? ICRL_WS_NONE : (ws == reinterpret_cast<const char*>(ag->xch_ws) ? ICRL_WS_XCH : ICRL_WS_PLANE);
 }
 
 // one-workgroup-per-env kernels (PersistArgs):  xch_obs | xch_rew | xch_cost | xch_done (to 256 B) | counter (512 B) | xg (granule mode)
@@ -4374,9 +4396,10 @@ static int launch_per_env(K kernel, int N, size_t dyn, hipStream_t s, A& args) {
 
 // single run of a multi kernel: G workgroups, or (packed) workgroups 0, 8, 16, ... of 8 (G - 1) + 1 so that all G sit on one XCD
 template <class K>
-static int launch_multi_run(K kernel, WideArgs& p, int G, size_t dyn, hipStream_t s) {
+static int launch_multi_run(K kernel, WideArgs& p, int G, size_t dyn, hipStream_t s, int* packed_out) {
   if (!persistent_fits(kernel, G, dyn)) return -1;
   const int packed = xcd_pack() && p.xcc != nullptr && G <= 32;
+  *packed_out = packed;
   void* params[] = {(void*)&p, (void*)&packed};
   const hipError_t e = hipLaunchCooperativeKernel((const void*)kernel, dim3(packed ? 8 * (G - 1) + 1 : G), dim3(256), params, (unsigned)dyn, s);
   if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
@@ -4385,13 +4408,14 @@ static int launch_multi_run(K kernel, WideArgs& p, int G, size_t dyn, hipStream_
 
 // n_runs runs of a multi kernel, argument blocks in device memory
 template <class K>
-static int launch_multi_runs(K kernel, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s) {
+static int launch_multi_runs(K kernel, const WideArgs* d_args, int n_runs, int G, size_t dyn, hipStream_t s, int* packed_out) {
   if (!persistent_fits(kernel, G, dyn)) return -1;
   // packed layout (a run's G workgroups on ONE XCD: workgroups b, b + 8, ...) when every XCD can hold its share of the grid at once
   // (32 CUs each); otherwise run-major, whose runs become resident oldest first
   int per_cu = 0;
   const int groups = (n_runs + 7) / 8;
   const bool packed = xcd_pack() && G <= 32 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, dyn) == hipSuccess && groups * G <= 32 * per_cu;
+  *packed_out = packed ? 1 : 0;
   if (packed) hipLaunchKernelGGL(kernel, dim3(8 * G * groups), dim3(256), dyn, s, d_args, n_runs, G, 1);
   else hipLaunchKernelGGL(kernel, dim3(G, n_runs), dim3(256), dyn, s, d_args, n_runs, G, 0);
   return (int)hipGetLastError();
@@ -4433,6 +4457,10 @@ static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane)
 //                        grid >= obs + 2, workspace                                             rollout_wide_kernel
 //   persistent           !(do_gae & 2), not a Point env, N <= 128, N obs <= 4096, workspace       rollout_persistent_kernel
 //   per-step             everything else: two launches per step                                 act_step_kernel | norm_step
+//                        (with training statistics and Box actions that is: fewer envs than multi / wide take AND more than persistent takes —
+//                        AntWall, obs 113, at 37..114 envs: 37 x 113 > 4096, 114 < obs + 2 workgroups, 114 / 29 < 4 envs per owner group — and Point
+//                        envs below 12; with frozen statistics or Discrete actions: above 128 envs or 4096 observation doubles)
+// What a call took is kept per host thread: icrl_debug_last_route (errors.hip), written where a route returns after its launch.
 // Routes of a batch (rollout_collect_batch_impl):
 //   multi                !ICRL_BATCH_NO_MULTI, not `few`, Box actions, training, multi_shape, every run has a workspace      rollout_multi_batch[_analytic]_kernel
 //   persistent           N <= 128, N obs <= 4096 (else refused)                                 rollout_persistent_batch[_analytic]_kernel
@@ -4441,6 +4469,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                                            const float* noise, const float* action_low, const float* action_high,
                                            double reward_gamma, double reward_gae_lambda, double cost_gamma, double cost_gae_lambda,
                                            int do_gae, const icrl_monitor_t* mon, void* stream) {
+  note_route(ICRL_FAMILY_ROLLOUT);      // (route 0 until a ladder rung below has launched)
   double* raw_plane = nullptr;
   if (int e = mon_plane("icrl_rollout_collect_ex_mon", mon, &raw_plane)) return e;
   const int N = env->n_envs, O = env->obs_dim, T = buf->T;
@@ -4463,6 +4492,11 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   KernelPick k;
   k.small = small_shape(O, net); k.analytic = cf != nullptr; k.mon = raw_plane != nullptr;
   auto finish = [&](int err) { return finish_with_gae(err, do_gae, buf, ag, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, stream); };
+  // the route record, written where a rung returns after its launch(es): workspace source, working workgroups, envs per workgroup, packed, launches
+  auto routed = [&](int err, int route, const char* ws, int wgs, int E, int packed, int launches) {
+    if (err == 0) note_route(ICRL_FAMILY_ROLLOUT, route, ws_source(ag, ws), wgs, E, pick_bits(k, route), packed, 1, launches);
+    return err;
+  };
   if (generic) {
     // a policy with layers above 64 units / an `arch` descriptor, or a constraint net above 64 units / two layers: the reference's
     // per-step loop as four launches per step on this stream — policy_generic_kernel (generic.hip), cn_cost_rows_kernel (cn_train.hip),
@@ -4489,7 +4523,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         if (e != hipSuccess) return (int)e;
         const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
         const int perr = with_generic_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, ga); });
-        if (perr >= 0) return finish(perr != 0 ? perr : (int)hipGetLastError());
+        if (perr >= 0) return finish(routed(perr != 0 ? perr : (int)hipGetLastError(), ICRL_ROUTE_GENERIC_PERSISTENT, ws, N, 1, 0, 1));
       }
     }
     GenStepArgs g;
@@ -4513,7 +4547,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                      buf->new_observations + row * O, buf->rewards + row, buf->costs + row, ag->last_dones};
       launch_norm_step(b, s);
     }
-    return finish((int)hipGetLastError());
+    return finish(routed((int)hipGetLastError(), ICRL_ROUTE_GENERIC_PER_STEP, nullptr, N, 0, 0, (net != nullptr ? 4 : 3) * T));
   }
   ActStepArgs a;
   fill_act_args(a, env, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
@@ -4532,8 +4566,9 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       if (e != hipSuccess) return (int)e;
       k.cn128 = !net || net->in_dim <= 128; k.E = E;
       const size_t mdyn = multi_dyn_lds(N, O, env->act_dim, (n_stats + G - 1) / G);
-      const int err = with_multi_kernel<false>(k, [&](auto kernel) { return launch_multi_run(kernel, p, G, mdyn, s); });
-      if (err >= 0) return finish(err);
+      int packed = 0;
+      const int err = with_multi_kernel<false>(k, [&](auto kernel) { return launch_multi_run(kernel, p, G, mdyn, s, &packed); });
+      if (err >= 0) return finish(routed(err, ICRL_ROUTE_MULTI, ws, G, E, packed, 1));
     }
   }
   // many environments: persistent launch with the statistics partitioned by observation column (rollout_wide_kernel); measured
@@ -4559,7 +4594,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         k.prof = p.prof != 0;
         const int err = with_wide_kernel(k, [&](auto kernel) { return (int)launch_coresident(kernel, dim3(G), dim3(256), 0, s, p); });
         if (err == (int)hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); goto per_step; }
-        return finish(err);
+        return finish(routed(err, ICRL_ROUTE_WIDE, ws, G, E, 0, 1));
       }
     }
   }
@@ -4579,7 +4614,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       const int perr = with_persistent_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, p); });
       const int err = perr > 0 ? perr : (int)hipGetLastError();
       if (perr < 0) goto per_step;
-      return finish(err);
+      return finish(routed(err, ICRL_ROUTE_PERSISTENT, ws, N, 1, 0, 1));
     }
   }
 per_step:
@@ -4590,7 +4625,7 @@ per_step:
                    buf->new_observations + row * O, buf->rewards + row, buf->costs + row, ag->last_dones};
     launch_norm_step(b, s);
   }
-  return finish((int)hipGetLastError());
+  return finish(routed((int)hipGetLastError(), ICRL_ROUTE_PER_STEP, nullptr, N, 0, 0, 2 * T));
 }
 
 // what one run of a batch must share with run 0 and satisfy by itself.  same_training is inherited, not designed: the multi route also
@@ -4651,11 +4686,13 @@ static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs
     if (!no_multi && !few && !j0.pol->discrete && j0.nm->training && N <= NORM_MAX_N && T >= 1 && multi_shape(N, n_stats, &E, &G)) {
       WideArgs* d_args = (WideArgs*)args_ws;
       bool ok = true;
+      int src = ICRL_WS_NONE;      // (of the last run: the record has one word for it)
       for (int r = 0; r < n_runs && ok; ++r) {
         const icrl_rollout_job_t& j = jobs[r];
         if (int e_ = batch_run_check(r, j, j0, analytic, true)) return e_;
         char* ws = exchange_ws(j.ag, j.buf, wide_ws_bytes(N, O));
         if (ws == nullptr) { ok = false; break; }
+        src = ws_source(j.ag, ws);
         WideArgs p;
         if (int e_ = batch_act_args(p.act, r, j, mons, analytic, action_low, action_high)) return e_;
         p.nm = *j.nm; p.T = T; p.G = G; p.prof = 0;
@@ -4668,7 +4705,9 @@ static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs
       if (ok) {
         k.cn128 = net0 == nullptr || net0->in_dim <= 128; k.E = E;
         const size_t mdyn = multi_dyn_lds(N, O, j0.env->act_dim, (n_stats + G - 1) / G);
-        const int err = with_multi_kernel<true>(k, [&](auto kernel) { return launch_multi_runs(kernel, d_args, n_runs, G, mdyn, s); });
+        int packed = 0;
+        const int err = with_multi_kernel<true>(k, [&](auto kernel) { return launch_multi_runs(kernel, d_args, n_runs, G, mdyn, s, &packed); });
+        if (err == 0) note_route(ICRL_FAMILY_ROLLOUT, ICRL_ROUTE_MULTI_BATCH, src, G, E, pick_bits(k, ICRL_ROUTE_MULTI_BATCH), packed, n_runs, 1);
         if (err >= 0) return finish(err);
       }
     }
@@ -4679,11 +4718,13 @@ static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs
   const bool gran = (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX;
   const size_t need = persist_ws_bytes(N, O, gran);
   PersistArgs* d_args = (PersistArgs*)args_ws;
+  int src = ICRL_WS_NONE;
   for (int r = 0; r < n_runs; ++r) {
     const icrl_rollout_job_t& j = jobs[r];
     if (int e_ = batch_run_check(r, j, j0, analytic, false)) return e_;
     char* ws = exchange_ws(j.ag, j.buf, need);
     if (ws == nullptr) return fail("icrl_rollout_collect_batch: run %d: exchange workspace of %zu B needed (icrl_agent_t.xch_ws, ICRL_ROLLOUT_WS_BYTES)", r, need);
+    src = ws_source(j.ag, ws);
     PersistArgs p;
     if (int e_ = batch_act_args(p.act, r, j, mons, analytic, action_low, action_high)) return e_;
     p.nm = *j.nm; p.T = T; p.prof = 0;
@@ -4699,16 +4740,19 @@ static int rollout_collect_batch_impl(int n_runs, const icrl_rollout_job_t* jobs
   static const int minw_env = getenv("ICRL_ROLLOUT_MINW") ? atoi(getenv("ICRL_ROLLOUT_MINW")) : 0;
   k.gran = gran; k.minw = minw_env > 0 ? minw_env : ((long long)n_runs * N <= cus ? 1 : 2);
   const size_t dyn = persist_dyn_lds(N, O, j0.env->act_dim);
-  return finish(with_persistent_batch_kernel(k, [&](auto kernel) -> int {
+  const int err = with_persistent_batch_kernel(k, [&](auto kernel) -> int {
     if (!persistent_fits(kernel, N, dyn)) return fail("icrl_rollout_collect_batch: the %d workgroups of one run do not fit the device", N);
     hipLaunchKernelGGL(kernel, dim3(N, n_runs), dim3(256), dyn, s, d_args);
     return (int)hipGetLastError();
-  }));
+  });
+  if (err == 0) note_route(ICRL_FAMILY_ROLLOUT, ICRL_ROUTE_PERSISTENT_BATCH, src, N, 1, pick_bits(k, ICRL_ROUTE_PERSISTENT_BATCH), 0, n_runs, 1);
+  return finish(err);
 }
 
 extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
                                               const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
                                               double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+  note_route(ICRL_FAMILY_ROLLOUT);      // (the one clear of a batched call: rollout_collect_batch_impl below writes the record behind its launch)
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
   for (int r = 0; r < n_runs; ++r)      // (the analytic form is icrl_rollout_collect_batch_cost's)
     if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
@@ -4722,6 +4766,7 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
 extern "C" int icrl_rollout_collect_batch_cost(int n_runs, const icrl_rollout_job_t* jobs, const icrl_monitor_t* mons, const float* action_low,
                                                const float* action_high, double reward_gamma, double reward_gae_lambda, double cost_gamma,
                                                double cost_gae_lambda, int do_gae, void* args_ws, long long args_ws_bytes, void* stream) {
+  note_route(ICRL_FAMILY_ROLLOUT);
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch_cost: n_runs = %d (1..65535)", n_runs);
   int n_fn = 0, n_net = 0;
   for (int r = 0; r < n_runs; ++r) {

@@ -221,7 +221,7 @@ typedef struct {
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* ABI version (major*100+minor). */
-int icrl_abi_version(void);   /* 106: icrl_explained_variance, icrl_gae_dual_ws_bytes + the status word of the GAE workspace; 105: icrl_buffer_add, icrl_is_weights, icrl_cn_loss_fwd_bwd; 104: the fine-grained update entry points (csrc/fine.hip); 103: icrl_debug_stream_ref; 102: icrl_policy_t.arch; 101: icrl_sample_episodes takes stream_row0 / total_rows; the *_batch entry points */
+int icrl_abi_version(void);   /* 107: icrl_debug_last_route; 106: icrl_explained_variance, icrl_gae_dual_ws_bytes + the status word of the GAE workspace; 105: icrl_buffer_add, icrl_is_weights, icrl_cn_loss_fwd_bwd; 104: the fine-grained update entry points (csrc/fine.hip); 103: icrl_debug_stream_ref; 102: icrl_policy_t.arch; 101: icrl_sample_episodes takes stream_row0 / total_rows; the *_batch entry points */
 
 /* Every entry point returns a hipError_t.  When it is hipErrorInvalidValue because the arguments are outside what the
  * kernels were built for (env count, widths, batch size ...; the reference's Python raises ValueError / AssertionError with a
@@ -290,10 +290,12 @@ int icrl_policy_forward(const icrl_policy_t* pol, const double* obs, const float
                         float* actions, float* act_clipped, float* v_r, float* v_c, float* log_prob, void* stream);
 
 /* same, with options in `do_gae`: bit 0 = run the final dual-GAE launch (0: the caller launches icrl_gae_dual itself, e.g.
- * bracketed by events); bit 1 = force one launch pair per env step; bit 2 = diagnostic phase timers.  By default, when N <= 128 and N * obs_dim <= 4096, ALL
- * T steps run in ONE persistent launch (one workgroup per env, one device-wide barrier per step, normaliser statistics
- * replicated bit-identically in every workgroup); the not yet computed reward_advantages plane of the buffer serves as its
- * exchange scratch. */
+ * bracketed by events); bit 1 = force one launch pair per env step; bit 2 = diagnostic phase timers.  By default ALL T steps run in ONE persistent launch
+ * where one of the kernels serves the shape — which one, in which order, and what is left to the launch pair per step (AntWall with
+ * 37..114 envs, for one) is stated once, in the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip; icrl_debug_last_route reports
+ * what a call took.  Up to 96 envs with N * obs_dim <= 4096 (128 envs with frozen statistics) that is one workgroup per env, one
+ * device-wide barrier per step, normaliser statistics replicated bit-identically in every workgroup; its exchange scratch is
+ * icrl_agent_t.xch_ws, or the not yet computed reward_advantages plane of the buffer when xch_ws is absent or too small. */
 int icrl_rollout_collect_ex(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn,
                             const icrl_buffer_t* buf, const icrl_agent_t* ag, const float* noise,
                             const float* action_low, const float* action_high,
@@ -509,14 +511,22 @@ int icrl_ppo_generic_row_floats(const icrl_policy_t* pol);
  * processes (README.md:14-21, one `python run_me.py` per seed).  Here n_runs runs share one grid: every *_batch entry point takes
  * an array of n_runs job descriptors in HOST memory (same fields as the arguments of the single-run entry point it mirrors),
  * requires all runs to agree in every shape that decides the grid (refused otherwise), and computes for each run exactly what
- * the single-run call computes (bit-identical: tests/test_seed_batch_gpu.py).
+ * the single-run call computes with the same kernel (bit-identical: tests/test_seed_batch_gpu.py, tests/test_routes_gpu.py).  The
+ * rollout and GAE kernels all agree bit for bit, so there the kernel does not matter.  The update does not: up to 16 runs of obs <= 32
+ * get the kernel a run alone gets (wave quads, four workgroups per network); 17..40 runs its two-workgroup form and more than 40 the
+ * wave-pair kernel (hp._pad bits 5 / 4 on a single run), which sum partial gradients in another order.  The contract for more than 16
+ * runs is therefore: bit-identical to the single-run call with that hp._pad bit, within the update's bound against the oracle, and
+ * NOT promised bit-identical to the default single-run call (observed at 4 envs x 8 steps, minibatches of 16: the two-workgroup form
+ * happened to equal it, the wave-pair kernel differed; an observation at one shape, not a guarantee).  icrl_debug_last_route says which
+ * kernel a call took.
  *   args_ws: device scratch of >= n_runs * ICRL_BATCH_ARGS_BYTES bytes, any contents; it receives the per-run argument blocks
  *            (written on `stream` before the launch) and must not be reused by another call before this one has completed. */
 #define ICRL_BATCH_ARGS_BYTES 1024
 
-/* icrl_rollout_collect_ex for n_runs runs: ONE persistent launch of grid (n_envs, n_runs) + ONE batched dual-GAE launch (do_gae
- * bit 0).  Batched form exists for the one-workgroup-per-env persistent kernel only (n_envs <= 128, n_envs x obs_dim <= 4096:
- * BASELINE configs[1]); every run needs its exchange workspace (icrl_agent_t.xch_ws) or T * N * 4 >= ICRL_ROLLOUT_WS_BYTES.
+/* icrl_rollout_collect_ex for n_runs runs: ONE persistent launch + ONE batched dual-GAE launch (do_gae bit 0).  Two batched forms, in
+ * the order the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip states: the multi-env kernel (several envs per workgroup) and
+ * the one-workgroup-per-env kernel, grid (n_envs, n_runs) (n_envs <= 128, n_envs x obs_dim <= 4096: BASELINE configs[1]); every run
+ * needs its exchange workspace (icrl_agent_t.xch_ws) or T * N * 4 >= ICRL_ROLLOUT_WS_BYTES.
  * args_ws: 2 x n_runs x ICRL_BATCH_ARGS_BYTES (rollout + GAE argument blocks). */
 typedef struct {
   const icrl_env_t* env;
@@ -660,6 +670,57 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
                   const float* nominal, const float* expert, int Nn, int Ne,
                   const int32_t* ep_offsets, const int32_t* row_episode, int n_ep,
                   const icrl_cn_hyper_t* hp, float* work, float* metrics, void* stream);
+
+/* Diagnostic: which kernels the calling host thread's last call of a fused family launched.  The entry points below choose among several
+ * launch forms by shape, workspace and device (the single statement of the rollout's order is the comment above
+ * icrl_rollout_collect_ex_mon in csrc/rollout.hip; prepare_train in csrc/ppo_train.hip and icrl_gae_dual_ws in csrc/gae.hip for the
+ * other two) and step to the next form silently; this says which one ran.  Host state only, thread-local like icrl_last_error():
+ * a call clears its family's record on entry and writes it behind its launch, so a call refused before any launch leaves route 0.
+ * out8 receives 8 int32 (unused words 0).  Returns 0; a family outside 0..2 or a NULL out8 is refused with a message.
+ *   ICRL_FAMILY_ROLLOUT  icrl_rollout_collect[_ex][_mon] and icrl_rollout_collect_batch[_mon | _cost]:
+ *     [0] ICRL_ROUTE_*   [1] ICRL_WS_* (a batch: of its last run)   [2] working workgroups per run   [3] envs per workgroup (0: per-step)
+ *     [4] ICRL_PICK_* bits of the instantiation, the batched one-workgroup-per-env kernel's MINW at ICRL_PICK_MINW_SHIFT
+ *     [5] packed XCD layout (multi kernels)   [6] n_runs   [7] launches of the rollout proper, the GAE excluded: 1, 2 T (per-step),
+ *     4 T (generic per-step with a constraint net; 3 T without one)
+ *   ICRL_FAMILY_UPDATE   icrl_ppo_lag_train[_batch]:
+ *     [0] 0..7 as prepare_train names them (0 wave pairs, 1 row-owning waves, 2 the same with two workgroups per network, 3 column-split
+ *         tiles, 4 wave quads with two workgroups per network, 5 with four, 6 / 7 four workgroups per network at obs 65..128),
+ *         ICRL_UPDATE_GENERIC_PERSISTENT, ICRL_UPDATE_GENERIC_LAUNCHES
+ *     [1] workgroups per network (ICRL_UPDATE_GENERIC_PERSISTENT: of the whole grid)   [2] n_runs   [3] 1 packed XCD grid | 0 run-major
+ *   ICRL_FAMILY_GAE      icrl_gae_dual[_ex | _ws | _batch] (a rollout with do_gae bit 0 ends in one of them):
+ *     [0] ICRL_GAE_*   [1] the sequential kernel's shape code (4, 16, 101, 105..112), else the workgroups per tile C   [2] column tiles
+ *     [3] n_runs */
+#define ICRL_FAMILY_ROLLOUT 0
+#define ICRL_FAMILY_UPDATE 1
+#define ICRL_FAMILY_GAE 2
+#define ICRL_N_FAMILIES 3
+#define ICRL_ROUTE_NONE 0
+#define ICRL_ROUTE_PER_STEP 1
+#define ICRL_ROUTE_PERSISTENT 2
+#define ICRL_ROUTE_WIDE 3
+#define ICRL_ROUTE_MULTI 4
+#define ICRL_ROUTE_GENERIC_PERSISTENT 5
+#define ICRL_ROUTE_GENERIC_PER_STEP 6
+#define ICRL_ROUTE_PERSISTENT_BATCH 7
+#define ICRL_ROUTE_MULTI_BATCH 8
+#define ICRL_WS_NONE 0
+#define ICRL_WS_XCH 1     /* icrl_agent_t.xch_ws */
+#define ICRL_WS_PLANE 2   /* the buffer's reward_advantages plane */
+#define ICRL_PICK_SMALL 1
+#define ICRL_PICK_ANALYTIC 2
+#define ICRL_PICK_MON 4
+#define ICRL_PICK_GRAN 8
+#define ICRL_PICK_CN128 16
+#define ICRL_PICK_MINW_SHIFT 8
+#define ICRL_UPDATE_GENERIC_PERSISTENT 8
+#define ICRL_UPDATE_GENERIC_LAUNCHES 9
+#define ICRL_GAE_SEQUENTIAL 1
+#define ICRL_GAE_SPLIT 2            /* two-pass split scan */
+#define ICRL_GAE_REGSPLIT 3         /* register-resident split scan */
+#define ICRL_GAE_BATCH_SPLIT 4
+#define ICRL_GAE_BATCH_REGSPLIT 5
+#define ICRL_GAE_BATCH_SINGLES 6    /* a batch issued as n_runs single launches */
+int icrl_debug_last_route(int family, int32_t* out8);
 
 /* Diagnostic: cycles per phase of workgroup 0 of the last persistent rollout that ran with do_gae bit 2 set
  * (out8: policy+env, barrier, tail, steps, exchange load, statistics, normalise, 0). */

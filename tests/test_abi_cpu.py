@@ -27,7 +27,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(L, name), f"{name} declared in include/icrl_hip.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
-    assert L.icrl_abi_version() == 106
+    assert L.icrl_abi_version() == 107
     assert L.icrl_cn_train_work_floats(521, 10000, 5000, 10) > 521 * 235
 
 
@@ -59,6 +59,48 @@ def test_refused_arguments_carry_a_reason():
     err = L.icrl_ppo_lag_train(ctypes.byref(pol), None, None, None, ctypes.byref(buf), None, None, ctypes.byref(hp), None, None, None)
     with pytest.raises(ValueError, match="batch_size 1"):
         _lib.check(err, "icrl_ppo_lag_train")
+
+
+def test_route_record_of_refused_calls_and_bad_families():
+    """icrl_debug_last_route (host state, no launch): a call refused before any launch leaves route 0 in its family's record, all
+    eight words; a family outside 0..2 or a NULL output is refused with a message and writes nothing."""
+    from icrl_amd import _lib, structs as S
+    L = _lib.lib()
+    pol = S.PolicyT(18, 6, 32, 64, 0, 1, None, None)
+    buf = S.BufferT(8, 4, 18, 0)
+    hp = S.PpoHyperT(64, 2, 0, 0)
+    assert L.icrl_ppo_lag_train(ctypes.byref(pol), None, None, None, ctypes.byref(buf), None, None, ctypes.byref(hp), None, None, None) == 1
+    assert _lib.last_route(_lib.FAMILY_UPDATE) == [0] * 8
+    assert L.icrl_ppo_lag_train_batch(0, None, None, 0, None) == 1
+    assert _lib.last_route(_lib.FAMILY_UPDATE) == [0] * 8
+    assert L.icrl_gae_dual(*([None] * 12), 0, 5, 0.99, 0.95, 0.99, 0.95, None) == 1
+    assert _lib.last_route(_lib.FAMILY_GAE) == [0] * 8
+    assert L.icrl_gae_dual_batch(0, None, 4, 4, 0.99, 0.95, 0.99, 0.95, None, 0, None) == 1
+    assert _lib.last_route(_lib.FAMILY_GAE) == [0] * 8
+    assert L.icrl_rollout_collect_batch(0, None, None, None, 0.99, 0.95, 0.99, 0.95, 1, None, 0, None) == 1
+    assert _lib.last_route(_lib.FAMILY_ROLLOUT) == [0] * 8
+    L.icrl_clear_error()
+    out = (ctypes.c_int32 * 8)(*([7] * 8))
+    for family in (-1, 3, 1 << 20):
+        assert L.icrl_debug_last_route(family, out) == 1
+        with pytest.raises(ValueError, match=rf"family {family} \(0 rollout, 1 update, 2 GAE\)"):
+            _lib.check(1, "icrl_debug_last_route")
+    assert L.icrl_debug_last_route(_lib.FAMILY_GAE, None) == 1 and b"out8 is NULL" in L.icrl_last_error()
+    L.icrl_clear_error()
+    assert list(out) == [7] * 8
+    # the header's names and the Python table are one list
+    src = open(os.path.join(ROOT, "include", "icrl_hip.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define (ICRL_(?:FAMILY|ROUTE|WS|PICK|UPDATE|GAE)_[A-Z0-9_]+) (\d+)", src)}
+    for name, code in _lib.ROUTE.items():
+        assert defs["ICRL_ROUTE_" + name.upper().replace("-", "_")] == code
+    for name, code in _lib.GAE_ROUTE.items():
+        if name != "none":
+            assert defs["ICRL_GAE_" + name.upper().replace("-", "_")] == code
+    assert (defs["ICRL_FAMILY_ROLLOUT"], defs["ICRL_FAMILY_UPDATE"], defs["ICRL_FAMILY_GAE"]) == (_lib.FAMILY_ROLLOUT, _lib.FAMILY_UPDATE, _lib.FAMILY_GAE)
+    assert (defs["ICRL_WS_NONE"], defs["ICRL_WS_XCH"], defs["ICRL_WS_PLANE"]) == (_lib.WS_NONE, _lib.WS_XCH, _lib.WS_PLANE)
+    assert [defs["ICRL_PICK_" + k] for k in ("SMALL", "ANALYTIC", "MON", "GRAN", "CN128", "MINW_SHIFT")] == \
+        [_lib.PICK_SMALL, _lib.PICK_ANALYTIC, _lib.PICK_MON, _lib.PICK_GRAN, _lib.PICK_CN128, _lib.PICK_MINW_SHIFT]
+    assert (defs["ICRL_UPDATE_GENERIC_PERSISTENT"], defs["ICRL_UPDATE_GENERIC_LAUNCHES"]) == (_lib.UPDATE_GENERIC_PERSISTENT, _lib.UPDATE_GENERIC_LAUNCHES)
 
 
 def test_generic_shape_limits_are_reported():

@@ -36,7 +36,7 @@ def test_entry_point_is_declared_exported_and_the_version_stays():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "icrl_hip.h")).read(), flags=re.S)
     assert re.search(r"\bicrl_cost_fn_rows\s*\(", src) and "icrl_cost_fn_t" in src and "ICRL_COST_FN" in src
     assert hasattr(L.lib(), "icrl_cost_fn_rows") and len(L.SIGNATURES["icrl_cost_fn_rows"]) == 6
-    assert L.lib().icrl_abi_version() == 106
+    assert L.lib().icrl_abi_version() == 107
 
 
 def _refused(err, L, text):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import tests.helpers.host_envs  # noqa: F401  (registers the Host* ids)
+from helpers import routes
 from helpers.cost_fn_cases import boundary_acs, boundary_obs
 
 pytestmark = pytest.mark.gpu
@@ -124,13 +125,29 @@ def test_rows_kernel_equals_numpy(N, od, ad):
 
 # ---- 2. every persistent kernel form against the per-step launches, bit for bit -----------------------------------------------------
 # one-workgroup-per-env | wide, two hops | wide, Ant (OCT 8) | multi, E = 4 with a ragged last workgroup | multi at Ant widths (40 envs
-# cannot hold the 115 statistics owners of the multi-env kernel and take the wide kernel; 128 envs = 32 workgroups of 4 reach it) |
-# generic persistent kernel around a policy with layers above 64 units
+# cannot hold the 115 statistics owners of the multi-env kernel, nor the 115 workgroups of the wide kernel, and are 4520 > 4096 observation
+# doubles: they run the per-step launches on both sides, which only shows that the forced flag is harmless there; 128 envs = 32 workgroups
+# of 4 reach the multi-env kernel) | generic persistent kernel around a policy with layers above 64 units
+# _FORM_ROUTES: what icrl_rollout_collect must have launched for each, asserted behind the call
+_FORM_ROUTES = {("hc", 7, "auto"): "persistent", ("hc", 130, "auto"): dict(route="wide", wgs=130), ("ant", 256, "auto"): dict(route="wide", wgs=256),
+                ("hc", 20, "multi"): dict(route="multi", envs_per_wg=4, wgs=5), ("ant", 40, "multi"): "per-step",
+                ("ant", 128, "multi"): dict(route="multi", envs_per_wg=4, wgs=32), ("hc", 12, "wide-policy"): "generic-persistent"}
 _FORMS = [("hc", 7, 33, "auto"), ("hc", 130, 24, "auto"), ("ant", 256, 6, "auto"), ("hc", 20, 33, "multi"), ("ant", 40, 10, "multi"),
           ("ant", 128, 6, "multi"), ("hc", 12, 40, "wide-policy")]
 
 
-@pytest.mark.parametrize("kind,N,T,kernel,cost", [f + (c,) for f in _FORMS for c in ("wall", "torque")] + [("hc", 7, 33, "auto", "both")])
+def _form_cases():
+    """every form under both costs; a forced kernel that does not take its shape carries what runs instead in its id"""
+    out = []
+    for f in _FORMS:
+        route = _FORM_ROUTES[f[0], f[1], f[3]]
+        falls = f[3] == "multi" and route == "per-step"
+        for c in ("wall", "torque"):
+            out.append(pytest.param(*f, c, id="-".join(str(x) for x in f) + ("-falls-to-per-step" if falls else "") + "-" + c))
+    return out + [pytest.param("hc", 7, 33, "auto", "both", id="hc-7-33-auto-both")]
+
+
+@pytest.mark.parametrize("kind,N,T,kernel,cost", _form_cases())
 def test_persistent_forms_equal_per_step_launches(kind, N, T, kernel, cost):
     limit = 1000 if kind == "hc" else 500
     akw = _WIDE_POLICY if kernel == "wide-policy" else None
@@ -148,7 +165,11 @@ def test_persistent_forms_equal_per_step_launches(kind, N, T, kernel, cost):
     fired = []
     for it in range(2):
         a_p.collect_rollouts(e_p, None, a_p.rollout_buffer, T, "cost", noise=noise[it])
+        got = routes.check_rollout(_FORM_ROUTES[kind, N, kernel], f"{kind} {N} {kernel} {cost}")
+        assert got["pick"] & routes.PICK_ANALYTIC      # (the instantiations without a cost-net register image)
         a_s.collect_rollouts(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise[it])
+        # (the launches per step: two, or the generic-shape path's policy forward, env step and normaliser — the analytic cost needs no launch)
+        routes.check_rollout(dict(route="generic-per-step", launches=3 * T) if kernel == "wide-policy" else dict(route="per-step", launches=2 * T), "steps")
         a_p.check_rollout_status()
         _assert_identical(a_p, e_p, a_s, e_s, it)
         assert a_p.rollout_buffer.dones.sum().item() == (N if it == 0 else a_s.rollout_buffer.dones.sum().item())

@@ -47,7 +47,7 @@ def test_entry_point_is_declared_exported_and_bound_like_its_sibling():
     assert args[-3:] == ["void* args_ws", "long long args_ws_bytes", "void* stream"]
     assert hasattr(L.lib(), "icrl_rollout_collect_batch_cost")
     assert L.SIGNATURES["icrl_rollout_collect_batch_cost"] == L.SIGNATURES["icrl_rollout_collect_batch_mon"]
-    assert L.lib().icrl_abi_version() == 106           # exports only: no struct and no existing signature changed
+    assert L.lib().icrl_abi_version() == 107           # exports only: no struct and no existing signature changed
 
 
 @pytest.mark.parametrize("fields,discrete,text", [

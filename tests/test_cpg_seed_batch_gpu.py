@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -109,6 +111,14 @@ _SHAPES = [("hc", 7, 33, ("wall", "torque", "both")), ("ant", 16, 6, ("wall", "t
            ("ant", 12, 6, ("torque", "wall")), ("hc", 80, 12, ("wall", "torque"))]
 
 
+# (kind, envs) -> (the words of a `few` batch, of any other batch; None: no other form serves the shape).  minw: the MINW the
+# one-workgroup-per-env kernel is instantiated with (the docstring's last template argument)
+_PB1, _PB2 = dict(route="persistent-batch", minw=1, envs_per_wg=1), dict(route="persistent-batch", minw=2, envs_per_wg=1)
+_BATCH_ROUTES = {("hc", 7): (_PB1, None), ("ant", 16): (_PB1, None), ("ant", 128): (_PB1, dict(route="multi-batch", envs_per_wg=4, wgs=32)),
+                 ("hc", 132): (None, dict(route="multi-batch", envs_per_wg=8, wgs=17)), ("clgw", 5): (_PB1, _PB2), ("ant", 12): (_PB1, None),
+                 ("hc", 80): (_PB2, dict(route="multi-batch", envs_per_wg=8, wgs=10))}
+
+
 @pytest.mark.parametrize("mon", [False, True], ids=["plain", "mon"])
 @pytest.mark.parametrize("kind,N,T,costs", _SHAPES, ids=[f"{k}-{n}x{t}-S{len(c)}" for k, n, t, c in _SHAPES])
 def test_batched_analytic_rollouts_equal_single_run_ones(kind, N, T, costs, mon):
@@ -117,8 +127,8 @@ def test_batched_analytic_rollouts_equal_single_run_ones(kind, N, T, costs, mon)
     equal bit for bit, and the first rollout's costs equal the numpy closed form on the rollout's own buffer.
 
     Kernels the batched call launches on an MI355X (256 CUs), as the dispatch of rollout_collect_batch_impl (csrc/rollout.hip) selects them
-    (`mon` adds the template argument MON = true); the selection is read off the dispatch code, a rocprofv3 --kernel-trace run to confirm
-    it is still owed.
+    (`mon` adds the template argument MON = true); the selection is asserted behind every batched call from the library's own record of it
+    (icrl_debug_last_route: _BATCH_ROUTES, with `few` = runs x envs within the device's compute units).
       hc-7x33-S3     rollout_persistent_batch_analytic_kernel<2, true, 1>     one workgroup per env, OCT 2, granule exchange, ragged count
       ant-16x6-S2    rollout_persistent_batch_analytic_kernel<8, false, 1>    one workgroup per env, OCT 8 (16 x 230 words: record exchange off)
       ant-128x6-S3   rollout_multi_batch_analytic_kernel<8, 4>                384 envs' worth of workgroups > CUs: 4 envs per workgroup, G = 32
@@ -142,6 +152,14 @@ def test_batched_analytic_rollouts_equal_single_run_ones(kind, N, T, costs, mon)
             a_s.collect_rollouts(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise[r, it])
             a_s.check_rollout_status()
         _batched_rollout([pair[1][0] for pair in runs], [noise[r, it] for r in range(S)])
+        few = S * N <= torch.cuda.get_device_properties(0).multi_processor_count and N <= 128
+        want = _BATCH_ROUTES[kind, N]
+        want = dict(want[0] if few or want[1] is None else want[1], n_runs=S, launches=1)
+        got_route = routes.check_rollout(want, f"{kind} {N} x {S}")
+        L = routes
+        assert got_route["pick"] & L.PICK_ANALYTIC and bool(got_route["pick"] & L.PICK_MON) == mon and bool(got_route["pick"] & L.PICK_SMALL) == (kind != "ant")
+        if got_route["route"] == "persistent-batch":
+            assert bool(got_route["pick"] & L.PICK_GRAN) == (N * (2 * {"hc": 18, "ant": 113, "clgw": 1}[kind] + 4) <= 3072)
         for r, ((a_s, e_s), (a_b, e_b)) in enumerate(runs):
             a_b.check_rollout_status()
             _assert_identical(a_b, e_b, a_s, e_s, (it, r))
@@ -243,6 +261,12 @@ def test_batched_cpg_equals_solo_cpg(shape, extra):
     solo = [_snapshot(*_solo(_cfg(sd, shape, extra))) for sd in seeds]
     out = run_cpg_seed_batch([_cfg(sd, shape, extra) for sd in seeds])
     assert len(out) == len(seeds)
+    # the batch's last rollout was ONE launch for the four runs (4 x 8 / 4 x 16 envs: one workgroup per env, the whole register file), and
+    # so was its last update at HalfCheetah widths (up to 16 runs: the kernel a run alone gets); at AntWall widths the updates go run
+    # after run through the single-run call (SeedBatch.per_run_wide_updates: four workgroups per network, minibatches of 64 rows)
+    got = routes.check_rollout(dict(route="persistent-batch", n_runs=len(seeds), minw=1, launches=1, wgs=16 if shape is _ANT else 8), "cpg batch")
+    assert bool(got["pick"] & routes.PICK_ANALYTIC) == (shape is _HC) and bool(got["pick"] & routes.PICK_MON) == ("--episode_stats" in extra)
+    routes.check_update(dict(kind=6, n_runs=1, wgs_per_network=4) if shape is _ANT else dict(kind=5, n_runs=len(seeds), wgs_per_network=4), "cpg batch")
     assert len({s["params"].tobytes() for s in solo}) == len(seeds)            # the runs really are different runs
     for sd, (model, history), want in zip(seeds, out, solo):
         assert model.num_timesteps == int(_cfg(sd, shape, extra).timesteps)

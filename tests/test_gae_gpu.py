@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import gae_cases as G
+from helpers import gae_cases as G, routes
 from oracle import gae as o_gae
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +147,8 @@ def test_gae_split_vs_oracle_random(T, N):
     ws = _ws(T, N)
     for rep in range(3):
         outs = _run_ws(arrs, params, 0, ws)
+        # (a workspace of icrl_gae_dual_ws_bytes at T <= 2048 and fewer than 1024 tiles: the register-resident split, 128 rows per workgroup)
+        routes.check_gae(dict(route="regsplit", code=-(-T // 128), tiles=-(-N // 64), n_runs=1), f"{T}x{N}")
         for got, key in zip(outs, ("reward_advantages", "cost_advantages", "reward_returns", "cost_returns")):
             assert np.allclose(got, o[key], rtol=2e-7, atol=1e-7), (key, rep)
             assert (got != o[key]).mean() < 1e-5
@@ -175,20 +177,25 @@ def test_gae_register_resident_split_golden(golden, case):
 def test_gae_mid_range_vs_oracle(T, N):
     """8 192 .. 65 472 envs (between the cache-resident and the streaming regime) through the DEFAULT heuristic with the
     workspace the library asks for: 2 048 .. 16 368 workgroups of the register-resident split scan, non-temporal accesses; ragged tiles and
-    ragged chunks; <= 1 ulp of float32 from the sequential scan and almost everywhere equal (ref: buffers.py:493-552)."""
+    ragged chunks; <= 1 ulp of float32 from the sequential scan and almost everywhere equal (ref: buffers.py:493-552).  That the automatic
+    call took the register-resident split is asserted from the library's record of it (128 rows per workgroup; the automatic choice takes
+    that form below 1024 column tiles, and 65 472 envs are 1023)."""
     arrs = _random_arrs(T, N)
     params = (0.99, 0.95, 0.99, 0.9)
     o = o_gae.dual_gae(arrs["rewards"], arrs["costs"], arrs["reward_values"], arrs["cost_values"],
                        arrs["dones"].astype(np.float32), arrs["last_v_r"], arrs["last_v_c"], arrs["last_dones"], *params)
     ws = _ws(T, N)
+    assert -(-N // 64) < 1024
     for rep in range(2):
         outs = _run_ws(arrs, params, 0, ws)
+        routes.check_gae(dict(route="regsplit", code=-(-T // 128), tiles=-(-N // 64), n_runs=1), f"{T}x{N}")
         for got, key in zip(outs, ("reward_advantages", "cost_advantages", "reward_returns", "cost_returns")):
             assert np.allclose(got, o[key], rtol=2e-7, atol=1e-7), (key, rep)
             assert (got != o[key]).mean() < 1e-5
     assert int(ws.view(torch.int32)[-1].item()) == 0
-    # and it IS the split scan that ran: the same launch with the sequential shape forced is bit-exact, this one is not required to be
+    # the sequential shape forced on the same inputs is bit-exact against the oracle (the split scan above is not required to be)
     seq = _run_ws(arrs, params, 1, ws)
+    routes.check_gae(dict(route="sequential", code=101, n_runs=1), "forced")
     assert np.array_equal(seq[0], o["reward_advantages"])
 
 
@@ -277,6 +284,9 @@ def test_gae_every_form_at_every_parameter_set_and_done_pattern(shape, N, p, pat
     arrs, params, o = G.form_case(N, p, pattern)
     ws = _ws(G.T_FORMS, N) if shape in (203, 500, 0) else None
     (outs,) = _run_guarded(arrs, params, shape, ws)
+    routes.check_gae({1: dict(route="sequential", code=101), 4: dict(route="sequential", code=4), 16: dict(route="sequential", code=16),
+                      106: dict(route="sequential", code=106), 108: dict(route="sequential", code=108), 111: dict(route="sequential", code=111),
+                      203: dict(route="split", code=3), 500: dict(route="regsplit", code=3), 0: dict(route="regsplit", code=3)}[shape], f"form {shape}")
     for got, key in zip(outs, G.OUT_KEYS):
         if shape in (1, 106, 108, 111):
             assert np.array_equal(got, o[key]), key
@@ -305,6 +315,9 @@ def _assert_split_bounds(got, want, key):
         assert (got != want).mean() < 1e-5, (key, int((got != want).sum()))
 
 
+_TWO_PASS_C = {(2049, 70): 16, (2304, 130): 10, (4096, 64): 16, (2304, 1100): 14, (512, 200): 4, (1000, 130): 16}      # workgroups per tile (the docstring's)
+
+
 @pytest.mark.parametrize("T,N,shape", [(2049, 70, 0), (2304, 130, 0), (4096, 64, 0), (2304, 1100, 0), (512, 200, 204), (1000, 130, 216)])
 def test_gae_two_pass_split_where_it_is_the_default_and_over_several_tiles(T, N, shape):
     """gae_dual_split_kernel: the default for every T > 2048 with a workspace (shape 0: 16 / 10 / 16 workgroups per tile; 18 tiles under the
@@ -314,6 +327,7 @@ def test_gae_two_pass_split_where_it_is_the_default_and_over_several_tiles(T, N,
     for outs in _run_guarded(arrs, _SWAP_PARAMS, shape, ws, launches=2):
         for got, key in zip(outs, G.OUT_KEYS):
             _assert_split_bounds(got, o[key], key)
+    routes.check_gae(dict(route="split", code=_TWO_PASS_C[T, N], tiles=-(-N // 64), n_runs=1), f"{T}x{N} shape {shape}")
     assert _status(ws) == 0
 
 
@@ -369,6 +383,10 @@ _BATCH_CASES = [(300, 130, 3, ""),              # register-resident batch kernel
                 (300, 130, 3, "no_args_ws")]    # no argument scratch: n_runs single launches
 
 
+_BATCH_ROUTES = {(300, 130, ""): "batch-regsplit", (2048, 64, ""): "batch-regsplit", (2304, 70, ""): "batch-split", (2304, 1100, ""): "batch-split",
+                 (1025, 16400, ""): "batch-regsplit", (300, 130, "job1_no_ws"): "batch-singles", (300, 130, "no_args_ws"): "batch-singles"}
+
+
 @pytest.mark.parametrize("T,N,n_runs,variant", _BATCH_CASES)
 def test_gae_dual_batch_vs_oracle_and_vs_the_single_launch(T, N, n_runs, variant):
     """icrl_gae_dual_batch on its own: every branch (register-resident, non-temporal register-resident, two-pass, the fallback to single
@@ -384,6 +402,7 @@ def test_gae_dual_batch_vs_oracle_and_vs_the_single_launch(T, N, n_runs, variant
     for launch in range(2):
         _lib.check(L.icrl_gae_dual_batch(n_runs, garr, T, N, *[float(p) for p in _SWAP_PARAMS], _lib.ptr(args_ws),
                                          args_ws.numel() if args_ws is not None else 0, _lib.current_stream()), "icrl_gae_dual_batch")
+        routes.check_gae(dict(route=_BATCH_ROUTES[T, N, variant], tiles=-(-N // 64), n_runs=n_runs), f"batch {T}x{N} {variant}")
         torch.cuda.synchronize()
         for r in runs:
             _check_guard(r.outs, T)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 EXPERT = os.path.join(HERE, "golden/expert_hc.npz")
@@ -343,6 +345,12 @@ def _batch_gail(cfgs):
     from icrl_amd.seed_batch import GailSeedBatch
     sb = GailSeedBatch(cfgs)
     out = sb.learn()
+    # the batch's last rollout was ONE launch for all runs (S x 4 envs: one workgroup per env, the whole register file; no cost in a GAIL
+    # chain), and so was its last update at HalfCheetah widths (up to 16 runs: the kernel a run alone gets); at AntWall widths the updates
+    # go run after run through the single-run call (SeedBatch.per_run_wide_updates: four workgroups per network, minibatches of 64 rows)
+    S, ant = len(cfgs), "AntWall" in cfgs[0].train_env_id
+    routes.check_rollout(dict(route="persistent-batch", n_runs=S, minw=1, launches=1, wgs=4), "gail batch")
+    routes.check_update(dict(kind=6, n_runs=1, wgs_per_network=4) if ant else dict(kind=5, n_runs=S, wgs_per_network=4), "gail batch")
     snaps = []
     for st, (model, disc, history) in zip(sb.states, out):
         snaps.append(_snap(model, disc, history, _logged(st["logger"])))
@@ -408,6 +416,8 @@ def test_icrl_seeds_end_to_end(tmp_path):
             "-ft", "1000", "-ni", "2", "-bi", "5", "-dno", "-dnr", "-dnc", "-nt", "2", "--n_steps", "250", "-s", "0",
             "--expert_agent_path", expert, "-v", "0", "--cn_batch_size", "64"]
     got = I.main(argv + ["--seeds", "0", "1", "--save_dir", str(tmp_path / "cli")])
+    lgw_batch = (dict(route="persistent-batch", n_runs=2, wgs=2, launches=1, minw=1), dict(kind=5, n_runs=2, wgs_per_network=4))      # Discrete, obs 1
+    routes.check_rollout(lgw_batch[0], "icrl --seeds"); routes.check_update(lgw_batch[1], "icrl --seeds")
     for sd in (0, 1):
         d = tmp_path / "cli" / f"seed_{sd}"
         for name in ("config.json", "best_nominal_model.zip", "best_nominal_model_policy.pth", "best_cn_model.pt", "train_env_stats.pkl",
@@ -416,6 +426,7 @@ def test_icrl_seeds_end_to_end(tmp_path):
     base = vars(I.build_parser().parse_args(argv))
     base.update(rank=0, world_size=1, seeds=[0, 1])
     _, want, _ = run_seed_batch(utils.seed_configs(base), 2)
+    routes.check_rollout(lgw_batch[0], "run_seed_batch"); routes.check_update(lgw_batch[1], "run_seed_batch")
     assert len(got) == len(want) == 2
     for sd in (0, 1):
         a, b = got[sd][-1], want[sd][-1]

@@ -31,7 +31,7 @@ def test_host_episode_step_is_declared_and_listed():
         assert t is (ctypes.c_void_p if "*" in a else ctypes.c_int), a
     assert "icrl_host_episode_step" not in _lib.RESTYPES         # returns int (hipError_t), like its neighbours
     # an additive change: the ABI version stays where icrl_host_step left it
-    assert "icrl_abi_version(void) { return 106; }" in open(os.path.join(ROOT, "icrl_amd", "csrc", "gae.hip")).read()
+    assert "icrl_abi_version(void) { return 107; }" in open(os.path.join(ROOT, "icrl_amd", "csrc", "gae.hip")).read()
 
 
 def test_readme_documents_the_switch():

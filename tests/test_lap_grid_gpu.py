@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
 from oracle import loop as o_loop, nets as o_nets, ppo as o_ppo
 
 pytestmark = pytest.mark.gpu
@@ -78,6 +79,7 @@ def test_learn_matches_reference_golden(golden):
         p = np.zeros((3, N * T), np.int64)
         p[:len(perms[it])] = perms[it]
         agent.train(perms=p)
+        routes.check_update(dict(kind=5, wgs_per_network=4, n_runs=1), "lgw golden")      # obs 1: wave quads, four workgroups per network
     from icrl_amd import logger
     lg = logger.Logger.CURRENT.name_to_value
     assert lg["train/early_stop_epoch"] == g["log/early_stop_epoch"].item()
@@ -165,6 +167,10 @@ def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None):
     if hset is not None:      # conditions on the inputs, from the oracle's trace, before the kernel runs
         H.check_trace(trace, dict(hp, ent_coef=ent), n_steps=E * (-(-N * T // B)))
     agent.train(perms=perms)
+    # which update ran: the generic-shape path as one persistent launch for layers above 64 / an `arch` / more than 256 rows (three launches
+    # per step under ICRL_GEN_LAUNCHES), else wave quads with four workgroups per network up to 32 observations, wave pairs up to 64
+    want = (9 if os.environ.get("ICRL_GEN_LAUNCHES") else 8) if (wide or B > 256) else (5 if O <= 32 else 0)
+    routes.check_update(dict(kind=want, n_runs=1), f"categorical obs {O} B {B} wide {wide}")
     lg = logger.Logger.CURRENT.name_to_value
     n_steps = agent.policy.adam_step
     for k, v in agent.policy.state_dict().items():

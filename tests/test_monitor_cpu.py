@@ -44,7 +44,7 @@ def test_new_entry_points_are_exported_and_the_abi_version_stays():
     b, bm = L.SIGNATURES["icrl_rollout_collect_batch"], L.SIGNATURES["icrl_rollout_collect_batch_mon"]
     assert bm == b[:2] + [ctypes.c_void_p] + b[2:]
     assert L.SIGNATURES["icrl_monitor_scan"] == [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
-    assert lib.icrl_abi_version() == 106
+    assert lib.icrl_abi_version() == 107
     # scratch of the scan: 4 ints + one count per row + one prefix per row and 64-column chunk
     assert lib.icrl_monitor_ws_bytes(64, 2048) == 4 * (4 + 64 + 64 * 32)
     assert lib.icrl_monitor_ws_bytes(2048, 64) == 4 * (4 + 2048 + 2048)

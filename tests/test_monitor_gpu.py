@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -161,7 +163,7 @@ CASES = {
     "persistent-hc-1": (1, 64, "hc", None, {}, None),
     "persistent-hc-7": (7, 64, "hc", None, {}, None),
     "persistent-hc-64": (64, 128, "hc", None, {}, None),
-    "persistent-hc-128": (128, 64, "hc", None, {}, None),
+    "wide-hc-128": (128, 64, "hc", None, {}, None),      # (more than 96 envs: the column-partitioned kernel without being asked for)
     "steps-hc-16": (16, 64, "hc", "steps", {}, None),
     "wide-ant-256": (256, 32, "ant", "wide", {}, None),
     "multi-hc-64": (64, 128, "hc", "multi", {}, None),
@@ -171,6 +173,13 @@ CASES = {
     "lgw-6": (6, 64, "lgw", None, {}, None),
     "clgw-6": (6, 64, "clgw", None, {}, None),
 }
+
+
+# what icrl_rollout_collect_ex_mon must have launched for each form (helpers/routes.py); every one-launch form is the instantiation that
+# stores the raw-reward plane
+ROUTES = {"persistent-hc-1": "persistent", "persistent-hc-7": "persistent", "persistent-hc-64": "persistent", "wide-hc-128": "wide",
+          "steps-hc-16": "per-step", "wide-ant-256": "wide", "multi-hc-64": "multi", "multi-hc-2048": "multi",
+          "generic-policy-hc-12": "generic-persistent", "wide-cn-hc-12": "generic-per-step", "lgw-6": "persistent", "clgw-6": "persistent"}
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -192,6 +201,8 @@ def test_kernel_form_against_python_monitor(case):
     ended_inside = 0
     for it in range(3):
         assert agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost", noise=noise[it]) is True
+        got = routes.check_rollout(ROUTES[case], case)
+        assert bool(got["pick"] & routes.PICK_MON) == (not ROUTES[case].endswith("per-step"))
         agent.check_rollout_status()
         rew, done = _twin_rows(twin, agent, T)
         # the buffer's own done flags are the twin's (row t + 1 = step t; last_dones = the last step)
@@ -221,6 +232,9 @@ def test_seed_batch_entry_point_against_python_monitor():
     for it in range(3):
         jobs = [a._rollout_begin(None, a.rollout_buffer, T, noise[r][it]) for r, a in enumerate(agents)]
         sb._launch_rollouts(agents, jobs)
+        # 3 x 8 envs: ONE launch of the one-workgroup-per-env batch kernel, the instantiation that stores the raw-reward plane
+        got = routes.check_rollout(dict(route="persistent-batch", n_runs=S, wgs=N, launches=1, minw=1), "3 x 8 with monitors")
+        assert got["pick"] & _lib.PICK_MON
         for r, (a, env, _) in enumerate(runs):
             a._rollout_end(jobs[r], env, None, a.rollout_buffer, T)
             a.check_rollout_status()

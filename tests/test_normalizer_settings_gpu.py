@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import norm_cases as nc
+from helpers import norm_cases as nc, routes
 from oracle import loop as o_loop, stats as o_stats
 
 pytestmark = pytest.mark.gpu
@@ -99,14 +99,16 @@ _PLANES = ("observations", "orig_observations", "new_observations", "actions", "
 # persistent kernel (rollout_generic_kernel).  Every kernel has an hc case (upper reward clip) and an ant / antbroken one (lower).
 # ant 128x10 on multi: rollout_multi_kernel takes a shape only with >= 4 envs per group of statistics owners (115 statistics: >= 116
 # envs); ant 32x20 with `multi` forced is served by the persistent kernel, so this is the Ant case that RUNS the multi-env kernel.
-_FUSED = [("auto", "hc", 7, 33, "tight"), ("auto", "hc", 64, 40, "tight"), ("auto", "ant", 32, 20, "tight"), ("auto", "hc", 64, 40, "eps"),
-          ("wide", "hc", 130, 24, "tight"), ("wide", "antbroken", 512, 10, "tight"),
-          ("multi", "hc", 37, 21, "tight"), ("multi", "hc", 300, 12, "tight"), ("multi", "ant", 32, 20, "tight"), ("multi", "hc", 37, 21, "eps"),
-          ("multi", "ant", 128, 10, "tight"),
-          ("steps", "hc", 7, 33, "tight"), ("steps", "ant", 32, 20, "tight"),
-          ("wide-policy", "hc", 16, 40, "tight"),
-          ("auto", "hc", 64, 40, "tight_no_rew"), ("multi", "hc", 64, 40, "tight_no_rew"),
-          ("auto", "hc", 64, 40, "tight_no_obs"), ("multi", "hc", 64, 40, "tight_no_obs")]
+# The last field is what icrl_rollout_collect must have launched (helpers/routes.py), asserted behind the call.
+_FUSED = [("auto", "hc", 7, 33, "tight", "persistent"), ("auto", "hc", 64, 40, "tight", "persistent"), ("auto", "ant", 32, 20, "tight", "persistent"),
+          ("auto", "hc", 64, 40, "eps", "persistent"),
+          ("wide", "hc", 130, 24, "tight", "wide"), ("wide", "antbroken", 512, 10, "tight", "wide"),
+          ("multi", "hc", 37, 21, "tight", "multi"), ("multi", "hc", 300, 12, "tight", "multi"), ("multi", "ant", 32, 20, "tight", "persistent"),
+          ("multi", "hc", 37, 21, "eps", "multi"), ("multi", "ant", 128, 10, "tight", "multi"),
+          ("steps", "hc", 7, 33, "tight", "per-step"), ("steps", "ant", 32, 20, "tight", "per-step"),
+          ("wide-policy", "hc", 16, 40, "tight", "generic-persistent"),
+          ("auto", "hc", 64, 40, "tight_no_rew", "persistent"), ("multi", "hc", 64, 40, "tight_no_rew", "multi"),
+          ("auto", "hc", 64, 40, "tight_no_obs", "persistent"), ("multi", "hc", 64, 40, "tight_no_obs", "multi")]
 
 
 def _gpu_chain(kind, N, T, kw, o, kernel="auto", net_arch=None, seed=7):
@@ -135,8 +137,13 @@ def _gpu_chain(kind, N, T, kw, o, kernel="auto", net_arch=None, seed=7):
     return agent, env
 
 
-@pytest.mark.parametrize("kernel,kind,N,T,case", _FUSED, ids=[f"{k}-{e}-{n}x{t}-{c}" for k, e, n, t, c in _FUSED])
-def test_fused_rollout_vs_port_under_settings(kernel, kind, N, T, case):
+def _fused_id(k, e, n, t, c, route):
+    """a forced kernel that does not take its shape carries what runs instead in its id"""
+    return f"{k}-{e}-{n}x{t}-{c}" + (f"-falls-to-{route}" if k in ("wide", "multi") and route != k else "")
+
+
+@pytest.mark.parametrize("kernel,kind,N,T,case,route", _FUSED, ids=[_fused_id(*f) for f in _FUSED])
+def test_fused_rollout_vs_port_under_settings(kernel, kind, N, T, case, route):
     """test_fused_rollout_vs_port's comparison (same planes, same statistics checks, same bound) with the normaliser at a named setting."""
     wide = kernel == "wide-policy"
     o = nc.oracle_rollout(kind, N, T, case, net_arch=nc.WIDE_ARCH if wide else None)
@@ -144,6 +151,7 @@ def test_fused_rollout_vs_port_under_settings(kernel, kind, N, T, case):
     nc.check_rollout_inputs(case, kind, b, o["counter"], N, RTOL, ATOL)
     agent, env = _gpu_chain(kind, N, T, nc.CASES[case], o, kernel, nc.WIDE_ARCH if wide else None)
     agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost", noise=torch.as_tensor(o["noise"], device="cuda"))
+    routes.check_rollout(route, f"{kernel} {kind} {N}x{T} {case}")
     agent.check_rollout_status()
     rb = agent.rollout_buffer
     worst = {}
@@ -164,8 +172,21 @@ def test_fused_rollout_vs_port_under_settings(kernel, kind, N, T, case):
 
 
 # ---- c. kernel against kernel, bit for bit ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", ["auto", "wide", "multi"])
-@pytest.mark.parametrize("kind,N,T", [("hc", 7, 33), ("hc", 130, 24), ("hc", 300, 12), ("ant", 32, 20)])
+# what each case launches: test_rollout_gpu.ONE_LAUNCH_ROUTES, asserted in the body.  hc 7 and ant 32 are fewer envs than `wide` (obs + 2
+# workgroups: 20 / 115) and `multi` (4 envs per group of statistics owners: 20 / 116) take: forced, they run what `auto` runs there, the
+# one-workgroup-per-env kernel, and their ids say so; hc 20, ant 115 and ant 116 are the smallest shapes the named kernels do run.
+def _tight_cases():
+    out = []
+    for kernel in ("auto", "wide", "multi"):
+        for kind, N, T in (("hc", 7, 33), ("hc", 130, 24), ("hc", 300, 12), ("ant", 32, 20)):
+            falls = kernel != "auto" and (kind, N) in (("hc", 7), ("ant", 32))
+            out.append(pytest.param(kind, N, T, kernel, id=f"{kind}-{N}-{T}-{kernel}" + ("-falls-to-persistent" if falls else "")))
+    out += [pytest.param("hc", 20, 12, "wide", id="hc-20-12-wide"), pytest.param("hc", 20, 12, "multi", id="hc-20-12-multi"),
+            pytest.param("ant", 115, 20, "wide", id="ant-115-20-wide"), pytest.param("ant", 116, 20, "multi", id="ant-116-20-multi")]
+    return out
+
+
+@pytest.mark.parametrize("kind,N,T,kernel", _tight_cases())
 def test_one_launch_rollouts_equal_per_step_launches_under_tight(kind, N, T, kernel):
     """test_persistent_rollout_equals_per_step_launches with both chains under `tight` (a forced kernel that does not take a shape leaves
     it to the next one in line: wide needs >= obs + 2 workgroups, multi >= 4 envs per group of statistics owners)."""
@@ -308,6 +329,7 @@ def test_batched_launch_reads_each_runs_own_normaliser(N, T):
             a._setup_learn(N * T)
             e.unwrapped.t_ep.fill_(o["start"])
         a_s.collect_rollouts(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise)
+        routes.check_rollout("multi" if N >= 20 else "persistent", f"solo {N}")      # (fewer than 20 hc envs: the forced multi-env kernel declines)
         a_s.check_rollout_status()
     agents = [pair[1][0] for pair in pairs]
     jobs = [a._rollout_begin(None, a.rollout_buffer, T, noise) for a in agents]
@@ -318,6 +340,9 @@ def test_batched_launch_reads_each_runs_own_normaliser(N, T):
     _lib.check(_lib.lib().icrl_rollout_collect_batch(3, arr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
                                                      float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, p(ws), ws.numel(), _lib.current_stream()),
                "icrl_rollout_collect_batch")
+    # (3 x N workgroups within the compute units: one workgroup per env; beyond: the multi-env kernel, 8 envs per workgroup)
+    few = 3 * N <= torch.cuda.get_device_properties(0).multi_processor_count
+    routes.check_rollout(dict(route="persistent-batch", minw=1) if few else dict(route="multi-batch", envs_per_wg=8), f"3 x {N}")
     for a, j in zip(agents, jobs):
         a._rollout_end(j, a.env, None, a.rollout_buffer, T)
     torch.cuda.synchronize()

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import point_env
+from helpers import point_env, routes
 from oracle import loop as o_loop, nets as o_nets, stats as o_stats
 from oracle.streams import SeededStreams
 from test_point_env_cpu import IDS, KINDS, SEQS, compare_with_golden
@@ -96,8 +96,13 @@ def test_step_kernel_vs_reference_recording(golden, env_id):
 # env_step_wave), the per-step launches below 12 envs, the column-partitioned kernel above 96 (128); "multi": several envs per workgroup
 # forced (its Point envs step through env_step_wave, one env per wave; 8 envs: refused by its shape rule, per-step launches);
 # "steps": one launch per env step
+# (envs, rollout_kernel) -> what icrl_rollout_collect must have launched (9 observations: 11 statistics, the multi-env kernel takes >= 12 envs)
+_ROUTES = {(4, "auto"): "per-step", (64, "auto"): dict(route="multi", envs_per_wg=8, wgs=8), (64, "multi"): dict(route="multi", envs_per_wg=8, wgs=8),
+           (8, "multi"): "per-step", (128, "auto"): dict(route="wide", wgs=128), (4, "steps"): "per-step"}
+
+
 @pytest.mark.parametrize("cost", ["wall", "cn"])
-@pytest.mark.parametrize("N,T,kernel", [(4, 160, "auto"), (64, 40, "auto"), (64, 40, "multi"), (8, 160, "multi"), (128, 20, "auto"), (4, 40, "steps")])
+@pytest.mark.parametrize("N,T,kernel", [(4, 160, "auto"), (64, 40, "auto"), (64, 40, "multi"), pytest.param(8, 160, "multi", id="8-160-multi-falls-to-per-step"), (128, 20, "auto"), (4, 40, "steps")])
 def test_fused_rollout_vs_port(N, T, kernel, cost):
     from icrl_amd.ppo_lag import PPOLagrangian
     from icrl_amd.true_constraint_net import AnalyticCost
@@ -131,6 +136,7 @@ def test_fused_rollout_vs_port(N, T, kernel, cost):
         env.unwrapped.t_ep.fill_(near_end)
         stack.env.t_ep[:] = near_end
     agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost", noise=torch.as_tensor(noise, device="cuda"))
+    routes.check_rollout(_ROUTES[N, kernel], f"point {N} {kernel} {cost}")
     agent.check_rollout_status()
     b = port.collect_rollouts(noise)
     rb = agent.rollout_buffer

@@ -41,7 +41,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import norm_cases as nc, policy_states as ps
+from helpers import norm_cases as nc, policy_states as ps, routes
 from oracle import loop as o_loop, nets as o_nets
 
 pytestmark = pytest.mark.gpu
@@ -281,6 +281,7 @@ def test_batched_rollout_reads_each_runs_own_policy(N, T):
             a._setup_learn(N * T)
             e.unwrapped.t_ep.fill_(os_[0]["start"])
         a_s.collect_rollouts(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise)
+        routes.check_rollout("multi" if N >= 20 else "persistent", f"solo {N}")      # (fewer than 20 hc envs: the forced multi-env kernel declines)
         a_s.check_rollout_status()
     agents = [pair[1][0] for pair in pairs]
     jobs = [a._rollout_begin(None, a.rollout_buffer, T, noise) for a in agents]
@@ -291,6 +292,9 @@ def test_batched_rollout_reads_each_runs_own_policy(N, T):
     _lib.check(_lib.lib().icrl_rollout_collect_batch(3, arr, p(a0._alow), p(a0._ahigh), float(a0.reward_gamma), float(a0.reward_gae_lambda),
                                                      float(a0.cost_gamma), float(a0.cost_gae_lambda), 1, p(ws), ws.numel(), _lib.current_stream()),
                "icrl_rollout_collect_batch")
+    # (3 x N workgroups within the compute units: one workgroup per env; beyond: the multi-env kernel, 8 envs per workgroup)
+    few = 3 * N <= torch.cuda.get_device_properties(0).multi_processor_count
+    routes.check_rollout(dict(route="persistent-batch", minw=1) if few else dict(route="multi-batch", envs_per_wg=8), f"3 x {N}")
     for a, j in zip(agents, jobs):
         a._rollout_end(j, a.env, None, a.rollout_buffer, T)
     torch.cuda.synchronize()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
 from oracle import nets as o_nets, ppo as o_ppo
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +92,27 @@ def test_three_steps_on_one_batch_golden(golden, name, arch):
                 off += n
         osd = pol.optimizer_state_dict(lr=3e-4)
         assert tuple(osd["state"][1]["exp_avg"].shape) == g["w0/" + list(pol.shapes)[1]].shape      # (logical shape of the first weight)
+
+
+# Which kernel a single run must get, asserted behind every train() of the oracle comparisons below (icrl_debug_last_route; the numbering is
+# prepare_train's in csrc/ppo_train.hip, 8 / 9 the generic-shape path as one persistent launch / as three launches per optimiser step).
+# (env, train_kernel) -> kind; for obs 113 by minibatch rows as well.  The switches that child processes of this file set are part of it.
+_HC_KINDS = {None: 5, "halves": 4, "pairs": 0, "tiles": 3}
+_ANT_KINDS = {None: (6, 7), "rows": (1, 2), "rows1": (1, 1), "tiles": (3, 3)}      # (one chunk or more than two, minibatches of 65..128 rows)
+# what the persistent form declines (launch_train_generic_persistent): more than 131 072 parameters (huge), an LDS row image above 904
+# floats (ant-wide: 128 observation columns + 688 units), 481..512-row minibatches unless two of its workgroups fit a compute unit
+_GENERIC_AS_LAUNCHES = {("hc", "huge", 64), ("ant", "wide", 128), ("hc", "", 512)}      # (env, architecture of helpers/arches.py or "", rows)
+
+
+def _update_kind(kind, shape, B, train_kernel=None):
+    if shape or B > 256:
+        return 9 if os.environ.get("ICRL_GEN_LAUNCHES") or (kind, shape, B) in _GENERIC_AS_LAUNCHES else 8
+    if kind == "hc":
+        return _HC_KINDS[train_kernel]
+    two_chunks = 64 < B <= 128
+    if train_kernel is None and two_chunks and os.environ.get("ICRL_QUARTERS_PASSES", "")[:1] == "1":
+        return 6
+    return _ANT_KINDS[train_kernel][two_chunks]
 
 
 ADAM_DEV_BOUND = 5e-4      # 3 x the largest deviation measured on MI355X (1.7e-4 x lr x steps; absolute: <= 9e-8, ~1 ulp)
@@ -185,6 +207,8 @@ def test_train_vs_oracle(kind, N, T, B, E, tk, one_workgroup_per_network=False, 
     perms = np.stack([rng.permutation(T * N) for _ in range(E)])
     nu = agent.dual.nu().item()
     agent.train(perms=perms)
+    forced = train_kernel if train_kernel is not None else ("rows1" if one_workgroup_per_network else None)
+    routes.check_update(dict(kind=_update_kind(kind, shape, B, forced), n_runs=1), f"{kind}-{shape} B={B} {forced}")
     pol, out = _oracle_train(sd0, buf, perms, kind, nu, lr=lr, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=tk, okw=okw)
     _compare_with_oracle(agent, {k: p_.detach().numpy() for k, p_ in pol.params.items()}, out, kind, B, lr)
 
@@ -204,7 +228,8 @@ def _hp_cases():
     for kernel in ("halves", "pairs"):
         add([("hc", 8, 32, 64, 3), ("hc", 5, 60, 200, 2)], "A", kernel)
     add([("ant", 24, 16, 128, 2), ("ant", 6, 32, 64, 2)], "AB", "rows"); add([("ant", 24, 16, 128, 2)], "A", "rows1")
-    # generic-shape path, persistent form (its other forms: test_generic_shape_update_as_one_persistent_launch selects these cases too)
+    # generic-shape path, persistent form — 512-row minibatches: its three launches per optimiser step, see _GENERIC_AS_LAUNCHES — (the other forms:
+    # test_generic_shape_update_as_one_persistent_launch selects these cases too)
     add([("hc-wide", 8, 32, 64, 3), ("hc-trunk", 9, 48, 144, 2), ("hc", 8, 128, 512, 3)], "AB")
     return cases
 
@@ -236,6 +261,7 @@ def test_train_hparams_vs_oracle(kind, N, T, B, E, hset, train_kernel, policy_st
     from icrl_amd import logger
     logger.configure()                 # (an empty log: keys of an earlier test's agent do not count)
     agent.train(perms=case["perms"])
+    routes.check_update(dict(kind=_update_kind(kind, shape, B, train_kernel), n_runs=1), f"{kind}-{shape} B={B} {train_kernel}")
     rel = _compare_with_oracle(agent, case["params"], case["out"], kind, B, lr)
     print(f"ADAM_DEV_HP {kind}{'-' + shape if shape else ''} {N}x{T} B={B} E={E} set {hset} kernel {train_kernel or 'default'} state {policy_state or 'fresh'}: "
           f"{rel:.3g} x lr x steps = {rel / ADAM_DEV_BOUND:.3f} of the bound")

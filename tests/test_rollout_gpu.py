@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
 from oracle import loop as o_loop, nets as o_nets, stats as o_stats
 from oracle.synth_env import SynthVecEnv
 
@@ -175,15 +176,28 @@ def test_fused_rollout_vs_reference_golden(golden):
     assert agent.num_timesteps == N * T
 
 
-# ant 96 / hc 256 / antbroken 512: per-step launches (generic normaliser kernel); the others: persistent kernel.
+# What each case launches is stated in _PORT_ROUTES below and asserted (icrl_debug_last_route): the one-workgroup-per-env persistent kernel
+# up to 96 envs and 4096 observation doubles, the column-partitioned kernel beyond (hc 256, antbroken 512: it needs obs + 2 workgroups),
+# the per-step launches where neither serves (ant 96: 10 848 doubles, 96 < 115 workgroups).
 # hc 256 = the per-GPU shard of BASELINE configs[3] (2048 envs / 8), antbroken 512 = that of configs[4] (4096 envs / 8) with the
 # reference's committed AntBroken constraint net loaded through the (quirky) ConstraintNet.load and action[4:] zeroed.
 # kernel "multi": rollout_multi_kernel (MFMA tiles, several envs per workgroup: every seed-batch rollout and any run with more than 1024
 # envs) forced at shapes the other kernels normally serve, so that it is compared with the ORACLE directly and not only with the
 # per-step launches (on_policy_algorithm.py:340-421, policies.py:716-731).
+# (kind, envs, rollout_kernel) -> what icrl_rollout_collect must have launched
+_PORT_ROUTES = {("hc", 64, "auto"): "persistent", ("ant", 96, "auto"): "per-step", ("ant", 32, "auto"): "persistent", ("hc", 256, "auto"): "wide",
+                ("antbroken", 512, "auto"): "wide", ("hc", 64, "multi"): dict(route="multi", envs_per_wg=8, wgs=8),
+                ("antbroken", 512, "multi"): dict(route="multi", envs_per_wg=8, wgs=64), ("ant", 96, "multi"): "per-step",
+                ("ant", 116, "multi"): dict(route="multi", envs_per_wg=4, wgs=29),
+                ("hc", 16, "wide-policy"): "generic-persistent", ("ant", 8, "wide-policy"): "generic-persistent"}
+
+
 @pytest.mark.parametrize("kind,N,T,kernel", [("hc", 64, 300, "auto"), ("ant", 96, 40, "auto"), ("ant", 32, 60, "auto"), ("hc", 256, 40, "auto"),
                                              ("antbroken", 512, 12, "auto"), ("hc", 64, 300, "multi"), ("antbroken", 512, 12, "multi"),
-                                             ("ant", 96, 40, "multi"),
+                                             # 96 Ant envs are fewer than the multi-env kernel takes (4 envs per group of statistics owners: 116 with the
+                                             # 115 statistics of AntWall), and fewer than every other one-launch form takes: the per-step launches
+                                             pytest.param("ant", 96, 40, "multi", id="ant-96-40-multi-falls-to-per-step"),
+                                             ("ant", 116, 12, "multi"),
                                              # a policy with layers above 64 (-pl 128 96 -rvl 80 128 -cvl 128 128, icrl/utils.py:636-655): the
                                              # per-step launches of icrl_rollout_collect with the generic-shape forward kernel
                                              ("hc", 16, 120, "wide-policy"), ("ant", 8, 30, "wide-policy")])
@@ -232,6 +246,7 @@ def test_fused_rollout_vs_port(kind, N, T, kernel):
     if near_end is not None:
         stack.env.t_ep[:] = near_end
     agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost", noise=torch.as_tensor(noise, device="cuda"))
+    routes.check_rollout(_PORT_ROUTES[kind, N, kernel], f"{kind} {N} {kernel}")
     agent.check_rollout_status()
     b = port.collect_rollouts(noise)
     rb = agent.rollout_buffer
@@ -280,14 +295,17 @@ _BUF_KEYS = ("observations", "orig_observations", "new_observations", "new_orig_
 
 def test_stepped_rollout_equals_fused_rollout():
     """the per-step loop over the fine-grained entry points (the reference's own structure, on_policy_algorithm.py:340-421)
-    and the fused launch sequence are two drivers of the same kernels: identical buffers and normaliser statistics."""
+    and the fused call — 16 hc envs: ONE launch of the one-workgroup-per-env persistent kernel, asserted — compute the same rollout
+    with different kernels: buffers within the fp32 tolerance of the two policy forwards, normaliser statistics to 1e-12."""
     N, T = 16, 48
     (a_f, e_f, _), (a_s, e_s, _) = _pair_of_agents(N, T, 11)
     noise = torch.as_tensor(np.random.RandomState(3).randn(2, T, N, 6).astype(np.float32), device="cuda")
     a_f._setup_learn(2 * N * T); a_s._setup_learn(2 * N * T)
     for it in range(2):
         a_f.collect_rollouts(e_f, None, a_f.rollout_buffer, T, "cost", noise=noise[it])
+        routes.check_rollout(dict(route="persistent", wgs=N, launches=1), "16 hc envs, fused")
         a_s._collect_rollouts_stepped(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise[it])
+        routes.check_rollout(dict(route="persistent", wgs=N, launches=1), "the stepped loop calls no rollout entry point: the record stays")
         for k in _BUF_KEYS:
             got, ref = getattr(a_s.rollout_buffer, k).cpu().numpy(), getattr(a_f.rollout_buffer, k).cpu().numpy()
             assert np.allclose(got, ref, rtol=2e-5, atol=2e-6), (it, k, np.abs(got - ref).max())
@@ -295,14 +313,21 @@ def test_stepped_rollout_equals_fused_rollout():
     assert a_s.num_timesteps == a_f.num_timesteps == 2 * N * T
 
 
+_GENERIC_ROUTES = {("hc", "wide", 12): "generic-persistent", ("hc", "trunk", 12): "generic-persistent", ("ant", "deep", 12): "generic-persistent",
+                   ("hc", "wide-cn", 12): dict(route="generic-per-step", launches=4 * 40), ("ant", "deep-cn", 12): dict(route="generic-per-step", launches=4 * 40),
+                   ("hc", "both", 12): dict(route="generic-per-step", launches=4 * 40), ("hc", "trunk", 64): "generic-persistent",
+                   ("ant", "deep", 33): dict(route="generic-per-step", launches=4 * 40)}
+
+
 @pytest.mark.parametrize("kind,shape,N", [("hc", "wide", 12), ("hc", "trunk", 12), ("ant", "deep", 12), ("hc", "wide-cn", 12), ("ant", "deep-cn", 12), ("hc", "both", 12),
                                           ("hc", "trunk", 64), ("ant", "deep", 33)])
 def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=None, policy_state=None):
     """policies / constraint nets of the generic-shape path (layers above 64 units, shared trunk, other depths): icrl_rollout_collect runs the
     whole rollout as ONE persistent launch (rollout_generic_kernel: the one-workgroup-per-env loop around the table-driven forward with four
-    units per lane) — or, for a constraint net beyond the register image, the reference's per-step loop as four launches per step —
-    (csrc/rollout.hip) and must leave exactly what the Python loop over the fine-grained entry points leaves: every unit's value is the same
-    chain of fused multiply-adds in the same order."""
+    units per lane) — or, for a constraint net beyond the register image, a policy the fast kernels serve, or more envs than granule mode
+    takes (envs x (2 obs + 4) > 3072: 33 Ant envs), the reference's per-step loop as four launches per step — (csrc/rollout.hip; which of
+    the two: _GENERIC_ROUTES) and must leave exactly what the Python loop over the fine-grained entry points leaves: every unit's value is
+    the same chain of fused multiply-adds in the same order."""
     from helpers.arches import ARCHES
     T = 40
     net_arch = {"wide": [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])], "both": [dict(pi=[128, 96], vf=[80, 128], cvf=[128, 128])]}.get(shape, ARCHES.get(shape))
@@ -315,6 +340,7 @@ def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=No
     a_f._setup_learn(2 * N * T); a_s._setup_learn(2 * N * T)
     for it in range(2):
         a_f.collect_rollouts(e_f, None, a_f.rollout_buffer, T, "cost", noise=noise[it])
+        routes.check_rollout(_GENERIC_ROUTES[kind, shape, N], f"{kind} {shape} {N}")
         a_s._collect_rollouts_stepped(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise[it])
         for k in _BUF_KEYS:
             got, ref = getattr(a_s.rollout_buffer, k).cpu().numpy(), getattr(a_f.rollout_buffer, k).cpu().numpy()
@@ -380,15 +406,34 @@ def test_analytic_env_cost_through_cost_wrapper():
     assert get_true_cost_function("HCWithPosTest-v0")(np.array([[-3.5, 0.0]]), None)[0]
 
 
-# N <= 128: rollout_persistent_kernel (statistics replicated per workgroup); beyond: rollout_wide_kernel (statistics partitioned by
-# observation column, two hops per step; 512 envs = two envs per workgroup).  hc 256 / ant 256 / antbroken 512 are the per-GPU
-# shards of BASELINE configs[3], [2] and [4].
+# N <= 96: rollout_persistent_kernel (statistics replicated per workgroup); beyond (hc 128 too): rollout_wide_kernel (statistics
+# partitioned by observation column, two hops per step; 512 envs = two envs per workgroup).  hc 256 / ant 256 / antbroken 512 are the
+# per-GPU shards of BASELINE configs[3], [2] and [4].
+# ONE_LAUNCH_ROUTES: (kind, envs, rollout_kernel) -> what icrl_rollout_collect must have launched, for every case of this file and of the
+# files that call this test's body, with a training normaliser, a constraint net and Box actions.  A forced kernel that does not take a
+# shape leaves it to the next form in line (the order: the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip): `multi` needs
+# 4 envs per group of statistics owners (hc: 20 envs, ant: 116), `wide` obs + 2 workgroups (hc: 20, ant: 115).
+_HC_MULTI = {20: (4, 5), 37: (4, 10), 64: (8, 8), 128: (8, 16), 130: (8, 17), 300: (8, 38), 1000: (8, 125), 2048: (8, 256)}      # envs: (envs per workgroup, workgroups)
+ONE_LAUNCH_ROUTES = {**{("hc", n, "auto"): "persistent" for n in (7, 64)},
+                     **{("hc", n, "auto"): dict(route="wide", wgs=n) for n in (128, 130, 256)},
+                     ("hc", 300, "auto"): "wide", ("hc", 1000, "auto"): "wide", ("ant", 256, "auto"): dict(route="wide", wgs=256), ("antbroken", 512, "auto"): "wide",
+                     ("ant", 32, "auto"): "persistent", ("ant", 128, "auto"): dict(route="wide", wgs=128),
+                     ("hc", 7, "wide"): "persistent", ("hc", 20, "wide"): dict(route="wide", wgs=20), ("hc", 130, "wide"): dict(route="wide", wgs=130),
+                     ("hc", 300, "wide"): "wide", ("ant", 32, "wide"): "persistent", ("ant", 115, "wide"): dict(route="wide", wgs=115),
+                     ("hc", 7, "multi"): "persistent", ("ant", 32, "multi"): "persistent",
+                     **{("hc", n, "multi"): dict(route="multi", envs_per_wg=e, wgs=g) for n, (e, g) in _HC_MULTI.items()},
+                     ("ant", 116, "multi"): dict(route="multi", envs_per_wg=4, wgs=29), ("ant", 128, "multi"): dict(route="multi", envs_per_wg=4, wgs=32),
+                     ("ant", 256, "multi"): dict(route="multi", envs_per_wg=8, wgs=32), ("antbroken", 512, "multi"): dict(route="multi", envs_per_wg=8, wgs=64),
+                     ("antbroken", 4096, "multi"): dict(route="multi", envs_per_wg=16, wgs=256)}
+
+
 @pytest.mark.parametrize("kind,N,T", [("hc", 64, 300), ("hc", 7, 33), ("hc", 128, 20), ("hc", 256, 40), ("hc", 130, 24), ("ant", 256, 12),
                                       ("antbroken", 512, 10), ("hc", 1000, 6)])
 def test_persistent_rollout_equals_per_step_launches(kind, N, T, kernel="auto", cn_kwargs=None, norm_kwargs=None, policy_state=None):
     """the one-launch rollout (device-wide exchange per step inside the kernel) against the launch pair per
     step: every buffer plane, the normaliser state and the agent's carry-over state are bit-identical, across two
-    consecutive rollouts and across episode ends."""
+    consecutive rollouts and across episode ends.  Both launch forms are asserted: ONE_LAUNCH_ROUTES for the one under test, two
+    launches per step for the other."""
     ekind = "ant" if kind == "antbroken" else kind
     ad = 6 if ekind == "hc" else 8
     limit = 1000 if ekind == "hc" else 500
@@ -401,7 +446,9 @@ def test_persistent_rollout_equals_per_step_launches(kind, N, T, kernel="auto", 
         env.unwrapped.t_ep.fill_(limit - T // 2)           # every env crosses its time limit inside the first rollout
     for it in range(2):
         a_p.collect_rollouts(e_p, None, a_p.rollout_buffer, T, "cost", noise=noise[it])
+        routes.check_rollout(ONE_LAUNCH_ROUTES[kind, N, kernel], f"{kind} {N} {kernel}")
         a_s.collect_rollouts(e_s, None, a_s.rollout_buffer, T, "cost", noise=noise[it])
+        routes.check_rollout(dict(route="per-step", launches=2 * T), f"{kind} {N} steps")
         a_p.check_rollout_status()
         for k in _BUF_KEYS:
             got, ref = getattr(a_p.rollout_buffer, k).cpu().numpy(), getattr(a_s.rollout_buffer, k).cpu().numpy()
@@ -419,9 +466,9 @@ def test_persistent_rollout_equals_per_step_launches(kind, N, T, kernel="auto", 
 
 
 # rollout_multi_kernel: E = 4 or 8 envs per workgroup evaluated interleaved, statistics owners on all four waves.  hc 64 = the
-# shape of a seed batch's runs (8 workgroups x 8 envs), hc 20 / 37 = ragged last workgroups (E = 4), hc 300 / ant 256 / antbroken 512 =
-# the many-environment shapes (ant: 29+ workgroups needed for the 115 statistics)
-@pytest.mark.parametrize("kind,N,T", [("hc", 64, 300), ("hc", 20, 33), ("hc", 37, 21), ("hc", 128, 20), ("hc", 300, 12), ("ant", 256, 12),
+# shape of a seed batch's runs (8 workgroups x 8 envs), hc 20 / 37 = ragged last workgroups (E = 4; 20 and ant 116: the fewest envs the
+# kernel takes), hc 300 / ant 256 / antbroken 512 = the many-environment shapes (ant: 29+ workgroups needed for the 115 statistics)
+@pytest.mark.parametrize("kind,N,T", [("hc", 64, 300), ("hc", 20, 33), ("hc", 37, 21), ("hc", 128, 20), ("hc", 300, 12), ("ant", 256, 12), ("ant", 116, 10),
                                       ("antbroken", 512, 10), ("hc", 1000, 6),
                                       # beyond 1024 envs per GPU (BASELINE configs[3] / configs[4] whole on ONE GPU): 8 / 16 envs per
                                       # workgroup, 256 workgroups; the per-step normaliser handles up to 4096 envs as well

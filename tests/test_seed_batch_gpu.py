@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import routes
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -55,6 +57,10 @@ def test_batched_runs_equal_solo_runs(extra, envs, n_steps):
         st, m = _solo(_cfg(sd, extra, envs, n_steps), 2)
         solo.append(_snapshot(st, m))
     states, metrics, dt = run_seed_batch([_cfg(sd, extra, envs, n_steps) for sd in seeds], 2)
+    # the batch's last rollout and update were ONE launch each (4 x 8 or 16 envs are within any device's compute units: one workgroup
+    # per env with the whole register file; up to 16 runs: the update kernel a run alone gets), not the single-run calls run by run
+    routes.check_rollout(dict(route="persistent-batch", n_runs=len(seeds), minw=1, wgs=envs, launches=1), "seed batch")
+    routes.check_update(dict(kind=5, n_runs=len(seeds), wgs_per_network=4), "seed batch")
     assert len({s["nu"] for s in solo}) == len(seeds)            # the runs really are different runs
     for i, sd in enumerate(seeds):
         got = _snapshot(states[i], metrics[i])
@@ -110,6 +116,7 @@ def test_batched_update_reads_each_runs_own_hyper_parameters():
     for hset in sets:
         a, case = agent(hset)
         a.train(perms=case["perms"])
+        routes.check_update(dict(kind=5, wgs_per_network=4, n_runs=1), f"solo {hset}")
         solo.append(snapshot(a))
     assert not np.array_equal(solo[0][0], solo[1][0]) and not np.array_equal(solo[0][0], solo[2][0]) and not np.array_equal(solo[1][0], solo[2][0])
     agents, jobs = [], []
@@ -120,6 +127,7 @@ def test_batched_update_reads_each_runs_own_hyper_parameters():
     assert np.array_equal(np.asarray(case["buf"]["log_probs"]), agents[0].rollout_buffer.log_probs.cpu().numpy().reshape(T, N))      # one buffer for all three
     args_ws = torch.empty(len(agents) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=agents[0].device)
     launch_trains(agents, jobs, args_ws)             # (what SeedBatch._launch_trains calls: the launch alone, no ICRL loop around the agents)
+    routes.check_update(dict(kind=5, wgs_per_network=4, n_runs=3), "3 runs")      # (up to 16 runs: the kernel a run alone gets)
     torch.cuda.synchronize()
     for i, (a, j) in enumerate(zip(agents, jobs)):
         got = snapshot(a)
