@@ -129,6 +129,7 @@ ROUTE = {"none": 0, "per-step": 1, "persistent": 2, "wide": 3, "multi": 4, "gene
          "persistent-batch": 7, "multi-batch": 8}
 WS_NONE, WS_XCH, WS_PLANE = 0, 1, 2
 PICK_SMALL, PICK_ANALYTIC, PICK_MON, PICK_GRAN, PICK_CN128, PICK_MINW_SHIFT = 1, 2, 4, 8, 16, 8
+PICK_DISC = 32
 UPDATE_GENERIC_PERSISTENT, UPDATE_GENERIC_LAUNCHES = 8, 9
 GAE_ROUTE = {"none": 0, "sequential": 1, "split": 2, "regsplit": 3, "batch-split": 4, "batch-regsplit": 5, "batch-singles": 6}
 

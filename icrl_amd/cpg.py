@@ -68,26 +68,24 @@ def setup(config, log=print):
         if cost_function is null_cost:      # (an id without a ground-truth cost: the null cost, in its device form)
             cost_function = AnalyticCost.null()
     elif config.load_gail:
-        # ref: icrl/cpg.py:54-83 — the cost is the discriminator's output D itself (apply_log=False); numpy in / numpy out like the
-        # reference's callable, so it runs through VecCostWrapper's callable branch and the per-step rollout loop
-        from .gail_utils import GailDiscriminator
+        # ref: icrl/cpg.py:54-83 — the cost is the discriminator's output D itself (apply_log=False): a DiscriminatorCost, numpy in /
+        # numpy out like the reference's callable, and a descriptor the rollout kernels evaluate (icrl_cost_disc_t)
+        from .gail_utils import DiscriminatorCost, GailDiscriminator
         action_low, action_high = None, None
         if isinstance(train_env.action_space, spaces.Box):
             action_low, action_high = train_env.action_space.low, train_env.action_space.high
         gail = GailDiscriminator.load(config.cn_path, obs_dim=obs_dim, acs_dim=acs_dim, is_discrete=is_discrete,
                                       obs_select_dim=config.cn_obs_select_dim, acs_select_dim=config.cn_acs_select_dim,
                                       clip_obs=None, obs_mean=None, obs_var=None, action_low=action_low, action_high=action_high)
-
-        def cost_function(obs, acs):
-            return gail.reward_function(obs, acs, apply_log=False).cpu().numpy()
+        cost_function = DiscriminatorCost(gail)
     else:
         constraint_net = ConstraintNet.load(config.cn_path, obs_dim=obs_dim, acs_dim=acs_dim, is_discrete=is_discrete,
                                             obs_select_dim=config.cn_obs_select_dim, acs_select_dim=config.cn_acs_select_dim,
                                             clip_obs=None, obs_mean=None, obs_var=None)
         cost_function = constraint_net.cost_function
-    # a ConstraintNet cost and an AnalyticCost (the ground-truth cost, the null cost) run inside the fused rollout launch (device envs:
-    # icrl_rollout_collect_ex, host envs: icrl_host_step); the --load_gail callable goes through VecCostWrapper's callable branch and
-    # the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped), as does an AnalyticCost under ICRL_ANALYTIC_COST_STEPPED=1
+    # a ConstraintNet cost, an AnalyticCost (the ground-truth cost, the null cost) and the --load_gail DiscriminatorCost run inside the
+    # fused rollout launch (device envs: icrl_rollout_collect_ex, host envs: icrl_host_step); ICRL_ANALYTIC_COST_STEPPED=1 /
+    # ICRL_DISC_COST_STEPPED=1 send the same cost object through the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped)
     train_env.set_cost_function(cost_function)
     eval_env.set_cost_function(cost_function)
     model = PPOLagrangian(

@@ -1,6 +1,8 @@
 // Analytic costs (icrl_cost_fn_t): the ground-truth constraints of icrl/true_constraint_net.py:40-54, 104-111 and the null cost as
 // closed forms on (previous raw observation, clipped action) — what the rollout kernels hold in LDS in the wave that runs the
 // constraint net.  A descriptor whose n_hidden is ICRL_COST_FN travels through every `const icrl_costnet_t*` argument.
+// Discriminator costs (icrl_cost_disc_t, n_hidden == ICRL_COST_DISC) travel the same way: a constraint net read as D = zeta instead of
+// 1 - zeta (cpg --load_gail).  The entry point unwraps `net` and picks the kernels whose cost wave returns zeta (KernelPick::disc).
 #pragma once
 #include "common.h"
 
@@ -14,6 +16,29 @@ inline const icrl_cost_fn_t* as_cost_fn(const icrl_costnet_t* cn) {
 inline int refuse_cost_fn(const char* who) {
   return fail("%s: an analytic cost descriptor (n_hidden == ICRL_COST_FN) is not served here: icrl_rollout_collect[_ex][_mon], icrl_host_step[_mon], "
               "icrl_cost_mlp_forward and icrl_cost_fn_rows take one", who);
+}
+
+inline const icrl_cost_disc_t* as_cost_disc(const icrl_costnet_t* cn) {
+  return (cn != nullptr && cn->n_hidden == ICRL_COST_DISC) ? reinterpret_cast<const icrl_cost_disc_t*>(cn) : nullptr;
+}
+
+// the entry points that serve no discriminator cost
+inline int refuse_cost_disc(const char* who) {
+  return fail("%s: a discriminator cost descriptor (icrl_cost_disc_t, n_hidden == ICRL_COST_DISC) is not served here: icrl_rollout_collect[_ex][_mon], "
+              "icrl_host_step[_mon] and icrl_cost_mlp_forward take one; the batched rollout kernels have no discriminator form yet, and "
+              "training, preparing or icrl_disc_reward want the inner net (icrl_cost_disc_t.net) itself", who);
+}
+
+// the inner net of a discriminator cost, or a reason; what the net must satisfy beyond that (cn_ok / bad_cn, params_t) is checked by the
+// entry point exactly as for a constraint net handed over directly
+inline int cost_disc_check(const char* who, const icrl_cost_disc_t* d) {
+  const icrl_costnet_t* net = d->net;
+  if (net == nullptr) return fail("%s: discriminator cost descriptor (icrl_cost_disc_t) with a NULL inner net", who);
+  if (net->n_hidden < 0) return fail("%s: discriminator cost descriptor (icrl_cost_disc_t) whose inner net is itself a tagged descriptor (n_hidden %d)", who, net->n_hidden);
+  if (d->obs_dim != net->obs_dim || d->acs_dim != net->acs_dim || d->in_dim != net->in_dim)
+    return fail("%s: discriminator cost descriptor (icrl_cost_disc_t) says obs_dim %d, acs_dim %d, in_dim %d, its inner net %d, %d, %d", who, d->obs_dim,
+                d->acs_dim, d->in_dim, net->obs_dim, net->acs_dim, net->in_dim);
+  return 0;
 }
 
 // discrete: 1 / 0 = the action space of the policy the cost runs beside, -1 = unknown (rows of a caller's own arrays);

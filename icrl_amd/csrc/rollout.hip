@@ -491,8 +491,16 @@ struct ActStepArgs {
   double* raw_plane;    // [T,N] float64 or NULL: the raw env reward of every step (icrl_monitor_t.raw_rewards), stored next to ag.raw_rew
 };
 
-template <int OCT, int CIT>
+// DISC: the constraint net read as D = zeta (icrl_cost_disc_t, cost_fn.h) — a compile-time form of cost_forward_wave's `mode` in every
+// rollout kernel: the forms that existed before it keep their device code, symbol for symbol.  Where a family's kernels are wrappers
+// around a shared body (one workgroup per env, generic, multi) the D form is a wrapper of its own name around the body with DISC = true.
+// Here, in rollout_wide_kernel and in host_step_kernel the kernel IS the body (moving it into a by-reference body function changed the
+// register allocation of all 18 shipped instantiations), so the D form is the same kernel instantiated with CIT | CIT_DISC.
+constexpr int CIT_DISC = 0x100;
+template <int OCT, int CITF>
 __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
+  constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
+  constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
   __shared__ ActShared sh;
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
@@ -529,7 +537,7 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
   } else if (w == 3) {
     float cost = 0.f;
     if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
-    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
     if (lane == 0) { a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost; }
   } else if (w == 2) {
     float* ob = a.buf.observations + tn * O;
@@ -1125,7 +1133,7 @@ static inline size_t persist_dyn_lds(int N, int O, int A) { return ((size_t)O * 
 // across the step loop of every launch (ppo_train_halves.hip: 2.5 % there)
 // MON: store the raw reward of every step into ActStepArgs.raw_plane (icrl_monitor_t.raw_rewards) — a compile-time variant like PROF: the
 // instantiations without it are the kernels as they were, with not one more value in the step loop's registers
-template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true>
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true, bool DISC = false>
 __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ ActShared sh;
@@ -1231,7 +1239,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
     } else if (w == 3) {
       float cost = 0.f;
       if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
-      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
       if (lane == 0) {
         if (GRAN) rstore(((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
         else xstore(as_global(p.xch_cost) + par * N + n, cost);
@@ -1393,7 +1401,7 @@ struct GenRolloutArgs {
   GenNet net;
   const float* P;      // the policy's parameters in their natural layout (log_std of the Gaussian head)
 };
-template <int OCT, int CIT, bool MON>
+template <int OCT, int CIT, bool MON, bool DISC = false>
 __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
   constexpr bool GRAN = true;
   const PersistArgs& p = ga.p;
@@ -1511,7 +1519,7 @@ __device__ __forceinline__ void rollout_generic_body(const GenRolloutArgs& ga) {
     } else if (w == 3) {
       float cost = 0.f;
       if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
-      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+      else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
       if (lane == 0) {
         if (GRAN) rstore(((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
         else xstore(as_global(p.xch_cost) + par * N + n, cost);
@@ -1674,6 +1682,16 @@ __global__ void __launch_bounds__(256) rollout_persistent_kernel(PersistArgs p) 
   rollout_persistent_body<OCT, CIT, GRAN, PROF, MON, false>(p);      // (without the Point step: env_step_wave)
 }
 
+// the discriminator-cost forms (DISC, see act_step_kernel) of the two kernels above, single runs, no phase timers
+template <int OCT, int CIT, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_generic_disc_kernel(GenRolloutArgs ga) {
+  rollout_generic_body<OCT, CIT, MON, true>(ga);
+}
+template <int OCT, int CIT, bool GRAN, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_persistent_disc_kernel(PersistArgs p) {
+  rollout_persistent_body<OCT, CIT, GRAN, false, MON, false, true>(p);
+}
+
 // several independent runs in ONE launch: grid (N, n_runs), run = blockIdx.y, argument blocks in device memory.  Workgroups are
 // dispatched x-fastest, so a run's N workgroups become resident together and the oldest run of the grid is always complete: runs
 // whose workgroups do not fit yet simply start when earlier runs have finished (the exchange waits are bounded by seconds).
@@ -1731,8 +1749,10 @@ struct WideArgs {
   unsigned long long* xcc;     // multi-env kernel, packed batched launches: G zeroed words (the workgroups' XCD ids), else NULL
 };
 
-template <int OCT, int CIT, bool PROF = false, bool MON = false>      // PROF: the phase timers (do_gae bits 2 / 3) as a compile-time variant, MON: the raw-reward plane (rollout_persistent_body)
+template <int OCT, int CITF, bool PROF = false, bool MON = false>      // PROF: the phase timers (do_gae bits 2 / 3) as a compile-time variant, MON: the raw-reward plane (rollout_persistent_body); CITF: CIT [| CIT_DISC] (act_step_kernel)
 __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
+  constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
+  constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
   __shared__ ActShared sh[WIDE_E];
   __shared__ double Bl[MAX_OBS * MAX_ACT];
   __shared__ double colbuf[WIDE_MAX_N + 64], dev2buf[WIDE_MAX_N], retbuf[WIDE_MAX_N];
@@ -1832,7 +1852,7 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
       } else if (w == 3) {
         float cost = 0.f;
         if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh[e].s_old, sh[e].act_clip);
-        else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh[e].s_old, sh[e].act_clip, sh[e].cx, sh[e].ch);
+        else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh[e].s_old, sh[e].act_clip, sh[e].cx, sh[e].ch, DISC ? 1 : 0);
         if (lane == 0) {
           rstore(xrs, xrec + 16 * (O + 1), rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
           a.buf.orig_costs[tn] = cost;
@@ -2221,7 +2241,7 @@ __device__ __noinline__ void env_step_wave3(int O, int A, int flags, int max_ste
   }
 }
 
-template <int OCT, int CIT, int E, bool MON>
+template <int OCT, int CIT, int E, bool MON, bool DISC = false>
 __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int g_arg) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ MultiShared<E, CIT> sh;
@@ -2614,7 +2634,7 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
       if (prof) pcB += prof_now() - tl;                 // (cost wave: hidden layers done)
       const float zz = tile_sum64(z) + sh.cst[3][CST_BO];
       const float zeta = 1.f / (1.f + expf(-zz));
-      const float cost = 1.f - zeta;
+      const float cost = DISC ? zeta : 1.f - zeta;
       if (q4 == 0 && r16 < Eg) {
         const int n = g + r16 * G;
         rstore(xrs, ((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
@@ -2835,6 +2855,14 @@ __global__ void __launch_bounds__(256) rollout_multi_batch_analytic_kernel(const
   }
   __syncthreads();
   rollout_multi_body<OCT, 0, E, MON>(p, g);
+}
+
+// the discriminator-cost form (DISC) of rollout_multi_kernel, single runs.  It calls the env_step_wave3 instantiations the kernels above
+// call, so its name sorts behind all of theirs (mangled: by length first) for the reason given at rollout_multi_analytic_kernel
+template <int OCT, int CIT, int E, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_multi_net_as_discriminator_kernel(WideArgs p, int packed) {
+  if (packed && (blockIdx.x & 7) != 0) return;
+  rollout_multi_body<OCT, CIT, E, MON, true>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
 }
 
 // VecNormalizeWithCost.reset (vec_normalize.py:148-157, 270-278)
@@ -3407,8 +3435,10 @@ struct HostCopy {
         ret(base + 2 * O + 7), cost_ret(base + 2 * O + 7 + N), cost(base + 2 * O + 7 + 2 * N) {}
 };
 
-template <int OCT, int CIT>
+template <int OCT, int CITF>      // CITF: CIT [| CIT_DISC] (act_step_kernel)
 __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
+  constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
+  constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
   __shared__ ActShared sh;
   __shared__ double vec[2][128], dev2[2][128], ret_s[128], cret_s[128], rawr_s[128];
   __shared__ float rawc_s[128];
@@ -3561,7 +3591,7 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
   } else if (w == 3) {
     float cost = 0.f;
     if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
-    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch);
+    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
     if (lane == 0) {
       a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
       dst.cost[n] = (double)cost;              // read by every workgroup of launch k + 1 (ag.raw_cost[n] is rewritten by launch k + 1)
@@ -3673,6 +3703,7 @@ extern "C" int icrl_policy_prepare(const icrl_policy_t* p, void* stream) {
 
 extern "C" int icrl_costnet_prepare(const icrl_costnet_t* cn, void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_costnet_prepare");
+  if (as_cost_disc(cn)) return refuse_cost_disc("icrl_costnet_prepare");      // (prepare the inner net)
   if (cn->n_hidden > 2 || cn->n_hidden == 0) return 0;      // served 64 rows per workgroup from `params` (cn_train.hip): no transposed copy
   if (!costnet_is_wide(cn) && !cn_ok(cn)) return bad_cn("icrl_costnet_prepare", cn);
   CnLayout L = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2);
@@ -4010,6 +4041,10 @@ extern "C" int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, co
 extern "C" int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* cost,
                                      void* stream) {
   if (const icrl_cost_fn_t* cf = as_cost_fn(cn)) return icrl_cost_fn_rows(cf, obs, acs, N, cost, stream);
+  if (const icrl_cost_disc_t* cd = as_cost_disc(cn)) {      // the inner net read as D: one zeta, stored as it is
+    if (int e = cost_disc_check("icrl_cost_mlp_forward", cd)) return e;
+    return icrl_disc_reward(cd->net, obs, acs, N, cost, 0, stream);
+  }
   if (N <= 0) return fail("cost forward: N = %d rows", N);
   if (costnet_is_wide(cn)) return launch_cn_cost_rows(cn, obs, acs, N, cost, 0, (hipStream_t)stream);
   if (!cn_ok(cn)) return bad_cn("cost forward", cn);
@@ -4022,6 +4057,7 @@ extern "C" int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs
 extern "C" int icrl_disc_reward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* out, int apply_log,
                                 void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_disc_reward");
+  if (as_cost_disc(cn)) return refuse_cost_disc("icrl_disc_reward");
   if (N <= 0) return fail("cost forward: N = %d rows", N);
   if (costnet_is_wide(cn)) return launch_cn_cost_rows(cn, obs, acs, N, out, apply_log ? 2 : 1, (hipStream_t)stream);
   if (!cn_ok(cn)) return bad_cn("cost forward", cn);
@@ -4042,6 +4078,7 @@ static int make_gail_args(const char* who, int n_runs, const icrl_gail_job_t* jo
     GailArgs& a = out[r];
     if (j.disc == nullptr) return fail("%s: run %d has no discriminator descriptor", who, r);
     if (as_cost_fn(j.disc)) return refuse_cost_fn(who);
+    if (as_cost_disc(j.disc)) return refuse_cost_disc(who);
     if (j.rows <= 0) return fail("%s: run %d: rows = %d", who, r, j.rows);
     if (j.actions == nullptr || j.raw_obs == nullptr) return fail("%s: run %d: actions = %p, raw_obs = %p", who, r, (const void*)j.actions, (void*)j.raw_obs);
     if (j.disc->obs_dim < 1) return fail("%s: run %d: obs_dim = %d", who, r, j.disc->obs_dim);
@@ -4204,8 +4241,9 @@ static bool multi_shape(int N, int n_stats, int* E, int* G) {
 
 // ---- which instantiation serves a shape.  One function per kernel family, used for the occupancy query and for the launch alike:
 // each hands the chosen kernel to `f` and returns what `f` returns.  Together they name exactly the instantiations the library
-// ships.  What is not listed (phase timers with a monitor plane or an analytic cost, MINW 2 / 3 outside small + granules, <8, 8>
-// outside the multi kernels) does not exist, and the `if constexpr`s keep it that way: every instantiation costs compile time.
+// ships.  What is not listed (phase timers with a monitor plane, an analytic or a discriminator cost, MINW 2 / 3 outside small +
+// granules, <8, 8> outside the multi kernels, a discriminator cost in a batch) does not exist, and the `if constexpr`s keep it that way:
+// every instantiation costs compile time.
 struct KernelPick {
   bool small = false;      // small_shape(): the <2, .> register images, else <8, .>
   bool analytic = false;   // an icrl_cost_fn_t behind the cost pointer: CIT == 0 (no cost-net register image), no phase timers
@@ -4213,6 +4251,7 @@ struct KernelPick {
   bool cn128 = false;      // multi kernels: the cost net reads <= 128 inputs (AntWall: 121) — 32 instead of 40 first-layer k steps in the register image
   bool gran = false;       // one-workgroup-per-env kernels: granule mode (N (2 obs + 4) <= 256 GRAN_MAX)
   bool prof = false;       // tools: the instantiations with the phase timers (do_gae bits 2 / 3)
+  bool disc = false;       // an icrl_cost_disc_t behind the cost pointer: the kernels whose cost wave returns zeta; single runs, no phase timers
   int E = 0;               // multi kernels: envs per workgroup (multi_shape)
   int minw = 1;            // batched one-workgroup-per-env kernels: workgroups per CU the register allocation leaves room for
   // what the dispatch below instantiated, written by it for the route record (pick_bits): the MINW of with_persistent_batch_kernel,
@@ -4242,14 +4281,29 @@ static int with_image(const KernelPick& k, F&& f) {
 }
 
 template <class F> static int with_act_step_kernel(const KernelPick& k, F&& f) {
-  return with_image(k, [&](auto im) { return f(act_step_kernel<decltype(im)::oct, decltype(im)::cit>); });
+  return with_image(k, [&](auto im) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    if constexpr (CIT != 0) {
+      if (k.disc) return f(act_step_kernel<OCT, CIT | CIT_DISC>);
+    }
+    return f(act_step_kernel<OCT, CIT>);
+  });
 }
 template <class F> static int with_host_step_kernel(const KernelPick& k, F&& f) {
-  return with_image(k, [&](auto im) { return f(host_step_kernel<decltype(im)::oct, decltype(im)::cit>); });
+  return with_image(k, [&](auto im) {
+    constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    if constexpr (CIT != 0) {
+      if (k.disc) return f(host_step_kernel<OCT, CIT | CIT_DISC>);
+    }
+    return f(host_step_kernel<OCT, CIT>);
+  });
 }
 template <class F> static int with_generic_kernel(const KernelPick& k, F&& f) {
   return with_image(k, [&](auto im) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    if constexpr (CIT != 0) {
+      if (k.disc) return k.mon ? f(rollout_generic_disc_kernel<OCT, CIT, true>) : f(rollout_generic_disc_kernel<OCT, CIT>);
+    }
     return k.mon ? f(rollout_generic_kernel<OCT, CIT, true>) : f(rollout_generic_kernel<OCT, CIT>);
   });
 }
@@ -4257,6 +4311,9 @@ template <class F> static int with_persistent_kernel(const KernelPick& k, F&& f)
   return with_image(k, [&](auto im) { return with_flag(k.gran, [&](auto gran) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
     constexpr bool GRAN = decltype(gran)::value;
+    if constexpr (CIT != 0) {
+      if (k.disc) return k.mon ? f(rollout_persistent_disc_kernel<OCT, CIT, GRAN, true>) : f(rollout_persistent_disc_kernel<OCT, CIT, GRAN>);
+    }
     if (k.mon) return f(rollout_persistent_kernel<OCT, CIT, GRAN, false, true>);
     if constexpr (CIT != 0) {
       if (k.prof) return f(rollout_persistent_kernel<OCT, CIT, GRAN, true>);
@@ -4267,6 +4324,9 @@ template <class F> static int with_persistent_kernel(const KernelPick& k, F&& f)
 template <class F> static int with_wide_kernel(const KernelPick& k, F&& f) {
   return with_image(k, [&](auto im) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
+    if constexpr (CIT != 0) {
+      if (k.disc) return k.mon ? f(rollout_wide_kernel<OCT, CIT | CIT_DISC, false, true>) : f(rollout_wide_kernel<OCT, CIT | CIT_DISC>);
+    }
     if (k.mon) return f(rollout_wide_kernel<OCT, CIT, false, true>);
     if constexpr (CIT != 0) {
       if (k.prof) return f(rollout_wide_kernel<OCT, CIT, true>);
@@ -4305,7 +4365,7 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
       if constexpr (BATCH && CIT == 0) return f(rollout_multi_batch_analytic_kernel<OCT, E, MON>);
       else if constexpr (BATCH) return f(rollout_multi_batch_kernel<OCT, CIT, E, MON>);
       else if constexpr (CIT == 0) return f(rollout_multi_analytic_kernel<OCT, E, MON>);
-      else return f(rollout_multi_kernel<OCT, CIT, E, MON>);
+      else return k.disc ? f(rollout_multi_net_as_discriminator_kernel<OCT, CIT, E, MON>) : f(rollout_multi_kernel<OCT, CIT, E, MON>);
     };
     return k.E == 16 ? kernel(Int<16>{}) : (k.E == 8 ? kernel(Int<8>{}) : kernel(Int<4>{}));
   }); });
@@ -4314,7 +4374,7 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
 // the route record's word 4: the KernelPick fields that chose the instantiation of `route` (ICRL_PICK_*), nothing that it ignores;
 // the <8, 8> image and MINW as the dispatch that launched it wrote them down (call this after the launch)
 static int pick_bits(const KernelPick& k, int route) {
-  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0);
+  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0) | (k.disc ? ICRL_PICK_DISC : 0);
   if (route == ICRL_ROUTE_PER_STEP || route == ICRL_ROUTE_GENERIC_PER_STEP) return b;
   b |= k.mon ? ICRL_PICK_MON : 0;
   if (route == ICRL_ROUTE_PERSISTENT || route == ICRL_ROUTE_PERSISTENT_BATCH) b |= k.gran ? ICRL_PICK_GRAN : 0;
@@ -4460,6 +4520,10 @@ static int mon_plane(const char* who, const icrl_monitor_t* mon, double** plane)
 //                        (with training statistics and Box actions that is: fewer envs than multi / wide take AND more than persistent takes —
 //                        AntWall, obs 113, at 37..114 envs: 37 x 113 > 4096, 114 < obs + 2 workgroups, 114 / 29 < 4 envs per owner group — and Point
 //                        envs below 12; with frozen statistics or Discrete actions: above 128 envs or 4096 observation doubles)
+// A discriminator cost (icrl_cost_disc_t, cost_fn.h) takes the route its inner net would take as a constraint net, on every rung, in that
+// rung's D form (rollout_generic_disc_kernel, rollout_multi_net_as_discriminator_kernel, rollout_persistent_disc_kernel; wide and per-step:
+// the kernel instantiated with CIT | CIT_DISC; generic per-step: cn_cost_rows / cost_forward with mode 1);
+// the phase-timer bits of do_gae are ignored with one, and ICRL_PICK_DISC is set in the record.
 // What a call took is kept per host thread: icrl_debug_last_route (errors.hip), written where a route returns after its launch.
 // Routes of a batch (rollout_collect_batch_impl):
 //   multi                !ICRL_BATCH_NO_MULTI, not `few`, Box actions, training, multi_shape, every run has a workspace      rollout_multi_batch[_analytic]_kernel
@@ -4478,7 +4542,12 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   const icrl_cost_fn_t* const cf = as_cost_fn(cn_arg);
   if (cf != nullptr)
     if (int e = cost_fn_check("icrl_rollout_collect", cf, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
-  const icrl_costnet_t* const net = cf != nullptr ? nullptr : cn_arg;
+  // a discriminator cost (icrl_cost_disc_t): `net` is its inner net, checked and routed below as a constraint net is; k.disc picks
+  // the kernels whose cost wave returns zeta
+  const icrl_cost_disc_t* const cd = as_cost_disc(cn_arg);
+  if (cd != nullptr)
+    if (int e = cost_disc_check("icrl_rollout_collect", cd)) return e;
+  const icrl_costnet_t* const net = cf != nullptr ? nullptr : (cd != nullptr ? cd->net : cn_arg);
   const bool cn = cn_arg != nullptr;
   const bool generic = policy_is_wide(pol) || (net != nullptr && costnet_is_wide(net));      // shapes of the generic-shape path: per-step launches
   if (!generic && !dims_ok(pol)) return bad_dims("icrl_rollout_collect", pol);
@@ -4490,7 +4559,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                 "numpy-ordered chain per column)", N, NORM_MAX_N);
   hipStream_t s = (hipStream_t)stream;
   KernelPick k;
-  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.mon = raw_plane != nullptr;
+  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.disc = cd != nullptr; k.mon = raw_plane != nullptr;
   auto finish = [&](int err) { return finish_with_gae(err, do_gae, buf, ag, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, stream); };
   // the route record, written where a rung returns after its launch(es): workspace source, working workgroups, envs per workgroup, packed, launches
   auto routed = [&](int err, int route, const char* ws, int wgs, int E, int packed, int launches) {
@@ -4539,7 +4608,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                                 buf->reward_values + row, buf->cost_values + row, buf->log_probs + row, stream);
       if (err) return err;
       if (net != nullptr) {
-        err = icrl_cost_mlp_forward(net, env->s, ag->act_clipped, N, ag->raw_cost, stream);
+        err = icrl_cost_mlp_forward(cn_arg, env->s, ag->act_clipped, N, ag->raw_cost, stream);      // (a discriminator descriptor: D)
         if (err) return err;
       }
       hipLaunchKernelGGL(act_step_generic_kernel, dim3(N), dim3(64), 0, s, g, t);
@@ -4590,7 +4659,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         const size_t clear = wide_ws_carve(ws, N, O, false, p);
         hipError_t e = hipMemsetAsync(p.xg, 0, clear, s);
         if (e != hipSuccess) return (int)e;
-        if (k.mon || k.analytic) p.prof = 0;      // (with the plane or an analytic cost: the instantiations without phase timers)
+        if (k.mon || k.analytic || k.disc) p.prof = 0;      // (with the plane, an analytic or a discriminator cost: the instantiations without phase timers)
         k.prof = p.prof != 0;
         const int err = with_wide_kernel(k, [&](auto kernel) { return (int)launch_coresident(kernel, dim3(G), dim3(256), 0, s, p); });
         if (err == (int)hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); goto per_step; }
@@ -4608,7 +4677,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       const size_t clear = persist_ws_carve(ws, N, O, gran, p);
       hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
       if (e != hipSuccess) return (int)e;
-      if (k.mon || k.analytic) p.prof = 0;      // (with the plane or an analytic cost: the instantiations without phase timers)
+      if (k.mon || k.analytic || k.disc) p.prof = 0;      // (with the plane, an analytic or a discriminator cost: the instantiations without phase timers)
       k.gran = gran; k.prof = p.prof != 0;
       const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
       const int perr = with_persistent_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, p); });
@@ -4756,6 +4825,8 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch: n_runs = %d (1..65535)", n_runs);
   for (int r = 0; r < n_runs; ++r)      // (the analytic form is icrl_rollout_collect_batch_cost's)
     if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
+  for (int r = 0; r < n_runs; ++r)
+    if (as_cost_disc(jobs[r].cn)) return refuse_cost_disc("icrl_rollout_collect_batch");
   return rollout_collect_batch_impl(n_runs, jobs, mons, action_low, action_high, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, do_gae,
                                     args_ws, args_ws_bytes, stream, false);
 }
@@ -4770,6 +4841,7 @@ extern "C" int icrl_rollout_collect_batch_cost(int n_runs, const icrl_rollout_jo
   if (n_runs < 1 || n_runs > 65535) return fail("icrl_rollout_collect_batch_cost: n_runs = %d (1..65535)", n_runs);
   int n_fn = 0, n_net = 0;
   for (int r = 0; r < n_runs; ++r) {
+    if (as_cost_disc(jobs[r].cn)) return refuse_cost_disc("icrl_rollout_collect_batch_cost");
     if (as_cost_fn(jobs[r].cn)) ++n_fn;
     else if (jobs[r].cn != nullptr) ++n_net;
   }
@@ -4825,7 +4897,12 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   const icrl_cost_fn_t* const cf = as_cost_fn(cn);
   if (cf != nullptr) {
     if (int e = cost_fn_check("icrl_host_step", cf, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
-  } else if (cn != nullptr && (costnet_is_wide(cn) || !cn_ok(cn))) return bad_cn("icrl_host_step", cn);
+  }
+  const icrl_cost_disc_t* const cd = as_cost_disc(cn);
+  if (cd != nullptr)
+    if (int e = cost_disc_check("icrl_host_step", cd)) return e;
+  const icrl_costnet_t* const net = cf != nullptr ? nullptr : (cd != nullptr ? cd->net : cn);      // the constraint net proper
+  if (net != nullptr && (costnet_is_wide(net) || !cn_ok(net))) return bad_cn("icrl_host_step", net);
   if (N < 1 || N > 128 || O < 1 || O > MAX_OBS || pol->obs_dim != O)
     return fail("icrl_host_step: %d envs (1..128), obs_dim %d (1..%d), policy obs_dim %d: other shapes take the per-step loop", N, O, MAX_OBS, pol->obs_dim);
   if (!nm->training) return fail("icrl_host_step: the normaliser is not training (statistics frozen): the per-step loop serves that");
@@ -4838,7 +4915,6 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   HostStepArgs h{};
   ActStepArgs& a = h.act;
   a.env.n_envs = N; a.env.obs_dim = O; a.env.act_dim = pol->discrete ? 1 : pol->act_dim;
-  const icrl_costnet_t* const net = cf != nullptr ? nullptr : cn;
   fill_act_args(a, nullptr, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
   h.nm = *nm; h.hs = *hs; h.N = N;
   // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
@@ -4850,7 +4926,7 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   h.hs.act_host = reinterpret_cast<float*>(act_dev);
   hipStream_t s = (hipStream_t)stream;
   KernelPick pick;
-  pick.small = small_shape(O, net); pick.analytic = cf != nullptr;
+  pick.small = small_shape(O, net); pick.analytic = cf != nullptr; pick.disc = cd != nullptr;
   with_host_step_kernel(pick, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, s, h, k); return 0; });
   return (int)hipGetLastError();
 }

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, callbacks, logger
 from .constraint_net import ConstraintNet
-from .structs import CnTrainMbJobT, GaeJobT, GailJobT, addr, p
+from .structs import COST_DISC, CnTrainMbJobT, CostDiscT, GaeJobT, GailJobT, addr, p
 from .true_constraint_net import AnalyticCost, null_cost
 
 
@@ -102,6 +102,31 @@ class GailDiscriminator(ConstraintNet):
                   g(action_high, "action_high"))
         net.load_state_dict(sd["network"])
         return net
+
+
+class DiscriminatorCost:
+    """The env cost of `cpg --load_gail` (ref: icrl/cpg.py:54-83): the loaded discriminator's output D(previous raw obs, clipped action),
+    reward_function with apply_log=False, as an object the rollout entry points can read (VecCostWrapper.discriminator_cost()).
+
+    numpy in -> the float32 numpy array the reference's closure returns; device tensors in -> the same values as a device tensor
+    (icrl_disc_reward on the tensors: no host copies).  `.struct()` is the icrl_cost_disc_t the rollout kernels evaluate in their cost
+    wave: the discriminator's own icrl_costnet_t behind the tag, read as zeta."""
+
+    def __init__(self, disc):
+        self.disc = disc
+
+    def __repr__(self):
+        return f"DiscriminatorCost({list(self.disc.hidden_sizes)}, in={self.disc.input_dims})"
+
+    def __call__(self, obs, acs):
+        out = self.disc.reward_function(obs, acs, apply_log=False)
+        return out if torch.is_tensor(obs) or torch.is_tensor(acs) else out.cpu().numpy()
+
+    def struct(self):
+        inner = self.disc.struct()
+        s = CostDiscT(inner.obs_dim, inner.acs_dim, inner.in_dim, COST_DISC, addr(inner))
+        s._inner = inner      # (the descriptor points at it: alive as long as the descriptor is)
+        return s
 
 
 def _args_ws(n_runs, device, args_ws=None):

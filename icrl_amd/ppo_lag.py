@@ -198,10 +198,13 @@ class PPOLagrangian:
 
     @staticmethod
     def _fused_cost_ok(cw):
-        """a cost the rollout kernels evaluate themselves: a device ConstraintNet, or an AnalyticCost (true_constraint_net.py; the ground-truth
-        and null costs of cpg) unless ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step loop over the same cost object."""
+        """a cost the rollout kernels evaluate themselves: a device ConstraintNet, an AnalyticCost (true_constraint_net.py; the ground-truth
+        and null costs of cpg) unless ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step loop over the same cost object, or a
+        DiscriminatorCost (gail_utils.py; cpg --load_gail) unless ICRL_DISC_COST_STEPPED=1 does."""
         if cw.constraint_net() is not None:
             return True
+        if cw.discriminator_cost() is not None:
+            return os.environ.get("ICRL_DISC_COST_STEPPED", "0") in ("", "0")
         return cw.analytic_cost() is not None and os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") in ("", "0")
 
     def _host_chain(self):
@@ -264,7 +267,7 @@ class PPOLagrangian:
         if noise is None:
             noise = self._draw_action_noise(n_rollout_steps)
         e, nm, pol, buf = senv.struct(), nenv.struct(), self.policy.struct(), rollout_buffer.struct()
-        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, or an analytic cost's)
+        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, an analytic or a discriminator cost's)
         ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
                     p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
                     p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
@@ -337,6 +340,8 @@ class PPOLagrangian:
             return False
         nenv, cw, henv = chain
         cn = cw.constraint_net() if cw is not None else None      # (None for an AnalyticCost: it has no shape limits of its own)
+        if cn is None and cw is not None and cw.discriminator_cost() is not None:
+            cn = cw.discriminator_cost().disc                    # (a DiscriminatorCost: its net, under a constraint net's limits)
         # the limits icrl_host_step checks (csrc/rollout.hip: dims_ok / cn_ok — obs <= MAX_OBS 128, act <= MAX_ACT 16, hidden <= MAX_H 64
         # (`wide`), cost-net inputs <= MAX_CN_IN 160 — and N <= 128); other shapes take the per-step loop
         pol_ok = not self.policy.wide and self.policy.obs_dim <= 128 and self.policy.act_dim <= 16
@@ -365,7 +370,7 @@ class PPOLagrangian:
         self._last_obs = self._last_obs.to(device=self.device, dtype=torch.float64).contiguous()
         hs = HostStepT(T, 0, p(st["dev"]), p(henv.s), st["act"].data_ptr(), p(self._host_ws), self._host_ws.numel() * 8)
         nm, pol, buf = nenv.struct(), self.policy.struct(), rollout_buffer.struct()
-        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, or an analytic cost's)
+        cn = cw.cost_struct() if cw is not None else None      # (a constraint net's descriptor, an analytic or a discriminator cost's)
         ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
                     p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
                     p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
@@ -439,8 +444,8 @@ class PPOLagrangian:
     def _collect_rollouts_stepped(self, env, callback, rollout_buffer, n_rollout_steps, cost_function, noise=None):
         """The reference's per-step loop, kept for everything the fused launch does not cover: a callable `cost_function`
         (warm-up with null_cost, icrl/icrl.py:187-193; costs are then evaluated on the observation AFTER the step and are not
-        normalised, on_policy_algorithm.py:392-394), an env cost that is an arbitrary Python function (cpg --load_gail; an
-        AnalyticCost under ICRL_ANALYTIC_COST_STEPPED=1), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
+        normalised, on_policy_algorithm.py:392-394), an env cost that is an arbitrary Python function (an AnalyticCost under
+        ICRL_ANALYTIC_COST_STEPPED=1 and cpg --load_gail's DiscriminatorCost under ICRL_DISC_COST_STEPPED=1 too), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
         rollout_buffer.reset()
         if callback is not None:
             callback.on_rollout_start()

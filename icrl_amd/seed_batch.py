@@ -557,8 +557,9 @@ class CpgSeedBatch(SeedBatch):
             if getattr(c, "world_size", 1) > 1:
                 raise ValueError("seed batch: the runs of a batch live on ONE rank (world_size > 1: launch one batch per GPU)")
             if c.load_gail:
-                raise ValueError("seed batch: --load_gail hands the rollout a Python callable (the per-step loop); a batch takes a constraint net, "
-                                 "the ground-truth cost or the null cost")
+                raise ValueError("seed batch: --load_gail (load_gail) reads the loaded net as a discriminator cost, and the batched rollout kernels have no "
+                                 "discriminator form yet (single runs make their rollouts in fused launches); a batch takes a constraint net, the "
+                                 "ground-truth cost or the null cost")
             if c.cost_info_str is None:
                 raise ValueError("seed batch: -cis None hands learn() the cost as a callable (the per-step loop); a batch needs the cost inside the env chain")
             diff = [k for k in CPG_SAME if getattr(c, k) != getattr(c0, k)]

@@ -40,6 +40,15 @@ class CostFnT(C.Structure):
                 ("lo", f64), ("hi", f64)]
 
 
+COST_DISC = -2    # ICRL_COST_DISC: the value of n_hidden that marks a discriminator cost
+
+
+class CostDiscT(C.Structure):
+    """icrl_cost_disc_t: a constraint net read as D = zeta (cpg --load_gail); its first four fields alias CostNetT's, `net` is the host
+    address of the inner CostNetT, which must outlive every call that takes this descriptor."""
+    _fields_ = [("obs_dim", i32), ("acs_dim", i32), ("in_dim", i32), ("n_hidden", i32), ("net", vp)]
+
+
 class BufferT(C.Structure):
     _fields_ = [("T", i32), ("N", i32), ("obs_dim", i32), ("act_store", i32),
                 ("observations", vp), ("new_observations", vp), ("orig_observations", vp), ("new_orig_observations", vp),

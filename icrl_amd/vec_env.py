@@ -482,11 +482,20 @@ class VecCostWrapper(VecEnvWrapper):
         from .true_constraint_net import AnalyticCost
         return self.cost_function if isinstance(self.cost_function, AnalyticCost) else None
 
+    def discriminator_cost(self):
+        """the DiscriminatorCost behind cost_function, if that is what it is (gail_utils.py: cpg --load_gail; evaluated inside the fused
+        rollout by the kernels that read the net as D)."""
+        from .gail_utils import DiscriminatorCost
+        return self.cost_function if isinstance(self.cost_function, DiscriminatorCost) else None
+
     def cost_struct(self):
-        """the descriptor the rollout entry points take for this wrapper's cost (icrl_costnet_t or icrl_cost_fn_t), or None."""
+        """the descriptor the rollout entry points take for this wrapper's cost (icrl_costnet_t, icrl_cost_fn_t or icrl_cost_disc_t), or None."""
         cn = self.constraint_net()
         if cn is not None:
             return cn.struct()
+        dc = self.discriminator_cost()
+        if dc is not None:
+            return dc.struct()
         ac = self.analytic_cost()
         if ac is None:
             return None
@@ -507,8 +516,8 @@ class VecCostWrapper(VecEnvWrapper):
         cn = self.constraint_net()
         if cn is not None:
             cost = cn.cost_function_device(self.previous_obs, self.actions)
-        elif self.analytic_cost() is not None and torch.is_tensor(self.previous_obs) and torch.is_tensor(self.actions):
-            cost = self.cost_function(self.previous_obs, self.actions)      # icrl_cost_fn_rows on the device tensors: no host copies
+        elif (self.analytic_cost() is not None or self.discriminator_cost() is not None) and torch.is_tensor(self.previous_obs) and torch.is_tensor(self.actions):
+            cost = self.cost_function(self.previous_obs, self.actions)      # icrl_cost_fn_rows / icrl_disc_reward on the device tensors: no host copies
         else:  # arbitrary Python callable: numpy in / numpy out, as in the reference
             po = self.previous_obs.cpu().numpy() if torch.is_tensor(self.previous_obs) else self.previous_obs
             ac = self.actions.cpu().numpy() if torch.is_tensor(self.actions) else self.actions

@@ -131,7 +131,8 @@ typedef struct {
  * descriptor carrying it as an icrl_cost_fn_t (cast the pointer).  Served by icrl_rollout_collect[_ex][_mon], icrl_host_step[_mon],
  * icrl_cost_mlp_forward (= icrl_cost_fn_rows) and, for seed batches, icrl_rollout_collect_batch_cost; refused with a reason by
  * icrl_rollout_collect_batch[_mon], icrl_cn_train*, icrl_cn_prepare,
- * icrl_disc_reward and icrl_costnet_prepare.  Operation for operation what numpy computes in the reference's callables:
+ * icrl_disc_reward and icrl_costnet_prepare.  (The other tagged descriptor is icrl_cost_disc_t below: n_hidden == ICRL_COST_DISC.)
+ * Operation for operation what numpy computes in the reference's callables:
  *   NULL           0
  *   WALL_BEHIND    obs[index] <= lo                      (float64 compare on the raw observation; wall_behind)
  *   WALL_INFRONT   obs[index] >= hi                      (wall_infront)
@@ -152,6 +153,20 @@ typedef struct {
   int32_t index;    /* observation column (wall kinds) / action value (ACTION_EQUALS) */
   double lo, hi;    /* thresholds */
 } icrl_cost_fn_t;
+
+/* Discriminator cost: a constraint net read as D = zeta instead of 1 - zeta — the cost of `cpg --load_gail` (icrl/cpg.py:54-83:
+ * GailDiscriminator.reward_function(previous raw obs, clipped action, apply_log = False)).  Like icrl_cost_fn_t a tagged descriptor
+ * behind a `const icrl_costnet_t*`: its first four int32 alias the first four of icrl_costnet_t (copies of the inner net's, n_hidden
+ * excepted), n_hidden == ICRL_COST_DISC is the tag, `net` the constraint net proper, prepared (icrl_costnet_prepare) and limited as a
+ * constraint net is.  zeta is computed once and returned: the bits of icrl_disc_reward(net, ..., apply_log = 0), never 1 - (1 - zeta).
+ * Served by icrl_rollout_collect[_ex][_mon] on every route of a single run, icrl_host_step[_mon] and icrl_cost_mlp_forward; refused
+ * with a reason by icrl_rollout_collect_batch[_mon | _cost] (the batched kernels have no discriminator form), icrl_cn_train*,
+ * icrl_cn_prepare, icrl_costnet_prepare, icrl_disc_reward and the GAIL batch entry points (hand those the inner net). */
+#define ICRL_COST_DISC (-2)          /* value of n_hidden that marks a discriminator cost */
+typedef struct {
+  int32_t obs_dim, acs_dim, in_dim, n_hidden /* ICRL_COST_DISC */;
+  const icrl_costnet_t* net;
+} icrl_cost_disc_t;
 
 /* RolloutBufferWithCost arrays (stable_baselines3/common/buffers.py:443-491), time-major [T,N,...] float32. */
 typedef struct {
@@ -423,7 +438,8 @@ int icrl_sample_episodes(const icrl_env_t* env, const icrl_norm_t* nm, const icr
                          double* obs, float* actions, double* ep_rewards, int32_t* ep_lengths, void* stream);
 
 /* ConstraintNet.cost_function (icrl/constraint_net.py:121-130): cost[n] = 1 - zeta(prepare(obs[n], acs[n])).
- * obs [N,obs] float64, acs [N,acs] float32 (class index in acs[n,0] when discrete). */
+ * obs [N,obs] float64, acs [N,acs] float32 (class index in acs[n,0] when discrete).  With an icrl_cost_disc_t behind `cn`:
+ * cost[n] = zeta, what icrl_disc_reward(cn->net, ..., apply_log = 0) stores. */
 int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* cost, void* stream);
 
 /* An analytic cost on N rows: cost[n] = f(obs[n], acs[n]), one row per thread.  obs [N, obs_dim] float64, acs [N, acs_dim] float32
@@ -711,6 +727,7 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
 #define ICRL_PICK_MON 4
 #define ICRL_PICK_GRAN 8
 #define ICRL_PICK_CN128 16
+#define ICRL_PICK_DISC 32     /* the constraint net read as D (icrl_cost_disc_t) */
 #define ICRL_PICK_MINW_SHIFT 8
 #define ICRL_UPDATE_GENERIC_PERSISTENT 8
 #define ICRL_UPDATE_GENERIC_LAUNCHES 9

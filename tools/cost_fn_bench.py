@@ -6,6 +6,12 @@
                 the path `cpg` without --cn_path took before the descriptor existed)
   (c) net       the persistent rollout with a [20] constraint net, for reference ((a) does strictly less device work)
 
+the same three for a discriminator cost (gail_utils.DiscriminatorCost, the cost of `cpg --load_gail`):
+
+  (d) fused     a [40, 40] discriminator read as D inside the persistent rollout launch (icrl_cost_disc_t)
+  (e) stepped   the same object through the per-step loop (ICRL_DISC_COST_STEPPED=1: the path `cpg --load_gail` took before)
+  (f) net       the persistent rollout with a [40, 40] constraint net: the device work of (d) but for one subtraction
+
 and (a), (b) for 8 envs over the do-nothing host env of tools/host_env_bench.py (icrl_host_step against the per-step loop).
 One JSON line per figure set, microseconds per env step.  usage: python tools/cost_fn_bench.py [--T 512] [--N 64] [--host_N 8]
 """
@@ -41,15 +47,17 @@ def _agent(env, T, cost):
 
 def _rollout(agent, env, T, stepped):
     """one rollout through collect_rollouts, the switch deciding the path; returns which path ran."""
-    if stepped:
-        os.environ["ICRL_ANALYTIC_COST_STEPPED"] = "1"
-    else:
-        os.environ.pop("ICRL_ANALYTIC_COST_STEPPED", None)
+    for switch in ("ICRL_ANALYTIC_COST_STEPPED", "ICRL_DISC_COST_STEPPED"):
+        if stepped:
+            os.environ[switch] = "1"
+        else:
+            os.environ.pop(switch, None)
     try:
         fused = agent._fused_rollout_ok("cost", T, agent.rollout_buffer) or agent._host_rollout_ok("cost", T, agent.rollout_buffer)
         agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost")
     finally:
         os.environ.pop("ICRL_ANALYTIC_COST_STEPPED", None)
+        os.environ.pop("ICRL_DISC_COST_STEPPED", None)
     return fused
 
 
@@ -63,6 +71,7 @@ def main():
     from host_env_bench import NullHC
     from icrl_amd import utils
     from icrl_amd.constraint_net import ConstraintNet
+    from icrl_amd.gail_utils import DiscriminatorCost, GailDiscriminator
     from icrl_amd.true_constraint_net import AnalyticCost
     from icrl_amd.vec_env import DummyVecEnv, VecCostWrapper, VecNormalizeWithCost
     T, N = args.T, args.N
@@ -83,6 +92,23 @@ def main():
     row = dict(env="device", N=N, T=T, fused_analytic_us=1e6 * a / T, stepped_analytic_us=1e6 * b / T, fused_net_us=1e6 * c / T)
     print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
     rows = [row]
+    # (d) - (f): a [40, 40] discriminator as the env cost, fused and through the per-step loop, and the constraint net of the same shape
+    torch.manual_seed(0)
+    disc = GailDiscriminator(18, 6, [40, 40], None, lambda x: 0.0, None, None, False, optimizer_class=None)
+    denv = device_env()
+    dagent = _agent(denv, T, DiscriminatorCost(disc))
+    assert _rollout(dagent, denv, T, False) and not _rollout(dagent, denv, T, True)
+    d = _time(lambda: _rollout(dagent, denv, T, False))
+    e = _time(lambda: _rollout(dagent, denv, T, True))
+    torch.manual_seed(0)
+    cn2 = ConstraintNet(18, 6, [40, 40], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=None, action_low=None, action_high=None)
+    fenv = device_env()
+    fagent = _agent(fenv, T, cn2.cost_function)
+    f = _time(lambda: _rollout(fagent, fenv, T, False))
+    row = dict(env="device", cost="discriminator [40, 40]", N=N, T=T, fused_disc_us=1e6 * d / T, stepped_disc_us=1e6 * e / T, fused_net_us=1e6 * f / T,
+               stepped_over_fused=e / d)
+    print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in row.items()}), flush=True)
+    rows.append(row)
     if args.host_N > 0:
         H = args.host_N
         henv = VecNormalizeWithCost(VecCostWrapper(DummyVecEnv([NullHC] * H)))

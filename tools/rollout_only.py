@@ -1,5 +1,7 @@
 """rollout timing: persistent launch vs the per-step launch pairs, at HC x 64 / HC x 256 / AntWall x 256 / AntWallBroken x 512
-(CFGS=point64: PointCircle x 64 with the reference's Point transfer constraint net)."""
+(CFGS=point64: PointCircle x 64 with the reference's Point transfer constraint net).  DISC_COST=1: the env cost is a discriminator cost
+(gail_utils.DiscriminatorCost, the cost of `cpg --load_gail`) of the same shape — for the Point env the reference's Point gail_discriminator.pt —
+instead of the constraint net: the same launches with the D-output kernels."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -17,6 +19,16 @@ def run(kind, N, T, broken=False):
         lo = -np.ones(ad, np.float32)
         cn = ConstraintNet(od, ad, [20] if kind == "hc" else [40, 40], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
     env.set_cost_function(cn.cost_function)
+    if os.environ.get("DISC_COST", "0") not in ("", "0"):
+        from icrl_amd.gail_utils import DiscriminatorCost, GailDiscriminator
+        if kind.startswith("point"):
+            disc = GailDiscriminator.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                       "tests/golden/ref_artifacts/ConstraintTransfer/GAIL/Point/files/gail_discriminator.pt"),
+                                          obs_dim=od, acs_dim=ad, is_discrete=False, obs_select_dim=[0, 1], acs_select_dim=[-1])
+        else:
+            disc = GailDiscriminator(od, ad, list(cn.hidden_sizes), None, lambda x: 0.0, None, None, False, optimizer_class=None)
+        env.set_cost_function(DiscriminatorCost(disc))
+        kind = kind + "+D"
     agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, batch_size=64, seed=0)
     agent._setup_learn(N * T)
     for mode in os.environ.get("MODES", "auto,steps,auto,steps").split(","):
