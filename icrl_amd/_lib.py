@@ -67,6 +67,11 @@ SIGNATURES = {
     "icrl_buffer_add": [c_void_p, c_int] + [c_void_p] * 13,
     "icrl_is_weights": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "icrl_cn_loss_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    # the networks' own forward + backward for arbitrary upstream gradients (csrc/mlp_grad.hip; icrl_amd/torch_ops.py)
+    "icrl_policy_fwd_bwd_ws_bytes": [c_void_p, c_int],
+    "icrl_policy_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10 + [ctypes.c_longlong, c_void_p],
+    "icrl_cost_mlp_fwd_bwd_ws_bytes": [c_void_p, c_int],
+    "icrl_cost_mlp_fwd_bwd": [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [ctypes.c_longlong, c_void_p],
     "icrl_cn_train_minibatch": [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p],
     # batched forms (several independent runs in one launch, run = blockIdx.y): n_runs, jobs[n_runs], ..., args_ws, bytes, stream
@@ -84,7 +89,7 @@ SIGNATURES = {
     "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

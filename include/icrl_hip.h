@@ -761,6 +761,9 @@ int icrl_debug_rollout_trace_wide(unsigned long long* out, int n_workgroups);
  *   dual.update_parameter(average_cost)    common/dual_variable.py:47-57                -> icrl_dual_step
  *   rollout_buffer.add(...)                common/buffers.py:554-592                    -> icrl_buffer_add
  *   compute_is_weights / the cn loss       icrl/constraint_net.py:231-256, 188-202      -> icrl_is_weights, icrl_cn_loss_fwd_bwd
+ * and, for a host that keeps no torch network at all (csrc/mlp_grad.hip; icrl_amd/torch_ops.py wraps them as autograd functions):
+ *   policy.evaluate_actions + autograd     common/policies.py:752-767                   -> icrl_policy_fwd_bwd
+ *   constraint_net.forward + autograd      icrl/constraint_net.py:101-130               -> icrl_cost_mlp_fwd_bwd
  * Launch-bound by construction (a minibatch is 64..512 rows); the fused persistent kernels are the fast path. */
 
 /* flat_idx[n]: env-major indices (i = env * T + t, buffers.py:53-65) -> the rows of the [T, N] buffer: obs [n, obs_dim], actions
@@ -814,6 +817,29 @@ int icrl_is_weights(const float* preds_old, const float* preds_new, int N, const
  * reference (nominal_loss = mean(w) * mean(log zeta)). */
 int icrl_cn_loss_fwd_bwd(const float* nominal_preds, const float* expert_preds, const float* is_weights, int Bn, int Be, float reg_coeff, float eps,
                          int mode, float* terms6, float* d_nominal, float* d_expert, void* stream);
+
+/* Forward and backward of the policy's three networks for ARBITRARY upstream gradients (csrc/mlp_grad.hip).  Outputs as
+ * ActorTwoCriticsPolicy.evaluate_actions (common/policies.py:752-767) on obs [N, obs_dim] float32 (what icrl_minibatch_gather writes) and
+ * actions [N, act_store]: v_r, v_c, log_prob, entropy [N] each, any may be NULL.  grad [n_params] is OVERWRITTEN with
+ *   sum_n d_v_r[n] dv_r[n]/dθ + d_v_c[n] dv_c[n]/dθ + d_log_prob[n] dlog_prob[n]/dθ + d_entropy[n] dentropy[n]/dθ
+ * in the layout of pol->params (log_std takes the log-prob and the entropy part; Categorical: the entropy goes through the logits; entries
+ * of a zero-padded layer get exactly 0).  A NULL d_* stands for zeros; grad NULL (then every d_* NULL) = forward only, the same output bits.
+ * Reads pol->params, never params_t: no icrl_policy_prepare is needed between optimiser steps.  The backward recomputes the forward.
+ * Arithmetic in float64 on the float32 parameters and inputs: outputs and grad are the float64 values rounded once to float32.
+ * Deterministic: row tiles of 16 are summed in a fixed order, at most 64 float64 partial sums in ws, added in index order by a second plain
+ * launch; no atomics, no cooperative launch.  Served: arch == NULL, h1 == h2 <= 64, obs_dim <= 128, act_dim <= 16, 1 <= N <= 65536;
+ * everything else, a NULL required pointer and a ws below icrl_policy_fwd_bwd_ws_bytes (needed with grad only; 0 + a reason for a
+ * refused shape) return hipErrorInvalidValue with the reason, before any device call. */
+size_t icrl_policy_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
+int icrl_policy_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
+                        const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
+                        void* ws, long long ws_bytes, void* stream);
+/* The same for a constraint net on x [N, in_dim] (the rows icrl_cn_prepare writes): zeta = sigmoid(MLP_relu(x)) [N] (may be NULL),
+ * grad [n_params] overwritten with sum_n d_zeta[n] dzeta[n]/dθ.  d_zeta and grad both NULL = forward only.  Served: one or two hidden
+ * layers of up to 64 units, in_dim <= 128, 1 <= N <= 65536; the tagged descriptors (icrl_cost_fn_t, icrl_cost_disc_t) are refused. */
+size_t icrl_cost_mlp_fwd_bwd_ws_bytes(const icrl_costnet_t* cn, int N);
+int icrl_cost_mlp_fwd_bwd(const icrl_costnet_t* cn, const float* x, int N, const float* d_zeta, float* zeta, float* grad, void* ws,
+                          long long ws_bytes, void* stream);
 
 /* Diagnostic (bench.py `roofline.copy_gbs`; no reference counterpart): the memory traffic of the streaming dual-GAE launch without
  * its recurrence.  mode 0: grid, access pattern and bytes of icrl_gae_dual at N >= 131 072 (five [T,N] float arrays read, four written,
