@@ -20,7 +20,7 @@ import torch
 from . import callbacks, distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import AnalyticCost, get_true_cost_function, null_cost
+from .true_constraint_net import AnalyticCost, get_true_cost_function, null_cost, true_cost_for
 from . import envs, spaces
 
 
@@ -64,7 +64,7 @@ def setup(config, log=print):
     if config.use_null_cost:
         cost_function = AnalyticCost.null()
     elif config.cn_path is None:
-        cost_function = get_true_cost_function(config.eval_env_id)
+        cost_function = true_cost_for(config.eval_env_id)
         if cost_function is null_cost:      # (an id without a ground-truth cost: the null cost, in its device form)
             cost_function = AnalyticCost.null()
     elif config.load_gail:
@@ -114,7 +114,7 @@ def setup(config, log=print):
                                   # opt-in (a seed batch sets it): evaluation noise from the run's own streams, not the process-wide generator
                                   noise_streams=getattr(config, "streams", None) if getattr(config, "eval_noise_from_streams", False) else None,
                                   callback_on_new_best=callbacks.SaveEnvStatsCallback(train_env, config.save_dir if rank == 0 else None)),
-           callbacks.AdjustedRewardCallback(get_true_cost_function(config.eval_env_id)), hist]
+           callbacks.AdjustedRewardCallback(true_cost_for(config.eval_env_id)), hist]
     if config.save_dir and rank == 0:
         cbs.insert(0, callbacks.CheckpointCallback(int(config.save_every), os.path.join(config.save_dir, "models"), verbose=0))
     if world > 1 or getattr(config, "force_collective", False):      # env shards (BASELINE configs[4]: 4096 envs over 8 GPUs): one all-reduce per rollout + update

@@ -305,7 +305,9 @@ __device__ __forceinline__ float cost_forward_wave(const icrl_costnet_t& cn, con
 // POINT = false: the kernels that do not serve the Point envs (see env_step_wave)
 template <bool POINT = true>
 __device__ __forceinline__ double env_reset_value(const icrl_env_t& e, uint32_t key, uint32_t ctr, int i) {
-  if (POINT && e.reward_form >= 4) return 0.0;    // the Point envs: init_qpos = init_qvel = 0, reset noise scale 0 (point.py:147-160)
+  // the Point envs: init_qpos = init_qvel = 0, reset noise scale 0 (point.py:147-160); the Two Bridges envs: the start position,
+  // (3, 5) for DDCDD2B and (0, 0) otherwise (two_bridges.py:80-86,323-328), the continuous ones zeros (:344-356)
+  if (POINT && e.reward_form >= 4) return e.reward_form == 12 ? (i == 0 ? 3.0 : 5.0) : 0.0;
   if (e.reward_form >= 2) return -1.0;   // ((0 - 0) * 2) / 40 - 1
   return (unit_uniform(key, ctr, (uint32_t)(e.obs_dim + i)) - 0.5) * 0.2;
 }
@@ -347,16 +349,112 @@ __device__ __forceinline__ void lap_grid_step_wave(const icrl_env_t& e, int n, c
   done = d;
 }
 
-// The Point envs (ref: custom_envs/custom_envs/envs/point.py:22-276; reward_form 4 PointCircle, 5 PointCircleTest,
-// 6 PointCircleTestBack, 7 PointNullReward, 8 PointNullRewardTest; obs 9 = qpos (x, y, ori), qvel (0, 0, 0), torso position
+struct PointStep { double rew; int done; };
+// The Two Bridges envs (ref: custom_envs/custom_envs/envs/two_bridges.py:94-117,251-311,358-410 and envs/utils.py:9-69; reward_form
+// 10 DD2B, 11 CDD2B, 12 DDCDD2B: obs (x, y), the action is the index 0..3 as a float; 13 C2B, 14 CC2B: obs (x, y, ori), two actions
+// clipped to +-2).  A 20 x 20 field, three water rectangles that leave two bridges, on forms 11 / 12 / 14 the constraint
+// rectangle over the lower bridge.  float64, one rounding per operation, the reference's operation order; the segment tests compare
+// the orientation value with 0 exactly as the reference does (the discrete agent walks along lattice lines: the collinear cases count).
+// None of the envs ends an episode itself: gym's TimeLimit does.  An action index outside 0..3 moves nowhere (the reference raises
+// a KeyError there).
+__device__ __forceinline__ int bridge_orientation(double p0, double p1, double q0, double q1, double r0, double r1) {
+  const double val = ((q1 - p1) * (r0 - q0)) - ((q0 - p0) * (r1 - q1));      // utils.py:15-20
+  return val == 0.0 ? 0 : (val > 0.0 ? 1 : -1);
+}
+__device__ __forceinline__ bool bridge_on_segment(double p0, double p1, double q0, double q1, double r0, double r1) {      // :9-13
+  return r0 <= fmax(p0, q0) && r0 >= fmin(p0, q0) && r1 <= fmax(p1, q1) && r1 >= fmin(p1, q1);
+}
+// in_regions for ONE rectangle (origin (ox, oy), width w, height h): an end point strictly inside, or the move meets a boundary segment
+__device__ __forceinline__ bool bridge_in_region(double sx, double sy, double nx, double ny, double ox, double oy, double w, double h) {
+  const double x1 = ox + w, y1 = oy + h;
+  if (sx > ox && sx < x1 && sy > oy && sy < y1) return true;      // :62-69, strict
+  if (nx > ox && nx < x1 && ny > oy && ny < y1) return true;
+  bool hit = false;
+#pragma unroll 1
+  for (int b = 0; b < 4; ++b) {                                    // boundaries(): bottom, left, right, top (:53-60)
+    const double bp0 = b == 2 ? x1 : ox, bp1 = b == 3 ? y1 : oy;
+    const double bq0 = b == 1 ? ox : x1, bq1 = b == 0 ? oy : y1;
+    const int o1 = bridge_orientation(sx, sy, nx, ny, bp0, bp1);   // intersects((prev, next), bound) (:22-37)
+    const int o2 = bridge_orientation(sx, sy, nx, ny, bq0, bq1);
+    const int o3 = bridge_orientation(bp0, bp1, bq0, bq1, sx, sy);
+    const int o4 = bridge_orientation(bp0, bp1, bq0, bq1, nx, ny);
+    if (o1 != o2 && o3 != o4) hit = true;
+    if (o1 == 0 && bridge_on_segment(sx, sy, nx, ny, bp0, bp1)) hit = true;
+    if (o2 == 0 && bridge_on_segment(sx, sy, nx, ny, bq0, bq1)) hit = true;
+    if (o3 == 0 && bridge_on_segment(bp0, bp1, bq0, bq1, sx, sy)) hit = true;
+    if (o4 == 0 && bridge_on_segment(bp0, bp1, bq0, bq1, nx, ny)) hit = true;
+  }
+  return hit;
+}
+// Every lane computes the env's whole step; lane i < obs_dim stores component i.  Not inlined, arguments by value, (reward, done) back
+// in registers: point_step_wave's conventions and reasons.
+__device__ __noinline__ PointStep bridge_step_wave(int form, int max_steps, double* s_all, int32_t* t_ep_all, uint32_t* step_count_all,
+                                                   int n, double x0, double y0, double ori0, float act0, float act1, uint32_t ctr_new,
+                                                   int tep, double* s_new_lds) {
+  const int lane = threadIdx.x & 63;
+  const bool cont = form >= 13;
+  double nx, ny, ori = 0.0;
+  if (cont) {
+    const double a0 = fmin(fmax((double)act0, -2.0), 2.0);         // two_bridges.py:359
+    const double a1 = fmin(fmax((double)act1, -2.0), 2.0);
+    ori = ori0 + a1;                                               // :362-363 (kept when the move is rejected)
+    double sn, cs;
+    sincos(ori, &sn, &cs);
+    const double dx = cs * a0, dy = sn * a0;                       // :364-365
+    nx = fmin(fmax(x0 + dx, -20.0), 20.0);                         // :369-370
+    ny = fmin(fmax(y0 + dy, -20.0), 20.0);
+  } else {
+    const int ix = (int)act0;                                      // :244-247: 0.7 * {(1, 0), (-1, 0), (0, 1), (0, -1)}
+    const double mx = ix == 0 ? 0.7 : (ix == 1 ? -0.7 : 0.0), my = ix == 2 ? 0.7 : (ix == 3 ? -0.7 : 0.0);
+    nx = rint((x0 + mx) * 1e6) / 1e6;                              // np.around(state + action, 6) (:281)
+    ny = rint((y0 + my) * 1e6) / 1e6;
+  }
+  bool rejected = fmin(nx, ny) < 0.0 || fmax(nx, ny) > 20.0;       // :283, :382
+  const int n_regions = (form == 10 || form == 13) ? 3 : 4;        // water ((4,0),4,5), ((4,6),4,8), ((4,15),4,5); constraint ((4,5),4,1)
+#pragma unroll 1
+  for (int r = 0; r < n_regions; ++r) {
+    const double oy = r == 0 ? 0.0 : (r == 1 ? 6.0 : (r == 2 ? 15.0 : 5.0)), h = r == 1 ? 8.0 : (r == 3 ? 1.0 : 5.0);
+    if (!rejected && bridge_in_region(x0, y0, nx, ny, 4.0, oy, 4.0, h)) rejected = true;
+  }
+  double rew;
+  if (rejected) {                                                  // back in the same spot (:286-289)
+    nx = x0; ny = y0; rew = -2.0;
+  } else {
+    const double gx = 20.0 - nx, gy = 0.0 - ny;
+    const double d2 = gx * gx + gy * gy;
+    if (d2 < 1.0) rew = cont ? 250.0 : 12.0;                       // the goal: no end of the episode (:291-296, :390-393)
+    else if (nx > 4.0) {                                           // the right half (:298-306, :397-405)
+      rew = 10.0 / sqrt(d2);
+      if (cont && ny < 6.0) rew = rew * 20.0;
+    } else rew = -1.0;                                             // the left half
+  }
+  const int d = tep >= max_steps ? 1 : 0;                          // gym's TimeLimit: the reward is kept
+  const int O = cont ? 3 : 2;
+  if (lane < O) {
+    double v = lane == 0 ? nx : (lane == 1 ? ny : ori);
+    if (d) v = form == 12 ? (lane == 0 ? 3.0 : 5.0) : 0.0;         // on done: the start position (env_reset_value)
+    as_global(s_all)[(size_t)n * O + lane] = v;
+    if (s_new_lds != nullptr) s_new_lds[lane] = v;
+  }
+  if (lane == 0) {
+    as_global(t_ep_all)[n] = d ? 0 : tep;
+    as_global(step_count_all)[n] = ctr_new;
+  }
+  return PointStep{rew, d};
+}
+
+// The Point envs (ref: custom_envs/custom_envs/envs/point.py:22-376; reward_form 4 PointCircle, 5 PointCircleTest,
+// 6 PointCircleTestBack, 7 PointNullReward, 8 PointNullRewardTest, 9 PointTrack; obs 9 = qpos (x, y, ori), qvel (0, 0, 0), torso position
 // (x, y, 0)): closed-form kinematics in float64, one rounding per operation, the reference's operation order.
 // Every lane computes the env's whole step; lane i < 9 stores component i.  Not inlined: the double-precision sincos is a long
 // sequence that would otherwise enter the register allocation of every rollout kernel; so the env's scalars and arrays come in
 // by value, as for env_step_wave3, and the reward / done pair comes back in registers.
-struct PointStep { double rew; int done; };
 __device__ __noinline__ PointStep point_step_wave(int form, int max_steps, double* s_all, int32_t* t_ep_all, uint32_t* step_count_all,
                                                   int n, double x0, double y0, double ori0, float act0, float act1, uint32_t ctr_new,
                                                   int tep, double* s_new_lds) {
+  // the Two Bridges forms: their own callee, same signature.  musttail: a jump, not a call, so this function keeps no return address
+  // and has no stack frame (without it the compiler calls and spills one register: 16 bytes of scratch in every caller)
+  if (form >= 10) [[clang::musttail]] return bridge_step_wave(form, max_steps, s_all, t_ep_all, step_count_all, n, x0, y0, form >= 13 ? ori0 : 0.0, act0, act1, ctr_new, tep, s_new_lds);
   const int lane = threadIdx.x & 63;
   const double a0 = fmin(fmax((double)act0, -0.25), 0.25);         // point.py:167
   const double a1 = fmin(fmax((double)act1, -0.25), 0.25);
@@ -370,6 +468,10 @@ __device__ __noinline__ PointStep point_step_wave(int form, int max_steps, doubl
   if (form <= 6) {                                                 // the circle reward (:185-186)
     const double num = y * dx - x * dy;
     rew = num / (1.0 + fabs(sqrt(x * x + y * y) - 10.0));
+  } else if (form == 9) {                                          // PointTrack: movement + track reward, ctrl weight 0.0 (:353-368)
+    const double ctrl = a0 * a0 + a1 * a1;
+    const double track = fabs(sqrt(x * x + y * y) - 10.0) < 2.0 ? 1.0 : 0.0;
+    rew = (((-y) * dx + x * dy) + track) + 0.0 * ctrl;
   }
   int d = 0;
   // STRICT inequalities (:98, :230, :266): x == -3 does not end the episode
@@ -401,8 +503,10 @@ __device__ __forceinline__ void env_step_wave(const icrl_env_t& e, int n, const 
   if (POINT && e.reward_form >= 4) {
     const int tep = tep_io + 1;
     ctr_io = ctr_io + 1u;
+    // (one call site: the Two Bridges forms branch on inside the callee, so that a caller saves and restores its live registers around
+    // one call, as before them; a discrete bridge env has no second action, and its s_old[2] is an unused LDS word)
     const PointStep r = point_step_wave(e.reward_form, e.max_steps, e.s, e.t_ep, e.step_count, n, s_old[0], s_old[1], s_old[2],
-                                        act[0], act[1], ctr_io, tep, s_new_lds);
+                                        act[0], e.act_dim > 1 ? act[1] : 0.f, ctr_io, tep, s_new_lds);
     tep_io = r.done ? 0 : tep;
     reward = r.rew;
     done = r.done;

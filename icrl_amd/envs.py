@@ -23,6 +23,10 @@ ENV_IDS = {
     "PointCircle-v0": ("point_circle", False, False), "PointCircleTest-v0": ("point_circle_test", True, False),
     "PointCircleTestBack-v0": ("point_circle_test_back", True, False),
     "PointNullReward-v0": ("point_null", False, False), "PointNullRewardTest-v0": ("point_null_test", True, False),
+    "PointTrack-v0": ("point_track", False, False),
+    # custom_envs/__init__.py — the dense Two Bridges envs, stepped exactly; none ends an episode before the 200-step limit
+    "DD2B-v0": ("dd2b", False, False), "CDD2B-v0": ("cdd2b", False, False), "DDCDD2B-v0": ("ddcdd2b", False, False),
+    "C2B-v0": ("c2b", False, False), "CC2B-v0": ("cc2b", False, False),
 }
 
 _REGISTRY = {}

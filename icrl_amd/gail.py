@@ -22,7 +22,7 @@ import torch
 from . import callbacks, distributed as D, envs, logger, spaces, utils
 from .gail_utils import GailCallback, GailDiscriminator
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import get_true_cost_function
+from .true_constraint_net import get_true_cost_function, true_cost_for
 
 
 class PPO(PPOLagrangian):
@@ -78,7 +78,7 @@ def setup(config, log=print):
                                           eps=config.disc_eps, device=dev)
     if getattr(config, "use_cost_shaping_callback", False):
         raise NotImplementedError("--use_cost_shaping_callback (a shaping ablation of the reference) is outside the hot path")
-    gail_update = GailCallback(discriminator, config.learn_cost, get_true_cost_function(config.eval_env_id), config.save_dir)
+    gail_update = GailCallback(discriminator, config.learn_cost, true_cost_for(config.eval_env_id), config.save_dir)
     model = PPO(policy=config.policy_name, env=train_env, learning_rate=config.learning_rate, n_steps=config.n_steps,
                 batch_size=config.batch_size, n_epochs=config.n_epochs, gamma=config.reward_gamma, gae_lambda=config.reward_gae_lambda,
                 clip_range=config.clip_range, clip_range_vf=config.clip_range_reward_vf, ent_coef=config.ent_coef,

@@ -20,7 +20,7 @@ import torch
 from . import distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import get_true_cost_function, mean_cost, null_cost
+from .true_constraint_net import get_true_cost_function, mean_cost, null_cost, true_cost_for
 from .vec_env import VecNormalize, sync_envs_normalization
 from . import envs, spaces
 
@@ -88,7 +88,7 @@ def setup(config):
 
     st = dict(config=config, rank=rank, world=world, train_env=train_env, sampling_env=sampling_env, eval_env=eval_env,
               constraint_net=constraint_net, create_nominal_agent=create_nominal_agent, agent=create_nominal_agent(),
-              expert_agent=expert_agent, true_cost_function=get_true_cost_function(config.eval_env_id),
+              expert_agent=expert_agent, true_cost_function=true_cost_for(config.eval_env_id),
               d_expert_obs=torch.as_tensor(np.asarray(expert_obs), device=dev),
               d_expert_acs=torch.as_tensor(np.asarray(expert_acs), device=dev),
               timesteps=0., start_time=time.time(),

@@ -5,7 +5,12 @@
 evaluates inside the fused rollout launches (icrl_cost_fn_t, csrc/cost_fn.h) and, on device tensors, through icrl_cost_fn_rows.  On numpy
 arrays they compute exactly what the reference's functions compute.  The module-level `wall_behind`, `null_cost` and `lap_grid_world` stay
 plain numpy functions (callables handed to `learn(cost_function=...)` keep the per-step loop and its semantics).
+
+`BridgesCost` is the reference's `bridges()` for CDD2B-v0 / CC2B-v0: host side only, a plain callable.  `true_cost_for` is the
+resolver the entry points call: a `BridgesCost` for those two ids, `get_true_cost_function` for every other.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -116,7 +121,8 @@ class AnalyticCost:
 
 
 TRUE_COSTS = {
-    # ref: icrl/true_constraint_net.py:13-34 (the bridge envs CDD2B / CC2B / CDD3B need the reference's gym env and are not served)
+    # ref: icrl/true_constraint_net.py:13-34 (the bridge envs are not in this table: CDD2B / CC2B are served by true_cost_for -> BridgesCost,
+    # not as an analytic kind; CDD3B is not served)
     **{k: ("wall_behind", -3) for k in ("HCWithPosTest-v0", "WalkerWithPosTest-v0", "SwimmerWithPosTest-v0", "AntWallTest-v0",
                                         "AntWallBrokenTest-v0", "PointCircleTestBack-v0")},
     **{k: ("wall_behind_and_infront", -3, +3) for k in ("PointNullRewardTest-v0", "PointCircleTest-v0", "AntCircleTest-v0")},
@@ -132,6 +138,89 @@ def get_true_cost_function(env_id):
         print("Cost function for %s is not implemented yet. Returning null cost function" % env_id)
         return null_cost
     return getattr(AnalyticCost, entry[0])(*entry[1:])
+
+
+# ---- the Two Bridges cost (ref: icrl/true_constraint_net.py:60-102, custom_envs/envs/utils.py:9-69) ---------------------------------
+def _orientation(p0, p1, q0, q1, r0, r1):
+    val = ((q1 - p1) * (r0 - q0)) - ((q0 - p0) * (r1 - q1))
+    return np.where(val == 0, 0, np.where(val > 0, 1, -1))
+
+
+def _on_segment(p0, p1, q0, q1, r0, r1):
+    return (r0 <= np.maximum(p0, q0)) & (r0 >= np.minimum(p0, q0)) & (r1 <= np.maximum(p1, q1)) & (r1 >= np.minimum(p1, q1))
+
+
+def in_region_rows(prev, nxt, region):
+    """utils.in_regions for one rectangle (origin, width, height), over rows: prev, nxt float64 [n, 2] -> bool [n].  An end point strictly
+    inside, or the segment prev -> nxt meets one of the four boundary segments (orientation compared with 0 exactly, as the reference)."""
+    (ox, oy), w, h = region
+    ox, oy, x1, y1 = float(ox), float(oy), float(ox + w), float(oy + h)
+    sx, sy, nx, ny = prev[:, 0], prev[:, 1], nxt[:, 0], nxt[:, 1]
+    hit = (sx > ox) & (sx < x1) & (sy > oy) & (sy < y1)
+    hit |= (nx > ox) & (nx < x1) & (ny > oy) & (ny < y1)
+    for (b0, b1), (c0, c1) in (((ox, oy), (x1, oy)), ((ox, oy), (ox, y1)), ((x1, oy), (x1, y1)), ((ox, y1), (x1, y1))):
+        o1, o2 = _orientation(sx, sy, nx, ny, b0, b1), _orientation(sx, sy, nx, ny, c0, c1)
+        o3, o4 = _orientation(b0, b1, c0, c1, sx, sy), _orientation(b0, b1, c0, c1, nx, ny)
+        hit |= (o1 != o2) & (o3 != o4)
+        hit |= (o1 == 0) & _on_segment(sx, sy, nx, ny, b0, b1)
+        hit |= (o2 == 0) & _on_segment(sx, sy, nx, ny, c0, c1)
+        hit |= (o3 == 0) & _on_segment(b0, b1, c0, c1, sx, sy)
+        hit |= (o4 == 0) & _on_segment(b0, b1, c0, c1, nx, ny)
+    return hit
+
+
+class BridgesCost:
+    """The reference's `bridges(env, obs, acs)` for CDD2B-v0 (discrete) and CC2B-v0 (continuous): 1 where the move from the raw
+    observation under the action touches the constraint rectangle ((4, 5), 4, 1) over the lower bridge, else 0 (int64), vectorised over
+    rows; `[batch, n_envs, .]` inputs give `[batch, n_envs]` costs as in the reference.
+
+    The continuous form keeps the reference's quirk (:92-95): `ob` is overwritten by the next position before `in_regions`, so the cost
+    only sees where the move ends (strictly inside the rectangle or exactly on its boundary), not what it crosses.  Actions are taken as
+    float64 (the reference's pinned numpy promotes a float32 action before anything is computed with it).  Device tensors are copied
+    to the host.  A plain callable: not an AnalyticCost, so a run that trains or evaluates against it takes the per-step loop."""
+
+    IDS = {"CDD2B-v0": False, "CC2B-v0": True}
+    CONSTRAINT = ((4, 5), 4, 1)
+    MOVES = 0.7 * np.array([(1, 0), (-1, 0), (0, 1), (0, -1)])      # two_bridges.py:243-247
+    SIZE, CTRL = 20.0, 2.0
+
+    def __init__(self, env_id):
+        if env_id not in self.IDS:
+            raise ValueError(f"BridgesCost: {env_id!r}; served: {', '.join(self.IDS)}")
+        self.env_id, self.continuous, self.name = env_id, self.IDS[env_id], "bridges"
+
+    def __repr__(self):
+        return f"BridgesCost({self.env_id})"
+
+    def __call__(self, obs, acs):
+        obs = obs.detach().cpu().numpy() if torch.is_tensor(obs) else np.asarray(obs)
+        acs = acs.detach().cpu().numpy() if torch.is_tensor(acs) else np.asarray(acs)
+        if obs.ndim > 2:
+            shape = obs.shape[:2]
+            obs, acs = obs.reshape(shape[0] * shape[1], -1), acs.reshape(shape[0] * shape[1], -1)
+        else:
+            shape = (obs.shape[0],)
+            acs = acs.reshape(obs.shape[0], -1)
+        ob = obs.astype(np.float64)
+        if not self.continuous:
+            prev = ob[:, :2]
+            nxt = np.around(prev + self.MOVES[acs[:, 0].astype(np.int64)], 6)
+        else:
+            ac = np.clip(acs.astype(np.float64), -self.CTRL, self.CTRL)
+            ori = ob[:, 2] + ac[:, 1]
+            dx = np.array([math.cos(v) for v in ori]) * ac[:, 0]
+            dy = np.array([math.sin(v) for v in ori]) * ac[:, 0]
+            nxt = np.stack([np.clip(ob[:, 0] + dx, -self.SIZE, self.SIZE), np.clip(ob[:, 1] + dy, -self.SIZE, self.SIZE)], axis=1)
+            prev = nxt
+        return in_region_rows(prev, nxt, self.CONSTRAINT).astype(np.int64).reshape(shape)
+
+
+def true_cost_for(env_id):
+    """what icrl / cpg / gail train and evaluate against: BridgesCost for the two constrained Two Bridges ids, get_true_cost_function for
+    every other id (which itself, and the analytic kinds of icrl_cost_fn_t, do not know the bridge cost: DESIGN §21)."""
+    if env_id in BridgesCost.IDS:
+        return BridgesCost(env_id)
+    return get_true_cost_function(env_id)
 
 
 def mean_cost(fn, obs, acs):

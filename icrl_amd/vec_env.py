@@ -31,18 +31,24 @@ KINDS = {"hc": (18, 6, 1000, 0), "ant": (113, 8, 500, 1),
          # the Point envs restated exactly (custom_envs/envs/point.py:22-276, custom_envs/__init__.py:123-163):
          # obs = qpos (x, y, ori), qvel (0, 0, 0), torso position (x, y, 0)
          "point_circle": (9, 2, 150, 4), "point_circle_test": (9, 2, 150, 5), "point_circle_test_back": (9, 2, 150, 6),
-         "point_null": (9, 2, 150, 7), "point_null_test": (9, 2, 150, 8)}
-DISCRETE_ACTIONS = {"lgw": 2, "clgw": 2}
-POINT_KINDS = ("point_circle", "point_circle_test", "point_circle_test_back", "point_null", "point_null_test")
+         "point_null": (9, 2, 150, 7), "point_null_test": (9, 2, 150, 8), "point_track": (9, 2, 150, 9),
+         # the dense Two Bridges envs restated exactly (custom_envs/envs/two_bridges.py, custom_envs/__init__.py): the discrete
+         # ones observe (x, y) and take Discrete(4), the continuous ones observe (x, y, ori) and take two actions in [-2, 2]
+         "dd2b": (2, 1, 200, 10), "cdd2b": (2, 1, 200, 11), "ddcdd2b": (2, 1, 200, 12), "c2b": (3, 2, 200, 13), "cc2b": (3, 2, 200, 14)}
+DISCRETE_ACTIONS = {"lgw": 2, "clgw": 2, "dd2b": 4, "cdd2b": 4, "ddcdd2b": 4}
+POINT_KINDS = ("point_circle", "point_circle_test", "point_circle_test_back", "point_null", "point_null_test", "point_track")
 POINT_CTRL = 0.25        # the actuators' ctrlrange (xmls/point_circle.xml); the env clips to it again (point.py:167)
+BRIDGE_DISCRETE_KINDS = ("dd2b", "cdd2b", "ddcdd2b")
+BRIDGE_CONTINUOUS_KINDS = ("c2b", "cc2b")
+BRIDGE_SIZE, BRIDGE_CTRL = 20.0, 2.0      # two_bridges.py:16, :339
 ENV_IDS = _ENV_IDS   # reference gym ids -> (kind, early termination, broken); defined in envs.py (no torch there)
 
 
 def dynamics_matrix(kind):
     """B ~ N(0, 0.05^2) drawn once from RandomState(1234)."""
     o, a, _, _ = KINDS[kind]
-    if kind in DISCRETE_ACTIONS or kind in POINT_KINDS:
-        return np.zeros((o, a), np.float64)      # no linear dynamics: the grid world and the Point envs are stepped exactly
+    if kind in DISCRETE_ACTIONS or kind in POINT_KINDS or kind in BRIDGE_CONTINUOUS_KINDS:
+        return np.zeros((o, a), np.float64)      # no linear dynamics: the grid world, the Point and the Two Bridges envs are stepped exactly
     return (np.random.RandomState(1234).randn(o, a) * 0.05).astype(np.float64)
 
 
@@ -126,14 +132,21 @@ def _as_device_f32(x, device):
 
 
 class HipSynthVecEnv(VecEnv):
-    """N synthetic HCWithPos-/AntWall-shaped envs (or exact LapGridWorlds / Point envs) stepped by one kernel launch; float64 state in HBM."""
+    """N synthetic HCWithPos-/AntWall-shaped envs (or exact LapGridWorlds / Point / Two Bridges envs) stepped by one kernel launch; float64 state in HBM."""
 
     def __init__(self, n_envs, kind="hc", seed=0, env_index_offset=0, wall_terminate=False, broken=False, device="cuda"):
         self.kind, self.device = kind, torch.device(device)
         o, a, ms, rf = KINDS[kind]
         self.obs_dim, self.act_dim, self.max_steps, self.reward_form = o, a, ms, rf
         self.wall_terminate, self.broken = bool(wall_terminate), bool(broken)
-        if kind in DISCRETE_ACTIONS:
+        if kind in BRIDGE_DISCRETE_KINDS:
+            # ref: two_bridges.py:70-72, :249 — Box((0, 0), (20, 20)) float32 observations, Discrete(4)
+            super().__init__(n_envs, spaces.Box(0.0, BRIDGE_SIZE, (o,), np.float32), spaces.Discrete(DISCRETE_ACTIONS[kind]))
+        elif kind in BRIDGE_CONTINUOUS_KINDS:
+            # ref: two_bridges.py:336-342 — Box((0, 0, 0), (20, 20, inf)) float32 observations, Box(-2, 2, (2,)) float32 actions
+            super().__init__(n_envs, spaces.Box(np.zeros(3, np.float32), np.array([BRIDGE_SIZE, BRIDGE_SIZE, np.inf], np.float32), (o,), np.float32),
+                             spaces.Box(-BRIDGE_CTRL, BRIDGE_CTRL, (a,), np.float32))
+        elif kind in DISCRETE_ACTIONS:
             # ref: lap_grid_world.py:50-53 — Box(0, 40) float32 observation space (the env itself emits 2 pos / 40 - 1)
             super().__init__(n_envs, spaces.Box(0.0, 40.0, (o,), np.float32), spaces.Discrete(DISCRETE_ACTIONS[kind]))
         elif kind in POINT_KINDS:

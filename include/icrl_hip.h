@@ -59,7 +59,13 @@ typedef struct {
                            * 4: PointCircle, 5: PointCircleTest (ends at |x| > 3), 6: PointCircleTestBack (ends at x < -3),
                            * 7: PointNullReward, 8: PointNullRewardTest (custom_envs/envs/point.py:22-276 stepped exactly;
                            *    obs_dim 9, act_dim 2, max_steps 150; B / key unused; the variant decides how an episode
-                           *    ends, wall_terminate is not read) */
+                           *    ends, wall_terminate is not read)
+                           * 9: PointTrack (point.py:284-376: the Point kinematics, reward movement + track, never ends early)
+                           * 10: DD2B, 11: CDD2B (+ the constraint rectangle), 12: DDCDD2B (as 11, start (3, 5)): the dense discrete
+                           *    Two Bridges envs (custom_envs/envs/two_bridges.py:94-117,237-328 stepped exactly; obs_dim 2,
+                           *    act_dim 1 = the Discrete(4) action index as a float, max_steps 200)
+                           * 13: C2B, 14: CC2B (+ the constraint rectangle): the continuous ones (:331-418; obs_dim 3 = x, y, ori,
+                           *    act_dim 2 clipped to +-2, max_steps 200).  9..14: B / key unused, episodes end at max_steps only */
   int32_t wall_terminate; /* "Test" variants: done & reward 0 when obs[0] <= -3 */
   int32_t broken;         /* AntWallBroken: action[4:] = 0 */
   int32_t _pad;

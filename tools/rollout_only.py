@@ -1,5 +1,6 @@
 """rollout timing: persistent launch vs the per-step launch pairs, at HC x 64 / HC x 256 / AntWall x 256 / AntWallBroken x 512
-(CFGS=point64: PointCircle x 64 with the reference's Point transfer constraint net).  DISC_COST=1: the env cost is a discriminator cost
+(CFGS=point64: PointCircle x 64 with the reference's Point transfer constraint net; CFGS=dd2b64,c2b64: the Two Bridges envs x 64 with the
+null cost, as `cpg --use_null_cost` trains them).  DISC_COST=1: the env cost is a discriminator cost
 (gail_utils.DiscriminatorCost, the cost of `cpg --load_gail`) of the same shape — for the Point env the reference's Point gail_discriminator.pt —
 instead of the constraint net: the same launches with the D-output kernels."""
 import os, sys, time
@@ -12,13 +13,16 @@ from icrl_amd.constraint_net import ConstraintNet
 def run(kind, N, T, broken=False):
     env = VecNormalizeWithCost(VecCostWrapper(HipSynthVecEnv(N, kind, 0, broken=broken)))
     od, ad = env.unwrapped.obs_dim, env.unwrapped.act_dim
-    if kind.startswith("point"):      # the reference's AntWall -> Point transfer net on (x, y), as `cpg -cosd 0 1 -casd -1` loads it
+    if kind in ("dd2b", "c2b"):
+        from icrl_amd.true_constraint_net import AnalyticCost
+        cn = None
+    elif kind.startswith("point"):      # the reference's AntWall -> Point transfer net on (x, y), as `cpg -cosd 0 1 -casd -1` loads it
         cn = ConstraintNet.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests/golden/ref_artifacts/point_best_cn_model.pt"),
                                 obs_dim=od, acs_dim=ad, obs_select_dim=[0, 1], acs_select_dim=[-1])
     else:
         lo = -np.ones(ad, np.float32)
         cn = ConstraintNet(od, ad, [20] if kind == "hc" else [40, 40], None, lambda x: 0.05, None, None, False, 0.5, clip_obs=20, action_low=lo, action_high=-lo)
-    env.set_cost_function(cn.cost_function)
+    env.set_cost_function(cn.cost_function if cn is not None else AnalyticCost.null())
     if os.environ.get("DISC_COST", "0") not in ("", "0"):
         from icrl_amd.gail_utils import DiscriminatorCost, GailDiscriminator
         if kind.startswith("point"):
@@ -100,6 +104,6 @@ def run(kind, N, T, broken=False):
         agent.profile_phases = 0
 
 CFGS = dict(hc64=("hc", 64, 2048), hc256=("hc", 256, 1024), ant256=("ant", 256, 512), antb512=("ant", 512, 256, True), hc128=("hc", 128, 1024), hc16=("hc", 16, 2048),
-            ant256x2048=("ant", 256, 2048), point64=("point_circle", 64, 2048))
+            ant256x2048=("ant", 256, 2048), point64=("point_circle", 64, 2048), dd2b64=("dd2b", 64, 2048), c2b64=("c2b", 64, 2048))
 for name in os.environ.get("CFGS", "hc64,hc256,ant256,antb512").split(","):
     run(*CFGS[name])
