@@ -48,6 +48,8 @@ SIGNATURES = {
     "icrl_rollout_collect_batch_mon": [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_double] * 4 + [c_int, c_void_p, ctypes.c_longlong, c_void_p],
     "icrl_host_episode_step": [c_void_p] * 6 + [c_int, c_int, c_void_p],
     "icrl_ppo_lag_train": [c_void_p] * 11,
+    "icrl_ppo_stream_ws_bytes": [c_void_p] * 3,
+    "icrl_ppo_lag_train_stream": [c_void_p] * 11 + [ctypes.c_longlong, c_void_p],
     "icrl_ppo_generic_row_floats": [c_void_p],
     "icrl_cn_prepare": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "icrl_cn_train_work_floats": [c_int, c_int, c_int, c_int],
@@ -89,7 +91,7 @@ SIGNATURES = {
     "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

@@ -31,7 +31,47 @@ struct TrainArgs {
   const struct PlanChunk* plan_chunks;   // rows kernel: per 64-row chunk (+5 zero entries); two entries per step in split mode
   int n_steps;
   u64* gx;                               // split mode (two workgroups per network): partial-gradient granules, ICRL_PPO_SPLIT_BYTES
+  const float* srec;                     // minibatch stream (icrl_ppo_lag_train_stream): one StreamRec-shaped record per 16-row tile, in plan order
+  const float* sstat;                    // ... and {mean_r, istd_r, mean_c, 0} per optimiser step (+2 entries)
 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// The pre-gathered minibatch stream (ppo_stream.hip writes it, the STREAM instantiations of ppo_train_halves.hip read it)
+// ---------------------------------------------------------------------------------------------------------------
+// One record per 16-row tile of every 64-row chunk, records in the order of plan_chunks (epoch, minibatch, chunk, tile), one chunk of
+// records more behind the last (the step loop prefetches one chunk ahead).  A record is [obs_dim + act_store + 7][16 rows] floats:
+// observation components, then the stored action components, then the seven per-row scalar planes below — component-major, so that four
+// consecutive rows of one component are one 16-byte load and (observations, scalars) one 16-byte LDS store into the [feature][row] images.
+// Rows beyond a chunk's `rows` hold the row of the chunk's first position, as the in-kernel gather stages them.
+enum { SR_LOGP = 0, SR_ADV_R = 1, SR_ADV_C = 2, SR_VAL_R = 3, SR_RET_R = 4, SR_VAL_C = 5, SR_RET_C = 6, SR_PLANES = 7 };
+struct StreamRec {
+  int O, AS;
+  __host__ __device__ int comps() const { return O + AS + SR_PLANES; }
+  __host__ __device__ int floats() const { return 16 * comps(); }
+  __host__ __device__ int vec4(int comp, int rows4) const { return 4 * comp + rows4; }      // 16-byte word of rows 4 rows4.. of a component
+};
+
+// advantage statistics of one minibatch (ref: ppo_lag.py:215-219): a wave's partial sums over its 64 rows, and mean / 1 / (std + 1e-8) /
+// cost mean from the two or four partials — ONE definition for the in-kernel gather path and the stream's pre-pass (same sums, same order)
+__device__ __forceinline__ void adv_wave_partials(bool in, float ar, float ac, float& s_r, float& s_c, float& s_rr) {
+  s_r = wave_sum_fast(in ? ar : 0.f); s_c = wave_sum_fast(in ? ac : 0.f); s_rr = wave_sum_fast(in ? ar * ar : 0.f);
+}
+// part: [4][3] partials {s_r, s_c, s_rr} of the waves (LDS)
+__device__ __forceinline__ void adv_stats_from_partials(const float* part, bool big_mb, int nb, float& mean_r, float& istd_r, float& mean_c) {
+  float s_r = part[0] + part[3];
+  float s_c = part[1] + part[4];
+  float s_rr = part[2] + part[5];
+  if (big_mb) {
+    s_r += part[6] + part[9];
+    s_c += part[7] + part[10];
+    s_rr += part[8] + part[11];
+  }
+  const float inv = __builtin_amdgcn_rcpf((float)nb);
+  mean_r = s_r * inv;
+  mean_c = s_c * inv;
+  const float var = fmaxf(s_rr - s_r * mean_r, 0.f) * __builtin_amdgcn_rcpf((float)(nb - 1));
+  istd_r = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(var) + 1e-8f);
+}
 
 // the schedule of a launch, tabulated once by ppo_plan_kernel so that the persistent kernel carries no epoch / minibatch /
 // cursor arithmetic in scalar registers: which rows of which permutation form each minibatch and chunk, and Adam's bias
@@ -178,6 +218,10 @@ int launch_train_pairs(const TrainArgs& a, int nt1, bool discrete, hipStream_t s
 // parts = 2 | 4 workgroups per network (round 6: four — 16 rows of every chunk each)
 int launch_train_halves(const TrainArgs& a, bool discrete, int parts, hipStream_t s, int* packed);
 int launch_train_halves_batch(const TrainArgs* d_args, int n_runs, int obs, bool discrete, int parts, bool prof, hipStream_t s, int* packed);      // prof: hp._pad & 1 (the runs of a batch share it)
+// ppo_stream.hip: the pre-gathered minibatch stream of a single-run wave-quad launch (a.srec set: launch_train_halves runs the STREAM instantiation)
+long long stream_n_chunks(int n_total, int batch_size, int n_epochs);
+size_t stream_bytes(int obs, int act_store, long long n_chunks, long long n_steps);      // records (+ one chunk) and the per-step statistics table
+int launch_stream_prepass(TrainArgs& a, void* ws, hipStream_t s);                        // two plain launches behind prepare_train's; sets a.srec / a.sstat
 // ppo_train_quarters.hip: four workgroups per network at obs 65..128 (wave quads, the row-owning kernel's parameter ownership); single-run launches
 int launch_train_quarters_wide(const TrainArgs& a, bool discrete, hipStream_t s, int* packed);
 // ppo_train_quarters2.hip: the same for minibatches of 65..128 rows: both chunks in one pass, two row tiles per wave (chunk plan with two entries per step)

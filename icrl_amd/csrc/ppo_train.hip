@@ -947,7 +947,7 @@ static int prepare_train(const icrl_policy_t* pol, float* exp_avg, float* exp_av
   a.params = pol->params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.adam_t = adam_step;
   a.buf = *buf; a.perms = perms; a.nu = nu; a.hp = *hp; a.stats = stats; a.xch = (u64*)sync_ws;
   a.t_magic = buf->T == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned long long)buf->T);
-  a.plan_steps = nullptr; a.plan_chunks = nullptr; a.n_steps = 0; a.gx = nullptr;
+  a.plan_steps = nullptr; a.plan_chunks = nullptr; a.n_steps = 0; a.gx = nullptr; a.srec = nullptr; a.sstat = nullptr;
   hipError_t e = hipMemsetAsync(sync_ws, 0, 512, s);      // granule slots: 2 step parities x (3 roles x 8 waves, padded to 32) x 8 B
   if (e != hipSuccess) return bad((int)e);
   e = hipMemsetAsync(stats, 0, (32 + hp->n_epochs) * sizeof(float), s);
@@ -1035,17 +1035,41 @@ static int train_generic(const icrl_policy_t* pol, float* exp_avg, float* exp_av
 
 // the route record of a launched update, its one writer (the generic-shape path has its own in generic.hip): workgroups per network
 // of `kind` (prepare_train) and the grid layout the launcher reported, behind the launcher's error
-static int routed_update(int err, int kind, int n_runs, int packed) {
+static int routed_update(int err, int kind, int n_runs, int packed, int streamed = 0) {
   static const int wgs[8] = {1, 1, 2, 1, 2, 4, 4, 4};
-  if (err == 0) note_route(ICRL_FAMILY_UPDATE, kind, wgs[kind], n_runs, packed);
+  if (err == 0) note_route(ICRL_FAMILY_UPDATE, kind, wgs[kind], n_runs, packed, streamed);
   return err;
 }
 
 extern "C" int icrl_ppo_generic_row_floats(const icrl_policy_t* pol) { return generic_row_floats(pol); }
 
-extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
-                                  const icrl_buffer_t* buf, const int32_t* perms, const float* nu,
-                                  const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream) {
+// bytes of the minibatch stream of this call (records + statistics table), 0 with the reason as the last error where the stream does not serve it: the
+// shapes of the single-run wave-quad launches (prepare_train's kinds 4 and 5) and a workspace the kernel's 32-bit byte offsets reach
+extern "C" size_t icrl_ppo_stream_ws_bytes(const icrl_policy_t* pol, const icrl_buffer_t* buf, const icrl_ppo_hyper_t* hp) {
+  auto no = [](int) { return (size_t)0; };
+  if (pol->arch != nullptr || pol->h1 != HD || pol->h2 != HD)
+    return no(fail("icrl_ppo_stream_ws_bytes: hidden widths (%d, %d)%s: the minibatch stream serves the wave-quad update kernel (%d x %d, no `arch` descriptor)", pol->h1, pol->h2,
+                   pol->arch != nullptr ? " with an `arch` descriptor" : "", HD, HD));
+  if (pol->obs_dim < 1 || pol->obs_dim > 32 || pol->act_dim < 1 || pol->act_dim > 16)
+    return no(fail("icrl_ppo_stream_ws_bytes: obs_dim %d / act_dim %d: the minibatch stream serves the wave-quad update kernel (obs_dim 1..32, act_dim 1..16)", pol->obs_dim, pol->act_dim));
+  if (hp->batch_size < 2 || hp->batch_size > MAXB || hp->n_epochs < 1)
+    return no(fail("icrl_ppo_stream_ws_bytes: batch_size %d (2..%d), n_epochs %d (>= 1): the minibatch stream serves the persistent update kernels' minibatches", hp->batch_size, MAXB, hp->n_epochs));
+  if (hp->_pad & (2 | 4 | 16))
+    return no(fail("icrl_ppo_stream_ws_bytes: hp->_pad = %d asks for another update kernel; the minibatch stream serves the wave-quad kernel", hp->_pad));
+  if (buf->obs_dim != pol->obs_dim || buf->T < 1 || buf->N < 1 || buf->act_store < 1 || buf->act_store > 16 || (long long)buf->T * buf->N >= (1ll << 31))
+    return no(fail("icrl_ppo_stream_ws_bytes: buffer obs_dim %d vs policy %d, T = %d, N = %d, act_store = %d", buf->obs_dim, pol->obs_dim, buf->T, buf->N, buf->act_store));
+  const int n_total = buf->T * buf->N;
+  const long long n_mb = (n_total + hp->batch_size - 1) / hp->batch_size, n_steps = (long long)hp->n_epochs * n_mb;
+  const long long n_chunks = stream_n_chunks(n_total, hp->batch_size, hp->n_epochs);
+  const double approx = 4.0 * (double)(n_chunks + 1) * 64.0 * (double)(pol->obs_dim + buf->act_store + SR_PLANES);
+  if (n_steps >= (1ll << 21) || approx >= 4294967296.0 - 65536.0)
+    return no(fail("icrl_ppo_stream_ws_bytes: %lld optimiser steps, %.0f bytes of records: beyond the kernel's 32-bit byte offsets into the stream", n_steps, approx));
+  return stream_bytes(pol->obs_dim, buf->act_store, n_chunks, n_steps);
+}
+
+static int train_single(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
+                        const icrl_buffer_t* buf, const int32_t* perms, const float* nu,
+                        const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream_ws, long long stream_ws_bytes, void* stream) {
   TrainArgs a;
   hipStream_t s = (hipStream_t)stream;
   note_route(ICRL_FAMILY_UPDATE);
@@ -1055,8 +1079,16 @@ extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, floa
   const int kind = prepare_train(pol, exp_avg, exp_avg_sq, adam_step, buf, perms, nu, hp, stats, sync_ws, s, a, &err, 1);
   if (kind < 0) return err;
   const int nt1 = (pol->obs_dim + 15) / 16;
-  int packed = 0;
-  auto routed = [&](int e) { return routed_update(e, kind, 1, packed); };
+  int packed = 0, streamed = 0;
+  auto routed = [&](int e) { return routed_update(e, kind, 1, packed, streamed); };
+  if ((kind == 4 || kind == 5) && stream_ws != nullptr) {      // the minibatch stream, where the caller brought room for it
+    const size_t need = icrl_ppo_stream_ws_bytes(pol, buf, hp);
+    if (need == 0) icrl_clear_error();      // (not served: the in-kernel gather, silently — this entry point then IS icrl_ppo_lag_train)
+    else if (stream_ws_bytes >= (long long)need) {
+      if (const int e = launch_stream_prepass(a, stream_ws, s)) return e;
+      streamed = 1;
+    }
+  }
   if (kind == 4 || kind == 5) return routed(launch_train_halves(a, pol->discrete != 0, kind == 5 ? 4 : 2, s, &packed));
   if (kind == 6) return routed(launch_train_quarters_wide(a, pol->discrete != 0, s, &packed));
   if (kind == 7) return routed(launch_train_quarters_wide2(a, pol->discrete != 0, s, &packed));
@@ -1070,6 +1102,18 @@ extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, floa
   if (nt1 <= 2) return routed(launch_train<2, false>(a, s, &packed));
   if (nt1 <= 4) return routed(launch_train<4, false>(a, s, &packed));
   return routed(launch_train<8, false>(a, s, &packed));
+}
+
+extern "C" int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
+                                  const icrl_buffer_t* buf, const int32_t* perms, const float* nu,
+                                  const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream) {
+  return train_single(pol, exp_avg, exp_avg_sq, adam_step, buf, perms, nu, hp, stats, sync_ws, nullptr, 0, stream);
+}
+
+extern "C" int icrl_ppo_lag_train_stream(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
+                                         const icrl_buffer_t* buf, const int32_t* perms, const float* nu,
+                                         const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream_ws, long long stream_ws_bytes, void* stream) {
+  return train_single(pol, exp_avg, exp_avg_sq, adam_step, buf, perms, nu, hp, stats, sync_ws, stream_ws, stream_ws_bytes, stream);
 }
 
 extern "C" int icrl_ppo_lag_train_batch(int n_runs, const icrl_ppo_train_job_t* jobs, void* args_ws, long long args_ws_bytes,

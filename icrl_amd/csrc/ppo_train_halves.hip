@@ -89,9 +89,13 @@ __device__ __forceinline__ float* halves_smem() {
 
 // PROF (late round 6): the diagnostic phase timers (hp._pad & 1) are a compile-time variant — as a run-time flag their eight 64-bit accumulators and the
 // flag's lane mask sat in scalar registers across the step loop of EVERY launch (~100 instructions and 15 scalar reloads per step: 5.96 -> 5.81 us)
-template <int NT1, bool DISC, int OBS, bool BATCH, int NQ, bool PROF>
+// STREAM (single-run launches through icrl_ppo_lag_train_stream): the minibatches were gathered before the launch (ppo_stream.hip) — the step loop
+// reads one contiguous record per 16-row tile and the advantage statistics from a per-step table; no permutation, chunk plan or rollout-buffer pointer,
+// no index pipeline and no statistics gather is alive in it.  Everything behind the input side is the same code.
+template <int NT1, bool DISC, int OBS, bool BATCH, int NQ, bool PROF, bool STREAM = false>
 __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const TrainArgs* const ka, const int slot_j) {
 #define GPH(x) (BATCH ? as_global(x) : (x))
+  static_assert(!(STREAM && BATCH), "the stream serves single-run launches");
   using S = SmemH<NT1>;
   constexpr int SX = S::SX;
   static_assert(NT1 == 2, "one observation tile per weight-gradient wave half");
@@ -266,7 +270,52 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
     pact = p_act[off * (unsigned)AS + (unsigned)(gpart < AS ? gpart : AS - 1)];      // (the critics fetch the action bytes too: a load is cheaper than a branch here)
     psc = p_sc[off];
   };
+  // STREAM: stager thread (tile stile, slot sslot) owns ONE 16-byte word of its tile's record — four consecutive rows of one component — and that word's
+  // place in LDS; the words a role does not use (the other roles' scalars, the critics' actions) are not fetched
+  constexpr int OKC = OBS > 0 ? OBS : S::O16;      // observation components staged (OBS == 0: the pad columns repeat component O - 1, as the gather fills them)
+  const StreamRec srl{O, AS};
+  const int sslot = tid & 255, sr4 = tid & 3;
+  const bool s_stager = STREAM && (tid >> 8) < NJS;
+  const int stile = s_stager ? tid >> 8 : 0;
+  int skind = 3, ssrc = 0, sdst = 0;               // 0 observations (sdst relative to the X^T image), 1 actions, 2 per-row scalars, 3 nothing
+  if (STREAM) {
+    const int n_obs4 = 4 * OKC, n_act4 = role == 0 ? 4 * AS : 0, n_sc4 = role == 0 ? 12 : 8;
+    const int srow = 16 * stile + 4 * sr4;
+    if (sslot < n_obs4) {
+      const int k = sslot >> 2;
+      skind = 0; ssrc = srl.vec4(k < O ? k : O - 1, sr4); sdst = k * STH + srow;
+    } else if (sslot < n_obs4 + n_act4) {
+      const int c = (sslot - n_obs4) >> 2;
+      skind = 1; ssrc = srl.vec4(O + c, sr4); sdst = S::ACT + srow * SAH + pos_of(c);
+    } else if (sslot < n_obs4 + n_act4 + n_sc4) {
+      const int c = (sslot - n_obs4 - n_act4) >> 2;      // old log-prob | old value, reward advantage | return, cost advantage
+      const int plane = role == 0 ? SR_LOGP + c : (role == 1 ? SR_VAL_R + c : SR_VAL_C + c);
+      skind = 2; ssrc = srl.vec4(O + AS + plane, sr4); sdst = (c == 0 ? S::OLP : (c == 1 ? S::ADR : S::ADC)) + srow;
+    }
+  }
+  const unsigned rec_bytes = 4u * (unsigned)srl.floats();
+  const unsigned s_off = (unsigned)((HRQ / 16) * half + stile) * rec_bytes + 16u * (unsigned)ssrc;      // this thread's word inside a chunk's four records
+  const char* const p_srec = reinterpret_cast<const char*>(a.srec);
+  const f32x4* const p_sstat = reinterpret_cast<const f32x4*>(a.sstat);
+  f32x4 prow = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto issue_rec = [&](int g) {      // chunk g of the launch (unconditional, every thread: see the rules above)
+    prow = *reinterpret_cast<const f32x4*>(p_srec + ((unsigned)g * (4u * rec_bytes) + s_off));
+  };
+  auto ld_stat = [&](int i) -> f32x4 {
+    asm volatile("" : "+v"(i));
+    return p_sstat[i];
+  };
   auto commit_rows = [&](int xbase) {
+    if constexpr (STREAM) {
+      if (!s_stager) return;
+      if (skind == 0) *reinterpret_cast<f32x4*>(sm + xbase + sdst) = prow;
+      else if (skind == 2) *reinterpret_cast<f32x4*>(sm + sdst) = prow;
+      else if (skind == 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sm[sdst + i * SAH] = prow[i];
+      }
+      return;
+    }
     if (NQ == 4 && !stager) return;
 #pragma unroll
     for (int i = 0; i < XRL; ++i) { const int k = gpart + 16 * i; if (OBS > 0 ? k < OBS : k < S::O16) sm[xbase + k * STH + gb_row] = px[i]; }
@@ -281,27 +330,15 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
   };
   const bool big_mb = a.hp.batch_size > 128;
   auto stats_partials = [&](int nb) {      // (both halves: the statistics are the whole minibatch's, formed identically)
-    if (role != 0 || w < SW0 || w > SW0 + (big_mb ? 3 : 1)) return;
-    const bool in = stid < nb;
-    const float s_r = wave_sum_fast(in ? sar : 0.f), s_c = wave_sum_fast(in ? sac : 0.f), s_rr = wave_sum_fast(in ? sar * sar : 0.f);
+    if (STREAM || role != 0 || w < SW0 || w > SW0 + (big_mb ? 3 : 1)) return;      // (STREAM: the statistics come from the pre-pass's table)
+    float s_r, s_c, s_rr;
+    adv_wave_partials(stid < nb, sar, sac, s_r, s_c, s_rr);
     if (lane == 0) { sm[S::MISC + 3 * (w - SW0)] = s_r; sm[S::MISC + 3 * (w - SW0) + 1] = s_c; sm[S::MISC + 3 * (w - SW0) + 2] = s_rr; }
   };
   float mean_r = 0.f, istd_r = 1.f, mean_c = 0.f;
   auto read_stats = [&](int nb) {
-    if (role != 0) return;
-    float s_r = sm[S::MISC + 0] + sm[S::MISC + 3];
-    float s_c = sm[S::MISC + 1] + sm[S::MISC + 4];
-    float s_rr = sm[S::MISC + 2] + sm[S::MISC + 5];
-    if (big_mb) {
-      s_r += sm[S::MISC + 6] + sm[S::MISC + 9];
-      s_c += sm[S::MISC + 7] + sm[S::MISC + 10];
-      s_rr += sm[S::MISC + 8] + sm[S::MISC + 11];
-    }
-    const float inv = __builtin_amdgcn_rcpf((float)nb);
-    mean_r = s_r * inv;
-    mean_c = s_c * inv;
-    const float var = fmaxf(s_rr - s_r * mean_r, 0.f) * __builtin_amdgcn_rcpf((float)(nb - 1));
-    istd_r = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(var) + 1e-8f);
+    if (STREAM || role != 0) return;
+    adv_stats_from_partials(sm + S::MISC, big_mb, nb, mean_r, istd_r, mean_c);
   };
   auto refresh_gauss = [&]() {   // wave W_LS, lanes q == 0 own log_std r: derived constants of the Gaussian head
     if (!DISC && role == 0 && w == W_LS && q == 0) {
@@ -349,12 +386,23 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
 
   // ---- pipeline prologue
   int g_chunk = 0;
-  int idx_next = chunk_idx(ld_chunk(1)), idx_nx2 = chunk_idx(ld_chunk(2));
-  int2 pc_nx3 = ld_chunk(3);
-  issue_rows(chunk_idx(ld_chunk(0)));
+  int idx_next = 0, idx_nx2 = 0, sidx_next = 0;
+  int2 pc_nx3 = int2{0, 0};
+  f32x4 sv_next = f32x4{0.f, 1.f, 0.f, 0.f}, sv_nx2 = sv_next, sv_nx3 = sv_next;      // STREAM: the statistics table rides the step table's pipeline
+  if constexpr (STREAM) {
+    issue_rec(0);
+  } else {
+    idx_next = chunk_idx(ld_chunk(1)); idx_nx2 = chunk_idx(ld_chunk(2));
+    pc_nx3 = ld_chunk(3);
+    issue_rows(chunk_idx(ld_chunk(0)));
+  }
   int4 ps_next = ld_step(0), ps_nx2 = ld_step(1), ps_nx3 = ld_step(2);
-  issue_stats(stat_idx(ps_next));
-  int sidx_next = stat_idx(ps_nx2);
+  if constexpr (STREAM) {
+    sv_next = ld_stat(0); sv_nx2 = ld_stat(1); sv_nx3 = ld_stat(2);
+  } else {
+    issue_stats(stat_idx(ps_next));
+    sidx_next = stat_idx(ps_nx2);
+  }
   if (tid == 0) sm[S::MISC + 14] = run_on_one_xcd(xch0, slot_j, 3 * NQ, NQ == 4) ? 1.f : 0.f;
   __syncthreads();                      // initial weights visible (refresh_gauss reads log_std)
   const bool xcd_local = __builtin_amdgcn_readfirstlane(__float_as_int(sm[S::MISC + 14])) != 0;      // (as a compile-time constant: 5.88 -> 5.87 us per step, nothing)
@@ -402,10 +450,15 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
     ps_nx3 = ld_step(st + 3 < n_steps + 2 ? st + 3 : n_steps + 1);
     const int nb = ps.nb_flags & NB_MASK;
     const float inv_nb = __builtin_amdgcn_rcpf((float)nb);
-    const float c_mean_r = mean_r, c_mean_c = mean_c, c_istd_r = istd_r;
+    const float c_mean_r = STREAM ? sv_next[0] : mean_r, c_mean_c = STREAM ? sv_next[2] : mean_c, c_istd_r = STREAM ? sv_next[1] : istd_r;
     const float cpol_nb = inv_nb * __builtin_amdgcn_rcpf(1.f + nu);
-    issue_stats(sidx_next);
-    sidx_next = stat_idx(ps_nx2);
+    if constexpr (STREAM) {
+      sv_next = sv_nx2; sv_nx2 = sv_nx3;
+      sv_nx3 = ld_stat(st + 3 < n_steps + 2 ? st + 3 : n_steps + 1);
+    } else {
+      issue_stats(sidx_next);
+      sidx_next = stat_idx(ps_nx2);
+    }
     float mb_s0 = 0.f, mb_s1 = 0.f, mb_s2 = 0.f, mb_s3 = 0.f, mb_s4 = 0.f;
     const int xrole = ((int)(step & 1) * 3 + role) * NQ * HX_BLK;      // the NQ blocks of this role and step parity
     const int xmine = xrole + half * HX_BLK, xtheirs = xrole + (1 - half) * HX_BLK;      // (xtheirs: NQ == 2)
@@ -452,6 +505,7 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
         *reinterpret_cast<f32x4*>(sm + S::H1R + b * SRM + 16 * fq + 4 * q) = h1c;
       }
       auto prefetch_next = [&]() {  // the next chunk's rows (random pieces of the rollout buffer: several microseconds away)
+        if constexpr (STREAM) { issue_rec(g_chunk + 1); return; }      // (one contiguous 16-byte word per thread)
         const int idx_now = idx_next;
         idx_next = idx_nx2;
         idx_nx2 = chunk_idx(pc_nx3);
@@ -1052,12 +1106,12 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
   }
 }
 
-template <int NT1, bool DISC, int OBS, int NQ, bool PROF>
+template <int NT1, bool DISC, int OBS, int NQ, bool PROF, bool STREAM>
 __global__ void __launch_bounds__(THH) ppo_train_halves_kernel(TrainArgs a, int packed) {
   int run = 0, j = (int)blockIdx.x;
   if (packed && !packed_slot(3 * NQ, 1, run, j)) return;
   const TrainArgs* const ka = (const TrainArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  ppo_train_halves_body<NT1, DISC, OBS, false, NQ, PROF>(a, ka, j);
+  ppo_train_halves_body<NT1, DISC, OBS, false, NQ, PROF, STREAM>(a, ka, j);
 }
 
 // several independent runs in ONE launch: the packed 1-D grid of ppo_common.h (a run's workgroups on one XCD), or grid (3 NQ, n_runs)
@@ -1075,7 +1129,9 @@ static int launch_halves(const TrainArgs* one, const TrainArgs* d_args, int n_ru
   static_assert(SmemH<NT1>::TOTAL * sizeof(float) <= 160 * 1024, "LDS budget");
   if (one != nullptr) {
     TrainArgs arg = *one;
-    return launch_update_single(ppo_train_halves_kernel<NT1, DISC, OBS, NQ, PROF>, 3 * NQ, dim3(THH), 0, s, arg, packed);
+    if (arg.srec != nullptr)      // the minibatch stream was written in front of this launch (icrl_ppo_lag_train_stream)
+      return launch_update_single(ppo_train_halves_kernel<NT1, DISC, OBS, NQ, PROF, true>, 3 * NQ, dim3(THH), 0, s, arg, packed);
+    return launch_update_single(ppo_train_halves_kernel<NT1, DISC, OBS, NQ, PROF, false>, 3 * NQ, dim3(THH), 0, s, arg, packed);
   }
   const int pg = packed_grid(3 * NQ, n_runs);
   hipLaunchKernelGGL((ppo_train_halves_batch_kernel<NT1, DISC, OBS, NQ, PROF>), pg ? dim3(pg) : dim3(3 * NQ, n_runs), dim3(THH), 0, s, d_args, n_runs, pg ? 1 : 0);

@@ -25,6 +25,14 @@ from .structs import AgentT, HostStepT, MonitorT, PpoHyperT, p
 from .vec_env import HipSynthVecEnv, HostVecEnv, VecCostWrapper, VecEnv, VecNormalize, VecNormalizeWithCost
 
 
+# train(): the minibatches of all epochs are gathered in front of the persistent update launch (icrl_ppo_lag_train_stream, csrc/ppo_stream.hip) where the
+# library serves the shape and the records fit under the cap: ~124 B per row and epoch at HCWithPos — 0.17 GB for the 64-env x 2048-step x 10-epoch
+# update, 0.7 GB for a 256-env shard; beyond 1 GiB the update gathers in-kernel as before rather than hold that much device memory for a few per cent of
+# one phase.  ICRL_UPDATE_STREAM=0 keeps the in-kernel gather everywhere (A/B; read once).
+UPDATE_STREAM = os.environ.get("ICRL_UPDATE_STREAM", "1") != "0"
+UPDATE_STREAM_CAP_BYTES = 1 << 30
+
+
 def _const_fn(v):
     return v if callable(v) else (lambda _progress: v)
 
@@ -890,11 +898,38 @@ class PPOLagrangian:
         if getattr(self, "train_events", None) is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        _lib.check(_lib.lib().icrl_ppo_lag_train(b(job["ps"]), p(pol.exp_avg), p(pol.exp_avg_sq), p(ws["t"]), b(job["bs"]), p(job["perms"]), p(ws["nu"]),
-                                                 b(job["hp"]), p(ws["stats"]), p(ws["sync"]), _lib.current_stream()), "icrl_ppo_lag_train")
+        stream_ws = self._update_stream_ws(job)
+        if stream_ws is not None:
+            _lib.check(_lib.lib().icrl_ppo_lag_train_stream(b(job["ps"]), p(pol.exp_avg), p(pol.exp_avg_sq), p(ws["t"]), b(job["bs"]), p(job["perms"]), p(ws["nu"]),
+                                                            b(job["hp"]), p(ws["stats"]), p(ws["sync"]), p(stream_ws), stream_ws.numel(), _lib.current_stream()),
+                       "icrl_ppo_lag_train_stream")
+        else:
+            _lib.check(_lib.lib().icrl_ppo_lag_train(b(job["ps"]), p(pol.exp_avg), p(pol.exp_avg_sq), p(ws["t"]), b(job["bs"]), p(job["perms"]), p(ws["nu"]),
+                                                     b(job["hp"]), p(ws["stats"]), p(ws["sync"]), _lib.current_stream()), "icrl_ppo_lag_train")
         if ev is not None:
             ev[1].record()
         job["ev"] = ev
+
+    def _update_stream_ws(self, job):
+        """device bytes for the pre-gathered minibatch stream of this update (allocated once, kept in _train_ws), or None: the library does not
+        serve the shape, the records exceed UPDATE_STREAM_CAP_BYTES, the allocation failed, or ICRL_UPDATE_STREAM=0 — the in-kernel gather then."""
+        if not UPDATE_STREAM:
+            return None
+        ws, L = self._train_ws, _lib.lib()
+        need = int(L.icrl_ppo_stream_ws_bytes(_lib.byref(job["ps"]), _lib.byref(job["bs"]), _lib.byref(job["hp"])))
+        if need == 0:
+            L.icrl_clear_error()
+            return None
+        if need > UPDATE_STREAM_CAP_BYTES or need >= ws.get("stream_refused", need + 1):
+            return None
+        if ws.get("stream") is None or ws["stream"].numel() < need:
+            ws["stream"] = None
+            try:
+                ws["stream"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            except RuntimeError:                       # (out of device memory: this size is not asked for again)
+                ws["stream_refused"] = need
+                return None
+        return ws["stream"]
 
     def train_readback(self):
         """device tensor with everything _train_end reads back: [32 + n_epochs statistics | adam step | mean / sum of orig_costs |

@@ -242,7 +242,7 @@ typedef struct {
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* ABI version (major*100+minor). */
-int icrl_abi_version(void);   /* 107: icrl_debug_last_route; 106: icrl_explained_variance, icrl_gae_dual_ws_bytes + the status word of the GAE workspace; 105: icrl_buffer_add, icrl_is_weights, icrl_cn_loss_fwd_bwd; 104: the fine-grained update entry points (csrc/fine.hip); 103: icrl_debug_stream_ref; 102: icrl_policy_t.arch; 101: icrl_sample_episodes takes stream_row0 / total_rows; the *_batch entry points */
+int icrl_abi_version(void);   /* 107: icrl_debug_last_route (additive since, no bump: icrl_ppo_stream_ws_bytes, icrl_ppo_lag_train_stream, word [4] of the update route); 106: icrl_explained_variance, icrl_gae_dual_ws_bytes + the status word of the GAE workspace; 105: icrl_buffer_add, icrl_is_weights, icrl_cn_loss_fwd_bwd; 104: the fine-grained update entry points (csrc/fine.hip); 103: icrl_debug_stream_ref; 102: icrl_policy_t.arch; 101: icrl_sample_episodes takes stream_row0 / total_rows; the *_batch entry points */
 
 /* Every entry point returns a hipError_t.  When it is hipErrorInvalidValue because the arguments are outside what the
  * kernels were built for (env count, widths, batch size ...; the reference's Python raises ValueError / AssertionError with a
@@ -522,6 +522,23 @@ int icrl_rollout_collect(const icrl_env_t* env, const icrl_norm_t* nm, const icr
 int icrl_ppo_lag_train(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
                        const icrl_buffer_t* buf, const int32_t* perms, const float* nu, const icrl_ppo_hyper_t* hp,
                        float* stats, void* sync_ws, void* stream);
+/* icrl_ppo_lag_train with the minibatches gathered BEFORE the persistent launch (csrc/ppo_stream.hip): the permutations of all epochs
+ * are known up front, so two plain launches over the whole device write every minibatch, in step order, as one contiguous record per
+ * 16-row tile ([obs_dim + act_store + 7][16 rows] floats: observations, stored actions, old log-prob, reward / cost advantage, old
+ * reward value, reward return, old cost value, cost return; rows beyond a ragged chunk repeat the chunk's first row) and a table of
+ * {mean, 1 / (std + 1e-8), cost mean} of the advantages per optimiser step; the step loop then reads records instead of carrying an
+ * index pipeline, scattered 4-byte gathers and the statistics on every dependent step.  Same values, same order of every sum: results
+ * are bit-identical to icrl_ppo_lag_train.
+ *   icrl_ppo_stream_ws_bytes: bytes of records + table for this call (host arithmetic, no launch); 0 with the reason in icrl_last_error()
+ *     where the stream does not serve the call.  Served: what runs as a single-run wave-quad launch (obs_dim <= 32, hidden 64 x 64 without
+ *     `arch`, batch_size 2..256, no kernel override in hp->_pad bits 1, 2, 4) whose records stay below 4 GiB.
+ *   icrl_ppo_lag_train_stream: with stream_ws (device, 256-byte aligned, any contents) of at least that many bytes and a served call, the
+ *     pre-pass on `stream` followed by the STREAM instantiation of the wave-quad kernel; otherwise (NULL, too small, not served) exactly
+ *     icrl_ppo_lag_train — same kernels, same results.  Word [4] of the update family's route record says which. */
+size_t icrl_ppo_stream_ws_bytes(const icrl_policy_t* pol, const icrl_buffer_t* buf, const icrl_ppo_hyper_t* hp);
+int icrl_ppo_lag_train_stream(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step,
+                              const icrl_buffer_t* buf, const int32_t* perms, const float* nu, const icrl_ppo_hyper_t* hp,
+                              float* stats, void* sync_ws, void* stream_ws, long long stream_ws_bytes, void* stream);
 /* the `row_floats` argument of ICRL_PPO_GENERIC_BYTES for this policy (host arithmetic, no launch), or -1 with the reason in
  * icrl_last_error() when the generic-shape path does not serve its architecture */
 int icrl_ppo_generic_row_floats(const icrl_policy_t* pol);
@@ -709,7 +726,8 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
  *         tiles, 4 wave quads with two workgroups per network, 5 with four, 6 / 7 four workgroups per network at obs 65..128),
  *         ICRL_UPDATE_GENERIC_PERSISTENT, ICRL_UPDATE_GENERIC_LAUNCHES
  *     [1] workgroups per network (ICRL_UPDATE_GENERIC_PERSISTENT: of the whole grid)   [2] n_runs   [3] 1 packed XCD grid | 0 run-major
- *   ICRL_FAMILY_GAE      icrl_gae_dual[_ex | _ws | _batch] (a rollout with do_gae bit 0 ends in one of them):
+ *     [4] 1 the step loop read the pre-gathered minibatch stream (icrl_ppo_lag_train_stream) | 0 it gathered its rows itself
+ *   ICRL_FAMILY_GAE     icrl_gae_dual[_ex | _ws | _batch] (a rollout with do_gae bit 0 ends in one of them):
  *     [0] ICRL_GAE_*   [1] the sequential kernel's shape code (4, 16, 101, 105..112), else the workgroups per tile C   [2] column tiles
  *     [3] n_runs */
 #define ICRL_FAMILY_ROLLOUT 0
