@@ -985,21 +985,38 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
     }
     lds_barrier();   // (S6) norm partials, next minibatch and its statistics visible
     STAMP(5)   // staging + granule wait
+    // every LDS word this segment consumes — the 24 norm partials, the flags, the advantage-statistics partials, the wave's master weights and its bias-group
+    // entries — is requested in ONE batch directly behind the barrier: left to itself the compiler emits read -> lgkmcnt(0) -> use for each of them (16 full waits
+    // in this segment), on the chain every wave of every workgroup sits on: the clip coefficient, and so all of Adam, waits for the total.  No predicates: the
+    // words a critic or a kh = 1 wave does not use are valid addresses, and the batch stays one basic block (with the `lowk` branch inside it: 5.71-5.78 against
+    // 5.69-5.72 us per step, parent 5.78-5.81).  Nothing is fetched BEFORE the barrier, no register is alive across the poll (that was ADAM_PRELOAD).
+    // Same values, same arithmetic, same order (profiles/update_lds_batch.md)
+    f32x4 nn_[6];
+#pragma unroll
+    for (int g = 0; g < 6; ++g) nn_[g] = lds128(sm + S::MISC + 24 + 4 * g);
+    const float fl_stop = sm[S::MISC + 12], fl_tmo = sm[S::MISC + 13];      // (the two words alone: a 16-byte read's dead half collides with the next fetch's registers)
+    f32x4 sp_[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    if (!STREAM) {
+#pragma unroll
+      for (int g = 0; g < 3; ++g) sp_[g] = lds128(sm + S::MISC + 4 * g);
+    }
+    f32x4 pW1 = load_own_w1(), pW2[2] = {load_own_w2(0), load_own_w2(1)}, pWh = load_own_wh(), pbg = f32x4{sm[S::B1 + jb], sm[S::B2 + jb], sm[ex_s], 0.f};
+    __builtin_amdgcn_sched_barrier(0);
     float total = 0.f;
     {
 #pragma unroll
-      for (int g = 0; g < 6; ++g) {     // fixed order: every wave of every role and half forms the same total
-        const f32x4 n = lds128(sm + S::MISC + 24 + 4 * g);
-        total += (n[0] + n[1]) + (n[2] + n[3]);
-      }
-      const f32x4 fl = lds128(sm + S::MISC + 12);
-      stop = fl[0] != 0.f;
-      if (fl[1] != 0.f) { status = 1; stop = true; }
+      for (int g = 0; g < 6; ++g)       // fixed order: every wave of every role and half forms the same total
+        total += (nn_[g][0] + nn_[g][1]) + (nn_[g][2] + nn_[g][3]);
+      stop = fl_stop != 0.f;
+      if (fl_tmo != 0.f) { status = 1; stop = true; }
     }
     total = __builtin_amdgcn_sqrtf(total);
     float coef = max_grad_norm * __builtin_amdgcn_rcpf(total + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
-    read_stats(nb_next > 0 ? nb_next : 2);
+    if (!STREAM && role == 0) {      // (read_stats on the prefetched partials)
+      const float part[12] = {sp_[0][0], sp_[0][1], sp_[0][2], sp_[0][3], sp_[1][0], sp_[1][1], sp_[1][2], sp_[1][3], sp_[2][0], sp_[2][1], sp_[2][2], sp_[2][3]};
+      adv_stats_from_partials(part, big_mb, nb_next > 0 ? nb_next : 2, mean_r, istd_r, mean_c);
+    }
 
     // ================= Adam (torch.optim.Adam, single-tensor form) on the wave's own elements =================
     {
@@ -1022,18 +1039,18 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
         for (int i = 0; i < 4; ++i) p[i] = fmaf(-step_size, m[i] * __builtin_amdgcn_rcpf(d[i]), p[i]);
       };
       // pad elements (k >= obs, o >= n_out) have g = m = v = p = 0 and stay 0: no masks needed
-      { f32x4 p_ = load_own_w1(); adam4(gW1r, mW1, vW1, p_); store_w1(p_); }
+      { adam4(gW1r, mW1, vW1, pW1); store_w1(pW1); }
       if (lowk) {
-        f32x4 g_ = f32x4{gb1r, gb2r, ex_g >= 0 ? gex : 0.f, 0.f}, p_ = f32x4{sm[S::B1 + jb], sm[S::B2 + jb], sm[ex_s], 0.f};
+        f32x4 g_ = f32x4{gb1r, gb2r, ex_g >= 0 ? gex : 0.f, 0.f}, p_ = pbg;
         f32x4 m_ = f32x4{mb1, mb2, mex, 0.f}, v_ = f32x4{vb1, vb2, vex, 0.f};
         adam4(g_, m_, v_, p_);      // identical arithmetic in the four q lanes, lane q == 0 stores
         mb1 = m_[0]; mb2 = m_[1]; mex = m_[2]; vb1 = v_[0]; vb2 = v_[1]; vex = v_[2];
         if (q == 0) { sm[S::B1 + jb] = p_[0]; sm[S::B2 + jb] = p_[1]; sm[ex_s] = p_[2]; }
       }
 #pragma unroll
-      for (int cc = 0; cc < 2; ++cc) { f32x4 p_ = load_own_w2(cc); adam4(gW2r[cc], mW2[cc], vW2[cc], p_); store_w2(cc, p_); }
+      for (int cc = 0; cc < 2; ++cc) { adam4(gW2r[cc], mW2[cc], vW2[cc], pW2[cc]); store_w2(cc, pW2[cc]); }
       if (lowk) {
-        { f32x4 p_ = load_own_wh(); adam4(gWhr, mWh, vWh, p_); store_wh(p_); }
+        { adam4(gWhr, mWh, vWh, pWh); store_wh(pWh); }
         __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the log_std store has landed before refresh_gauss re-reads it
         refresh_gauss();
       }
