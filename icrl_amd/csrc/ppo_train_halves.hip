@@ -962,6 +962,14 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
     // in front of the partial-gradient sums it queues in front of the partners' blocks and measured slower: DESIGN 5, NORM_LOOK_EARLY)
     u64 v_first = 0;
     if (poller) v_first = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the clip threshold is requested HERE, behind the first look's issue, and held in a scalar register across (S6): its trip runs under the staging.  Left to
+    // itself the compiler re-reads it from the argument block by an `s_load_dword` behind the square root of the total, and with a scalar load in the basic block
+    // of the (S6) batch the wait that ends the batch is a full `lgkmcnt(0)` — all 14 fetches — where it now is `lgkmcnt(8)`: the total is formed as soon as the
+    // six fetches of the partials are in, and Adam's waits are counted ones too (5.62-5.65 -> 5.53-5.57 us per step; requested directly in front of the barrier
+    // the load shares the batch's block again and nothing moves: profiles/update_norm_hop.md)
+    // (the minibatch-stream instantiations only: the in-kernel-gather lines of the coarse check, configs[3] whole and its shard, came out 2.5 % slower with it)
+    float clip_norm = max_grad_norm;
+    if constexpr (STREAM) asm volatile("" : "+s"(clip_norm));
     if (!STAGE_HOP) {
       commit_rows(xnext);
       stats_partials(nb_next);
@@ -989,7 +997,8 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
     // entries — is requested in ONE batch directly behind the barrier: left to itself the compiler emits read -> lgkmcnt(0) -> use for each of them (16 full waits
     // in this segment), on the chain every wave of every workgroup sits on: the clip coefficient, and so all of Adam, waits for the total.  No predicates: the
     // words a critic or a kh = 1 wave does not use are valid addresses, and the batch stays one basic block (with the `lowk` branch inside it: 5.71-5.78 against
-    // 5.69-5.72 us per step, parent 5.78-5.81).  Nothing is fetched BEFORE the barrier, no register is alive across the poll (that was ADAM_PRELOAD).
+    // 5.69-5.72 us per step, parent 5.78-5.81).  Nothing is fetched from LDS BEFORE the barrier, no vector register is alive across the poll (that was ADAM_PRELOAD, DESIGN 5;
+    // the one scalar that is: clip_norm above).
     // Same values, same arithmetic, same order (profiles/update_lds_batch.md)
     f32x4 nn_[6];
 #pragma unroll
@@ -1011,7 +1020,7 @@ __device__ __forceinline__ void ppo_train_halves_body(const TrainArgs& a, const 
       if (fl_tmo != 0.f) { status = 1; stop = true; }
     }
     total = __builtin_amdgcn_sqrtf(total);
-    float coef = max_grad_norm * __builtin_amdgcn_rcpf(total + 1e-6f);
+    float coef = clip_norm * __builtin_amdgcn_rcpf(total + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
     if (!STREAM && role == 0) {      // (read_stats on the prefetched partials)
       const float part[12] = {sp_[0][0], sp_[0][1], sp_[0][2], sp_[0][3], sp_[1][0], sp_[1][1], sp_[1][2], sp_[1][3], sp_[2][0], sp_[2][1], sp_[2][2], sp_[2][3]};
