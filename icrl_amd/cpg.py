@@ -37,6 +37,9 @@ class _History(callbacks.BaseCallback):
         for k in ("rollout/adjusted_reward", "eval/true_cost", "eval/mean_reward", "eval/best_mean_reward"):
             if k in lg:
                 rec[k] = float(lg[k])
+        for k in lg:      # (present with -ucde / -uls only: icrl_amd/exploration.py)
+            if k.startswith("exploration/"):
+                rec[k] = float(lg[k])
         self.history.append(rec)
         if self.log:
             self.log(json.dumps(rec))
@@ -47,6 +50,10 @@ def setup(config, log=print):
     learn() calls on the result; cpg() below is setup + one learn()."""
     logger.configure()          # a fresh scalar log per run (the reference configures its logger in learn())
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
+    use_curiosity, use_lambda = bool(getattr(config, "use_curiosity_driven_exploration", False)), bool(getattr(config, "use_lambda_shaping", False))
+    if use_curiosity or use_lambda:      # ref: icrl/cpg.py:176-184; refused before anything is launched where the callbacks are not served
+        from . import exploration
+        exploration.refuse_batched(config)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
     envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=True,
@@ -61,6 +68,10 @@ def setup(config, log=print):
     is_discrete = isinstance(train_env.action_space, spaces.Discrete)
     obs_dim = train_env.observation_space.shape[0]
     acs_dim = train_env.action_space.n if is_discrete else train_env.action_space.shape[0]
+    if is_discrete and (use_curiosity or use_lambda):
+        flag = "--use_curiosity_driven_exploration (-ucde)" if use_curiosity else "--use_lambda_shaping (-uls)"
+        raise ValueError(f"{flag}: a Box action space is needed; {config.train_env_id} has a discrete one (the buffer stores a discrete action as "
+                         "one index column, which the reference reshapes to acs_dim columns: not a meaningful network input)")
     if config.use_null_cost:
         cost_function = AnalyticCost.null()
     elif config.cn_path is None:
@@ -114,7 +125,12 @@ def setup(config, log=print):
                                   # opt-in (a seed batch sets it): evaluation noise from the run's own streams, not the process-wide generator
                                   noise_streams=getattr(config, "streams", None) if getattr(config, "eval_noise_from_streams", False) else None,
                                   callback_on_new_best=callbacks.SaveEnvStatsCallback(train_env, config.save_dir if rank == 0 else None)),
-           callbacks.AdjustedRewardCallback(true_cost_for(config.eval_env_id)), hist]
+           callbacks.AdjustedRewardCallback(true_cost_for(config.eval_env_id))]
+    if use_curiosity:      # ref: icrl/cpg.py:176-184 — after AdjustedRewardCallback, exploration before lambda
+        cbs.append(exploration.ExplorationRewardCallback(obs_dim, acs_dim, device=dev))
+    if use_lambda:
+        cbs.append(exploration.LambdaShapingCallback(obs_dim, acs_dim, device=dev))
+    cbs.append(hist)
     if config.save_dir and rank == 0:
         cbs.insert(0, callbacks.CheckpointCallback(int(config.save_every), os.path.join(config.save_dir, "models"), verbose=0))
     if world > 1 or getattr(config, "force_collective", False):      # env shards (BASELINE configs[4]: 4096 envs over 8 GPUs): one all-reduce per rollout + update

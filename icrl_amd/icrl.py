@@ -5,7 +5,8 @@ ref: icrl/icrl.py:45-312 (icrl), :314-464 (main / flag set).  Per outer iteratio
   sample    sync_envs_normalization + sample_from_agent on a 1-env copy        (icrl.py:216-218)
   backward  constraint_net.train(...)                                          (icrl.py:235)  -> icrl_cn_train
   metrics   true cost, evaluate_policy (10 episodes), forward / reverse KL     (icrl.py:243-252)
-Out of scope: W&B, plotting, video, curiosity / shaping callbacks, the GAIL baseline.
+`-ucde` hands the forward learn() an ExplorationRewardCallback (icrl.py:180-183, 210 -> icrl_amd/exploration.py), not the warm-up.
+Out of scope: W&B, plotting, video.
 """
 import argparse
 import json
@@ -28,6 +29,10 @@ from . import envs, spaces
 def setup(config):
     """everything of icrl() before the loop (ref: icrl/icrl.py:45-197): env stacks, expert data, constraint net, nominal agent."""
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
+    use_curiosity = bool(getattr(config, "use_curiosity_driven_exploration", False))
+    if use_curiosity:      # refused before anything is launched where the callback is not served
+        from . import exploration
+        exploration.refuse_batched(config)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
     envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=True,
@@ -47,6 +52,9 @@ def setup(config):
     action_low, action_high = None, None
     if isinstance(sampling_env.action_space, spaces.Box):
         action_low, action_high = sampling_env.action_space.low, sampling_env.action_space.high
+    if use_curiosity and is_discrete:
+        raise ValueError(f"--use_curiosity_driven_exploration (-ucde): a Box action space is needed; {config.train_env_id} has a discrete one (the buffer "
+                         "stores a discrete action as one index column, which the reference reshapes to acs_dim columns: not a meaningful network input)")
 
     (expert_obs, expert_acs), expert_mean_reward = utils.load_expert_data(config.expert_path, config.expert_rollouts)
     expert_agent = None
@@ -93,6 +101,8 @@ def setup(config):
               d_expert_acs=torch.as_tensor(np.asarray(expert_acs), device=dev),
               timesteps=0., start_time=time.time(),
               best=dict(reward=-np.inf, cost=np.inf, fkl=np.inf, rkl=np.inf))
+    if use_curiosity:      # ref: icrl/icrl.py:180-183 — handed to the forward learn() only, not to the warm-up (:190, :207-211)
+        st["exploration_callback"] = exploration.ExplorationRewardCallback(obs_dim, acs_dim, device=dev)
     if world > 1 or getattr(config, "force_collective", False):     # common history of the running moments for the exact cross-rank merge: the (identical) initial state
         st["rms_list"] = [train_env.obs_rms, train_env.ret_rms, train_env.cost_rms]
         st["rms_prev"] = [D.moments_to_sums(r.mean, r.var, r.count) for r in st["rms_list"]]
@@ -139,7 +149,7 @@ def outer_iteration(st, itr):
     nominal_agent = st["agent"]
     current_progress_remaining = 1 - float(itr) / float(config.n_iters)
     # ---- forward step
-    nominal_agent.learn(total_timesteps=config.forward_timesteps, cost_function="cost")
+    nominal_agent.learn(total_timesteps=config.forward_timesteps, cost_function="cost", callback=st.get("exploration_callback"))
     forward_metrics = dict(logger.Logger.CURRENT.name_to_value)
     st["timesteps"] += nominal_agent.num_timesteps
     # ---- nominal trajectories

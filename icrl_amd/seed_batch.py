@@ -29,7 +29,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, logger, utils
+from . import _lib, exploration, logger, utils
 from .streams import PrivateStreams
 from .structs import CnTrainJobT, CostFnT, MonitorT, PpoTrainJobT, RolloutJobT, SampleJobT, addr, p
 from .true_constraint_net import mean_cost
@@ -136,6 +136,10 @@ class SeedBatch:
     per_run_wide_updates = False
 
     def __init__(self, configs=None, states=None, on_setup=None):
+        if states is None:      # refused before anything is set up
+            configs = list(configs)
+            for c in configs:
+                exploration.refuse_batched(c, seed_batch=True)
         self.states = setup_runs(configs, on_setup) if states is None else states
         if any(isinstance(st["train_env"].unwrapped, HostVecEnv) for st in self.states):
             _refuse_host_envs(*[st["config"].train_env_id for st in self.states])
@@ -548,6 +552,8 @@ class CpgSeedBatch(SeedBatch):
         if not configs:
             raise ValueError("seed batch: no runs")
         c0 = configs[0]
+        for c in configs:
+            exploration.refuse_batched(c, seed_batch=True)
         if os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") not in ("", "0"):
             raise ValueError("seed batch: ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step rollout loop, which has no batched form")
         for c in configs:

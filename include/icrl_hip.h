@@ -865,6 +865,33 @@ size_t icrl_cost_mlp_fwd_bwd_ws_bytes(const icrl_costnet_t* cn, int N);
 int icrl_cost_mlp_fwd_bwd(const icrl_costnet_t* cn, const float* x, int N, const float* d_zeta, float* zeta, float* grad, void* ws,
                           long long ws_bytes, void* stream);
 
+/* One full-batch regression step of MLP(in -> h1 -> ReLU -> h2 -> ReLU -> out), the reference's create_mlp(in, out, [h1, h2]) with no
+ * output squashing: the rollout-end step of the exploration callbacks (icrl/exploration.py:50-67, 227-261; csrc/reg_mlp.hip).
+ * params / exp_avg / exp_avg_sq: flat float32 buffers of EXACTLY n_params = h1 (in + 1) + h2 (h1 + 1) + out (h2 + 1) entries in torch's
+ * state_dict order, row-major: W1 [h1, in], b1, W2 [h2, h1], b2, W3 [out, h2], b3.  Inputs: xa [rows, in_a] and xb [rows, in_b], row-major,
+ * read as ONE concatenated row of in = in_a + in_b values (the buffer's observations and actions planes in their time-major row
+ * order; xa may be NULL when in_a == 0); target [rows, out].  Per call, on the parameters as they are:
+ *   e = (MLP(x) - target)^2 per element; row_err[r] = sum_j e[r, j] (float32 [rows]; may be NULL);
+ *   loss = mean over rows x out of e = MSELoss(reduction='none').mean(); backward of loss; one torch.optim.Adam step (lr, beta1,
+ *   beta2, eps as the doubles torch holds; no weight decay, no clipping; bias corrections in double from *adam_step + 1, which is then incremented on the device);
+ *   out4 (device) = {loss, mean(row_err), population std(row_err) as np.std, 0}, all from the PRE-step predictions.
+ * Arithmetic: the forward pass, the errors and their row sums in float64 on the matrix cores (v_mfma_f64_16x16x4_f64 on the float32
+ * parameters and inputs): row_err, the loss and the statistics are the float64 values rounded once.  The backward products of a 32-row
+ * group are float32 tiles (v_mfma_f32_16x16x4_f32, exact float32) of the float32 roundings of errors and activations; their sums over
+ * groups and workgroups, and the bias sums, are float64, rounded once.  Layers are zero-padded to the 16 x 4 granule in LDS and
+ * registers only.  Three plain launches, no cooperative launch, no waits between workgroups, no atomics; the grid is
+ * min(ceil(rows / 32), 256) workgroups and every sum has a fixed order: the same call from the same state gives the same bits.
+ * Served: 1 <= h1, h2 <= 64, 0 <= in_a <= 128, 1 <= in_b <= 16, 1 <= out <= 128, 1 <= rows <= 2^21.  Everything else, a NULL required
+ * pointer and a ws below icrl_reg_mlp_ws_bytes(...) (0 + a reason for a refused shape) return hipErrorInvalidValue with the reason,
+ * before any device call.  Allocates nothing, does not synchronise. */
+size_t icrl_reg_mlp_ws_bytes(long long rows, int in_a, int in_b, int h1, int h2, int out);
+int icrl_reg_mlp_step(float* params, float* exp_avg, float* exp_avg_sq, int32_t* adam_step, const float* xa, const float* xb,
+                      const float* target, long long rows, int in_a, int in_b, int h1, int h2, int out, double lr, double beta1,
+                      double beta2, double eps, float* row_err, float* out4, void* ws, long long ws_bytes, void* stream);
+/* LambdaShapingCallback's `cost_advantages /= (1 + exploration_reward)` (icrl/exploration.py:311): adv[r] = adv[r] / (1.0f + row_err[r]),
+ * a correctly rounded float32 division, bit for bit numpy's; rows >= 1. */
+int icrl_shape_advantages(float* adv, const float* row_err, long long rows, void* stream);
+
 /* Diagnostic (bench.py `roofline.copy_gbs`; no reference counterpart): the memory traffic of the streaming dual-GAE launch without
  * its recurrence.  mode 0: grid, access pattern and bytes of icrl_gae_dual at N >= 131 072 (five [T,N] float arrays read, four written,
  * 16-byte non-temporal accesses, one wave per 256 columns walking the rows downwards); mode 1: in0..in3 copied to out0..out3 by
