@@ -35,14 +35,19 @@ G13_WIDTHS = dict(policy_net=(32, 48), value_net=(64, 32), cost_value_net=(16, 6
 POLICY_SHAPES = OrderedDict(hc=(18, 6, False, (64, 64)), ant=(113, 8, False, (64, 64)), point=(9, 2, False, (64, 64)), lgw=(1, 2, True, (64, 64)),
                             g13=(18, 6, False, G13_WIDTHS))
 POLICY_ROWS = (1, 15, 16, 17, 64, 100, 257)             # the row-tile edge (16), a ragged last tile, more than one workgroup
-POLICY_CASES = [(s, n) for s in ("hc", "ant", "point", "lgw") for n in POLICY_ROWS] + [("g13", 100)]
+# past the grid cap of mlp_fwd_bwd_kernel (16-row tiles on min(tiles, 64) workgroups; weight gradients stay in registers across a workgroup's
+# tiles): 1025 rows = 65 tiles, workgroup 0 alone walks a second one, which holds one live row; 2064 rows = 129 tiles, workgroup 0 walks three,
+# the others two; 65536 rows = the served maximum, 64 tiles per workgroup
+POLICY_ROWS_WALK = (1025, 2064)
+POLICY_CASES = ([(s, n) for s in ("hc", "ant", "point", "lgw") for n in POLICY_ROWS] + [("g13", 100)]
+                + [(s, n) for s in ("hc", "ant") for n in POLICY_ROWS_WALK] + [("lgw", 1025), ("hc", 65536)])
 # name -> obs_dim, acs_dim, hidden, obs_select_dim, acs_select_dim.  "point": the Point fixture's selection (-cosd 0 1 -casd -1)
 COST_SHAPES = OrderedDict(h20=(18, 6, (20,), None, None), h64=(18, 6, (64, 64), None, None), ant=(113, 8, (40, 40), None, None),
                           point=(9, 2, (40, 40), (0, 1), (-1,)))
 COST_ROWS = (1, 63, 64, 65, 257)
-COST_CASES = [(s, n) for s in COST_SHAPES for n in COST_ROWS]
+COST_CASES = [(s, n) for s in COST_SHAPES for n in COST_ROWS] + [(s, n) for s in ("h20", "ant") for n in POLICY_ROWS_WALK]      # h20: sdz1 = sdz
 RELU_MARGIN = 1e-5
-COST_SEED = {("ant", 257): 2}                           # every other case: seed 0 (min |z| asserted in cost_case)
+COST_SEED = {("ant", 257): 2, ("ant", 1025): 3, ("ant", 2064): 18}      # every other case: seed 0 (min |z| asserted in cost_case)
 OUT_TOL = dict(v_r=(1e-5, 2e-6), v_c=(1e-5, 2e-6), zeta=(1e-5, 2e-6), log_prob=(1e-5, 2e-5), entropy=(1e-5, 2e-5))      # rtol, atol: the fp32-MLP tolerance
 GRAD_UNITS = 4.0
 
@@ -314,6 +319,12 @@ DEV32 = {
     'lgw-100': [1.06e-06, 7.54e-07, 7.14e-07, 4.23e-07, 3.39e-06, 9.73e-07, 1.33e-06, 7.1e-07, 9e-07, 1.3e-06, 4.64e-07, 5.51e-07, 3.68e-06, 8.6e-07, 2.65e-06, 1.26e-06, 1.25e-06, 6.49e-07],
     'lgw-257': [1.46e-06, 2.13e-06, 1.13e-06, 6.91e-07, 1.15e-06, 2.12e-06, 6.24e-07, 1.04e-06, 2.54e-06, 2.63e-06, 7.38e-07, 7.21e-07, 3.84e-06, 2.37e-06, 1.72e-06, 9.13e-07, 2.21e-06, 7.54e-07],
     'g13-100': [7.71e-06, 7.83e-06, 6.83e-06, 5.75e-06, 3.32e-06, 1.55e-06, 7.14e-07, 1.98e-06, 1.01e-06, 1.27e-06, 5.44e-07, 2.6e-06, 6.37e-07, 3.54e-05, 2.13e-05, 1.88e-06, 1.66e-06, 5.59e-06, 1.11e-06],
+    'hc-1025': [8.51e-05, 4.71e-05, 1.76e-05, 2.9e-05, 1.47e-05, 4.65e-06, 2.89e-06, 5.12e-06, 3.14e-06, 6.43e-06, 2.41e-06, 5.84e-06, 2.23e-06, 8.04e-05, 1.95e-05, 1.29e-05, 9.09e-07, 1.44e-05, 3.21e-06],
+    'hc-2064': [4.89e-05, 5.85e-05, 2.14e-05, 3.95e-05, 1.82e-05, 8.82e-06, 2.95e-06, 8.82e-06, 3.23e-06, 1.05e-05, 2.96e-06, 6.97e-06, 3.78e-06, 0.000207, 3.16e-05, 2.35e-05, 3.02e-06, 1.83e-05, 2.98e-06],
+    'ant-1025': [0.000477, 0.000135, 2.96e-05, 7.47e-05, 4.17e-05, 5.33e-06, 2.46e-06, 6.43e-06, 2.33e-06, 7.32e-06, 2.33e-06, 9.36e-06, 3.14e-06, 0.000313, 4.93e-05, 1.67e-05, 2.03e-07, 1.24e-05, 1.55e-06],
+    'ant-2064': [0.000169, 0.000129, 4.1e-05, 9.37e-05, 3.44e-05, 8.19e-06, 3.14e-06, 1.2e-05, 2.98e-06, 1.21e-05, 3.63e-06, 1.24e-05, 3.19e-06, 0.000575, 0.00015, 2.29e-05, 1.16e-07, 1.8e-05, 8.86e-06],
+    'lgw-1025': [2.04e-06, 2.55e-06, 1.18e-06, 1.24e-06, 2.43e-06, 3.72e-06, 2.12e-06, 2.54e-06, 3.59e-06, 3.74e-06, 2.55e-06, 1.62e-06, 4.87e-06, 4.1e-06, 7.4e-06, 6.65e-06, 5.42e-06, 5.69e-06],
+    'hc-65536': [0.000845, 0.000307, 0.000191, 0.000253, 0.000101, 4.93e-05, 2.11e-05, 4.14e-05, 1.23e-05, 5.39e-05, 2.84e-05, 5.09e-05, 1.89e-05, 0.00121, 0.000262, 0.000571, 2.2e-05, 0.000448, 8.47e-06],
     'cost-h20-1': [3.22e-08, 5.11e-09, 8.86e-08, 1.7e-08],
     'cost-h20-63': [1.85e-07, 4.33e-08, 5.14e-07, 4.17e-09],
     'cost-h20-64': [1.74e-07, 3.19e-08, 9.02e-07, 3.99e-07],
@@ -334,6 +345,10 @@ DEV32 = {
     'cost-point-64': [4.64e-08, 9.65e-09, 5.1e-08, 1.91e-08, 4.8e-07, 8.35e-08],
     'cost-point-65': [2.05e-08, 1.88e-08, 8.6e-08, 3.71e-08, 2.77e-07, 5.87e-07],
     'cost-point-257': [2.37e-07, 2.59e-08, 6e-07, 1.03e-07, 6.63e-07, 7.95e-08],
+    'cost-h20-1025': [1.14e-06, 1.53e-07, 1.9e-06, 3e-07],
+    'cost-h20-2064': [2.01e-06, 3.12e-07, 4.01e-06, 1.39e-06],
+    'cost-ant-1025': [5.5e-07, 1.21e-07, 6.43e-07, 1.53e-07, 2.71e-06, 2.64e-07],
+    'cost-ant-2064': [9.24e-07, 9.6e-08, 1.02e-06, 2.9e-07, 3.69e-06, 1.37e-06],
     'loss-policy': [1.97e-05, 1.28e-05, 5.84e-06, 1.31e-05, 3.96e-06, 2.22e-08, 1.18e-08, 2.21e-08, 1.39e-08, 5.94e-09, 1.58e-09, 4.05e-09, 2.72e-09, 3.26e-05, 3.98e-06, 7.16e-08, 3.73e-08, 8.47e-09, 2.38e-09],
     'loss-zeta': [2.42e-09, 9.37e-10, 8.61e-09, 5.61e-09, 4.79e-08, 4.26e-08],
 }
@@ -357,6 +372,10 @@ DEV32 = {
 # cost-point-64: seed 0, min |z| = 0.000258
 # cost-point-65: seed 0, min |z| = 0.000258
 # cost-point-257: seed 0, min |z| = 9.38e-05
+# cost-h20-1025: seed 0, min |z| = 5.47e-05
+# cost-h20-2064: seed 0, min |z| = 4.21e-05
+# cost-ant-1025: seed 3, min |z| = 1.01e-05
+# cost-ant-2064: seed 18, min |z| = 1.07e-05
 # DEV32_END
 
 

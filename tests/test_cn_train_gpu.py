@@ -99,11 +99,16 @@ def test_policy_evaluate_actions(golden):
     assert np.allclose(ent.cpu().numpy(), oent.numpy(), rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("kind,n", [("hc", 257), ("hc", 1000), ("ant", 333), ("narrow", 100)])
+ROWS_GRID_CAP = 1024 * 16      # policy_rows_kernel: 16-row tiles on min(tiles, 1024) workgroups; row 16384 opens a workgroup's second tile
+
+
+@pytest.mark.parametrize("kind,n", [("hc", 257), ("hc", 1000), ("ant", 333), ("narrow", 100), ("hc", 16385), ("ant", 16400)])
 def test_policy_rows_kernel_equals_one_workgroup_per_row(kind, n):
     """icrl_policy_forward / icrl_policy_evaluate over >= 64 rows run 16 rows per workgroup pass as fp32 MFMA tiles
     (policy_rows_kernel); below, one workgroup per row with per-lane fmaf chains.  Same values bit for bit: evaluate / forward
-    the rows at once, and in chunks of 50."""
+    the rows at once, and in chunks of 50.  Past the grid cap (16385 rows: workgroup 0 takes a second tile of one live row; 16400:
+    a full second tile and a second workgroup's ragged one) the chunks cover the rows from 16320 on: the last four tiles of the first
+    trip and all of the second."""
     from icrl_amd.policies import ActorTwoCriticsPolicy
     from icrl_amd import spaces
     od, ad = (113, 8) if kind == "ant" else (18, 6)
@@ -114,17 +119,21 @@ def test_policy_rows_kernel_equals_one_workgroup_per_row(kind, n):
     obs = rng.randn(n, od) * 2.0
     act = rng.randn(n, ad).astype(np.float32)
     noise = rng.randn(n, ad).astype(np.float32)
-    whole = [t.cpu().numpy() for t in pol.evaluate_actions(obs, act)]
-    parts = [pol.evaluate_actions(obs[i:i + 50], act[i:i + 50]) for i in range(0, n, 50)]
+    lo = ROWS_GRID_CAP - 64 if n > ROWS_GRID_CAP else 0      # the first row evaluated again in chunks
+    assert (n - lo) <= 1000
+    whole = [t.cpu().numpy()[lo:] for t in pol.evaluate_actions(obs, act)]
+    assert all(len(w) == n - lo for w in whole)
+    parts = [pol.evaluate_actions(obs[i:i + 50], act[i:i + 50]) for i in range(lo, n, 50)]
     for k, name in enumerate(("reward_values", "cost_values", "log_prob", "entropy")):
         ref = np.concatenate([pt[k].cpu().numpy() for pt in parts])
         assert np.array_equal(whole[k], ref), (name, np.abs(whole[k] - ref).max())
     for det in (False, True):
         a, vr, vc, lp = pol.forward(obs, deterministic=det, noise=noise)
         cl = pol.last_clipped
-        got = [t.cpu().numpy() for t in (a, vr, vc, lp, cl)]
+        got = [t.cpu().numpy()[lo:] for t in (a, vr, vc, lp, cl)]
+        assert all(len(g_) == n - lo for g_ in got)
         ref = [[], [], [], [], []]
-        for i in range(0, n, 50):
+        for i in range(lo, n, 50):
             a2, vr2, vc2, lp2 = pol.forward(obs[i:i + 50], deterministic=det, noise=noise[i:i + 50])
             for lst, t in zip(ref, (a2, vr2, vc2, lp2, pol.last_clipped)):
                 lst.append(t.cpu().numpy())
@@ -188,7 +197,8 @@ from helpers.arches import ARCHES, oracle_arch_kwargs
 
 
 @pytest.mark.parametrize("kind,n", [("hc", 64), ("hc", 1000), ("ant", 333), ("narrow", 200), ("wide", 40), ("wide", 300),
-                                    ("trunk", 150), ("deep", 70), ("trunk-only", 33), ("bare", 20)])
+                                    ("trunk", 150), ("deep", 70), ("trunk-only", 33), ("bare", 20),
+                                    ("hc", 16385), ("ant", 16400)])      # past the grid cap: a second tile per workgroup, every row compared
 def test_policy_rows_kernel_vs_oracle(kind, n):
     """policy_rows_kernel (>= 64 rows: 16 rows per workgroup pass as fp32 MFMA tiles; the KL metrics' evaluate_actions and batched
     predict) against the oracle's ActorTwoCriticsPolicy.evaluate_actions / forward directly (policies.py:716-731, 752-767;
@@ -224,3 +234,10 @@ def test_policy_rows_kernel_vs_oracle(kind, n):
     for name, got, ref in (("actions", a, o_a), ("reward_values", fvr, o_fvr), ("cost_values", fvc, o_fvc), ("log_prob", flp, o_flp)):
         ref = ref.numpy().reshape(got.shape)
         assert np.allclose(got, ref, rtol=1e-5, atol=2e-6), (name, np.abs(got - ref).max())
+    if n > ROWS_GRID_CAP:      # the deterministic route past the cap as well (the smaller cases keep what they ran)
+        a, fvr, fvc, flp = [t.cpu().numpy() for t in pol.forward(obs, deterministic=True, noise=noise)]
+        with torch.no_grad():
+            o_a, o_fvr, o_fvc, o_flp = op.forward(torch.as_tensor(obs), noise=torch.as_tensor(noise), deterministic=True)
+        for name, got, ref in (("actions", a, o_a), ("reward_values", fvr, o_fvr), ("cost_values", fvc, o_fvc), ("log_prob", flp, o_flp)):
+            ref = ref.numpy().reshape(got.shape)
+            assert np.allclose(got, ref, rtol=1e-5, atol=2e-6), ("deterministic", name, np.abs(got - ref).max())

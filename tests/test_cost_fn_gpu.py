@@ -77,9 +77,13 @@ def _numpy_cost(cost, rb, env):
 
 
 # ---- 1. icrl_cost_fn_rows against numpy, exact --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("od,ad", [(18, 6), (113, 8)])
-@pytest.mark.parametrize("N", [1, 63, 257])
+_ROWS_GRID = 1024 * 256      # cost_fn_rows_kernel: min(blocks, 1024) x 256 threads; row 262144 is thread 0's second
+
+
+@pytest.mark.parametrize("N,od,ad", [(N, od, ad) for od, ad in ((18, 6), (113, 8)) for N in (1, 63, 257)] + [(_ROWS_GRID + 256, 18, 6)])
 def test_rows_kernel_equals_numpy(N, od, ad):
+    """N = 262400: one block's worth of threads takes a second row, and those rows are the edge rows (tiled), so that the second trip meets
+    the thresholds themselves."""
     from icrl_amd.true_constraint_net import AnalyticCost
     rng = np.random.RandomState(N + od)
     index = od - 1
@@ -94,6 +98,11 @@ def test_rows_kernel_equals_numpy(N, od, ad):
     acs[:min(N, len(eacs))] = eacs[:N]
     if N == 1:
         acs[0, ad - 1] = -np.nextafter(np.float32(thr), np.float32(1))
+    if N > _ROWS_GRID:
+        tail = N - _ROWS_GRID
+        assert tail >= len(edge) and tail >= len(eacs)
+        obs[_ROWS_GRID:] = edge[np.arange(tail) % len(edge)]
+        acs[_ROWS_GRID:] = eacs[np.arange(tail) % len(eacs)]
     disc = rng.randint(0, 3, size=(N, 1)).astype(np.float32)
     to, ta, td = (torch.as_tensor(x, device="cuda") for x in (obs, acs, disc))
     col = obs[:, index]

@@ -104,8 +104,9 @@ def test_the_same_call_twice_gives_the_same_bits(golden):
         assert np.array_equal(a, b)
 
 
-def _against_torch(obs, act, out_dim, rows, hidden, n_steps, seed):
-    """n_steps chained steps on `rows` rows against float32 and float64 torch runs of an nn.Sequential built here, by the rule."""
+def _against_torch(obs, act, out_dim, rows, hidden, n_steps, seed, all_through_xb=False):
+    """n_steps chained steps on `rows` rows against float32 and float64 torch runs of an nn.Sequential built here, by the rule.
+    all_through_xb: in_a = 0, the (observation | action) rows handed over as one xb plane and xa = None."""
     torch.manual_seed(seed)
     net32 = X.make_net(obs + act, out_dim, hidden)
     sd = {k: v.clone() for k, v in net32.state_dict().items()}
@@ -122,8 +123,12 @@ def _against_torch(obs, act, out_dim, rows, hidden, n_steps, seed):
     d_target = torch.as_tensor(target, device="cuda").contiguous()
     net = _net(obs + act, out_dim, hidden, sd)
     row_err, row_whole = _padded(rows)
+    xa, xb = dev["observations"], dev["actions"]
+    if all_through_xb:
+        xa, xb = None, torch.cat([xa.reshape(rows, obs), xb.reshape(rows, act)], -1).contiguous()
+        assert tuple(xb.shape) == (rows, obs + act)
     for s in range(n_steps):
-        out4 = net.step(dev["observations"], dev["actions"], d_target, row_err).cpu().numpy()
+        out4 = net.step(xa, xb, d_target, row_err).cpu().numpy()
         e32, e64 = ref[np.float32]["steps"][s], ref[np.float64]["steps"][s]
         X.check(f"step {s} row_err", row_err.cpu().numpy(), e32[0], e64[0])
         X.check(f"step {s} loss", out4[0], e32[1], e64[1])
@@ -137,6 +142,19 @@ def _against_torch(obs, act, out_dim, rows, hidden, n_steps, seed):
 def test_more_rows_than_the_sibling_entry_points_serve():
     """70 001 rows at (obs 9, act 2): above the 65 536 rows of icrl_cost_mlp_fwd_bwd, every workgroup walks several groups, ragged tail."""
     _against_torch(9, 2, 9, 70001, (50, 50), 2, 11)
+
+
+@pytest.mark.parametrize("rows", [8192, 8193])
+def test_the_edge_of_the_grid_cap(rows):
+    """reg_mlp_tile_kernel walks 32-row groups on min(groups, 256) workgroups.  8192 rows: 256 groups, every workgroup takes exactly one;
+    8193 rows: 257 groups, workgroup 0 alone takes a second one, which holds a single live row."""
+    assert -(-rows // 32) == 256 + (rows > 8192)
+    _against_torch(9, 2, 9, rows, (50, 50), 2, 13)
+
+
+def test_all_inputs_through_xb():
+    """in_a = 0 (xa = None), the 11 inputs in the xb plane, 45 rows: a served shape (rm_check: in_a 0..) that no caller takes."""
+    _against_torch(9, 2, 9, 45, (50, 50), 2, 14, all_through_xb=True)
 
 
 def test_the_largest_served_shape():

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import fine_cases as F      # the banded minibatch, the oracle's row gradients, the is-weights case, the CPU-measured bounds
 from oracle import nets as o_nets, ppo as o_ppo
 
 pytestmark = pytest.mark.gpu
@@ -92,10 +93,19 @@ def test_loss_fwd_bwd_and_clip_adam_reproduce_the_reference_steps(golden):
 
 def test_minibatch_gather_and_adv_stats():
     """buffers.py:53-65,594-627: flat env-major indices -> rows of the [T, N] buffer; ppo_lag.py:219-222 statistics."""
+    _gather_and_adv_stats(40, 7, 18, 6, 100)
+
+
+def test_minibatch_gather_and_adv_stats_past_one_trip_of_the_block():
+    """1000 rows out of a 40 x 32 buffer at 113 observations: adv_stats_kernel is one block of 256 threads, so every thread sums three rows and
+    232 a fourth, in both of its passes (the mean, then the deviations); the gather runs 1000 blocks."""
+    _gather_and_adv_stats(40, 32, 113, 8, 1000)
+
+
+def _gather_and_adv_stats(T, N, od, ad, n):
     from icrl_amd import _lib, spaces
     from icrl_amd.buffers import RolloutBufferWithCost
     L = _lib.lib()
-    T, N, od, ad, n = 40, 7, 18, 6, 100
     rb = RolloutBufferWithCost(T, spaces.Box(-np.inf, np.inf, (od,), np.float64), spaces.Box(-1, 1, (ad,), np.float32), "cuda", n_envs=N)
     rng = np.random.RandomState(1)
     ref = {}
@@ -107,6 +117,7 @@ def test_minibatch_gather_and_adv_stats():
     outs = dict(obs=torch.empty(n, od, device="cuda"), act=torch.empty(n, ad, device="cuda"))
     for k in ("lp", "ar", "ac", "rr", "rc", "vr", "vc"):
         outs[k] = torch.empty(n, device="cuda")
+    assert len(set(idx.tolist())) == n and n > 1
     s = rb.struct()
     d_idx = _dev(idx, torch.int32)
     _lib.check(L.icrl_minibatch_gather(ctypes.byref(s), _lib.ptr(d_idx), n, *[_lib.ptr(outs[k]) for k in ("obs", "act", "lp", "ar", "ac", "rr", "rc", "vr", "vc")],
@@ -147,14 +158,32 @@ def test_dual_step_follows_the_reference_trajectories(golden, case):
     assert np.allclose(got[:, 1], g["traj"][:, 1], rtol=2e-5, atol=1e-7)                                                   # loss = -nu (cost - budget)
 
 
+_PLANES = dict(obs="observations", orig_obs="orig_observations", new_obs="new_observations", new_orig_obs="new_orig_observations", action="actions",
+               reward="rewards", cost="costs", orig_cost="orig_costs", done="dones", reward_value="reward_values", cost_value="cost_values", log_prob="log_probs")
+
+
 def test_buffer_add_writes_row_t():
     """buffers.py:554-592: one step's arrays -> row t of every plane (float64 observations / rewards stored as float32)."""
+    _buffer_add(6, 5, 18, 6, 3)
+
+
+def test_buffer_add_over_several_blocks_first_and_last_row():
+    """64 envs x 113 observations = 7232 threads, 29 blocks of 256 (the existing case is one block of 90): `blockIdx.x * 256 + threadIdx.x`
+    against the three extents N x obs (the last block ragged), N x act = 512 (two blocks) and N = 64; row 0, then the last row of the
+    buffer (t x N x obs at its largest), each with its own values, the other rows untouched."""
+    assert -(-64 * 113 // 256) == 29
+    rb = _buffer_add(4, 64, 113, 8, 0)
+    _buffer_add(4, 64, 113, 8, 3, rb=rb, written=(0,), seed=5)
+
+
+def _buffer_add(T, N, od, ad, t, rb=None, written=(), seed=2):
     from icrl_amd import _lib, spaces
     from icrl_amd.buffers import RolloutBufferWithCost
     L = _lib.lib()
-    T, N, od, ad, t = 6, 5, 18, 6, 3
-    rb = RolloutBufferWithCost(T, spaces.Box(-np.inf, np.inf, (od,), np.float64), spaces.Box(-1, 1, (ad,), np.float32), "cuda", n_envs=N)
-    rng = np.random.RandomState(2)
+    if rb is None:
+        rb = RolloutBufferWithCost(T, spaces.Box(-np.inf, np.inf, (od,), np.float64), spaces.Box(-1, 1, (ad,), np.float32), "cuda", n_envs=N)
+    before = {name: getattr(rb, name).cpu().numpy().copy() for name in _PLANES.values()}
+    rng = np.random.RandomState(seed)
     host = dict(obs=rng.randn(N, od), orig_obs=rng.randn(N, od), new_obs=rng.randn(N, od), new_orig_obs=rng.randn(N, od), action=rng.randn(N, ad).astype(np.float32),
                 reward=rng.randn(N), cost=rng.rand(N), orig_cost=rng.rand(N).astype(np.float32), done=(rng.rand(N) < 0.5).astype(np.uint8),
                 reward_value=rng.randn(N).astype(np.float32), cost_value=rng.randn(N).astype(np.float32), log_prob=rng.randn(N).astype(np.float32))
@@ -162,14 +191,15 @@ def test_buffer_add_writes_row_t():
     s = rb.struct()
     order = ("obs", "orig_obs", "new_obs", "new_orig_obs", "action", "reward", "cost", "orig_cost", "done", "reward_value", "cost_value", "log_prob")
     _lib.check(L.icrl_buffer_add(ctypes.byref(s), t, *[_lib.ptr(dev[k]) for k in order], _lib.current_stream()), "icrl_buffer_add")
-    planes = dict(obs="observations", orig_obs="orig_observations", new_obs="new_observations", new_orig_obs="new_orig_observations", action="actions",
-                  reward="rewards", cost="costs", orig_cost="orig_costs", done="dones", reward_value="reward_values", cost_value="cost_values", log_prob="log_probs")
-    for k, name in planes.items():
+    for k, name in _PLANES.items():
         got = getattr(rb, name).cpu().numpy()
         assert np.array_equal(got[t].reshape(N, -1), host[k].astype(np.float32).reshape(N, -1)), k
-        assert not got[:t].any() and not got[t + 1:].any(), k          # only row t was touched
+        for r in range(T):          # only row t was touched: the rows written before keep their values, all others are still zero
+            if r != t:
+                assert np.array_equal(got[r], before[name][r]) and (r in written or not got[r].any()), (k, r)
     assert L.icrl_buffer_add(ctypes.byref(s), T, *[_lib.ptr(dev[k]) for k in order], _lib.current_stream()) == 1       # refused: t outside the buffer
     L.icrl_clear_error()
+    return rb
 
 
 @pytest.mark.parametrize("per_step", [False, True])
@@ -194,15 +224,57 @@ def test_is_weights_vs_oracle(per_step):
     assert abs(o[0] - kl_on.item()) <= 2e-5 * max(1.0, abs(kl_on.item())) and abs(o[1] - kl_no.item()) <= 2e-5 * max(1.0, abs(kl_no.item())) + 1e-6
 
 
+@pytest.mark.parametrize("per_step", [False, True])
+def test_is_weights_past_the_first_trip_of_every_walk_vs_float64_oracle(per_step):
+    """20 episodes on the kernel's 16 waves (waves 0..3 take a second episode), episodes of up to 1000 steps on a wave's 64 lanes (65 and 129
+    steps: one live lane in the last trip; 64, 128, 640: whole trips), N = 6489 rows on 1024 threads (a ragged seventh trip), in the products,
+    the ratio sum and the weight stores.  Reference: oracle.cn.is_weights_and_kls in float64 on the float32 inputs; bound per quantity
+    4 x max |oracle32 - oracle64| + 1e-12 (helpers/fine_cases.py; measured there: weights 1.0e-6 of up to 2.2 per episode, 2.3e-7 of up to
+    1.1 per step, kl_old_new 4.4e-8, kl_new_old 1.1e-7), printed beside the distance.  A numpy emulation of the kernel's lane-strided float32
+    product order lands 1.9e-6 from the float64 weights."""
+    from icrl_amd import _lib
+    L = _lib.lib()
+    lengths = list(F.IS_LENGTHS)
+    N, n_ep = sum(lengths), len(lengths)
+    assert n_ep == 20 and N == 6489 and max(lengths) == 1000
+    old, new = F.is_weights_inputs()
+    r64, r32, bounds = F.is_weights_oracles(per_step)
+    assert 0.1 < r64["prod"].min() and r64["prod"].max() < 2.0, (r64["prod"].min(), r64["prod"].max())      # nothing overflows or vanishes
+    offs = torch.as_tensor(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).cuda()
+    d_old, d_new = old.flatten().cuda().contiguous(), new.flatten().cuda().contiguous()
+    w, prod, out4 = torch.full((N + 64,), 7.0, device="cuda"), torch.full((n_ep + 16,), 7.0, device="cuda"), torch.zeros(4, device="cuda")
+    _lib.check(L.icrl_is_weights(_lib.ptr(d_old), _lib.ptr(d_new), N, _lib.ptr(offs), n_ep, F.IS_EPS, int(per_step), _lib.ptr(w), _lib.ptr(prod), _lib.ptr(out4),
+                                 _lib.current_stream()), "icrl_is_weights")
+    w, prod, o = w.cpu().numpy(), prod.cpu().numpy(), out4.cpu().numpy()
+    assert np.all(w[N:] == 7.0) and np.all(prod[n_ep:] == 7.0)      # nothing written past the rows / the episodes
+    dist = dict(w=float(np.abs(w[:N].astype(np.float64) - r64["w"]).max()), kl_on=abs(float(o[0]) - r64["kl_on"]), kl_no=abs(float(o[1]) - r64["kl_no"]))
+    for k in ("w", "kl_on", "kl_no"):
+        print(f"FINE_IS per_step={per_step} {k}: |kernel - float64| = {dist[k]:.3g}, bound {bounds[k]:.3g}, ratio {dist[k] / bounds[k]:.2f}")
+    for k in ("w", "kl_on", "kl_no"):
+        assert dist[k] <= bounds[k], (k, dist[k], bounds[k])
+
+
 @pytest.mark.parametrize("mode,weights", [(0, True), (0, False), (2, True), (1, False)])
 def test_cn_loss_fwd_bwd_vs_autograd(mode, weights):
     """constraint_net.py:188-202 (and gail_utils.py's BCE) on the network's outputs: loss terms and d loss / d prediction against torch
     autograd of the oracle's expressions.  mode 2: the per-step broadcast quirk (nominal_loss = mean(w) * mean(log zeta))."""
+    _cn_loss_fwd_bwd(mode, weights, 300, 170)
+
+
+@pytest.mark.parametrize("mode,weights", [(0, True), (0, False), (2, True), (1, False)])
+def test_cn_loss_fwd_bwd_vs_autograd_past_one_trip_of_the_block(mode, weights):
+    """Bn = 1000, Be = 700 on cn_loss_fwd_bwd_kernel's one block of 256 threads: every thread takes three nominal and two expert rows, 232
+    a fourth nominal and 188 a third expert one, in the sums and in the gradient stores (at Bn 300 / Be 170 only 44 threads took a second
+    nominal row, none a second expert row)."""
+    _cn_loss_fwd_bwd(mode, weights, 1000, 700)
+
+
+def _cn_loss_fwd_bwd(mode, weights, Bn, Be):
     from icrl_amd import _lib
     from oracle import cn as o_cn
     L = _lib.lib()
     rng = np.random.RandomState(4)
-    Bn, Be, reg, eps = 300, 170, 0.5, 1e-5
+    reg, eps = 0.5, 1e-5
     nom = torch.as_tensor(rng.uniform(0.05, 0.95, (Bn, 1)).astype(np.float32)).requires_grad_(True)
     exp = torch.as_tensor(rng.uniform(0.05, 0.95, (Be, 1)).astype(np.float32)).requires_grad_(True)
     w = torch.as_tensor(rng.uniform(0.5, 1.5, Bn).astype(np.float32)) if weights else torch.ones(Bn)
@@ -214,6 +286,7 @@ def test_cn_loss_fwd_bwd_vs_autograd(mode, weights):
     loss, e_l, n_l, r_l, _, _ = o_cn.cn_loss(_Net(), nom, exp, is_batch, reg, eps, gail=bool(mode & 1), factored=(mode == 2))
     loss.backward()
     d_nom, d_exp, terms = torch.zeros(Bn, device="cuda"), torch.zeros(Be, device="cuda"), torch.zeros(6, device="cuda")
+    assert nom.grad.abs().min() > 0 and exp.grad.abs().min() > 0      # (a row the kernel left at its zero fill would differ from the reference)
     dn, de = nom.detach().flatten().cuda().contiguous(), exp.detach().flatten().cuda().contiguous()
     dw = w.cuda().contiguous() if weights else None
     _lib.check(L.icrl_cn_loss_fwd_bwd(_lib.ptr(dn), _lib.ptr(de), _lib.ptr(dw), Bn, Be, reg, eps, mode, _lib.ptr(terms), _lib.ptr(d_nom), _lib.ptr(d_exp),
@@ -338,57 +411,24 @@ def test_explained_variance_of_a_constant_critic_is_nan(value, n):
     assert np.isnan(got[0]) and got[1] == 7.0, got
 
 
-class _Outputs:
-    """the networks' outputs as autograd leaves: oracle.ppo.minibatch_loss evaluates policy.evaluate_actions(obs, actions)."""
-
-    def __init__(self, v_r, v_c, lp, ent, dtype):
-        self.leaves = [torch.as_tensor(x, dtype=dtype).clone().requires_grad_(True) for x in (v_r, v_c, lp, ent)]
-
-    def evaluate_actions(self, obs, actions):
-        return tuple(self.leaves)
-
-
-def _hparam_batch(n):
-    """one banded minibatch of n rows (helpers/ppo_hparam_cases.py: no row on a kink of the ratio clip or of a value clip)."""
-    from helpers import ppo_hparam_cases as H
-    rng = np.random.RandomState(100 + n)
-    f = lambda x: np.asarray(x, np.float32)
-    out = dict(lp=f(-8 + 0.3 * rng.randn(n)), v_r=f(rng.randn(n)), v_c=f(rng.rand(n)), ent=f(8.5 + 0.1 * rng.randn(n)), adv_r=f(2 * rng.randn(n)),
-               adv_c=f(rng.rand(n)), ret_r=f(rng.randn(n)), ret_c=f(rng.rand(n)))
-    out["old_lp"], out["old_v_r"], out["old_v_c"] = H.banded(rng, out["lp"], out["v_r"], out["v_c"], H.SET_A["clip_range_reward_vf"], H.SET_A["clip_range_cost_vf"])
-    return out
-
-
-def _loss_and_row_grads(b, hp, nu, dtype):
-    """oracle.ppo.minibatch_loss on the outputs + autograd: (terms in the library's order, d loss / d (lp, v_r, v_c, entropy))."""
-    t = lambda k: torch.as_tensor(b[k], dtype=dtype)
-    pol = _Outputs(b["v_r"], b["v_c"], b["lp"], b["ent"], dtype)
-    loss, tr = o_ppo.minibatch_loss(pol, None, None, t("old_lp"), t("adv_r"), t("adv_c"), t("ret_r"), t("ret_c"), t("old_v_r"), t("old_v_c"), nu, 0.2,
-                                    hp["ent_coef"], hp["reward_vf_coef"], hp["cost_vf_coef"], hp["clip_range_reward_vf"], hp["clip_range_cost_vf"])
-    loss.backward()
-    v_r, v_c, lp, ent = pol.leaves
-    terms = [loss.item()] + [tr[k].item() for k in ("policy_loss", "reward_value_loss", "cost_value_loss", "entropy_loss", "approx_kl", "clip_fraction")]
-    ratio = torch.exp(lp.detach() - t("old_lp"))
-    margins = (float(torch.minimum((ratio - 0.8).abs(), (ratio - 1.2).abs()).min()),
-               float(((v_r.detach() - t("old_v_r")).abs() - hp["clip_range_reward_vf"]).abs().min()),
-               float(((v_c.detach() - t("old_v_c")).abs() - hp["clip_range_cost_vf"]).abs().min()))
-    shares = (tr["clip_fraction"].item(), float(((v_r.detach() - t("old_v_r")).abs() > hp["clip_range_reward_vf"]).double().mean()),
-              float(((v_c.detach() - t("old_v_c")).abs() > hp["clip_range_cost_vf"]).double().mean()))
-    return terms, dict(d_lp=lp.grad.numpy(), d_vr=v_r.grad.numpy(), d_vc=v_c.grad.numpy(), d_en=ent.grad.numpy()), margins, shares
-
-
-# Per-row output gradients: max |float32 oracle - float64 oracle| over the four (set, rows) cases below, measured on the CPU:
-# d_lp 3.5e-9 (of values up to 0.025), d_vr 3.4e-9 (of 0.091), d_vc 5.5e-10 (of 0.0087), d_en 3.5e-12 (of 1.6e-4: float32(ent_coef) / n).
+_hparam_batch, _loss_and_row_grads = F.hparam_batch, F.loss_and_row_grads
+# Per-row output gradients: max |float32 oracle - float64 oracle| per row count n, measured on the CPU (helpers/fine_cases.py holds the table
+# and the command that prints it).  n = 64 and 100 share the entry measured over their four cases: d_lp 3.5e-9 (of values up to 0.025), d_vr
+# 3.4e-9 (of 0.091), d_vc 5.5e-10 (of 0.0087), d_en 3.5e-12 (of 1.6e-4: float32(ent_coef) / n).  n = 300: d_lp 1.18e-9 (of 0.0069), d_vr 1.15e-9
+# (of 0.017), d_vc 2.48e-10 (of 0.0017), d_en 3.71e-13 (of 3.3e-5).  n = 1000: d_lp 4.76e-10 (of 0.0025), d_vr 5.86e-10 (of 0.0069), d_vc 8.02e-11
+# (of 5.7e-4), d_en 2.53e-13 (of 1e-5).
 # The bound is 3 x that: the kernel's reductions (advantage mean and standard deviation) run in another order than torch's.
-ROW_GRAD_F32_DEV = dict(d_lp=3.5e-9, d_vr=3.4e-9, d_vc=5.5e-10, d_en=3.5e-12)
+ROW_GRAD_F32_DEV = F.ROW_GRAD_F32_DEV
 
 
-@pytest.mark.parametrize("n", [64, 100])
+@pytest.mark.parametrize("n", [64, 100, 300, 1000])
 @pytest.mark.parametrize("hset", ["A", "B"])
 def test_loss_fwd_bwd_with_value_clipping_vs_float64_autograd(hset, n):
     """icrl_ppo_lag_loss_fwd_bwd with both old-value pointers set (value clipping on for both critics), the entropy bonus, separate critic
     weights; then icrl_clip_adam_step in the branch of the norm clip the set takes (A: max_grad_norm 0.3 below the norm, B: 50 above it)
-    — against float64 autograd of oracle.ppo.minibatch_loss on the same outputs and the explicit clip / Adam formulas."""
+    — against float64 autograd of oracle.ppo.minibatch_loss on the same outputs and the explicit clip / Adam formulas.
+    n = 300, 1000: past the first trip of loss_fwd_bwd_kernel's one block of 256 threads (44 threads take a second row; every thread three
+    and 232 a fourth), where the seven per-thread sums carry over."""
     from helpers import ppo_hparam_cases as H
     from icrl_amd import _lib, structs as S
     L = _lib.lib()
@@ -413,20 +453,39 @@ def test_loss_fwd_bwd_with_value_clipping_vs_float64_autograd(hset, n):
     for i, key in enumerate(("loss", "policy_loss", "rvl", "cvl", "entropy_loss", "approx_kl", "clip_fraction")):
         print(f"FINE_HP set {hset} n={n} {key}: {t[i]:.9g} vs {ref_terms[i]:.9g}")
     for k in got:
-        print(f"FINE_HP set {hset} n={n} {k}: max |kernel - float64| = {np.abs(got[k].cpu().numpy() - ref_g[k]).max():.3g} (bound {3 * ROW_GRAD_F32_DEV[k]:.3g})")
+        print(f"FINE_HP set {hset} n={n} {k}: max |kernel - float64| = {np.abs(got[k].cpu().numpy() - ref_g[k]).max():.3g} (bound {3 * ROW_GRAD_F32_DEV[n][k]:.3g})")
     for i, key in enumerate(("loss", "policy_loss", "rvl", "cvl", "entropy_loss", "approx_kl", "clip_fraction")):
         assert abs(t[i] - ref_terms[i]) <= 2e-6 + 2e-5 * abs(ref_terms[i]), (key, t[i], ref_terms[i])
     for k in got:      # row by row
-        assert np.abs(got[k].cpu().numpy() - ref_g[k]).max() <= 3 * ROW_GRAD_F32_DEV[k], (k, np.abs(got[k].cpu().numpy() - ref_g[k]).max())
+        assert np.abs(got[k].cpu().numpy() - ref_g[k]).max() <= 3 * ROW_GRAD_F32_DEV[n][k], (k, np.abs(got[k].cpu().numpy() - ref_g[k]).max())
     # ---- clip_grad_norm_ + Adam, two steps on a flat buffer of 20 blocks with a ragged tail
-    rng = np.random.RandomState(n)
-    n_p = 5001
+    _clip_adam_steps(hset, hpd, hp, 5001, n)
+
+
+def _clip_adam_steps(hset, hpd, hp, n_p, seed, preset=False):
+    """two icrl_clip_adam_step calls on a flat buffer of n_p parameters against clip_coef_explicit / adam_step_explicit in float64.
+    preset: then a third call with the step counter set to 999 and the moments as they stand (non-zero), against the same formulas at t = 1000."""
+    from icrl_amd import _lib
+    L, st = _lib.lib(), _lib.current_stream()
+    rng = np.random.RandomState(seed)
     p0, grads = rng.randn(n_p).astype(np.float32), [(rng.randn(n_p) / np.sqrt(n_p) * s).astype(np.float32) for s in (1.0, 2.5)]      # norms ~ 1 and ~ 2.5
-    flat, m, v = _dev(p0), torch.zeros(n_p, device="cuda"), torch.zeros(n_p, device="cuda")
+    if preset:
+        grads.append((rng.randn(n_p) / np.sqrt(n_p) * 1.7).astype(np.float32))
+    flat, m, v = _dev(np.concatenate([p0, np.full(300, 7.0, np.float32)])), torch.zeros(n_p + 300, device="cuda"), torch.zeros(n_p + 300, device="cuda")
+    m[n_p:], v[n_p:] = 7.0, 7.0                                                                   # sentinels behind the n_p entries of all three
     step, work, out2 = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(256, device="cuda"), torch.zeros(2, device="cuda")
     rp, rm, rv, qm, qv = (torch.as_tensor(x, dtype=torch.float64) for x in (p0, np.zeros(n_p), np.zeros(n_p), np.zeros(n_p), np.zeros(n_p)))
     w1 = np.float32(1.0 - float(np.float32(0.9)))
+    t = 0
     for s, g in enumerate(grads):
+        if s == 2:      # the step counter far from its start: bias corrections 1 - 0.9^1000 = 1 and 1 - 0.999^1000 = 0.632 (at t = 1..3: 0.1 .. 0.27, 0.001 .. 0.003)
+            step.fill_(999)
+            t = 999
+            rm, rv = m[:n_p].cpu().double(), v[:n_p].cpu().double()      # the reference continues from the moments the call reads
+            qm, qv = rm.clone(), rv.clone()
+            rp = flat[:n_p].cpu().double()
+            assert float(rm.abs().max()) > 0 and float(rv.max()) > 0
+        t += 1
         total, coef = o_ppo.clip_coef_explicit([torch.as_tensor(g)], hpd["max_grad_norm"])
         assert (coef < 1.0) == (hset == "A") and abs(total - hpd["max_grad_norm"]) > 0.1      # the branch the set is about, away from its kink
         gd = _dev(g)
@@ -435,18 +494,39 @@ def test_loss_fwd_bwd_with_value_clipping_vs_float64_autograd(hset, n):
         o = out2.cpu().numpy()
         assert abs(o[0] - total) <= 1e-5 * max(1.0, total), (o, total)
         assert abs(o[1] - coef) <= 1e-5 * coef and (o[1] == 1.0) == (hset == "B"), (o, coef)
+        assert all(bool((x[n_p:] == 7.0).all()) for x in (flat, m, v)), "a store behind the last parameter"
+        got_p, got_m, got_v = (x[:n_p].cpu().numpy() for x in (flat, m, v))
         # what enters the moments is g x coef, rounded once.  After the first step exp_avg is (1 - beta1) x that, bit for bit: with the coefficient
         # capped at 1 (set B) the first moment is (1 - beta1) g itself, the gradient's direction and scale untouched
         gi = g * o[1]
         if s == 0:
-            assert np.array_equal(m.cpu().numpy(), w1 * gi)
-            assert np.array_equal(m.cpu().numpy(), w1 * g) == (hset == "B")
+            assert np.array_equal(got_m, w1 * gi)
+            assert np.array_equal(got_m, w1 * g) == (hset == "B")
         gc = torch.as_tensor(g, dtype=torch.float64) * coef
-        rp, rm, rv = o_ppo.adam_step_explicit(rp, gc, rm, rv, s + 1, 3e-4, eps=1e-5)
-        assert np.allclose(flat.cpu().numpy(), rp.numpy(), rtol=1e-5, atol=3e-7), np.abs(flat.cpu().numpy() - rp.numpy()).max()
+        rp, rm, rv = o_ppo.adam_step_explicit(rp, gc, rm, rv, t, 3e-4, eps=1e-5)
+        print(f"FINE_ADAM set {hset} n_p={n_p} t={t}: max |kernel - float64| of the parameters = {np.abs(got_p - rp.numpy()).max():.3g} (atol 3e-7, rtol 1e-5)")
+        assert np.allclose(got_p, rp.numpy(), rtol=1e-5, atol=3e-7), np.abs(got_p - rp.numpy()).max()
         # the moments: the explicit formula with the betas as icrl_ppo_hyper_t carries them (float32: 1 - float32(0.999) is smaller than 0.001 by 1.3e-5 of it,
         # which the parameter tolerance above and ADAM_DEV_BOUND absorb)
         b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
         qm, qv = b1 * qm + (1 - b1) * gc, b2 * qv + (1 - b2) * gc * gc
-        assert np.allclose(m.cpu().numpy(), qm.numpy(), rtol=1e-5, atol=1e-9) and np.allclose(v.cpu().numpy(), qv.numpy(), rtol=1e-5, atol=1e-12)
-    assert int(step.item()) == 2
+        assert np.allclose(got_m, qm.numpy(), rtol=1e-5, atol=1e-9) and np.allclose(got_v, qv.numpy(), rtol=1e-5, atol=1e-12)
+        assert int(step.item()) == t
+    assert int(step.item()) == (1000 if preset else 2)
+
+
+@pytest.mark.parametrize("hset", ["A", "B"])
+def test_clip_adam_step_past_one_grid_pass_and_at_step_1000(hset):
+    """70 001 parameters: icrl_clip_adam_step caps its grid at 256 blocks of 256 threads (65 536 per pass), so every thread of sqnorm_partials_kernel
+    and clip_adam_kernel takes a second element and 4465 do not (the ragged end), and clip_adam_kernel folds 256 partial sums, one per thread.
+    The same two-step check as at 5001 parameters, the gradients scaled to norms ~ 1 and ~ 2.5 (set A: max_grad_norm 0.3 below, B: 50 above),
+    then a call with the step counter preset to 999 on the moments of those two steps."""
+    from helpers import ppo_hparam_cases as H
+    from icrl_amd import structs as S
+    hpd = H.hparams(hset)
+    hp = S.PpoHyperT(64, 1, 0, 0)
+    hp.clip_range, hp.ent_coef, hp.reward_vf_coef, hp.cost_vf_coef, hp.max_grad_norm = 0.2, hpd["ent_coef"], hpd["reward_vf_coef"], hpd["cost_vf_coef"], hpd["max_grad_norm"]
+    hp.clip_range_reward_vf, hp.clip_range_cost_vf = hpd["clip_range_reward_vf"], hpd["clip_range_cost_vf"]
+    hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps = 3e-4, 0.9, 0.999, 1e-5
+    assert 256 * 256 < 70001 < 2 * 256 * 256
+    _clip_adam_steps(hset, hpd, hp, 70001, 70001, preset=True)

@@ -171,7 +171,7 @@ def _true_cost(name):
             "torque": lambda: AnalyticCost.torque(0.5), "null": AnalyticCost.null, "NULL": lambda: None}[name]()
 
 
-def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost, eps=1e-8):
+def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost, eps=1e-8, rows=_ROWS):
     """per run: a discriminator, normalised float32 observations [rows, obs], actions, statistics, rewards and the references — the torch
     expressions of the callback (un-normalise, mean cost) and icrl_disc_reward plus a torch add."""
     from icrl_amd import _lib
@@ -183,43 +183,43 @@ def _gail_runs(obs_dim, act_dim, discrete, stats, costs, hidden, learn_cost, eps
     for r, cost in enumerate(costs):
         torch.manual_seed(3 + r)
         disc = GailDiscriminator(obs_dim, 2 if discrete else act_dim, list(hidden), None, lambda x: 0.01, None, None, discrete, eps=1e-5)
-        obs = torch.as_tensor(rng.randn(_ROWS, obs_dim).astype(np.float32), device="cuda")
+        obs = torch.as_tensor(rng.randn(rows, obs_dim).astype(np.float32), device="cuda")
         if discrete:
-            acs = torch.as_tensor(rng.randint(0, 2, (_ROWS, 1)).astype(np.float32), device="cuda")
+            acs = torch.as_tensor(rng.randint(0, 2, (rows, 1)).astype(np.float32), device="cuda")
         else:
-            acs = torch.as_tensor(rng.uniform(-1.2, 1.2, (_ROWS, act_dim)).astype(np.float32), device="cuda")
+            acs = torch.as_tensor(rng.uniform(-1.2, 1.2, (rows, act_dim)).astype(np.float32), device="cuda")
         mean = torch.as_tensor(rng.randn(obs_dim) * 0.7, device="cuda") if stats else None
         var = torch.as_tensor(rng.uniform(0.2, 3.0, obs_dim), device="cuda") if stats else None
-        rewards = torch.as_tensor(rng.randn(_ROWS).astype(np.float32), device="cuda")
+        rewards = torch.as_tensor(rng.randn(rows).astype(np.float32), device="cuda")
         # ---- references
         raw = obs.double()
         if stats:
             raw = raw * torch.sqrt(var + eps) + mean
         tc = _true_cost(cost)
         ref_mean = 0.0 if tc is None else mean_cost(tc, raw, acs)
-        logd = torch.empty(_ROWS, device="cuda")
+        logd = torch.empty(rows, device="cuda")
         s = disc.struct()
-        _lib.check(_lib.lib().icrl_disc_reward(_lib.byref(s), p(raw.contiguous()), p(acs), _ROWS, p(logd), 1, _lib.current_stream()), "icrl_disc_reward")
+        _lib.check(_lib.lib().icrl_disc_reward(_lib.byref(s), p(raw.contiguous()), p(acs), rows, p(logd), 1, _lib.current_stream()), "icrl_disc_reward")
         ref_rewards = rewards + logd if learn_cost else logd.clone()
         runs.append(dict(disc=disc, obs=obs, acs=acs, mean=mean, var=var, eps=eps, rewards=rewards.clone(), tc=tc, ref_raw=raw, ref_mean=ref_mean,
                          ref_rewards=ref_rewards, cost=cost))
     return runs
 
 
-def _run_gail_kernels(runs, learn_cost, obs_dim, act_store):
+def _run_gail_kernels(runs, learn_cost, obs_dim, act_store, rows=_ROWS):
     from icrl_amd import _lib
     from icrl_amd.structs import GailJobT, addr, p
     S = len(runs)
-    keep, rows = [], []
+    keep, jobs = [], []
     for r in runs:
-        r["raw"] = torch.full((_ROWS, obs_dim), float("nan"), dtype=torch.float64, device="cuda")
+        r["raw"] = torch.full((rows, obs_dim), float("nan"), dtype=torch.float64, device="cuda")
         r["cost_mean"] = torch.full((1,), float("nan"), dtype=torch.float64, device="cuda")
         ds = r["disc"].struct()
         cs = None if r["tc"] is None else r["tc"].struct(obs_dim, act_store)
         keep += [ds, cs]
-        rows.append(GailJobT(addr(ds), addr(cs), p(r["obs"]), p(r["acs"]), p(r["mean"]), p(r["var"]), r["eps"], p(r["raw"]), p(r["rewards"]),
-                             p(r["cost_mean"]), _ROWS, int(learn_cost)))
-    arr = (GailJobT * S)(*rows)
+        jobs.append(GailJobT(addr(ds), addr(cs), p(r["obs"]), p(r["acs"]), p(r["mean"]), p(r["var"]), r["eps"], p(r["raw"]), p(r["rewards"]),
+                             p(r["cost_mean"]), rows, int(learn_cost)))
+    arr = (GailJobT * S)(*jobs)
     ws = torch.empty(S * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device="cuda")
     L = _lib.lib()
     _lib.check(L.icrl_gail_unnormalize_batch(S, arr, p(ws), ws.numel(), _lib.current_stream()), "icrl_gail_unnormalize_batch")
@@ -250,6 +250,30 @@ def test_gail_rollout_end_kernels_equal_the_torch_expressions(obs_dim, act_dim, 
             assert float(r["cost_mean"].item()) == r["ref_mean"], (n_runs, i, r["cost"], float(r["cost_mean"].item()), r["ref_mean"])
             fired.append(r["ref_mean"])
         if not discrete and n_runs == 3:
+            live = [m for m, c in zip(fired, costs) if c not in ("null", "NULL")]
+            assert all(0.0 < m < 2.0 for m in live), fired            # the closed forms fire in some rows and not in others
+
+
+@pytest.mark.parametrize("learn_cost", [0, 1], ids=["replace", "learn_cost"])
+@pytest.mark.parametrize("obs_dim,act_dim,stats,hidden,rows", [(113, 8, True, (64, 64), 4700), (18, 6, True, (30,), 1100)], ids=["ant-stats-4700", "hc-stats-1100"])
+def test_gail_rollout_end_kernels_past_one_grid_pass(obs_dim, act_dim, stats, hidden, rows, learn_cost):
+    """the same comparison past the first trip of the kernels' walks.  gail_unnormalize_kernel runs min(blocks, 2048) x 256 threads over
+    rows x obs_dim: 4700 x 113 = 531 100 elements are more than the 524 288 of one grid pass, so the first 6812 threads take a second element.
+    gail_cost_mean_kernel is one block of 1024 threads over the rows: 4700 rows are five trips with a ragged last one, 1100 rows one full trip
+    and 76 threads' second.  Everything else (costs, statistics, references, bit equality, n_runs 3 and 1) as in the 132-row test."""
+    assert rows > 1024 and (rows * obs_dim > 2048 * 256) == (obs_dim == 113)
+    costs = ("wall", "both", "torque") if obs_dim == 18 else ("torque", "NULL", "wall")
+    for n_runs in (3, 1):
+        runs = _gail_runs(obs_dim, act_dim, False, stats, costs[:n_runs], hidden, learn_cost, rows=rows)
+        _run_gail_kernels(runs, learn_cost, obs_dim, act_dim, rows=rows)
+        fired = []
+        for i, r in enumerate(runs):
+            assert r["raw"].shape == (rows, obs_dim) and r["rewards"].shape == (rows,)
+            assert torch.equal(r["raw"], r["ref_raw"]), (n_runs, i, (r["raw"] - r["ref_raw"]).abs().max().item())
+            assert torch.equal(r["rewards"], r["ref_rewards"]), (n_runs, i, (r["rewards"] - r["ref_rewards"]).abs().max().item())
+            assert float(r["cost_mean"].item()) == r["ref_mean"], (n_runs, i, r["cost"], float(r["cost_mean"].item()), r["ref_mean"])
+            fired.append(r["ref_mean"])
+        if n_runs == 3:
             live = [m for m, c in zip(fired, costs) if c not in ("null", "NULL")]
             assert all(0.0 < m < 2.0 for m in live), fired            # the closed forms fire in some rows and not in others
 
