@@ -51,6 +51,9 @@ def setup(config, log=print):
     logger.configure()          # a fresh scalar log per run (the reference configures its logger in learn())
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     use_curiosity, use_lambda = bool(getattr(config, "use_curiosity_driven_exploration", False)), bool(getattr(config, "use_lambda_shaping", False))
+    if getattr(config, "use_sde", False):      # -us with -ucde / -uls or several ranks: refused before anything is launched
+        from . import exploration
+        exploration.refuse_sde(config)
     if use_curiosity or use_lambda:      # ref: icrl/cpg.py:176-184; refused before anything is launched where the callbacks are not served
         from . import exploration
         exploration.refuse_batched(config)

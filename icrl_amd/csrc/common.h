@@ -35,6 +35,15 @@ int launch_cn_cost_rows(const icrl_costnet_t* cn, const double* obs, const float
 int launch_gail_relabel_rows(int n_runs, const icrl_gail_job_t* jobs, void* args_ws, hipStream_t s);
 inline bool costnet_is_wide(const icrl_costnet_t* cn) { return cn->n_hidden > 2 || cn->n_hidden == 0 || cn->h1 > MAX_H || (cn->n_hidden == 2 && cn->h2 > MAX_H); }
 
+// rollout.hip: icrl_policy_forward's one-workgroup-per-row kernel with the gSDE head behind the three branch forwards (sde.hip: icrl_policy_forward_sde)
+int launch_policy_forward_sde(const icrl_policy_t* p, const double* obs, const float* expl, long long expl_stride, int N, int deterministic, const float* alow,
+                              const float* ahigh, float* actions, float* act_clipped, float* v_r, float* v_c, float* log_prob, hipStream_t s);
+// mlp_grad.hip: icrl_policy_fwd_bwd's kernel with the gSDE head (sde.hip: icrl_policy_sde_fwd_bwd); the check returns 0 or the fail() code
+int sde_fwd_bwd_check(const char* who, const icrl_policy_t* p, int N);
+int sde_fwd_bwd_parts(int N);
+int launch_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c, const float* d_log_prob,
+                       const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad, void* ws, hipStream_t s);
+
 // argument rejection: formats the reason into the calling thread's icrl_last_error() text, returns hipErrorInvalidValue
 int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // what a fused call launched, for icrl_debug_last_route (errors.hip; the words per family: include/icrl_hip.h).  An entry point clears its
@@ -284,6 +293,17 @@ __host__ __device__ inline PolLayout make_pol_layout(int O, int A, int H1, int H
   L.Wc = off; off += H2;
   L.bc = off; off += 1;
   L.n = off;
+  return L;
+}
+
+// The same policy with the gSDE head (policies.py: use_sde): log_std is a MATRIX, logical [H2, A], stored [MAX_H, A] with zero rows beyond H2 —
+// still the first tensor of the buffer — and everything behind it keeps its order, MAX_H * A - A entries further on.
+__host__ __device__ inline PolLayout make_sde_layout(int O, int A, int H1, int H2) {
+  PolLayout L = make_pol_layout(O, A, H1, H2, 0);
+  const int shift = (MAX_H - 1) * A;
+  for (int w = 0; w < 3; ++w) { L.W1[w] += shift; L.b1[w] += shift; L.W2[w] += shift; L.b2[w] += shift; }
+  L.Wa += shift; L.ba += shift; L.Wv += shift; L.bv += shift; L.Wc += shift; L.bc += shift;
+  L.n += shift;
   return L;
 }
 

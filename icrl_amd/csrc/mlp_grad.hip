@@ -31,11 +31,11 @@ constexpr int MG_ASTRIDE = 66;     // row stride (doubles) of the activation ima
 constexpr int MG_MAX_PARTS = 64;   // slices of partial sums in ws
 constexpr int MG_MAX_N = 65536;
 constexpr double MG_LOG_SQRT_2PI = 0.918938533204672741780329736406;
-enum { MG_GAUSS = 0, MG_CATEG = 1, MG_VALUE = 2, MG_ZETA = 3 };
+enum { MG_GAUSS = 0, MG_CATEG = 1, MG_VALUE = 2, MG_ZETA = 3, MG_SDE = 4 };
 
 struct MgNet {
   int K, H1, H2, AO, nh, kind;      // inputs, hidden widths, head outputs, hidden layers (1 | 2), what the head's outputs become
-  int W1, b1, W2, b2, Wh, bh, ls;   // offsets into params (W2 / b2 unused when nh == 1; ls: log_std, GAUSS only)
+  int W1, b1, W2, b2, Wh, bh, ls;   // offsets into params (W2 / b2 unused when nh == 1; ls: log_std, GAUSS [AO] | SDE [MG_H][AO])
   const float* d_out;               // VALUE / ZETA: d loss / d output [N] or NULL (zeros)
   float* out;                       // VALUE / ZETA: output [N] or NULL
 };
@@ -63,7 +63,10 @@ inline size_t mg_lds_floats(int K) {
   const int KP = (K + 3) & ~3;
   return (size_t)MG_H * (KP + 1) + MG_H * MG_WSTRIDE + 16 * MG_WSTRIDE + 160 + (size_t)MG_ROWS * KP + 32;
 }
-inline size_t mg_lds_bytes(int K) { return mg_lds_floats(K) * sizeof(float) + (3 * MG_ROWS * MG_ASTRIDE + 512) * sizeof(double); }
+// (the gSDE head adds one double image: exp(2 log_std) [64][16])
+inline size_t mg_lds_bytes(int K, bool sde = false) {
+  return mg_lds_floats(K) * sizeof(float) + (3 * MG_ROWS * MG_ASTRIDE + 512 + (sde ? MG_H * 16 : 0)) * sizeof(double);
+}
 
 template <bool RELU>
 __device__ __forceinline__ double mg_act(double z) {
@@ -119,7 +122,11 @@ __device__ __forceinline__ void mg_outer(double (&acc)[4][4], const double* dz, 
   }
 }
 
-template <bool RELU>
+// SDE: the policy branch may carry the state-dependent-noise head (MG_SDE; distributions.py:408-601 with full_std, exp, no squashing,
+// learn_features = False): log_std is a matrix [MG_H][AO] (rows beyond the last hidden width zero, like every padding), the variance of
+// action c is sum_h latent_h^2 exp(2 log_std[h][c]) + 1e-6 over the latent units in ascending order, and the latent is DETACHED in it:
+// log_std takes the log-prob's and the entropy's variance part, the network only the mean part.
+template <bool RELU, bool SDE = false>
 __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const MgNet n = a.net[blockIdx.y];
@@ -138,7 +145,8 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
   double* sh2 = sh1 + MG_ROWS * MG_ASTRIDE;
   double* sdz = sh2 + MG_ROWS * MG_ASTRIDE;
   double* so = sdz + MG_ROWS * MG_ASTRIDE;          // [16][16] head outputs, then d loss / d head outputs
-  double* sdf = so + 256;                           // [16][16] per-row d loss / d log_std
+  double* sdf = so + 256;                           // [16][16] per-row d loss / d log_std (SDE: the variances, then d loss / d variance)
+  double* sE2 = sdf + 256;                          // SDE only: [64][16] exp(2 log_std[h][c])
   const float* __restrict__ P = a.params;
 
   // ---- weights -> LDS, zero beyond the real widths
@@ -162,6 +170,11 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
     sbh[o] = o < n.AO ? P[n.bh + o] : 0.f;
     sls[o] = (n.kind == MG_GAUSS && o < n.AO) ? P[n.ls + o] : 0.f;
   }
+  if (SDE)
+    for (int i = tid; i < MG_H * 16; i += MG_THREADS) {
+      const int h = i >> 4, c = i & 15;
+      sE2[i] = (n.kind == MG_SDE && c < n.AO) ? exp(2. * (double)P[n.ls + h * n.AO + c]) : 0.;
+    }
 
   double accW1[2][4][4], accW2[4][4], accWh[4], accb = 0.;
   for (int h = 0; h < 2; ++h)
@@ -170,6 +183,7 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
   for (int jj = 0; jj < 4; ++jj)
     for (int kk = 0; kk < 4; ++kk) accW2[jj][kk] = 0.;
   for (int c = 0; c < 4; ++c) accWh[c] = 0.;
+  double accLs[4] = {0., 0., 0., 0.};      // SDE: sum over rows of d loss / d var[r][o] * latent[r][k0 + c]^2
   const int bj0 = (tid & 15) * 4, bk0 = (tid >> 4) * 4;      // this thread's 4 x 4 block of a 64 x 64 weight gradient
   double* const hl = n.nh == 2 ? sh2 : sh1;                  // what the head reads
   double* const sdz1 = n.nh == 2 ? sh2 : sdz;                // where d loss / d (first pre-activation) ends up
@@ -200,6 +214,14 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
         double acc = sbh[o];
         for (int k = 0; k < MG_H; ++k) acc = fma((double)sWh[o * MG_WSTRIDE + k], hl[r * MG_ASTRIDE + k], acc);
         so[r * 16 + o] = acc;
+        if (SDE && n.kind == MG_SDE) {
+          double var = 0.;
+          for (int k = 0; k < MG_H; ++k) {
+            const double l = hl[r * MG_ASTRIDE + k];
+            var = fma(l * l, sE2[k * 16 + o], var);
+          }
+          sdf[r * 16 + o] = var + 1e-6;
+        }
       }
     }
     __syncthreads();
@@ -218,6 +240,20 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
           en += 0.5 + MG_LOG_SQRT_2PI + ls;
           so[r * 16 + c] = dlp * (diff / var);                               // d log_prob / d mean
           sdf[r * 16 + c] = dlp * (diff * diff / var - 1.) + den;          // d log_prob / d log_std, d entropy / d log_std = 1
+        }
+        if (live && a.lp != nullptr) a.lp[row] = (float)lp;
+        if (live && a.ent != nullptr) a.ent[row] = (float)en;
+      } else if (SDE && n.kind == MG_SDE) {      // distributions.py:525-562: Normal(mean, sqrt(var)), log_prob and entropy summed over the actions
+        const double dlp = srow[r], den = srow[16 + r];
+        double lp = 0., en = 0.;
+        for (int c = 0; c < n.AO; ++c) {
+          const double var = sdf[r * 16 + c], lsd = 0.5 * log(var);
+          const double act = live ? (double)a.actions[(size_t)row * a.act_store + c] : 0.;
+          const double diff = act - so[r * 16 + c];
+          lp += -(diff * diff) / (2. * var) - lsd - MG_LOG_SQRT_2PI;
+          en += 0.5 + MG_LOG_SQRT_2PI + lsd;
+          so[r * 16 + c] = dlp * (diff / var);                                                  // d log_prob / d mean
+          sdf[r * 16 + c] = dlp * ((diff * diff / var - 1.) / (2. * var)) + den / (2. * var);      // d log_prob / d var, d entropy / d var
         }
         if (live && a.lp != nullptr) a.lp[row] = (float)lp;
         if (live && a.ent != nullptr) a.ent[row] = (float)en;
@@ -265,6 +301,10 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
           double h[4];
           mg_load4(hl + r * MG_ASTRIDE + k0, h);
           for (int c = 0; c < 4; ++c) accWh[c] = fma(d, h[c], accWh[c]);
+          if (SDE && n.kind == MG_SDE) {      // (the latent enters the variance as a constant: nothing goes back into it from here)
+            const double dv = sdf[r * 16 + o];
+            for (int c = 0; c < 4; ++c) accLs[c] = fma(dv, h[c] * h[c], accLs[c]);
+          }
         }
       if (tid >= 128 && tid < 144 && tid - 128 < n.AO)
         for (int r = 0; r < MG_ROWS; ++r) accb += so[r * 16 + tid - 128];
@@ -322,6 +362,9 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
     if (o < n.AO)
       for (int c = 0; c < 4; ++c)
         if (k0 + c < HL) dst[n.Wh + o * HL + k0 + c] = accWh[c];
+    // d var / d log_std[h][o] = 2 latent_h^2 exp(2 log_std[h][o]); all MG_H stored rows (a padded latent unit is exactly 0: so is its row)
+    if (SDE && n.kind == MG_SDE && o < n.AO)
+      for (int c = 0; c < 4; ++c) dst[n.ls + (k0 + c) * n.AO + o] = 2. * sE2[(k0 + c) * 16 + o] * accLs[c];
   }
   if (tid < 64) { if (tid < n.H1) dst[n.b1 + tid] = accb; }
   else if (tid < 128) { if (n.nh == 2 && tid - 64 < n.H2) dst[n.b2 + tid - 64] = accb; }
@@ -338,23 +381,23 @@ __global__ void __launch_bounds__(256) mlp_grad_fold_kernel(const double* __rest
   grad[i] = (float)s;
 }
 
-template <bool RELU>
+template <bool RELU, bool SDE = false>
 int mg_launch(MgArgs& a, int n_nets, int max_k, float* grad, void* ws, hipStream_t s) {
   const int parts = mg_parts(a.N);
   const bool bwd = grad != nullptr;
   a.part = bwd ? (double*)ws : nullptr;
-  const size_t lds = mg_lds_bytes(max_k);
+  const size_t lds = mg_lds_bytes(max_k, SDE);
   if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)mlp_fwd_bwd_kernel<RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)mlp_fwd_bwd_kernel<RELU, SDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(mlp_fwd_bwd_kernel<RELU>, dim3(parts, n_nets), dim3(MG_THREADS), lds, s, a);
+  hipLaunchKernelGGL((mlp_fwd_bwd_kernel<RELU, SDE>), dim3(parts, n_nets), dim3(MG_THREADS), lds, s, a);
   if (bwd) hipLaunchKernelGGL(mlp_grad_fold_kernel, dim3((a.n_params + 255) / 256), dim3(256), 0, s, (const double*)ws, parts, a.n_params, grad);
   return (int)hipGetLastError();
 }
 
 // 0, or the fail() code of a policy these entry points do not serve
-int mg_policy_check(const char* who, const icrl_policy_t* p, int N) {
+int mg_policy_check(const char* who, const icrl_policy_t* p, int N, bool sde = false) {
   if (p == nullptr) return fail("%s: NULL policy descriptor", who);
   if (p->arch != nullptr)
     return fail("%s: a policy described by an `arch` array is not served (arch == NULL, two hidden layers per branch with h1 == h2 <= %d)", who, MAX_H);
@@ -363,8 +406,11 @@ int mg_policy_check(const char* who, const icrl_policy_t* p, int N) {
   if (p->obs_dim < 1 || p->obs_dim > MAX_OBS) return fail("%s: obs_dim %d (1..%d)", who, p->obs_dim, MAX_OBS);
   if (p->act_dim < 1 || p->act_dim > MAX_ACT) return fail("%s: act_dim %d (1..%d)", who, p->act_dim, MAX_ACT);
   if (N < 1 || N > MG_MAX_N) return fail("%s: N = %d rows (1..%d)", who, N, MG_MAX_N);
-  const PolLayout L = make_pol_layout(p->obs_dim, p->act_dim, p->h1, p->h2, p->discrete);
-  if (p->n_params != L.n) return fail("%s: n_params %d, the layout of (%d, %d, %d, %d) has %d", who, p->n_params, p->obs_dim, p->act_dim, p->h1, p->h2, L.n);
+  if (sde && p->discrete) return fail("%s: a discrete policy has no gSDE head (Box action spaces only)", who);
+  const PolLayout L = sde ? make_sde_layout(p->obs_dim, p->act_dim, p->h1, p->h2) : make_pol_layout(p->obs_dim, p->act_dim, p->h1, p->h2, p->discrete);
+  if (p->n_params != L.n)
+    return fail("%s: n_params %d, the %slayout of (%d, %d, %d, %d) has %d", who, p->n_params, sde ? "gSDE (log_std [64, act_dim]) " : "", p->obs_dim, p->act_dim,
+                p->h1, p->h2, L.n);
   return 0;
 }
 
@@ -383,6 +429,27 @@ int mg_costnet_check(const char* who, const icrl_costnet_t* cn, int N) {
 }
 
 }  // namespace
+
+// ---- the gSDE head behind icrl_policy_sde_fwd_bwd (sde.hip: the exported entry points)
+int sde_fwd_bwd_check(const char* who, const icrl_policy_t* p, int N) { return mg_policy_check(who, p, N, true); }
+int sde_fwd_bwd_parts(int N) { return mg_parts(N); }
+int launch_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c, const float* d_log_prob,
+                       const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad, void* ws, hipStream_t s) {
+  const PolLayout L = make_sde_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2);
+  MgArgs a = {};
+  for (int b = 0; b < 3; ++b) {
+    MgNet& n = a.net[b];
+    n.K = L.O; n.H1 = L.H1; n.H2 = L.H2; n.nh = 2;
+    n.W1 = L.W1[b]; n.b1 = L.b1[b]; n.W2 = L.W2[b]; n.b2 = L.b2[b]; n.ls = L.log_std;
+  }
+  a.net[0].AO = L.A; a.net[0].kind = MG_SDE; a.net[0].Wh = L.Wa; a.net[0].bh = L.ba;
+  a.net[1].AO = 1; a.net[1].kind = MG_VALUE; a.net[1].Wh = L.Wv; a.net[1].bh = L.bv; a.net[1].d_out = d_v_r; a.net[1].out = v_r;
+  a.net[2].AO = 1; a.net[2].kind = MG_VALUE; a.net[2].Wh = L.Wc; a.net[2].bh = L.bc; a.net[2].d_out = d_v_c; a.net[2].out = v_c;
+  a.params = pol->params; a.x = obs; a.actions = actions; a.act_store = L.A; a.N = N; a.n_params = L.n;
+  a.d_lp = d_log_prob; a.d_ent = d_entropy; a.lp = log_prob; a.ent = entropy;
+  return mg_launch<false, true>(a, 3, L.O, grad, ws, s);
+}
+
 }  // namespace icrl
 
 using namespace icrl;

@@ -3024,6 +3024,57 @@ __global__ void __launch_bounds__(192) policy_forward_kernel(PolLayout pl, const
   }
 }
 
+// policy_forward_kernel with the gSDE head (policies.py use_sde; distributions.py:525-587): the three branch forwards ARE
+// policy_forward_block's (deterministic: act_raw = mean, g[0] = the policy branch's last tanh layer = latent_sde), so mean, v_r and v_c carry
+// icrl_policy_forward's bits for the same network weights.  Behind it lane a < A of wave 0 takes, over the latent units in ascending order,
+//   noise_a = sum_h latent_h E[h][a]        (E: this row's exploration matrix [MAX_H][A], or the one matrix when expl_stride == 0)
+//   var_a   = sum_h latent_h^2 exp(2 log_std[h][a]) + 1e-6
+// in float64 on the float32 latent (rounded once), action = mean + noise, log_prob = sum_a Normal(mean_a, sqrt(var_a)).log_prob(action_a).
+// PT: the transposes of the NETWORK (pl: the diagonal layout, whose log_std slot is the matrix's last row); ls: the matrix in `params`.
+template <int OCT>
+__global__ void __launch_bounds__(192) policy_forward_sde_kernel(PolLayout pl, const float* PT, const float* __restrict__ ls, const double* obs,
+                                                                 const float* __restrict__ expl, long long expl_stride, int deterministic,
+                                                                 const float* alow, const float* ahigh, float* actions, float* act_clipped,
+                                                                 float* v_r, float* v_c, float* log_prob) {
+  __shared__ ActShared sh;
+  PolRegs<OCT> R;
+  load_pol_regs<OCT>(pl, PT, R);
+  const int n = blockIdx.x, tid = threadIdx.x, A = pl.A;
+  for (int i = tid; i < MAX_OBS; i += 192) sh.x[i] = i < pl.O ? (float)obs[(size_t)n * pl.O + i] : 0.f;
+  __syncthreads();
+  policy_forward_block<OCT>(pl, R, sh, nullptr, 1, nullptr, nullptr);
+  __syncthreads();
+  if (tid < WAVE) {      // wave 0
+    double lp = 0.;
+    float act = 0.f, clip = 0.f;
+    if (tid < A) {
+      const float mean = sh.act_raw[tid];
+      const float* E = (deterministic || expl == nullptr) ? nullptr : expl + (size_t)n * (size_t)expl_stride;
+      double noise = 0., var = 0.;
+      for (int h = 0; h < pl.H2; ++h) {
+        const double l = sh.g[0][h];
+        if (E != nullptr) noise = fma(l, (double)E[h * A + tid], noise);
+        var = fma(l * l, exp(2. * (double)ls[h * A + tid]), var);
+      }
+      var += 1e-6;
+      act = E != nullptr ? (float)((double)mean + noise) : mean;
+      const double diff = (double)act - (double)mean;
+      lp = -(diff * diff) / (2. * var) - 0.5 * log(var) - 0.918938533204672741780329736406;
+      clip = act;
+      if (alow != nullptr && ahigh != nullptr) clip = fminf(fmaxf(act, alow[tid]), ahigh[tid]);
+      if (actions) actions[(size_t)n * A + tid] = act;
+      if (act_clipped) act_clipped[(size_t)n * A + tid] = clip;
+    }
+    double tot = 0.;      // in action order, every lane the same chain
+    for (int a = 0; a < A; ++a) tot += __shfl(lp, a, 64);
+    if (tid == 0) {
+      if (v_r) v_r[n] = sh.scal[0];
+      if (v_c) v_c[n] = sh.scal[1];
+      if (log_prob) log_prob[n] = (float)tot;
+    }
+  }
+}
+
 // The same forward for MANY rows (policy.evaluate_actions over the nominal / expert samples of the KL metrics, forward over a batch):
 // 16 rows per workgroup pass as fp32 MFMA tiles, exactly as rollout_multi_kernel evaluates 16 environments — every (unit, row) gets the
 // value of policy_forward_block's fmaf chain (TileRegs), the heads and the log-probability / entropy sums are taken in
@@ -3792,6 +3843,22 @@ static int bad_cn(const char* who, const icrl_costnet_t* cn) {
               cn->in_dim, MAX_CN_IN, cn->n_hidden, cn->h1, cn->h2, MAX_H, cn->obs_dim, MAX_OBS, cn->acs_dim, MAX_ACT);
 }
 
+// icrl_policy_forward_sde (sde.hip checked the descriptor): one workgroup per row at every N, the kernel icrl_policy_forward takes below
+// ROWS_KERNEL_MIN rows.  The network's transposes lie in params_t where icrl_policy_prepare leaves them for the descriptor of the network
+// alone — (params, params_t) + (MAX_H - 1) * act_dim, n_params less as much: the diagonal layout with the matrix's last row as log_std.
+int launch_policy_forward_sde(const icrl_policy_t* p, const double* obs, const float* expl, long long expl_stride, int N, int deterministic, const float* alow,
+                              const float* ahigh, float* actions, float* act_clipped, float* v_r, float* v_c, float* log_prob, hipStream_t s) {
+  const PolLayout L = make_pol_layout(p->obs_dim, p->act_dim, p->h1, p->h2, 0);
+  const float* PT = p->params_t + (MAX_H - 1) * p->act_dim;
+  if (L.O <= 32)
+    hipLaunchKernelGGL(policy_forward_sde_kernel<2>, dim3(N), dim3(192), 0, s, L, PT, (const float*)p->params, obs, expl, expl_stride, deterministic, alow,
+                       ahigh, actions, act_clipped, v_r, v_c, log_prob);
+  else
+    hipLaunchKernelGGL(policy_forward_sde_kernel<8>, dim3(N), dim3(192), 0, s, L, PT, (const float*)p->params, obs, expl, expl_stride, deterministic, alow,
+                       ahigh, actions, act_clipped, v_r, v_c, log_prob);
+  return (int)hipGetLastError();
+}
+
 }  // namespace icrl
 
 using namespace icrl;
@@ -3825,6 +3892,8 @@ extern "C" int icrl_policy_forward(const icrl_policy_t* p, const double* obs, co
                                  (hipStream_t)stream);
   if (!dims_ok(p)) return bad_dims("policy forward / evaluate", p);
   PolLayout L = make_pol_layout(p->obs_dim, p->act_dim, p->h1, p->h2, p->discrete);
+  if (p->n_params != L.n)      // (a gSDE policy's buffer — log_std a matrix — is served by icrl_policy_forward_sde / icrl_policy_sde_fwd_bwd alone)
+    return fail("policy forward / evaluate: n_params = %d, the layout of (%d, %d, %d, %d) needs %d", p->n_params, p->obs_dim, p->act_dim, p->h1, p->h2, L.n);
   if (N >= ROWS_KERNEL_MIN && !p->discrete) {
     const int grid = (N + 15) / 16 < 1024 ? (N + 15) / 16 : 1024;
     if (L.O <= 32)
@@ -3853,6 +3922,8 @@ extern "C" int icrl_policy_evaluate(const icrl_policy_t* p, const double* obs, c
     return launch_policy_generic(p, obs, nullptr, N, 1, nullptr, nullptr, nullptr, nullptr, v_r, v_c, log_prob, actions, entropy, (hipStream_t)stream);
   if (!dims_ok(p)) return bad_dims("policy forward / evaluate", p);
   PolLayout L = make_pol_layout(p->obs_dim, p->act_dim, p->h1, p->h2, p->discrete);
+  if (p->n_params != L.n)      // (a gSDE policy's buffer — log_std a matrix — is served by icrl_policy_forward_sde / icrl_policy_sde_fwd_bwd alone)
+    return fail("policy forward / evaluate: n_params = %d, the layout of (%d, %d, %d, %d) needs %d", p->n_params, p->obs_dim, p->act_dim, p->h1, p->h2, L.n);
   if (N >= ROWS_KERNEL_MIN && !p->discrete) {
     const int grid = (N + 15) / 16 < 1024 ? (N + 15) / 16 : 1024;
     if (L.O <= 32)

@@ -34,6 +34,28 @@ def refuse_batched(config, seed_batch=False):
             raise ValueError(REFUSE_RANKS.format(flag=flag))
 
 
+REFUSE_SDE_SEED_BATCH = ("--use_sde (-us): a gSDE agent runs the per-step rollout and the fine-grained update, which have no batched form; a seed batch "
+                         "(--seeds with more than one seed) does not take it (run the seeds one at a time)")
+REFUSE_SDE_CALLBACKS = ("--use_sde (-us) with {flag}: the exploration callbacks are served on the fused rollout's buffers only; a gSDE agent collects "
+                        "through the per-step loop (use one of the two)")
+REFUSE_SDE_RANKS = "--use_sde (-us): the per-rank exploration matrices and the fine-grained update are not covered by the rank collective; world_size > 1 is not served"
+
+
+def refuse_sde(config, seed_batch=False):
+    """raise, naming the flag, where `--use_sde` is not served: seed batches, the exploration callbacks, several ranks.  Called before
+    anything is launched (cpg / icrl / gail setup, the seed-batch constructors)."""
+    get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+    if not get("use_sde", False):
+        return
+    if seed_batch:
+        raise ValueError(REFUSE_SDE_SEED_BATCH)
+    for attr, flag in (("use_curiosity_driven_exploration", "--use_curiosity_driven_exploration (-ucde)"), ("use_lambda_shaping", "--use_lambda_shaping (-uls)")):
+        if get(attr, False):
+            raise ValueError(REFUSE_SDE_CALLBACKS.format(flag=flag))
+    if (get("world_size", 1) or 1) > 1:
+        raise ValueError(REFUSE_SDE_RANKS)
+
+
 class RegressionNet:
     """MLP(in_dim -> h1 -> ReLU -> h2 -> ReLU -> out_dim) with its Adam state as flat device buffers (torch's state_dict order)."""
 

@@ -47,6 +47,9 @@ def setup(config, log=print):
     from the run's own streams, as in cpg) and config.disc_perms_from_streams (the discriminator's permutation likewise)."""
     logger.configure()
     rank = getattr(config, "rank", 0)
+    if getattr(config, "use_sde", False):      # -us over several ranks: refused before anything is launched
+        from . import exploration
+        exploration.refuse_sde(config)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
     envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=False,

@@ -30,6 +30,9 @@ def setup(config):
     """everything of icrl() before the loop (ref: icrl/icrl.py:45-197): env stacks, expert data, constraint net, nominal agent."""
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     use_curiosity = bool(getattr(config, "use_curiosity_driven_exploration", False))
+    if getattr(config, "use_sde", False):      # -us with -ucde or several ranks: refused before anything is launched
+        from . import exploration
+        exploration.refuse_sde(config)
     if use_curiosity:      # refused before anything is launched where the callback is not served
         from . import exploration
         exploration.refuse_batched(config)

@@ -29,7 +29,8 @@ DEPTH_MAX = 4  # layers of the shared trunk / of one branch on the generic-shape
 
 
 def state_dict_names(discrete, n_hidden=2, n_shared=0):
-    """parameter names in the reference's state_dict order; n_hidden: one depth for the three branches or a (pi, vf, cvf) triple."""
+    """parameter names in the reference's state_dict order; n_hidden: one depth for the three branches or a (pi, vf, cvf) triple.
+    (A gSDE policy has the same names: its `log_std` is a matrix [H, A] instead of a vector [A].)"""
     depths = (n_hidden,) * 3 if isinstance(n_hidden, int) else tuple(n_hidden)
     names = [] if discrete else ["log_std"]
     for k in range(n_shared):
@@ -44,7 +45,7 @@ def state_dict_names(discrete, n_hidden=2, n_shared=0):
 
 class ActorTwoCriticsPolicy:
     def __init__(self, observation_space, action_space, lr_schedule=None, net_arch=None, log_std_init=0.0,
-                 ortho_init=True, optimizer_kwargs=None, device="cuda"):
+                 ortho_init=True, optimizer_kwargs=None, device="cuda", use_sde=False):
         self.observation_space, self.action_space = observation_space, action_space
         self.device = torch.device(device)
         self.obs_dim = int(observation_space.shape[0])
@@ -80,6 +81,21 @@ class ActorTwoCriticsPolicy:
             for b in BRANCHES:
                 desc += [len(self.layers[b]), *self.layers[b]]
             self.arch = np.ascontiguousarray(desc, dtype=np.int32)
+        # gSDE (ref: distributions.py:408-601, policies.py:434-441, 671-690 with PPOLagrangian's defaults: full_std, exp, no squashing, no
+        # sde_net_arch): log_std is a matrix, logical [H, A] over the policy branch's last layer, STORED [64, A] zero-padded and still first in
+        # the flat buffer.  A padded latent unit is exactly 0, so its row adds exactly 0 to every variance, receives a zero gradient and keeps
+        # zero Adam moments, as the padding above does.  Served by icrl_policy_forward_sde / icrl_policy_sde_fwd_bwd (csrc/sde.hip) alone.
+        self.use_sde = bool(use_sde)
+        if self.use_sde:
+            if self.discrete:
+                raise NotImplementedError("use_sde: gSDE needs a Box action space (the reference's StateDependentNoiseDistribution is continuous)")
+            if self.kind != "fast":
+                raise NotImplementedError(f"use_sde: gSDE is served for net_arch without a shared trunk, two hidden layers per branch and widths <= {HW} "
+                                          f"(the limit of csrc/sde.hip); got {net_arch}")
+            if self.obs_dim > 128 or self.act_dim > 16:
+                raise NotImplementedError(f"use_sde: gSDE is served up to obs_dim 128 and act_dim 16; got ({self.obs_dim}, {self.act_dim})")
+        self.sde_latent = self.layers["policy_net"][-1] if self.use_sde else 0
+        self.sde_E0 = self.sde_E = None
         self.optimizer_kwargs = dict(eps=1e-5) if optimizer_kwargs is None else dict(optimizer_kwargs)  # ref: policies.py:357-361
         self.lr_schedule = lr_schedule
         sd = self._init_host(log_std_init, ortho_init)
@@ -96,6 +112,8 @@ class ActorTwoCriticsPolicy:
         self.prepare()
 
     def _physical_shape(self, name, shp):
+        if name == "log_std" and self.use_sde:
+            return (HW, shp[1])
         if name == "log_std" or self.kind == "arch":
             return shp
         if name.startswith("mlp_extractor."):
@@ -135,8 +153,10 @@ class ActorTwoCriticsPolicy:
                 if k < len(self.layers[b]):
                     lins[b].append(Lin(last[b], self.layers[b][k]))
                     last[b] = self.layers[b][k]
-        heads = OrderedDict(action_net=Lin(last["policy_net"], self.act_dim), value_net=Lin(last["value_net"], 1),
-                            cost_value_net=Lin(last["cost_value_net"], 1))
+        heads = OrderedDict(action_net=Lin(last["policy_net"], self.act_dim))
+        if self.use_sde:                  # proba_distribution_net draws its first exploration matrices here (sample_weights: two rsamples)
+            torch.empty(last["policy_net"], self.act_dim).normal_(); torch.empty(1, last["policy_net"], self.act_dim).normal_()
+        heads["value_net"], heads["cost_value_net"] = Lin(last["value_net"], 1), Lin(last["cost_value_net"], 1)
         if ortho_init:                    # module.apply order: shared_net, policy_net, value_net, cost_value_net, then the heads
             for lin in shared + [lin for b in BRANCHES for lin in lins[b]]:
                 torch.nn.init.orthogonal_(lin.weight, gain=math.sqrt(2)); lin.bias.data.fill_(0.0)
@@ -144,7 +164,7 @@ class ActorTwoCriticsPolicy:
                 torch.nn.init.orthogonal_(lin.weight, gain=g); lin.bias.data.fill_(0.0)
         sd = OrderedDict()
         if not self.discrete:
-            sd["log_std"] = torch.ones(self.act_dim) * log_std_init
+            sd["log_std"] = (torch.ones(last["policy_net"], self.act_dim) if self.use_sde else torch.ones(self.act_dim)) * log_std_init
         for k, lin in enumerate(shared):
             sd[f"mlp_extractor.shared_net.{2 * k}.weight"] = lin.weight.data
             sd[f"mlp_extractor.shared_net.{2 * k}.bias"] = lin.bias.data
@@ -157,7 +177,12 @@ class ActorTwoCriticsPolicy:
         return sd
 
     # ---- C-ABI descriptor -------------------------------------------------------------------------------------
-    def struct(self):
+    def struct(self, sde=False):
+        """sde: the caller is one of the gSDE entry points' wrappers.  Every other call site builds the descriptor for an entry point that
+        reads the diagonal layout: a gSDE policy is refused here, before any device call."""
+        if self.use_sde and not sde:
+            raise NotImplementedError("use_sde: a gSDE policy (log_std [H, A]) is served by icrl_policy_forward_sde / icrl_policy_sde_fwd_bwd alone — the per-step "
+                                      "rollout and the fine-grained update; the fused launches and the other entry points read the diagonal layout")
         return PolicyT(self.obs_dim, self.act_dim, self.h1, self.h2, int(self.discrete), self.n_params, p(self.params), p(self.params_t),
                        None if self.arch is None else self.arch.ctypes.data)
 
@@ -170,14 +195,32 @@ class ActorTwoCriticsPolicy:
 
     def prepare(self):
         """refresh the transposed weight copy the rollout kernels read (call after params change)."""
-        s = self.struct()
+        if self.device.type == "cpu":      # storage only (state-dict handling on a host without a device): nothing reads a transposed copy there
+            return
+        if self.use_sde:      # the network alone, as a diagonal-layout descriptor whose log_std slot is the matrix's last row (include/icrl_hip.h)
+            skip = (HW - 1) * self.act_dim
+            s = PolicyT(self.obs_dim, self.act_dim, self.h1, self.h2, 0, self.n_params - skip, p(self.params[skip:]), p(self.params_t[skip:]), None)
+        else:
+            s = self.struct()
         _lib.check(_lib.lib().icrl_policy_prepare(_lib.byref(s), _lib.current_stream()), "icrl_policy_prepare")
 
     # ---- state dict (reference names; ref: expert_data/*/files/best_model.zip:policy.pth) --------------------------
     def state_dict(self):
         return self._split(self.params.detach().cpu())
 
+    def check_state_dict_kind(self, sd, where="state dict"):
+        """raise, with both kinds named, when `sd` holds the other action distribution's log_std (a vector [A]: diagonal Gaussian; a matrix [H, A]: gSDE)."""
+        ls = sd.get("log_std") if hasattr(sd, "get") else None
+        if ls is None or self.discrete:
+            return
+        theirs = np.ndim(ls) == 2
+        if theirs != self.use_sde:
+            kind = lambda sde: "a gSDE policy (use_sde=True, log_std [H, A])" if sde else "a diagonal-Gaussian policy (use_sde=False, log_std [A])"
+            raise ValueError(f"{where} holds {kind(theirs)} with log_std of shape {tuple(np.shape(ls))}; this agent has {kind(self.use_sde)}. Build or load the "
+                             f"agent with use_sde={theirs}.")
+
     def load_state_dict(self, sd):
+        self.check_state_dict_kind(sd)
         flat = torch.cat([self._pad(k, sd[k]).reshape(-1) for k in self.shapes])
         assert flat.numel() == self.n_params
         self.params.copy_(flat.to(self.device))
@@ -208,7 +251,59 @@ class ActorTwoCriticsPolicy:
 
     @property
     def log_std(self):
+        if self.use_sde:      # the real [H, A] block (a view)
+            return self.params[:HW * self.act_dim].view(HW, self.act_dim)[:self.sde_latent]
         return None if self.discrete else self.params[:self.act_dim]
+
+    # ---- gSDE ---------------------------------------------------------------------------------------------------------
+    def reset_noise(self, n_envs=1, streams=None):
+        """ref: policies.py:434-441 -> distributions.py:483-496 — draw the exploration matrices E0 [H, A] and E [n_envs, H, A] from
+        Normal(0, exp(log_std)); kept on the device in the stored [64, A] shape (zero rows beyond H).  `streams.sde_noise(shape)`, where the
+        agent's streams object has it, gives the standard normals (teacher forcing); otherwise torch draws them on the device."""
+        assert self.use_sde, "reset_noise: not a gSDE policy"
+        H, A, dev = self.sde_latent, self.act_dim, self.device
+        draw = getattr(streams, "sde_noise", None) if streams is not None else None
+        def normals(shape):
+            if draw is None:
+                return torch.randn(shape, device=dev)
+            z = draw(shape)
+            z = z if torch.is_tensor(z) else torch.as_tensor(np.asarray(z, np.float32))
+            return z.to(device=dev, dtype=torch.float32).reshape(shape)
+        std = torch.exp(self.log_std)
+        self.set_noise(normals((H, A)) * std, normals((int(n_envs), H, A)) * std)
+
+    def set_noise(self, E0, E):
+        """install exploration matrices given in their logical shapes [H, A] and [n, H, A]."""
+        H, A, dev = self.sde_latent, self.act_dim, self.device
+        E0 = torch.as_tensor(E0, device=dev).float().reshape(H, A)
+        E = torch.as_tensor(E, device=dev).float().reshape(-1, H, A)
+        self.sde_E0 = torch.zeros(HW, A, device=dev); self.sde_E0[:H] = E0
+        self.sde_E = torch.zeros(E.shape[0], HW, A, device=dev); self.sde_E[:, :H] = E
+
+    def _forward_sde(self, obs, deterministic, clip):
+        """icrl_policy_forward_sde with the matrices get_noise picks (distributions.py:577-587): E0 for one row or when the row count is not
+        the number of per-env matrices, else row i's own."""
+        dev = self.device
+        n = obs.shape[0]
+        expl, stride = None, 0
+        if not deterministic:
+            if self.sde_E is None:
+                self.reset_noise(1)
+            if n == 1 or n != self.sde_E.shape[0]:
+                expl = self.sde_E0
+            else:
+                expl, stride = self.sde_E, HW * self.act_dim
+        actions = torch.empty(n, self.act_dim, device=dev); clipped = torch.empty(n, self.act_dim, device=dev)
+        v_r, v_c, lp = (torch.empty(n, device=dev) for _ in range(3))
+        lo = hi = None
+        if clip:
+            lo = torch.as_tensor(self.action_space.low, device=dev).float().contiguous()
+            hi = torch.as_tensor(self.action_space.high, device=dev).float().contiguous()
+        s = self.struct(sde=True)
+        _lib.check(_lib.lib().icrl_policy_forward_sde(_lib.byref(s), p(obs), p(expl), stride, n, int(deterministic), p(lo), p(hi), p(actions), p(clipped),
+                                                      p(v_r), p(v_c), p(lp), _lib.current_stream()), "icrl_policy_forward_sde")
+        self.last_clipped = clipped
+        return actions, v_r.reshape(-1, 1), v_c.reshape(-1, 1), lp
 
     # ---- inference ------------------------------------------------------------------------------------------------
     def forward(self, obs, deterministic=False, noise=None, clip=True):
@@ -218,6 +313,8 @@ class ActorTwoCriticsPolicy:
         dev = self.device
         obs = torch.as_tensor(obs, device=dev).to(torch.float64).reshape(-1, self.obs_dim).contiguous()
         n = obs.shape[0]
+        if self.use_sde:      # (`noise` has no meaning here: the exploration matrices are the policy's state, reset_noise / set_noise)
+            return self._forward_sde(obs, deterministic, clip)
         if noise is None and not deterministic:
             noise = torch.rand(n, device=dev) if self.discrete else torch.randn(n, self.act_dim, device=dev)
         if noise is not None:
@@ -249,6 +346,11 @@ class ActorTwoCriticsPolicy:
         actions = torch.as_tensor(actions, device=dev).to(torch.float32).reshape(-1, a_store).contiguous()
         n = obs.shape[0]
         v_r, v_c, lp, ent = (torch.empty(n, device=dev) for _ in range(4))
+        if self.use_sde:      # the update's own kernel, forward only (float64 rounded once; reads `params`)
+            s, obs32 = self.struct(sde=True), obs.float().contiguous()
+            _lib.check(_lib.lib().icrl_policy_sde_fwd_bwd(_lib.byref(s), p(obs32), p(actions), n, None, None, None, None, p(v_r), p(v_c), p(lp), p(ent), None,
+                                                          None, 0, _lib.current_stream()), "icrl_policy_sde_fwd_bwd")
+            return v_r.reshape(-1, 1), v_c.reshape(-1, 1), lp, ent
         s = self.struct()
         _lib.check(_lib.lib().icrl_policy_evaluate(_lib.byref(s), p(obs), p(actions), n, p(v_r), p(v_c), p(lp), p(ent),
                                                    _lib.current_stream()), "icrl_policy_evaluate")

@@ -10,6 +10,8 @@ the work is enqueued as kernels of libicrl_hip.so:
                       no host sync)
   train            -> icrl_ppo_lag_train   (ONE persistent launch for all epochs x minibatches); the dual variable is one
                       float32 scalar updated on the host (dual_variable.py)
+A gSDE agent (use_sde=True) runs neither fused launch: its rollout is the per-step loop around icrl_policy_forward_sde and its
+update the fine-grained loop around icrl_policy_sde_fwd_bwd (_train_sde) — both on the device, one launch per piece.
 """
 import os
 import time
@@ -54,8 +56,9 @@ class PPOLagrangian:
                  penalty_learning_rate=0.01, penalty_min_value=None, update_penalty_after=1, budget=0.,
                  tensorboard_log=None, create_eval_env=False, pid_kwargs=None, policy_kwargs=None, verbose=0, seed=None,
                  device="cuda", _init_setup_model=True, action_noise="device", permutation="numpy", streams=None, episode_stats=None):
-        if use_sde:
-            raise NotImplementedError("gSDE is outside the hot path (no BASELINE config uses it)")
+        # gSDE (ref: ppo_lag.py:207-213, on_policy_algorithm.py:362-370): the policy keeps log_std [H, A] and its exploration matrices, which are redrawn at the
+        # start of every rollout and every sde_sample_freq steps (-1: only at the start)
+        self.use_sde, self.sde_sample_freq = bool(use_sde), int(sde_sample_freq)
         if policy not in ("TwoCriticsMlpPolicy", ActorTwoCriticsPolicy):
             raise NotImplementedError(f"policy {policy!r}: only TwoCriticsMlpPolicy is on the ICRL hot path")
         self.env: VecEnv = env
@@ -104,7 +107,7 @@ class PPOLagrangian:
                                                     self.reward_gamma, self.reward_gae_lambda, self.cost_gamma,
                                                     self.cost_gae_lambda, n_envs=self.n_envs)
         self.policy = ActorTwoCriticsPolicy(self.observation_space, self.action_space, self.lr_schedule,
-                                            device=self.device, **self.policy_kwargs)
+                                            device=self.device, **dict(self.policy_kwargs, use_sde=getattr(self, "use_sde", False)))
         if self.algo_type == "lagrangian":
             self.dual = DualVariable(self.budget, self.penalty_learning_rate, self.penalty_initial_value, self.penalty_min_value)
         elif self.algo_type == "pidlagrangian":
@@ -249,6 +252,8 @@ class PPOLagrangian:
     def collect_rollouts(self, env, callback, rollout_buffer, n_rollout_steps, cost_function="cost", noise=None):
         """ref: on_policy_algorithm.py:340-421."""
         assert self._last_obs is not None, "No previous observation was provided"
+        if self.use_sde:      # the exploration matrices are redrawn between steps: always the per-step loop, around icrl_policy_forward_sde
+            return self._collect_rollouts_stepped(env, callback, rollout_buffer, n_rollout_steps, cost_function, None)
         if not self._fused_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
             if self._host_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
                 return self._collect_rollouts_host(env, callback, rollout_buffer, n_rollout_steps, noise)
@@ -460,9 +465,13 @@ class PPOLagrangian:
         is_box = isinstance(self.action_space, spaces.Box)
         norm_env = env if isinstance(env, VecNormalizeWithCost) else None
         v_r = v_c = dones = None
-        if noise is None and self.streams is not None:      # teacher-forced streams serve this path like the fused one
+        if self.use_sde:      # ref: on_policy_algorithm.py:362-370 — one matrix per env, drawn here and on the sde_sample_freq cadence below
+            self.policy.reset_noise(env.num_envs, self.streams)
+        elif noise is None and self.streams is not None:      # teacher-forced streams serve this path like the fused one
             noise = self._draw_action_noise(n_rollout_steps)
         for t in range(n_rollout_steps):
+            if self.use_sde and self.sde_sample_freq > 0 and t % self.sde_sample_freq == 0:
+                self.policy.reset_noise(env.num_envs, self.streams)
             actions, v_r, v_c, log_probs = self.policy.forward(self._last_obs, noise=None if noise is None else noise[t])
             clipped = self.policy.last_clipped if is_box else actions
             new_obs, rewards, dones, infos = env.step(clipped)
@@ -592,7 +601,7 @@ class PPOLagrangian:
                     policy_kwargs=dict(net_arch=[*self.policy.shared, dict(pi=list(self.policy.layers["policy_net"]), vf=list(self.policy.layers["value_net"]),
                                                                            cvf=list(self.policy.layers["cost_value_net"]))]))
         # the rest of what the reference's __init__ leaves in self.__dict__ and its load() / _setup_model() / predict() read
-        data.update(verbose=int(getattr(self, "verbose", 0)), use_sde=False, sde_sample_freq=-1, tensorboard_log=None, action_noise=None,
+        data.update(verbose=int(getattr(self, "verbose", 0)), use_sde=bool(self.use_sde), sde_sample_freq=int(self.sde_sample_freq), tensorboard_log=None, action_noise=None,
                     _total_timesteps=int(getattr(self, "_total_timesteps", 0) or 0), _episode_num=0, start_time=None,
                     _current_progress_remaining=float(getattr(self, "_current_progress_remaining", 1.0)))
         data.update(policy_class=U.sb3_policy_class_entry(), observation_space=U.sb3_space_entry(self.observation_space),
@@ -672,6 +681,7 @@ class PPOLagrangian:
             if callable(getattr(model, k, None)) is False and not isinstance(getattr(model, k, None), (int, float)):
                 setattr(model, k, 0.2 if k == "clip_range" else None)
         model.policy_kwargs = dict(net_arch=net_arch)
+        model.use_sde, model.sde_sample_freq = bool(data.get("use_sde", False)), int(data.get("sde_sample_freq", -1))
         model.__dict__.update(kwargs)
         model._setup_model()
         model.load_parameters(path, dual=False)
@@ -684,7 +694,9 @@ class PPOLagrangian:
         with zipfile.ZipFile(str(path)) as z:
             names = set(z.namelist())
             rd = lambda n: torch.load(io.BytesIO(z.read(n)), map_location="cpu", weights_only=False)
-            self.policy.load_state_dict(rd("policy.pth"))
+            sd = rd("policy.pth")
+            self.policy.check_state_dict_kind(sd, str(path))      # a diagonal archive into a gSDE agent (or the reverse): a message, not a shape assert
+            self.policy.load_state_dict(sd)
             if "policy.optimizer.pth" in names:
                 self.policy.load_optimizer_state_dict(rd("policy.optimizer.pth"))
             if dual and hasattr(self.dual, "load_state_dict"):
@@ -735,6 +747,8 @@ class PPOLagrangian:
 
     def train(self, perms=None):
         """ref: ppo_lag.py:177-338."""
+        if self.use_sde:
+            return self._train_sde(perms)
         if perms is None and self._train_is_epochwise():
             return self._train_epochwise()
         job = self._train_begin(perms)
@@ -806,6 +820,79 @@ class PPOLagrangian:
         job["rng_state"] = states + [states[-1]] * (E - len(states))  # (indexable by executed epochs like the single launch's list)
         self._train_end(job, host=host)
 
+    def _train_sde(self, perms=None):
+        """train() of a gSDE agent (ref: ppo_lag.py:177-338): the fine-grained loop of INTEGRATION.md section 3a on the device, per minibatch
+          icrl_minibatch_gather -> icrl_policy_sde_fwd_bwd (forward) -> icrl_ppo_lag_loss_fwd_bwd -> icrl_policy_sde_fwd_bwd (backward; it
+          recomputes the forward) -> icrl_clip_adam_step,
+        with the permutations, the minibatch boundaries (the last one of an epoch may be short), the target-KL stop per epoch, the dual-variable step
+        and the logged keys of the fused path (_train_begin / _train_end are shared).  The loss normalises the advantages itself, so no separate
+        icrl_adv_stats launch is made.  The minibatches' loss terms stay on the device and are read ONCE PER EPOCH, for the KL test.
+        NOT made: the reference's reset_noise(batch_size) before every minibatch (ppo_lag.py:207-211).  That draw changes the exploration
+        matrices, which evaluate_actions and the loss never read and which the next rollout replaces before its first step; only the position of
+        the global generator differs afterwards."""
+        job = self._train_begin(perms)
+        rb, pol, dev, ws, L, b = self.rollout_buffer, self.policy, self.device, self._train_ws, _lib.lib(), _lib.byref
+        n, B, E = rb.buffer_size * rb.n_envs, int(self.batch_size), int(self.n_epochs)
+        starts = list(range(0, n, B))
+        if n - starts[-1] < 2:
+            raise ValueError(f"use_sde: the last minibatch of an epoch would hold {n - starts[-1]} row (rollout of {n} rows, batch_size {B}); the loss needs 2")
+        s = job["ps"]
+        if "sde" not in ws:
+            f = lambda *shape: torch.zeros(*shape, device=dev)
+            need = int(L.icrl_policy_sde_fwd_bwd_ws_bytes(b(s), B))
+            if need == 0:
+                _lib.check(1, "icrl_policy_sde_fwd_bwd_ws_bytes")
+            ws["sde"] = dict(obs=f(B, pol.obs_dim), act=f(B, pol.act_dim), rows={k: f(B) for k in ("old_lp", "adv_r", "adv_c", "ret_r", "ret_c", "old_vr", "old_vc", "v_r", "v_c",
+                                                                                                "lp", "ent", "d_lp", "d_vr", "d_vc", "d_ent")},
+                             grad=f(pol.n_params), fb=torch.zeros((need + 7) // 8, dtype=torch.float64, device=dev), work=f(256), out2=f(2),
+                             terms=f(E, len(starts), 8))
+        w = ws["sde"]
+        r, terms, st_ = w["rows"], w["terms"], _lib.current_stream()
+        terms.zero_()
+        vclip_r = p(r["old_vr"]) if self.clip_range_reward_vf is not None else None
+        vclip_c = p(r["old_vc"]) if self.clip_range_cost_vf is not None else None
+        ev = None
+        if getattr(self, "train_events", None) is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        st = np.zeros(32 + E, np.float32)
+        sums, steps, early_stop_epoch, last = np.zeros(8, np.float64), 0, E, None
+        hook = getattr(self, "sde_step_hook", None)      # optional callable(epoch, minibatch) after every optimiser step (trajectory checks)
+        for e in range(E):
+            for i, lo in enumerate(starts):
+                m = min(B, n - lo)
+                idx = job["perms"][e, lo:lo + m]
+                _lib.check(L.icrl_minibatch_gather(b(job["bs"]), idx.data_ptr(), m, p(w["obs"]), p(w["act"]), p(r["old_lp"]), p(r["adv_r"]), p(r["adv_c"]), p(r["ret_r"]),
+                                                   p(r["ret_c"]), p(r["old_vr"]), p(r["old_vc"]), st_), "icrl_minibatch_gather")
+                _lib.check(L.icrl_policy_sde_fwd_bwd(b(s), p(w["obs"]), p(w["act"]), m, None, None, None, None, p(r["v_r"]), p(r["v_c"]), p(r["lp"]), p(r["ent"]), None,
+                                                     None, 0, st_), "icrl_policy_sde_fwd_bwd")
+                _lib.check(L.icrl_ppo_lag_loss_fwd_bwd(p(r["lp"]), p(r["old_lp"]), p(r["adv_r"]), p(r["adv_c"]), p(r["v_r"]), p(r["v_c"]), p(r["ret_r"]), p(r["ret_c"]),
+                                                       vclip_r, vclip_c, p(r["ent"]), p(ws["nu"]), b(job["hp"]), m, terms[e, i].data_ptr(), p(r["d_lp"]), p(r["d_vr"]),
+                                                       p(r["d_vc"]), p(r["d_ent"]), st_), "icrl_ppo_lag_loss_fwd_bwd")
+                _lib.check(L.icrl_policy_sde_fwd_bwd(b(s), p(w["obs"]), p(w["act"]), m, p(r["d_vr"]), p(r["d_vc"]), p(r["d_lp"]), p(r["d_ent"]), None, None, None, None,
+                                                     p(w["grad"]), p(w["fb"]), w["fb"].numel() * 8, st_), "icrl_policy_sde_fwd_bwd")
+                _lib.check(L.icrl_clip_adam_step(p(pol.params), p(w["grad"]), p(pol.exp_avg), p(pol.exp_avg_sq), p(ws["t"]), pol.n_params, b(job["hp"]), p(w["work"]),
+                                                 p(w["out2"]), st_), "icrl_clip_adam_step")
+                if hook is not None:
+                    hook(e, i)
+            host = terms[e].cpu().numpy().astype(np.float64)      # [minibatches, 8]: the one read of this epoch
+            sums += host.sum(axis=0)
+            steps += len(starts)
+            last = host[-1]
+            st[32 + e] = st[7] = np.float32(np.mean(host[:, 5].astype(np.float32)))
+            if self.target_kl is not None and st[7] > 1.5 * self.target_kl:
+                early_stop_epoch = e
+                break
+        if ev is not None:
+            ev[1].record()
+        job["ev"] = ev
+        # one statistics row as the fused launch leaves it (_train_end): sums over the steps, the last epoch's KL, the last minibatch's loss
+        st[0], st[1] = early_stop_epoch, steps
+        st[2], st[3], st[4], st[5], st[6] = sums[4], sums[1], sums[2], sums[3], sums[6]
+        st[8] = last[0]      # (terms8[0] is the whole loss: the critics' weighted parts are inside it)
+        tail = self.train_readback().cpu().numpy()
+        self._train_end(job, host=np.concatenate([st.astype(np.float64), tail[32 + E:]]))
+
     # train() in three pieces (see _rollout_begin): descriptors, the launch (single here, batched in seed_batch.py), read-back + logs
     def _train_begin(self, perms=None, device_perms=None):
         lr = float(self.lr_schedule(self._current_progress_remaining))
@@ -839,7 +926,7 @@ class PPOLagrangian:
         hp = PpoHyperT(int(self.batch_size), int(self.n_epochs), int(self.target_kl is not None), int(getattr(self, "profile_phases", 0)) | {"tiles": 2, "rows": 4, "rows1": 12, "pairs": 16, "halves": 32}.get(getattr(self, "train_kernel", "auto"), 0), clip_range, float(self.ent_coef),
                        float(self.reward_vf_coef), float(self.cost_vf_coef), float(self.max_grad_norm),
                        float(self.target_kl or 0.0), crv, ccv, lr, 0.9, 0.999, float(pol.optimizer_kwargs.get("eps", 1e-8)))
-        return dict(ps=pol.struct(), bs=rb.struct(), hp=hp, perms=perms, rng_state=rng_state, injected=injected, clip_range=clip_range,
+        return dict(ps=pol.struct(sde=pol.use_sde), bs=rb.struct(), hp=hp, perms=perms, rng_state=rng_state, injected=injected, clip_range=clip_range,
                     clip_range_reward_vf=None if self.clip_range_reward_vf is None else crv, clip_range_cost_vf=None if self.clip_range_cost_vf is None else ccv)
 
     # The three workgroups of an update exchange one granule per optimiser step through the first 512 bytes of the `sync` workspace, and

@@ -140,6 +140,7 @@ class SeedBatch:
             configs = list(configs)
             for c in configs:
                 exploration.refuse_batched(c, seed_batch=True)
+                exploration.refuse_sde(c, seed_batch=True)
         self.states = setup_runs(configs, on_setup) if states is None else states
         if any(isinstance(st["train_env"].unwrapped, HostVecEnv) for st in self.states):
             _refuse_host_envs(*[st["config"].train_env_id for st in self.states])
@@ -554,6 +555,7 @@ class CpgSeedBatch(SeedBatch):
         c0 = configs[0]
         for c in configs:
             exploration.refuse_batched(c, seed_batch=True)
+            exploration.refuse_sde(c, seed_batch=True)
         if os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") not in ("", "0"):
             raise ValueError("seed batch: ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step rollout loop, which has no batched form")
         for c in configs:
@@ -632,6 +634,8 @@ class GailSeedBatch(SeedBatch):
             raise ValueError("seed batch: no runs")
         c0 = configs[0]
         for c in configs:      # ---- refused before anything is set up
+            exploration.refuse_sde(c, seed_batch=True)
+        for c in configs:
             _refuse_host_envs(c.train_env_id, c.eval_env_id)
             if getattr(c, "env_module", None) or getattr(c, "dummy_vec_env", False):
                 raise ValueError("seed batch: --env_module / --dummy_vec_env select host envs; the batched launches step device envs only")

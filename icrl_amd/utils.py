@@ -304,7 +304,9 @@ class SteppedEpisodeRun:
         dev, max_steps = senv.device, senv.max_steps
         A = 1 if pol.discrete else pol.act_dim
         rows = n_episodes * max_steps
-        if noise is None and not deterministic:
+        if getattr(pol, "use_sde", False):      # the exploration matrix is the policy's own (get_noise: E0 for one env), not a per-step draw
+            noise = None
+        elif noise is None and not deterministic:
             noise = torch.rand(rows, device=dev) if pol.discrete else torch.randn(rows, A, device=dev)
         if noise is not None:
             noise = torch.as_tensor(noise, device=dev).float().reshape(rows, -1).contiguous()
@@ -450,6 +452,10 @@ class HostEpisodeRun:
 def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel, chain=False):
     """chain: settle early-ending episodes' positions inside ONE launch where it serves (what sample_from_agent and evaluate_policy
     ask for); the default keeps the pass-by-pass protocol of EpisodeRun.prepare / launch / finish, with run.passes counting launches."""
+    if getattr(agent.policy, "use_sde", False):     # gSDE: the per-step loop around icrl_policy_forward_sde (the sampler kernels hold the diagonal head)
+        if env.unwrapped.max_steps is None:
+            raise ValueError("sampling / evaluation with use_sde needs the env's episode limit (max_episode_steps)")
+        return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
     if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: one launch per env step, or the reference's own loop
         if env.unwrapped.max_steps is None:
             raise ValueError("sampling / evaluation over a host env needs its episode limit: register it with max_episode_steps "
@@ -488,7 +494,7 @@ def sample_and_evaluate(agent, sampling_env, n_rollouts, eval_env, n_eval_episod
     deterministic, noise=eval_noise) as ONE launch of two jobs (icrl_sample_episodes_chain) where both serve, else one after the other;
     returns the pair of their results.  The caller vouches that nothing the evaluation reads (policy, normaliser statistics of eval_env)
     changes between the two phases it replaces.  Noise is drawn in the sequential order: sampling first, then evaluation."""
-    if episodes_fusable(sampling_env, eval_env):
+    if episodes_fusable(sampling_env, eval_env) and not getattr(agent.policy, "use_sde", False):
         s_run = EpisodeRun(agent, sampling_env, n_rollouts, False, sample_noise, parallel)
         e_run = EpisodeRun(agent, eval_env, n_eval_episodes, deterministic, eval_noise, False)
         if s_run.chain_ok() and e_run.chain_ok() and launch_chain([s_run.prepare_chain(), e_run.prepare_chain()]):

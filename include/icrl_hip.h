@@ -858,6 +858,30 @@ size_t icrl_policy_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
 int icrl_policy_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
                         const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
                         void* ws, long long ws_bytes, void* stream);
+/* The gSDE forms of icrl_policy_forward and icrl_policy_fwd_bwd (csrc/sde.hip; stable_baselines3/common/distributions.py:408-601 with what
+ * PPOLagrangian(use_sde=True) builds: full_std, exp, no squashing, learn_features = False).  A gSDE policy keeps the ordinary descriptor; its
+ * buffer holds log_std as a MATRIX — logical [H, A] over the policy branch's last tanh layer (the latent), stored [64, A] with zero rows beyond
+ * H, still the first tensor — and n_params = the diagonal layout's + 63 * act_dim says so: every other entry point that checks n_params refuses it.
+ *   variance of action a = sum_h latent_h^2 exp(2 log_std[h][a]) + 1e-6, the latent units in ascending order, the latent DETACHED in it.
+ * icrl_policy_forward_sde: obs [N, obs_dim] float64 -> actions = mean + latent . E (the mean when deterministic), their clip to
+ * [action_low, action_high] (both NULL: act_clipped = actions), v_r, v_c, log_prob [N]; any output may be NULL.  expl: exploration matrices
+ * [64, A] float32 row-major (zero rows beyond H are never read), row i's at expl + i * expl_stride: expl_stride = 64 * act_dim gives one matrix per
+ * row, 0 one matrix for all rows; NULL with deterministic only.  One workgroup per row at every N; the three branch forwards are
+ * icrl_policy_forward's own (below 64 rows), so mean, v_r and v_c carry its bits for the same network weights; the head is float64 on the
+ * float32 latent, rounded once.  Reads params_t for the network: icrl_policy_prepare on the descriptor of the network alone — params and
+ * params_t + 63 * act_dim, n_params - 63 * act_dim — leaves it there (ActorTwoCriticsPolicy.prepare does that).
+ * icrl_policy_sde_fwd_bwd: the contract of icrl_policy_fwd_bwd word for word — float64 on float32 parameters rounded once, grad OVERWRITTEN in
+ * the layout of pol->params (the [64, A] log_std block first, its padded rows exactly 0; log_std takes the variance part of log_prob and entropy,
+ * the network the mean part only), NULL d_* = zeros, grad NULL = forward only with the same output bits, fixed-order tile sums through ws, plain
+ * launches, no atomics.  Served: arch == NULL, continuous, h1 == h2 <= 64, obs_dim <= 128, act_dim <= 16, 1 <= N <= 65536; everything else
+ * returns hipErrorInvalidValue with the reason before any device call. */
+int icrl_policy_forward_sde(const icrl_policy_t* pol, const double* obs, const float* expl, long long expl_stride, int N, int deterministic,
+                            const float* action_low, const float* action_high, float* actions, float* act_clipped, float* v_r, float* v_c,
+                            float* log_prob, void* stream);
+size_t icrl_policy_sde_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
+int icrl_policy_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
+                            const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
+                            void* ws, long long ws_bytes, void* stream);
 /* The same for a constraint net on x [N, in_dim] (the rows icrl_cn_prepare writes): zeta = sigmoid(MLP_relu(x)) [N] (may be NULL),
  * grad [n_params] overwritten with sum_n d_zeta[n] dzeta[n]/dθ.  d_zeta and grad both NULL = forward only.  Served: one or two hidden
  * layers of up to 64 units, in_dim <= 128, 1 <= N <= 65536; the tagged descriptors (icrl_cost_fn_t, icrl_cost_disc_t) are refused. */

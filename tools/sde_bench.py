@@ -1,0 +1,147 @@
+"""What gSDE costs on the two paths it runs on, against the diagonal Gaussian head on the SAME two paths:
+
+  rollout   microseconds per env step of PPOLagrangian._collect_rollouts_stepped (HCWithPos, --envs envs): policy forward (icrl_policy_forward_sde |
+            icrl_policy_forward), env step, cost, normaliser, buffer row — one launch sequence per step, no host read;
+  update    microseconds per optimiser step of the fine-grained loop at (obs 18, act 6, batch 64): icrl_minibatch_gather, the policy forward
+            (icrl_policy_sde_fwd_bwd | icrl_policy_fwd_bwd, forward only), icrl_ppo_lag_loss_fwd_bwd, the same entry point with the gradient,
+            icrl_clip_adam_step — what PPOLagrangian._train_sde enqueues per minibatch.
+
+Neither figure says anything about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
+--warmup, one synchronisation at each end, host clock around it; --runs runs per form, interleaved.  Needs the GPU.
+
+    python tools/sde_bench.py [--steps 512 --warmup 64 --runs 3 --envs 4] [--out profiles/sde.json]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from icrl_amd import _lib, spaces, structs as S      # noqa: E402
+from icrl_amd.buffers import RolloutBufferWithCost   # noqa: E402
+from icrl_amd.policies import ActorTwoCriticsPolicy  # noqa: E402
+
+P = _lib.ptr
+OBS, ACT, BATCH = 18, 6, 64
+
+
+class UpdateLoop:
+    def __init__(self, use_sde, seed=0):
+        torch.manual_seed(seed)
+        rng = np.random.RandomState(seed)
+        self.L, self.use_sde = _lib.lib(), use_sde
+        T, n_envs = 64, 32
+        o, a = spaces.Box(-np.inf, np.inf, (OBS,), np.float64), spaces.Box(-1, 1, (ACT,), np.float32)
+        self.rb = RolloutBufferWithCost(T, o, a, "cuda", n_envs=n_envs)
+        for k in ("observations", "actions", "reward_advantages", "cost_advantages", "reward_returns", "cost_returns", "reward_values", "cost_values"):
+            t = getattr(self.rb, k)
+            t.copy_(torch.as_tensor(rng.randn(*t.shape).astype(np.float32)))
+        self.policy = pol = ActorTwoCriticsPolicy(o, a, use_sde=use_sde)
+        lp = pol.evaluate_actions(self.rb.observations.reshape(-1, OBS).double(), self.rb.actions.reshape(-1, ACT))[2]      # ratio 1 at the first step
+        self.rb.log_probs.copy_(lp.reshape(self.rb.log_probs.shape))
+        self.buf = self.rb.struct()
+        self.idx = torch.as_tensor(np.stack([rng.permutation(T * n_envs)[:BATCH] for _ in range(64)]).astype(np.int32)).cuda().contiguous()
+        self.params0 = pol.params.clone()
+        f = lambda *shape: torch.zeros(*shape, device="cuda")
+        self.grad, self.step = f(pol.n_params), torch.zeros(1, dtype=torch.int32, device="cuda")
+        self.work, self.out2, self.terms, self.nu = f(256), f(2), f(8), torch.full((1,), 0.5, device="cuda")
+        self.obs, self.act = f(BATCH, OBS), f(BATCH, ACT)
+        self.r = {k: f(BATCH) for k in ("old_lp", "adv_r", "adv_c", "ret_r", "ret_c", "old_vr", "old_vc", "v_r", "v_c", "lp", "ent", "d_lp", "d_vr", "d_vc", "d_ent")}
+        self.s = pol.struct(sde=use_sde)
+        self.fb = self.L.icrl_policy_sde_fwd_bwd if use_sde else self.L.icrl_policy_fwd_bwd
+        need = int((self.L.icrl_policy_sde_fwd_bwd_ws_bytes if use_sde else self.L.icrl_policy_fwd_bwd_ws_bytes)(ctypes.byref(self.s), BATCH))
+        self.ws = torch.zeros((need + 7) // 8, dtype=torch.float64, device="cuda")
+        hp = S.PpoHyperT(BATCH, 1, 0, 0)
+        hp.clip_range, hp.ent_coef, hp.reward_vf_coef, hp.cost_vf_coef, hp.max_grad_norm = 0.2, 0.0, 0.5, 0.5, 0.5
+        hp.clip_range_reward_vf = hp.clip_range_cost_vf = -1.0
+        hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps = 3e-5, 0.9, 0.999, 1e-5
+        self.hp = hp
+
+    def one_step(self, i):
+        L, r, st, b, pol = self.L, self.r, _lib.current_stream(), ctypes.byref, self.policy
+        _lib.check(L.icrl_minibatch_gather(b(self.buf), self.idx[i % 64].data_ptr(), BATCH, P(self.obs), P(self.act), P(r["old_lp"]), P(r["adv_r"]), P(r["adv_c"]),
+                                           P(r["ret_r"]), P(r["ret_c"]), P(r["old_vr"]), P(r["old_vc"]), st), "icrl_minibatch_gather")
+        _lib.check(self.fb(b(self.s), P(self.obs), P(self.act), BATCH, None, None, None, None, P(r["v_r"]), P(r["v_c"]), P(r["lp"]), P(r["ent"]), None, None, 0, st),
+                   "policy forward")
+        _lib.check(L.icrl_ppo_lag_loss_fwd_bwd(P(r["lp"]), P(r["old_lp"]), P(r["adv_r"]), P(r["adv_c"]), P(r["v_r"]), P(r["v_c"]), P(r["ret_r"]), P(r["ret_c"]), None,
+                                               None, P(r["ent"]), P(self.nu), b(self.hp), BATCH, P(self.terms), P(r["d_lp"]), P(r["d_vr"]), P(r["d_vc"]), P(r["d_ent"]),
+                                               st), "icrl_ppo_lag_loss_fwd_bwd")
+        _lib.check(self.fb(b(self.s), P(self.obs), P(self.act), BATCH, P(r["d_vr"]), P(r["d_vc"]), P(r["d_lp"]), P(r["d_ent"]), None, None, None, None, P(self.grad),
+                           P(self.ws), self.ws.numel() * 8, st), "policy backward")
+        _lib.check(L.icrl_clip_adam_step(P(pol.params), P(self.grad), P(pol.exp_avg), P(pol.exp_avg_sq), P(self.step), pol.n_params, b(self.hp), P(self.work),
+                                         P(self.out2), st), "icrl_clip_adam_step")
+
+    def run(self, steps, warmup):
+        pol = self.policy
+        pol.params.copy_(self.params0); pol.exp_avg.zero_(); pol.exp_avg_sq.zero_(); self.step.zero_()
+        for i in range(warmup):
+            self.one_step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(warmup, warmup + steps):
+            self.one_step(i)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(pol.params).all())
+        return 1e6 * (time.perf_counter() - t0) / max(steps, 1)
+
+
+class RolloutLoop:
+    def __init__(self, use_sde, envs, steps):
+        from icrl_amd import cpg
+        argv = ["cpg", "-tei", "HCWithPos-v0", "-eei", "HCWithPosTest-v0", "-nt", str(envs), "--n_steps", str(steps), "-s", "0", "-v", "0"] + (["-us", "-ssf", "8"] if use_sde else [])
+        cfg = vars(cpg.build_parser().parse_args(argv))
+        cfg.update(rank=0, world_size=1)
+        self.model, _cb, self.cost, _hist = cpg.setup(types.SimpleNamespace(**cfg), log=None)
+        self.steps = steps
+        self.model._setup_learn(envs * steps)
+
+    def run(self):
+        m = self.model
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert m._collect_rollouts_stepped(m.env, None, m.rollout_buffer, self.steps, self.cost) is True
+        torch.cuda.synchronize()
+        return 1e6 * (time.perf_counter() - t0) / self.steps
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--steps", type=int, default=512)
+    ap.add_argument("--warmup", type=int, default=64)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--envs", type=int, default=4)
+    ap.add_argument("--out", default=None, help="write the result as JSON to this file as well")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sde_bench needs the GPU: a time measured elsewhere says nothing about it")
+    result = dict(status="measured", device=torch.cuda.get_device_name(0), steps=a.steps, warmup=a.warmup, runs=a.runs, envs=a.envs,
+                  protocol="host clock between two synchronisations around --steps steps after --warmup; --runs runs per form, interleaved; "
+                           "update: obs 18, act 6, batch 64, fine-grained loop; rollout: HCWithPos, per-step loop, sde_sample_freq 8")
+    upd = {k: UpdateLoop(k == "gsde") for k in ("diagonal", "gsde")}
+    roll = {k: RolloutLoop(k == "gsde", a.envs, a.steps) for k in ("diagonal", "gsde")}
+    for loop in roll.values():
+        loop.run()      # warm-up rollout
+    us = {f"{what}_us_per_step_{k}": [] for what in ("update", "rollout") for k in ("diagonal", "gsde")}
+    for _ in range(a.runs):
+        for k in ("diagonal", "gsde"):
+            us[f"update_us_per_step_{k}"].append(round(upd[k].run(a.steps, a.warmup), 1))
+            us[f"rollout_us_per_step_{k}"].append(round(roll[k].run(), 1))
+    result.update(us)
+    for k, v in us.items():
+        print(f"{k}: {v}", flush=True)
+    print(json.dumps(result))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
