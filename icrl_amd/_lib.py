@@ -78,6 +78,9 @@ SIGNATURES = {
     "icrl_policy_forward_sde": [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int] + [c_void_p] * 8,
     "icrl_policy_sde_fwd_bwd_ws_bytes": [c_void_p, c_int],
     "icrl_policy_sde_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10 + [ctypes.c_longlong, c_void_p],
+    # the gSDE agent's update as one persistent launch (csrc/ppo_train_sde.hip; ppo_lag.py _train_sde)
+    "icrl_ppo_lag_train_sde_ws_bytes": [c_void_p] * 3,
+    "icrl_ppo_lag_train_sde": [c_void_p] * 11,
     # the exploration callbacks' regression step and the advantage shaping (csrc/reg_mlp.hip; icrl_amd/exploration.py)
     "icrl_reg_mlp_ws_bytes": [ctypes.c_longlong] + [c_int] * 5,
     "icrl_reg_mlp_step": [c_void_p] * 7 + [ctypes.c_longlong] + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 3 + [ctypes.c_longlong, c_void_p],
@@ -99,7 +102,7 @@ SIGNATURES = {
     "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_ppo_lag_train_sde_ws_bytes": ctypes.c_size_t,"icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

@@ -821,7 +821,54 @@ class PPOLagrangian:
         self._train_end(job, host=host)
 
     def _train_sde(self, perms=None):
-        """train() of a gSDE agent (ref: ppo_lag.py:177-338): the fine-grained loop of INTEGRATION.md section 3a on the device, per minibatch
+        """train() of a gSDE agent (ref: ppo_lag.py:177-338).  By default ONE persistent launch, icrl_ppo_lag_train_sde (csrc/ppo_train_sde.hip: the
+        three-workgroup update kernel with the gSDE head in the policy workgroup, fp32 on the matrix core).  The fine-grained loop (_train_sde_loop:
+        float64 rounded once, five launch groups per minibatch) stays where the launch does not serve the call — `sde_step_hook` set (its contract
+        is "after every optimiser step"), batch_size > 128, a shape icrl_ppo_lag_train_sde_ws_bytes declines — and as the check of the fused path:
+        ICRL_SDE_UPDATE_STEPPED=1 in the environment.  `last_sde_update` says which ran ("fused" | "loop"), `last_sde_update_reason` why the loop.
+        Permutations, minibatch boundaries, the target-KL stop per epoch, the dual-variable step, the logged keys and `epoch_kls` are shared
+        (_train_begin / _train_end)."""
+        job = self._train_begin(perms)
+        rb = self.rollout_buffer
+        n, B = rb.buffer_size * rb.n_envs, int(self.batch_size)
+        if n - (n - 1) // B * B < 2:
+            raise ValueError(f"use_sde: the last minibatch of an epoch would hold {n - (n - 1) // B * B} row (rollout of {n} rows, batch_size {B}); the loss needs 2")
+        reason = None
+        if os.environ.get("ICRL_SDE_UPDATE_STEPPED", "")[:1] == "1":
+            reason = "ICRL_SDE_UPDATE_STEPPED=1"
+        elif getattr(self, "sde_step_hook", None) is not None:
+            reason = "sde_step_hook is set"
+        elif B > 128:
+            reason = f"batch_size {B} > 128"
+        else:
+            L = _lib.lib()
+            need = int(L.icrl_ppo_lag_train_sde_ws_bytes(_lib.byref(job["ps"]), _lib.byref(job["bs"]), _lib.byref(job["hp"])))
+            if need == 0:
+                reason = L.icrl_last_error().decode()
+                L.icrl_clear_error()
+            elif need > self._train_ws["sync"].numel() * 8:
+                reason = f"the update workspace holds {self._train_ws['sync'].numel() * 8} bytes, the launch needs {need}"
+        self.last_sde_update, self.last_sde_update_reason = ("fused" if reason is None else "loop"), reason
+        if reason is None:
+            self._train_sde_fused(job)
+        else:
+            self._train_sde_loop(job)
+
+    def _train_sde_fused(self, job):
+        pol, ws, b = self.policy, self._train_ws, _lib.byref
+        ev = None
+        if getattr(self, "train_events", None) is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        _lib.check(_lib.lib().icrl_ppo_lag_train_sde(b(job["ps"]), p(pol.exp_avg), p(pol.exp_avg_sq), p(ws["t"]), b(job["bs"]), p(job["perms"]), p(ws["nu"]),
+                                                     b(job["hp"]), p(ws["stats"]), p(ws["sync"]), _lib.current_stream()), "icrl_ppo_lag_train_sde")
+        if ev is not None:
+            ev[1].record()
+        job["ev"] = ev
+        self._train_end(job, host=self.train_readback().cpu().numpy())
+
+    def _train_sde_loop(self, job):
+        """The fine-grained loop of INTEGRATION.md section 3a on the device, per minibatch
           icrl_minibatch_gather -> icrl_policy_sde_fwd_bwd (forward) -> icrl_ppo_lag_loss_fwd_bwd -> icrl_policy_sde_fwd_bwd (backward; it
           recomputes the forward) -> icrl_clip_adam_step,
         with the permutations, the minibatch boundaries (the last one of an epoch may be short), the target-KL stop per epoch, the dual-variable step
@@ -830,12 +877,9 @@ class PPOLagrangian:
         NOT made: the reference's reset_noise(batch_size) before every minibatch (ppo_lag.py:207-211).  That draw changes the exploration
         matrices, which evaluate_actions and the loss never read and which the next rollout replaces before its first step; only the position of
         the global generator differs afterwards."""
-        job = self._train_begin(perms)
         rb, pol, dev, ws, L, b = self.rollout_buffer, self.policy, self.device, self._train_ws, _lib.lib(), _lib.byref
         n, B, E = rb.buffer_size * rb.n_envs, int(self.batch_size), int(self.n_epochs)
         starts = list(range(0, n, B))
-        if n - starts[-1] < 2:
-            raise ValueError(f"use_sde: the last minibatch of an epoch would hold {n - starts[-1]} row (rollout of {n} rows, batch_size {B}); the loss needs 2")
         s = job["ps"]
         if "sde" not in ws:
             f = lambda *shape: torch.zeros(*shape, device=dev)

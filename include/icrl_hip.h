@@ -882,6 +882,26 @@ size_t icrl_policy_sde_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
 int icrl_policy_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
                             const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
                             void* ws, long long ws_bytes, void* stream);
+/* icrl_ppo_lag_train for a gSDE policy (csrc/ppo_train_sde.hip): PPOLagrangian.train of an agent built with use_sde=True as ONE persistent
+ * launch — the column-split tiles kernel of icrl_ppo_lag_train (three workgroups, one per network, weights in LDS, Adam moments in registers,
+ * one 8-byte granule per workgroup and step for the gradient norm) with the state-dependent-noise head in the policy workgroup: the variances
+ * as a second head GEMM on the squared latent and an LDS image of exp(2 log_std) that is rebuilt after every Adam step, log-prob and entropy per
+ * row, d log_std as a GEMM of the head-weight gradient's shape, the latent detached in the variance, the [64, A] entries of log_std and both
+ * moments owned in registers, padded rows exactly 0 throughout.  float32 on the matrix core: against the fine-grained loop
+ * (icrl_policy_sde_fwd_bwd: float64 rounded once) results differ in the last bits.
+ *   The arguments, the statistics row and the contract are icrl_ppo_lag_train's; pol is the gSDE descriptor (n_params = the diagonal layout's
+ *   + 63 * act_dim), hp->_pad: bit 0 only (phase timers).  After the launch the call refreshes params_t as icrl_policy_forward_sde reads it
+ *   (icrl_policy_prepare on the descriptor of the network alone), so the next rollout needs no further call.  The call leaves the
+ *   ICRL_FAMILY_UPDATE route record as it is.  Every inter-workgroup wait is bounded and reports through stats[11].
+ *   Served: arch == NULL, continuous, h1 == h2 == 64 (narrower layers stored zero-padded), obs_dim 1..128, act_dim 1..16, batch_size 2..128,
+ *   n_epochs >= 1, buf->act_store == act_dim (obs_dim 65..128 takes 161 920 of the workgroup's 163 840 bytes of LDS: the per-row variances
+ *   live in spare columns of another image).  Everything else, a NULL pointer and a buffer / policy obs_dim mismatch return
+ *   hipErrorInvalidValue with the reason before any device call.
+ *   icrl_ppo_lag_train_sde_ws_bytes: bytes of sync_ws for this call (host arithmetic; = ICRL_PPO_SYNC_BYTES(n_epochs, ceil(T*N / batch_size),
+ *   T*N)), 0 with the reason in icrl_last_error() where the call is not served. */
+size_t icrl_ppo_lag_train_sde_ws_bytes(const icrl_policy_t* pol, const icrl_buffer_t* buf, const icrl_ppo_hyper_t* hp);
+int icrl_ppo_lag_train_sde(const icrl_policy_t* pol, float* exp_avg, float* exp_avg_sq, int32_t* adam_step, const icrl_buffer_t* buf,
+                           const int32_t* perms, const float* nu, const icrl_ppo_hyper_t* hp, float* stats, void* sync_ws, void* stream);
 /* The same for a constraint net on x [N, in_dim] (the rows icrl_cn_prepare writes): zeta = sigmoid(MLP_relu(x)) [N] (may be NULL),
  * grad [n_params] overwritten with sum_n d_zeta[n] dzeta[n]/dθ.  d_zeta and grad both NULL = forward only.  Served: one or two hidden
  * layers of up to 64 units, in_dim <= 128, 1 <= N <= 65536; the tagged descriptors (icrl_cost_fn_t, icrl_cost_disc_t) are refused. */

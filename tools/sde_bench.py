@@ -4,12 +4,16 @@
             icrl_policy_forward), env step, cost, normaliser, buffer row — one launch sequence per step, no host read;
   update    microseconds per optimiser step of the fine-grained loop at (obs 18, act 6, batch 64): icrl_minibatch_gather, the policy forward
             (icrl_policy_sde_fwd_bwd | icrl_policy_fwd_bwd, forward only), icrl_ppo_lag_loss_fwd_bwd, the same entry point with the gradient,
-            icrl_clip_adam_step — what PPOLagrangian._train_sde enqueues per minibatch.
+            icrl_clip_adam_step — what PPOLagrangian._train_sde_loop enqueues per minibatch;
+  fused     microseconds per optimiser step of ONE persistent launch over the same buffer (2048 rows, batch 64: 32 minibatches per epoch,
+            --steps / 32 epochs; the warm-up is a launch of --warmup / 32 epochs): icrl_ppo_lag_train_sde for gSDE (what PPOLagrangian._train_sde
+            takes by default), and for the diagonal head icrl_ppo_lag_train with the column-split tiles kernel (hp._pad bit 1) — the kernel the gSDE
+            launch is built from, so the difference of the two is the cost of the head.
 
-Neither figure says anything about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
+The rollout and loop figures say nothing about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
 --warmup, one synchronisation at each end, host clock around it; --runs runs per form, interleaved.  Needs the GPU.
 
-    python tools/sde_bench.py [--steps 512 --warmup 64 --runs 3 --envs 4] [--out profiles/sde.json]
+    python tools/sde_bench.py [--steps 512 --warmup 64 --runs 3 --envs 4] [--wide] [--out profiles/sde.json]
 """
 import argparse
 import ctypes
@@ -33,11 +37,14 @@ OBS, ACT, BATCH = 18, 6, 64
 
 
 class UpdateLoop:
-    def __init__(self, use_sde, seed=0):
+    def __init__(self, use_sde, seed=0, obs=OBS, act=ACT, batch=BATCH):
+        OBS, ACT, BATCH = obs, act, batch      # (the shape of this loop; the module's are the default)
+        self.batch = batch
         torch.manual_seed(seed)
         rng = np.random.RandomState(seed)
         self.L, self.use_sde = _lib.lib(), use_sde
         T, n_envs = 64, 32
+        self.n_rows = T * n_envs
         o, a = spaces.Box(-np.inf, np.inf, (OBS,), np.float64), spaces.Box(-1, 1, (ACT,), np.float32)
         self.rb = RolloutBufferWithCost(T, o, a, "cuda", n_envs=n_envs)
         for k in ("observations", "actions", "reward_advantages", "cost_advantages", "reward_returns", "cost_returns", "reward_values", "cost_values"):
@@ -63,8 +70,12 @@ class UpdateLoop:
         hp.clip_range_reward_vf = hp.clip_range_cost_vf = -1.0
         hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps = 3e-5, 0.9, 0.999, 1e-5
         self.hp = hp
+        self.perms = torch.as_tensor(np.stack([rng.permutation(T * n_envs) for _ in range(64)]).astype(np.int32)).cuda().contiguous()
+        self.stats = f(32 + 64)
+        self.sync = None
 
     def one_step(self, i):
+        BATCH = self.batch
         L, r, st, b, pol = self.L, self.r, _lib.current_stream(), ctypes.byref, self.policy
         _lib.check(L.icrl_minibatch_gather(b(self.buf), self.idx[i % 64].data_ptr(), BATCH, P(self.obs), P(self.act), P(r["old_lp"]), P(r["adv_r"]), P(r["adv_c"]),
                                            P(r["ret_r"]), P(r["ret_c"]), P(r["old_vr"]), P(r["old_vc"]), st), "icrl_minibatch_gather")
@@ -92,6 +103,33 @@ class UpdateLoop:
         return 1e6 * (time.perf_counter() - t0) / max(steps, 1)
 
 
+    def fused(self, n_steps):
+        """one persistent launch of n_steps optimiser steps (whole epochs of the 2048-row buffer)."""
+        b, pol, n_mb = ctypes.byref, self.policy, self.n_rows // self.batch
+        E = max(1, min(64, n_steps // n_mb))
+        hp = S.PpoHyperT.from_buffer_copy(self.hp)
+        hp.n_epochs, hp._pad = E, (0 if self.use_sde else 2)      # diagonal: the column-split tiles kernel, the gSDE launch's parent
+        if self.sync is None:
+            n_bytes = 768 + 48 * 64 * n_mb + 4 * 64 * self.n_rows + 256 + _lib.PPO_SPLIT_BYTES      # ICRL_PPO_SYNC_BYTES at 64 epochs
+            self.sync = torch.zeros((n_bytes + 7) // 8, dtype=torch.int64, device="cuda")
+        call = self.L.icrl_ppo_lag_train_sde if self.use_sde else self.L.icrl_ppo_lag_train
+        _lib.check(call(b(self.s), P(pol.exp_avg), P(pol.exp_avg_sq), P(self.step), b(self.buf), P(self.perms), P(self.nu), b(hp), P(self.stats), P(self.sync),
+                        _lib.current_stream()), "fused update")
+        return E * n_mb
+
+    def run_fused(self, steps, warmup):
+        pol = self.policy
+        pol.params.copy_(self.params0); pol.exp_avg.zero_(); pol.exp_avg_sq.zero_(); self.step.zero_()
+        self.fused(warmup)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        done = self.fused(steps)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert bool(torch.isfinite(pol.params).all()) and float(self.stats[11]) == 0.0 and int(self.stats[1]) == done
+        return 1e6 * dt / done
+
+
 class RolloutLoop:
     def __init__(self, use_sde, envs, steps):
         from icrl_amd import cpg
@@ -117,22 +155,35 @@ def main():
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--envs", type=int, default=4)
+    ap.add_argument("--wide", action="store_true", help="also time the update forms at (obs 113, act 8, batch 128): keys ending in _113_8_128")
     ap.add_argument("--out", default=None, help="write the result as JSON to this file as well")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sde_bench needs the GPU: a time measured elsewhere says nothing about it")
     result = dict(status="measured", device=torch.cuda.get_device_name(0), steps=a.steps, warmup=a.warmup, runs=a.runs, envs=a.envs,
                   protocol="host clock between two synchronisations around --steps steps after --warmup; --runs runs per form, interleaved; "
-                           "update: obs 18, act 6, batch 64, fine-grained loop; rollout: HCWithPos, per-step loop, sde_sample_freq 8")
+                           "update: obs 18, act 6, batch 64, fine-grained loop; update_fused: the same buffer and shape, one persistent launch of "
+                           "steps / 32 epochs (gsde: icrl_ppo_lag_train_sde; diagonal: icrl_ppo_lag_train, tiles kernel); rollout: HCWithPos, per-step "
+                           "loop, sde_sample_freq 8")
     upd = {k: UpdateLoop(k == "gsde") for k in ("diagonal", "gsde")}
     roll = {k: RolloutLoop(k == "gsde", a.envs, a.steps) for k in ("diagonal", "gsde")}
     for loop in roll.values():
         loop.run()      # warm-up rollout
-    us = {f"{what}_us_per_step_{k}": [] for what in ("update", "rollout") for k in ("diagonal", "gsde")}
+    us = {f"{what}_us_per_step_{k}": [] for what in ("update", "update_fused", "rollout") for k in ("diagonal", "gsde")}
     for _ in range(a.runs):
         for k in ("diagonal", "gsde"):
             us[f"update_us_per_step_{k}"].append(round(upd[k].run(a.steps, a.warmup), 1))
+            us[f"update_fused_us_per_step_{k}"].append(round(upd[k].run_fused(a.steps, a.warmup), 2))
             us[f"rollout_us_per_step_{k}"].append(round(roll[k].run(), 1))
+    if a.wide:
+        wide = {k: UpdateLoop(k == "gsde", obs=113, act=8, batch=128) for k in ("diagonal", "gsde")}
+        for what in ("update", "update_fused"):
+            for k in ("diagonal", "gsde"):
+                us[f"{what}_us_per_step_{k}_113_8_128"] = []
+        for _ in range(a.runs):
+            for k in ("diagonal", "gsde"):
+                us[f"update_us_per_step_{k}_113_8_128"].append(round(wide[k].run(a.steps, a.warmup), 1))
+                us[f"update_fused_us_per_step_{k}_113_8_128"].append(round(wide[k].run_fused(a.steps, a.warmup), 2))
     result.update(us)
     for k, v in us.items():
         print(f"{k}: {v}", flush=True)
