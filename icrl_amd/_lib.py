@@ -78,7 +78,7 @@ SIGNATURES = {
     "icrl_policy_forward_sde": [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int] + [c_void_p] * 8,
     "icrl_policy_sde_fwd_bwd_ws_bytes": [c_void_p, c_int],
     "icrl_policy_sde_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10 + [ctypes.c_longlong, c_void_p],
-    # the gSDE agent's update as one persistent launch (csrc/ppo_train_sde.hip; ppo_lag.py _train_sde)
+    # the gSDE agent's update as one persistent launch (csrc/ppo_train_sde.hip, kernel in csrc/ppo_train_tiles.hip; ppo_lag.py _train_sde)
     "icrl_ppo_lag_train_sde_ws_bytes": [c_void_p] * 3,
     "icrl_ppo_lag_train_sde": [c_void_p] * 11,
     # the exploration callbacks' regression step and the advantage shaping (csrc/reg_mlp.hip; icrl_amd/exploration.py)

@@ -1,5 +1,6 @@
-// Shared pieces of the two PPO-Lagrangian update kernels (ppo_train.hip: column-split tiles, any obs width;
-// ppo_train_rows.hip: row-owning waves, obs <= 64) — gfx950.
+// Shared pieces of the persistent PPO-Lagrangian update kernels (ppo_train_tiles / _rows / _pairs / _halves / _quarters / _quarters2.hip),
+// the minibatch stream (ppo_stream.hip) and their dispatch layers (ppo_train.hip, ppo_train_sde.hip): the argument block, the schedule
+// tables, the small device helpers, the XCD placement and the launchers' declarations — gfx950.
 #pragma once
 #include "common.h"
 
@@ -13,6 +14,7 @@ constexpr int RB = 64;   // minibatch rows per chunk
 constexpr int HD = 64;   // hidden width (both layers)
 constexpr int SH = 72;   // LDS row stride of 64-wide matrices (= 8 mod 16: conflict-free ds_read_b128 operand fetch)
 constexpr int MAXB = 256;   // minibatch rows: up to four 64-row chunks
+constexpr int SDE_MAX_B = 128;   // ... of the gSDE update (icrl_ppo_lag_train_sde): up to two
 
 struct TrainArgs {
   PolLayout L;
@@ -210,6 +212,10 @@ inline int launch_update_single(K kernel, int M, dim3 block, size_t dyn_lds, hip
 #error "libicrl_hip: the XCD-local exchange of the persistent kernels is written for gfx950 (CDNA4) / gfx942"
 #endif
 
+// ppo_train_tiles.hip: column-split tiles kernel, one workgroup per network (nt1 <= 8: two, four or eight obs tiles; minibatches of up to 128
+// rows); head: the policy head — the gSDE head expects make_sde_layout's parameters
+enum { HEAD_GAUSS = 0, HEAD_CAT = 1, HEAD_SDE = 2 };
+int launch_train_tiles(const TrainArgs& a, int nt1, int head, hipStream_t s, int* packed);
 // ppo_train_rows.hip: row-owning-wave kernel (nt1 = ceil(obs / 16) <= 8), one wave per SIMD
 int launch_train_rows(const TrainArgs& a, int nt1, bool discrete, bool split, hipStream_t s, int* packed);
 // ppo_train_pairs.hip: wave-pair kernel, two waves per SIMD (nt1 rounded up to an even tile count)

@@ -821,7 +821,7 @@ class PPOLagrangian:
         self._train_end(job, host=host)
 
     def _train_sde(self, perms=None):
-        """train() of a gSDE agent (ref: ppo_lag.py:177-338).  By default ONE persistent launch, icrl_ppo_lag_train_sde (csrc/ppo_train_sde.hip: the
+        """train() of a gSDE agent (ref: ppo_lag.py:177-338).  By default ONE persistent launch, icrl_ppo_lag_train_sde (csrc/ppo_train_tiles.hip: the
         three-workgroup update kernel with the gSDE head in the policy workgroup, fp32 on the matrix core).  The fine-grained loop (_train_sde_loop:
         float64 rounded once, five launch groups per minibatch) stays where the launch does not serve the call — `sde_step_hook` set (its contract
         is "after every optimiser step"), batch_size > 128, a shape icrl_ppo_lag_train_sde_ws_bytes declines — and as the check of the fused path:

@@ -882,7 +882,7 @@ size_t icrl_policy_sde_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
 int icrl_policy_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
                             const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
                             void* ws, long long ws_bytes, void* stream);
-/* icrl_ppo_lag_train for a gSDE policy (csrc/ppo_train_sde.hip): PPOLagrangian.train of an agent built with use_sde=True as ONE persistent
+/* icrl_ppo_lag_train for a gSDE policy (csrc/ppo_train_sde.hip; kernel: csrc/ppo_train_tiles.hip, HEAD_SDE): PPOLagrangian.train of an agent built with use_sde=True as ONE persistent
  * launch — the column-split tiles kernel of icrl_ppo_lag_train (three workgroups, one per network, weights in LDS, Adam moments in registers,
  * one 8-byte granule per workgroup and step for the gradient norm) with the state-dependent-noise head in the policy workgroup: the variances
  * as a second head GEMM on the squared latent and an LDS image of exp(2 log_std) that is rebuilt after every Adam step, log-prob and entropy per

@@ -104,8 +104,15 @@ def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     _categorical_case(O, A, N, T, B, E, ent, wide)
 
 
-def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None):
-    """one Categorical update against the oracle's epoch loop; hset: a hyper-parameter set of helpers/ppo_hparam_cases.py on a banded buffer."""
+def test_categorical_update_on_the_tiles_kernel():
+    """the Categorical head of the column-split tiles kernel (csrc/ppo_train_tiles.hip, `train_kernel = "tiles"`): obs 40 = four 16-column
+    tiles, 16 classes, 128-row minibatches = two chunks."""
+    _categorical_case(40, 16, 8, 16, 128, 2, 0.05, False, train_kernel="tiles")
+
+
+def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None, train_kernel=None):
+    """one Categorical update against the oracle's epoch loop; hset: a hyper-parameter set of helpers/ppo_hparam_cases.py on a banded buffer;
+    train_kernel: the agent's switch for an update kernel behind the default ("tiles")."""
     from helpers import ppo_hparam_cases as H
     hp = {} if hset is None else {k: v for k, v in H.hparams(hset).items() if k != "ent_coef"}
     from helpers.arches import ARCHES, oracle_arch_kwargs
@@ -120,6 +127,8 @@ def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None):
     net_arch = ARCHES[wide] if isinstance(wide, str) else [dict(pi=[128, 72], vf=[100, 128], cvf=[128, 128])]
     akw = dict(policy_kwargs=dict(net_arch=net_arch)) if wide else {}
     agent = PPOLagrangian("TwoCriticsMlpPolicy", env, n_steps=T, seed=0, batch_size=B, n_epochs=E, target_kl=None, ent_coef=ent, **hp, **akw)
+    if train_kernel is not None:
+        agent.train_kernel = train_kernel
     sd0 = agent.policy.state_dict()
     assert "log_std" not in sd0 and agent.policy.wide == bool(wide)
     if head_scale is not None:      # a peaked categorical head (helpers/policy_states.py: LGW_K)
@@ -168,8 +177,9 @@ def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None):
         H.check_trace(trace, dict(hp, ent_coef=ent), n_steps=E * (-(-N * T // B)))
     agent.train(perms=perms)
     # which update ran: the generic-shape path as one persistent launch for layers above 64 / an `arch` / more than 256 rows (three launches
-    # per step under ICRL_GEN_LAUNCHES), else wave quads with four workgroups per network up to 32 observations, wave pairs up to 64
-    want = (9 if os.environ.get("ICRL_GEN_LAUNCHES") else 8) if (wide or B > 256) else (5 if O <= 32 else 0)
+    # per step under ICRL_GEN_LAUNCHES), else wave quads with four workgroups per network up to 32 observations, wave pairs up to 64 —
+    # or the column-split tiles kernel where the case asks for it
+    want = (9 if os.environ.get("ICRL_GEN_LAUNCHES") else 8) if (wide or B > 256) else (3 if train_kernel == "tiles" else (5 if O <= 32 else 0))
     routes.check_update(dict(kind=want, n_runs=1), f"categorical obs {O} B {B} wide {wide}")
     lg = logger.Logger.CURRENT.name_to_value
     n_steps = agent.policy.adam_step

@@ -372,6 +372,12 @@ def test_ant_update_kernel_behind_the_default(N, T, B, E, tk):
     test_train_vs_oracle("ant", N, T, B, E, tk, train_kernel="rows")
 
 
+def test_tiles_kernel_at_eight_obs_tiles_with_ragged_two_chunk_minibatches():
+    """`train_kernel = "tiles"` (hp._pad & 2) at obs 113: the diagonal head of csrc/ppo_train_tiles.hip with eight 16-column observation tiles,
+    150 rows as minibatches of 100 (chunks 64 + 36) and 50 — the hc-tiles route case reaches its two-tile form with one 16-row chunk only."""
+    test_train_vs_oracle("ant", 3, 50, 100, 2, None, train_kernel="tiles")
+
+
 def test_ant_chunk_by_chunk_form_at_128_rows():
     """ICRL_QUARTERS_PASSES=1 keeps ppo_train_quarters.hip (16 rows of each 64-row chunk, one chunk after the other) where ppo_train_quarters2.hip
     would run: the oracle cases with 100- and 128-row minibatches through it (child process: the switch is read once per process)."""

@@ -84,6 +84,15 @@ def test_hc_walks_follow_the_loop(N, T, B, E):
     _padding_is_zero(agent.policy, 64)
 
 
+def test_obs_40_act_4_ragged_walk_follows_the_loop():
+    """obs 40, act 4, 5 x 20 rows at batch 64 (64 + 36): the four-tile instantiation, between the two-tile HC walks above and the eight-tile case below."""
+    agent, sd, perms, snap = U.case(40, 4, 20, 5, 64, 2, seed=40, target_kl=None)
+    fused, loop, frac = U.both("obs40 5x20 B=64 E=2", agent, perms, snap)
+    assert fused["adam_step"] - snap["adam_step"] == 4
+    assert not np.array_equal(fused["params"][:64 * 4], snap["params"][:64 * 4].cpu().numpy())      # log_std moved
+    _padding_is_zero(agent.policy, 64)
+
+
 def test_hyper_parameters_off_their_defaults():
     kw = dict(clip_range_reward_vf=0.2, clip_range_cost_vf=0.3, ent_coef=0.01, reward_vf_coef=0.7, cost_vf_coef=0.3, max_grad_norm=0.3)
     agent, sd, perms, snap = U.case(18, 6, 32, 4, 64, 2, seed=3, target_kl=None, **kw)
