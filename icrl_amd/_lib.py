@@ -81,6 +81,8 @@ SIGNATURES = {
     # the gSDE agent's update as one persistent launch (csrc/ppo_train_sde.hip, kernel in csrc/ppo_train_tiles.hip; ppo_lag.py _train_sde)
     "icrl_ppo_lag_train_sde_ws_bytes": [c_void_p] * 3,
     "icrl_ppo_lag_train_sde": [c_void_p] * 11,
+    # the gSDE agent's rollout in the library (csrc/rollout.hip; ppo_lag.py sde_fused_rollout): expl, n_draws, sample_freq in the noise's place
+    "icrl_rollout_collect_sde": [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 2 + [c_double] * 4 + [c_int, c_void_p],
     # the exploration callbacks' regression step and the advantage shaping (csrc/reg_mlp.hip; icrl_amd/exploration.py)
     "icrl_reg_mlp_ws_bytes": [ctypes.c_longlong] + [c_int] * 5,
     "icrl_reg_mlp_step": [c_void_p] * 7 + [ctypes.c_longlong] + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 3 + [ctypes.c_longlong, c_void_p],
@@ -148,6 +150,7 @@ ROUTE = {"none": 0, "per-step": 1, "persistent": 2, "wide": 3, "multi": 4, "gene
 WS_NONE, WS_XCH, WS_PLANE = 0, 1, 2
 PICK_SMALL, PICK_ANALYTIC, PICK_MON, PICK_GRAN, PICK_CN128, PICK_MINW_SHIFT = 1, 2, 4, 8, 16, 8
 PICK_DISC = 32
+PICK_SDE = 64      # ICRL_PICK_SDE
 UPDATE_GENERIC_PERSISTENT, UPDATE_GENERIC_LAUNCHES = 8, 9
 GAE_ROUTE = {"none": 0, "sequential": 1, "split": 2, "regsplit": 3, "batch-split": 4, "batch-regsplit": 5, "batch-singles": 6}
 

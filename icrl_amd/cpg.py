@@ -117,7 +117,8 @@ def setup(config, log=print):
                         delta_p_ema_alpha=config.proportional_cost_ema_alpha, delta_d_ema_alpha=config.derivative_cost_ema_alpha),
         policy_kwargs=dict(net_arch=utils.get_net_arch(config)),
         action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-        streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
+        streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None),
+        sde_fused_rollout=getattr(config, "sde_fused_rollout", False))
     if world > 1:      # all ranks hold the same initial networks (same seed); from here on rank r draws its own noise / permutations
         D.decorrelate_streams(config.seed, rank)
     # ref: icrl/cpg.py:160-176
@@ -184,6 +185,9 @@ def build_parser():
     a("--pid_delay", "-pidd", type=int, default=1); a("--penalty_learning_rate", "-plr", type=float, default=0.1)
     a("--use_sde", "-us", action="store_true"); a("--use_curiosity_driven_exploration", "-ucde", action="store_true")
     a("--use_lambda_shaping", "-uls", action="store_true"); a("--sde_sample_freq", "-ssf", type=int, default=-1)
+    # -us: collect the rollout as a launch of the library (PPOLagrangian sde_fused_rollout).  Opt-in, and absent from the namespace unless given:
+    # the configs that runs store and seed batches compare stay what they were
+    a("--sde_fused_rollout", "-sfr", action="store_true", default=argparse.SUPPRESS)
     a("--use_null_cost", "-unc", action="store_true"); a("--cn_path", "-cp", type=str, default=None)
     a("--cn_obs_select_dim", "-cosd", type=int, default=None, nargs="+"); a("--cn_acs_select_dim", "-casd", type=int, default=None, nargs="+")
     a("--cn_device", "-cd", type=str, default=None); a("--load_gail", "-lg", action="store_true")

@@ -660,6 +660,109 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
   }
 }
 
+// ---- gSDE (icrl_rollout_collect_sde): the exploration matrices of the whole rollout are drawn up front, in the per-step loop's order, and
+// travel as a kernel argument of their own beside the argument blocks above, which keep their layout.
+struct SdeArgs {
+  const float* expl;        // [n_draws][N][MAX_H][A] float32: the matrix env n uses while draw d is current
+  long long draw_stride;    // N * MAX_H * A
+  long long env_stride;     // MAX_H * A
+  int sample_freq;          // > 0: step t uses draw t / sample_freq; < 0: draw 0 throughout
+  const float* ls;          // log_std [MAX_H][A] as it lies in `params` (rows beyond the latent width are zero and meet a zero latent)
+};
+__device__ __forceinline__ int sde_draw_of(int t, int sample_freq) { return sample_freq > 0 ? t / sample_freq : 0; }
+
+// The head of policy_forward_sde_kernel on wave 0, behind policy_forward_block(deterministic = 1): sh.act_raw holds the mean and sh.g[0] the
+// latent, both written by this wave (the latent before a workgroup barrier).  Same arithmetic, term for term: float64 fma chains over the
+// latent units in ascending order, action = (float)(mean + noise), the log-prob summed in action order, the clip to the action box.  Leaves
+// sh.act_raw, sh.act_clip and sh.scal[2] for the env step, the cost wave and the buffer stores, which read them behind the caller's barrier.
+// E: this env's current matrix (LDS or global); e2(i): exp(2 log_std) of entry i — evaluated per call, or read from the launch's LDS image.
+template <class E2>
+__device__ __forceinline__ void sde_head_wave(ActShared& sh, int A, int H2, const float* E, E2 e2, const float* alow, const float* ahigh) {
+  const int lane = threadIdx.x & 63;
+  double lp = 0.;
+  if (lane < A) {
+    const float mean = sh.act_raw[lane];
+    double noise = 0., var = 0.;
+#pragma unroll 8      // (the two chains stay sequential; unrolled, the operands of eight terms are fetched together)
+    for (int h = 0; h < H2; ++h) {
+      const double l = sh.g[0][h];
+      noise = fma(l, (double)E[h * A + lane], noise);
+      var = fma(l * l, e2(h * A + lane), var);
+    }
+    var += 1e-6;
+    const float act = (float)((double)mean + noise);
+    const double diff = (double)act - (double)mean;
+    lp = -(diff * diff) / (2. * var) - 0.5 * log(var) - 0.918938533204672741780329736406;
+    float clip = act;
+    if (alow != nullptr && ahigh != nullptr) clip = fminf(fmaxf(act, alow[lane]), ahigh[lane]);
+    sh.act_raw[lane] = act;
+    sh.act_clip[lane] = clip;
+  }
+  double tot = 0.;      // in action order, every lane the same chain
+  for (int a = 0; a < A; ++a) tot += __shfl(lp, a, 64);
+  if (lane == 0) sh.scal[2] = (float)tot;
+}
+
+// act_step_kernel for a gSDE policy: the same step with the head above (exp per call, as policy_forward_sde_kernel does); a.pl / a.PT are
+// the diagonal layout and the transposes of the network alone (launch_policy_forward_sde), a.noise is not read.  norm_step_kernel follows.
+template <int OCT, int CIT>
+__global__ void __launch_bounds__(256) act_step_sde_kernel(ActStepArgs a, SdeArgs sd, int t) {
+  __shared__ ActShared sh;
+  WaveRegs<OCT, CIT> R;
+  WaveRegs<OCT, CIT>& C = R;
+  load_pol_regs<OCT>(a.pl, a.PT, R);
+  if constexpr (CIT > 0) { if (threadIdx.x >= 192 && a.has_cn) load_cn_regs<CIT>(a.cn, a.cl, C); }
+  const icrl_cost_fn_t cf = a.cf;
+  const int n = blockIdx.x;
+  const uint32_t e_key = a.env.key[n];
+  uint32_t e_ctr = a.env.step_count[n];
+  int e_tep = a.env.t_ep[n];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int O = a.pl.O, A = a.pl.A, N = a.env.n_envs;
+  const int AS = a.buf.act_store;
+  for (int i = tid; i < MAX_OBS; i += 256) {
+    sh.x[i] = i < O ? (float)a.ag.last_obs[(size_t)n * O + i] : 0.f;
+    if (i < O) sh.s_old[i] = a.env.s[(size_t)n * O + i];
+  }
+  __syncthreads();
+  const size_t tn = (size_t)t * N + n;
+  policy_forward_block<OCT>(a.pl, R, sh, nullptr, 1, nullptr, nullptr);
+  if (w == 0) {
+    const float* E = sd.expl + (size_t)sde_draw_of(t, sd.sample_freq) * (size_t)sd.draw_stride + (size_t)n * (size_t)sd.env_stride;
+    const float* __restrict__ ls = sd.ls;
+    sde_head_wave(sh, A, a.pl.H2, E, [&](int i) { return exp(2. * (double)ls[i]); }, a.alow, a.ahigh);
+  }
+  __syncthreads();
+  if (w == 0) {
+    double rew; int done;
+    env_step_wave(a.env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
+    float* nob = a.buf.new_orig_observations + tn * O;
+    for (int i = lane; i < O; i += WAVE) nob[i] = (float)sh.s_new[i];
+    if (lane == 0) { a.ag.raw_rew[n] = rew; a.ag.dones[n] = (uint8_t)done; }
+  } else if (w == 3) {
+    float cost = 0.f;
+    if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+    else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, 0);
+    if (lane == 0) { a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost; }
+  } else if (w == 2) {
+    float* ob = a.buf.observations + tn * O;
+    float* oob = a.buf.orig_observations + tn * O;
+    for (int i = lane; i < O; i += WAVE) { ob[i] = sh.x[i]; oob[i] = (float)sh.s_old[i]; }
+    if (lane < AS) a.buf.actions[tn * AS + lane] = sh.act_raw[lane];
+    if (lane < A) a.ag.act_clipped[(size_t)n * A + lane] = sh.act_clip[lane];
+    if (lane == 0) {
+      a.buf.dones[tn] = (float)a.ag.last_dones[n];
+      a.buf.reward_values[tn] = sh.scal[0];
+      a.buf.cost_values[tn] = sh.scal[1];
+      a.buf.log_probs[tn] = sh.scal[2];
+      a.ag.last_v_r[n] = sh.scal[0];
+      a.ag.last_v_c[n] = sh.scal[1];
+    }
+  }
+}
+
 // act_step_kernel for policies / constraint nets the one-workgroup-per-env image does not hold (generic-shape path): the policy
 // forward (policy_generic_kernel: actions, values, log-probs straight into row t of the buffer, clipped actions into ag.act_clipped)
 // and the cost (cn_cost_rows_kernel: ag.raw_cost) have run as launches of their own on the same stream; this kernel is the rest
@@ -1237,8 +1340,13 @@ static inline size_t persist_dyn_lds(int N, int O, int A) { return ((size_t)O * 
 // across the step loop of every launch (ppo_train_halves.hip: 2.5 % there)
 // MON: store the raw reward of every step into ActStepArgs.raw_plane (icrl_monitor_t.raw_rewards) — a compile-time variant like PROF: the
 // instantiations without it are the kernels as they were, with not one more value in the step loop's registers
-template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true, bool DISC = false>
-__device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
+// SDE: the gSDE head (sde_head_wave) behind a deterministic forward, a compile-time form like MON and DISC: the instantiations without it keep
+// their code.  The launch's dynamic LDS then carries, behind the dynamics matrix, the float64 image of exp(2 log_std) [MAX_H][A] — log_std does
+// not change during a rollout: one exp per entry and launch, the per-call kernel's own bits — and the env's current exploration matrix
+// [MAX_H][A] float32, refilled from registers only where the draw index changes; the next draw's matrix is fetched one step ahead, as the
+// noise row is.
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true, bool DISC = false, bool SDE = false>
+__device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, const SdeArgs& sd = SdeArgs()) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ ActShared sh;
   double* const chunk = dyn_lds;                          // raw observations of the step, TRANSPOSED: [obs][NP], NP = N + 64
@@ -1282,6 +1390,18 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   auto rstore = [&](int byte_off, rec_u4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, xrs, byte_off, 0, 16); };     // sc1
   auto rload = [&](int byte_off) -> rec_u4 { return __builtin_amdgcn_raw_buffer_load_b128(xrs, byte_off, 0, 16); };
   for (int i = tid; i < O * NP; i += 256) chunk[i] = 0.0;
+  // gSDE (persist_sde_dyn_lds): the two images behind the dynamics matrix, and the matrix entries this thread carries from global memory to LDS
+  constexpr int SDE_REGS = MAX_H * MAX_ACT / 256;
+  double* const e2_s = SDE ? Bl + O * a.env.act_dim : nullptr;                        // exp(2 log_std) [MAX_H][A]
+  float* const E_s = SDE ? reinterpret_cast<float*>(e2_s + MAX_H * A) : nullptr;      // this env's current matrix [MAX_H][A]
+  const float* const expl_n = SDE ? as_global(sd.expl) + (size_t)n * (size_t)sd.env_stride : nullptr;
+  float e_reg[SDE_REGS];
+  if constexpr (SDE) {
+    const float* const ls_g = as_global(sd.ls);
+    for (int i = tid; i < MAX_H * A; i += 256) e2_s[i] = exp(2. * (double)ls_g[i]);
+#pragma unroll
+    for (int k = 0; k < SDE_REGS; ++k) { const int i = k * 256 + tid; e_reg[k] = i < MAX_H * A ? expl_n[i] : 0.f; }      // draw 0
+  }
   const bool has_cost = a.has_cn != 0;
   const uint32_t e_key = a.env.key[n];
   uint32_t e_ctr = a.env.step_count[n];
@@ -1303,7 +1423,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
   double st_m = 0.0, st_v = 1.0, st_c = 0.0;
   if (w == 3) { st_m = nm.ret_stats[0]; st_v = nm.ret_stats[1]; st_c = nm.ret_stats[2]; }
   if (w == 2) { st_m = nm.cost_stats[0]; st_v = nm.cost_stats[1]; st_c = nm.cost_stats[2]; }
-  float noise_reg = (tid < NA) ? noise_g[(size_t)n * NA + tid] : 0.f;
+  float noise_reg = (!SDE && tid < NA) ? noise_g[(size_t)n * NA + tid] : 0.f;
   double fin_rew = 0.0; float fin_cost = 0.f; int fin_done = 0;
   unsigned long long pc0 = 0, pc1 = 0, pc2 = 0, pc3 = 0, pc4 = 0, pc5 = 0, pc_rounds = 0, tl = PROF ? prof_now() : 0ull;
   int spin_limit = 1 << 22;
@@ -1311,13 +1431,32 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p) {
     const int par = t & 1;
     const size_t tn = (size_t)t * N + n;
     const unsigned gtag = (unsigned)(t + 1);
-    if (tid < NA) {
+    if (!SDE && tid < NA) {
       noise_s[tid] = noise_reg;
       if (t + 1 < T) noise_reg = noise_g[((size_t)(t + 1) * N + n) * NA + tid];     // lands during this step
     }
+    if constexpr (SDE) {
+      const int sf = sd.sample_freq;
+      if (t == 0 || (sf > 0 && t % sf == 0)) {      // a new draw: its matrix waits in the registers
+#pragma unroll
+        for (int k = 0; k < SDE_REGS; ++k) { const int i = k * 256 + tid; if (i < MAX_H * A) E_s[i] = e_reg[k]; }
+      }
+      if (t + 1 < T && sf > 0 && (t + 1) % sf == 0) {      // the next step starts a draw: its matrix lands during this step
+        const float* const nxt = expl_n + (size_t)((t + 1) / sf) * (size_t)sd.draw_stride;
+#pragma unroll
+        for (int k = 0; k < SDE_REGS; ++k) { const int i = k * 256 + tid; e_reg[k] = i < MAX_H * A ? nxt[i] : 0.f; }
+      }
+    }
     __syncthreads();
     // ---------------- phase A: kernel A's work for env n ----------------
-    policy_forward_block<OCT>(a.pl, R, sh, noise_s, 0, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+    if constexpr (SDE) {
+      // the mean and the latent, then the head on wave 0, which rewrites its own act_raw / act_clip / scal[2] (LDS accesses of one wave are
+      // ordered: no barrier in between); the barrier below publishes them to the env step, the cost wave and the buffer stores
+      policy_forward_block<OCT>(a.pl, R, sh, nullptr, 1, nullptr, nullptr);
+      if (w == 0) sde_head_wave(sh, A, a.pl.H2, E_s, [&](int i) { return e2_s[i]; }, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+    } else {
+      policy_forward_block<OCT>(a.pl, R, sh, noise_s, 0, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+    }
     __syncthreads();
     if (w == 0) {
       double rew; int done;
@@ -1795,6 +1934,13 @@ template <int OCT, int CIT, bool GRAN, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_persistent_disc_kernel(PersistArgs p) {
   rollout_persistent_body<OCT, CIT, GRAN, false, MON, false, true>(p);
 }
+// the gSDE form (SDE, see rollout_persistent_body): single runs, no phase timers, no raw-reward plane, no Point step, cost = 1 - zeta;
+// dynamic LDS: persist_sde_dyn_lds
+template <int OCT, int CIT, bool GRAN>
+__global__ void __launch_bounds__(256) rollout_persistent_sde_kernel(PersistArgs p, SdeArgs sd) {
+  rollout_persistent_body<OCT, CIT, GRAN, false, false, false, false, true>(p, sd);
+}
+static inline size_t persist_sde_dyn_lds(int N, int O, int A) { return persist_dyn_lds(N, O, A) + (size_t)MAX_H * (size_t)A * (sizeof(double) + sizeof(float)); }
 
 // several independent runs in ONE launch: grid (N, n_runs), run = blockIdx.y, argument blocks in device memory.  Workgroups are
 // dispatched x-fastest, so a run's N workgroups become resident together and the oldest run of the grid is always complete: runs
@@ -4427,7 +4573,8 @@ struct KernelPick {
   bool gran = false;       // one-workgroup-per-env kernels: granule mode (N (2 obs + 4) <= 256 GRAN_MAX)
   bool prof = false;       // tools: the instantiations with the phase timers (do_gae bits 2 / 3)
   bool disc = false;       // an icrl_cost_disc_t behind the cost pointer: the kernels whose cost wave returns zeta; single runs, no phase timers
-  int E = 0;               // multi kernels: envs per workgroup (multi_shape)
+  bool sde = false;        // icrl_rollout_collect_sde: the kernels with the gSDE head (with_act_step_sde_kernel, with_persistent_sde_kernel)
+  int E = 0;              // multi kernels: envs per workgroup (multi_shape)
   int minw = 1;            // batched one-workgroup-per-env kernels: workgroups per CU the register allocation leaves room for
   // what the dispatch below instantiated, written by it for the route record (pick_bits): the MINW of with_persistent_batch_kernel,
   // whether with_image took the <8, 8> image
@@ -4496,6 +4643,15 @@ template <class F> static int with_persistent_kernel(const KernelPick& k, F&& f)
     return f(rollout_persistent_kernel<OCT, CIT, GRAN>);
   }); });
 }
+// the gSDE forms: the four images, a constraint net read as 1 - zeta, an analytic cost or none; the one-workgroup-per-env kernel in both exchange modes
+template <class F> static int with_act_step_sde_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return f(act_step_sde_kernel<decltype(im)::oct, decltype(im)::cit>); });
+}
+template <class F> static int with_persistent_sde_kernel(const KernelPick& k, F&& f) {
+  return with_image(k, [&](auto im) { return with_flag(k.gran, [&](auto gran) {
+    return f(rollout_persistent_sde_kernel<decltype(im)::oct, decltype(im)::cit, decltype(gran)::value>);
+  }); });
+}
 template <class F> static int with_wide_kernel(const KernelPick& k, F&& f) {
   return with_image(k, [&](auto im) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
@@ -4549,7 +4705,7 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
 // the route record's word 4: the KernelPick fields that chose the instantiation of `route` (ICRL_PICK_*), nothing that it ignores;
 // the <8, 8> image and MINW as the dispatch that launched it wrote them down (call this after the launch)
 static int pick_bits(const KernelPick& k, int route) {
-  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0) | (k.disc ? ICRL_PICK_DISC : 0);
+  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0) | (k.disc ? ICRL_PICK_DISC : 0) | (k.sde ? ICRL_PICK_SDE : 0);
   if (route == ICRL_ROUTE_PER_STEP || route == ICRL_ROUTE_GENERIC_PER_STEP) return b;
   b |= k.mon ? ICRL_PICK_MON : 0;
   if (route == ICRL_ROUTE_PERSISTENT || route == ICRL_ROUTE_PERSISTENT_BATCH) b |= k.gran ? ICRL_PICK_GRAN : 0;
@@ -5054,6 +5210,107 @@ extern "C" int icrl_rollout_collect(const icrl_env_t* env, const icrl_norm_t* nm
                                     void* stream) {
   return icrl_rollout_collect_ex(env, nm, pol, cn, buf, ag, noise, action_low, action_high, reward_gamma, reward_gae_lambda,
                                  cost_gamma, cost_gae_lambda, 1, stream);
+}
+
+// ---- the rollout of a gSDE agent.  The matrices `expl` are drawn by the caller before the launch, in the order of the per-step loop
+// (ActorTwoCriticsPolicy.noise_schedule).  Routes, in the order they are tried:
+//   persistent   !(do_gae & 2), not a Point env, N <= 128, N obs <= 4096, workspace, co-resident      rollout_persistent_sde_kernel
+//   per-step     everything else: two launches per step                                              act_step_sde_kernel | norm_step
+// The multi-env and column-partitioned kernels have no gSDE form.  Every refusal is made on the host before any device call.
+template <class K>
+static int launch_per_env_sde(K kernel, int N, size_t dyn, hipStream_t s, PersistArgs& p, SdeArgs& sd) {
+  if (!persistent_fits(kernel, N, dyn)) return -1;
+  static const bool plain = getenv("ICRL_PLAIN_LAUNCH") != nullptr;
+  hipError_t e;
+  if (plain) {
+    hipLaunchKernelGGL(kernel, dim3(N), dim3(256), dyn, s, p, sd);
+    e = hipGetLastError();
+  } else {
+    void* params[] = {(void*)&p, (void*)&sd};
+    e = hipLaunchCooperativeKernel((const void*)kernel, dim3(N), dim3(256), params, (unsigned)dyn, s);
+  }
+  if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return -1; }
+  return (int)e;
+}
+
+extern "C" int icrl_rollout_collect_sde(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn_arg,
+                                        const icrl_buffer_t* buf, const icrl_agent_t* ag, const float* expl, int n_draws, int sample_freq,
+                                        const float* action_low, const float* action_high, double reward_gamma, double reward_gae_lambda,
+                                        double cost_gamma, double cost_gae_lambda, int do_gae, void* stream) {
+  const char* who = "icrl_rollout_collect_sde";
+  note_route(ICRL_FAMILY_ROLLOUT);
+  if (env == nullptr || nm == nullptr || pol == nullptr || buf == nullptr || ag == nullptr || expl == nullptr)
+    return fail("%s: NULL argument (env, nm, pol, buf, ag and expl are required)", who);
+  if (pol->params == nullptr || pol->params_t == nullptr) return fail("%s: NULL argument (pol->params and pol->params_t are required)", who);
+  if ((action_low == nullptr) != (action_high == nullptr)) return fail("%s: NULL argument (action_low and action_high: both or neither)", who);
+  if (pol->discrete) return fail("%s: a discrete policy has no gSDE head", who);
+  if (pol->arch != nullptr || pol->h1 != MAX_H || pol->h2 != MAX_H)
+    return fail("%s: hidden widths (%d, %d)%s; the gSDE rollout serves the fast kind: two hidden layers per branch, stored %d x %d, no `arch`", who, pol->h1,
+                pol->h2, pol->arch != nullptr ? " with an `arch` descriptor" : "", MAX_H, MAX_H);
+  if (pol->obs_dim < 1 || pol->obs_dim > MAX_OBS || pol->act_dim < 1 || pol->act_dim > MAX_ACT)
+    return fail("%s: policy obs_dim %d (1..%d), act_dim %d (1..%d)", who, pol->obs_dim, MAX_OBS, pol->act_dim, MAX_ACT);
+  const int n_diag = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, 0).n, n_sde = make_sde_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2).n;
+  if (pol->n_params != n_sde)
+    return fail("%s: n_params %d, the gSDE (log_std [%d, act_dim]) layout of (%d, %d, %d, %d) has %d%s", who, pol->n_params, MAX_H, pol->obs_dim, pol->act_dim,
+                pol->h1, pol->h2, n_sde, pol->n_params == n_diag ? " (that is the diagonal layout's count: icrl_rollout_collect_ex serves that policy)" : "");
+  const int N = env->n_envs, O = env->obs_dim, A = pol->act_dim, T = buf->T;
+  if (pol->obs_dim != O || env->act_dim != A || buf->N != N || buf->obs_dim != O || buf->act_store != A || N < 1 || T < 1)
+    return fail("%s: env (%d envs, obs_dim %d, act_dim %d) vs policy (obs_dim %d, act_dim %d) vs buffer (T = %d, %d envs, obs_dim %d, act_store %d)", who, N, O,
+                env->act_dim, pol->obs_dim, A, T, buf->N, buf->obs_dim, buf->act_store);
+  if (N > NORM_MAX_N)
+    return fail("%s: %d envs on one GPU, limit %d (shard the envs over ranks: the float64 normaliser statistics are one numpy-ordered chain per column)", who,
+                N, NORM_MAX_N);
+  if (sample_freq == 0) return fail("%s: sample_freq 0 (> 0: a draw every sample_freq steps; < 0: one draw for the rollout)", who);
+  const int need_draws = sample_freq > 0 ? (T + sample_freq - 1) / sample_freq : 1;
+  if (n_draws < need_draws) return fail("%s: n_draws %d, T = %d steps at sample_freq %d use %d", who, n_draws, T, sample_freq, need_draws);
+  if (do_gae & ~3) return fail("%s: do_gae %d (bit 0: the dual GAE behind the rollout, bit 1: the per-step launches; no other bit is served)", who, do_gae);
+  const icrl_cost_fn_t* const cf = as_cost_fn(cn_arg);
+  if (cf != nullptr)
+    if (int e = cost_fn_check(who, cf, O, A, 0)) return e;
+  if (as_cost_disc(cn_arg) != nullptr)
+    return fail("%s: a discriminator cost descriptor (icrl_cost_disc_t) is not served: the gSDE kernels have no discriminator form", who);
+  const icrl_costnet_t* const net = cf != nullptr ? nullptr : cn_arg;
+  if (net != nullptr && (costnet_is_wide(net) || !cn_ok(net)))
+    return fail("%s: a generic-shape constraint net (in_dim %d, %d hidden layers of (%d, %d), obs_dim %d, acs_dim %d) is not served: one or two hidden layers of "
+                "up to %d units, in_dim <= %d", who, net->in_dim, net->n_hidden, net->h1, net->h2, net->obs_dim, net->acs_dim, MAX_H, MAX_CN_IN);
+  const bool cn = cn_arg != nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  KernelPick k;
+  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.sde = true;
+  // the network alone, as launch_policy_forward_sde reads it: the diagonal layout, its transposes behind the matrix's first 63 rows
+  icrl_policy_t netpol = *pol;
+  netpol.params_t = pol->params_t + (MAX_H - 1) * A;
+  ActStepArgs a;
+  fill_act_args(a, env, buf, ag, &netpol, false, net, cf, nullptr, action_low, action_high, nullptr);
+  SdeArgs sd{expl, (long long)N * MAX_H * A, (long long)MAX_H * A, sample_freq, pol->params};
+  auto finish = [&](int err) { return finish_with_gae(err, do_gae, buf, ag, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, stream); };
+  auto routed = [&](int err, int route, const char* ws, int wgs, int E, int launches) {
+    if (err == 0) note_route(ICRL_FAMILY_ROLLOUT, route, ws_source(ag, ws), wgs, E, pick_bits(k, route), 0, 1, launches);
+    return err;
+  };
+  {
+    const bool gran = (size_t)N * (2 * O + 4) <= (size_t)256 * GRAN_MAX;
+    char* ws = exchange_ws(ag, buf, persist_ws_bytes(N, O, gran));
+    if (!(do_gae & 2) && env->reward_form < 4 && N <= 128 && N * O <= NORM_CHUNK && ws != nullptr) {
+      PersistArgs p;
+      p.act = a; p.nm = *nm; p.T = T; p.prof = 0;
+      const size_t clear = persist_ws_carve(ws, N, O, gran, p);
+      hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
+      if (e != hipSuccess) return (int)e;
+      k.gran = gran;
+      const size_t dyn = persist_sde_dyn_lds(N, O, A);
+      const int perr = with_persistent_sde_kernel(k, [&](auto kernel) { return launch_per_env_sde(kernel, N, dyn, s, p, sd); });
+      if (perr >= 0) return finish(routed(perr > 0 ? perr : (int)hipGetLastError(), ICRL_ROUTE_PERSISTENT, ws, N, 1, 1));
+    }
+  }
+  for (int t = 0; t < T; ++t) {
+    with_act_step_sde_kernel(k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, s, a, sd, t); return 0; });
+    const size_t row = (size_t)t * N;
+    NormStepArgs b{*nm, env->s, ag->raw_rew, cn ? ag->raw_cost : nullptr, ag->dones, N, O, ag->last_obs, nullptr, nullptr,
+                   buf->new_observations + row * O, buf->rewards + row, buf->costs + row, ag->last_dones};
+    launch_norm_step(b, s);
+  }
+  return finish(routed((int)hipGetLastError(), ICRL_ROUTE_PER_STEP, nullptr, N, 0, 2 * T));
 }
 
 // ---- rollout over host envs: one launch per env step (host_step_kernel) ----

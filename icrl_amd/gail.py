@@ -89,7 +89,8 @@ def setup(config, log=print):
                 sde_sample_freq=config.sde_sample_freq, target_kl=config.target_kl, seed=config.seed, device=dev, verbose=config.verbose,
                 policy_kwargs=dict(net_arch=[dict(pi=list(config.policy_layers), vf=list(config.reward_vf_layers), cvf=list(config.reward_vf_layers))]),
                 action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-                streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
+                streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None),
+                sde_fused_rollout=getattr(config, "sde_fused_rollout", False))
     cbs = [gail_update]
     if config.save_dir and rank == 0:
         cbs.append(callbacks.CheckpointCallback(int(config.save_every), os.path.join(config.save_dir, "models"), verbose=0))
@@ -141,6 +142,9 @@ def build_parser():
     a("--ent_coef", "-ec", type=float, default=0.); a("--reward_vf_coef", "-rvc", type=float, default=0.5)
     a("--target_kl", "-tk", type=float, default=None); a("--max_grad_norm", "-mgn", type=float, default=0.5)
     a("--learning_rate", "-lr", type=float, default=3e-4); a("--use_sde", "-us", action="store_true"); a("--sde_sample_freq", "-ssf", type=int, default=-1)
+    # -us: collect the rollout as a launch of the library (PPOLagrangian sde_fused_rollout).  Opt-in, and absent from the namespace unless given:
+    # the configs that runs store and seed batches compare stay what they were
+    a("--sde_fused_rollout", "-sfr", action="store_true", default=argparse.SUPPRESS)
     a("--freeze_gail_weights", "-fgw", action="store_true"); a("--gail_path", "-gp", type=str, default=None)
     a("--learn_cost", "-lc", action="store_true"); a("--disc_layers", "-dl", type=int, default=[64, 64], nargs="*")
     a("--disc_learning_rate", "-dlr", type=float, default=3e-4); a("--disc_batch_size", "-dbs", type=int, default=None)

@@ -91,7 +91,8 @@ def setup(config):
                             delta_p_ema_alpha=config.proportional_cost_ema_alpha, delta_d_ema_alpha=config.derivative_cost_ema_alpha),
             policy_kwargs=dict(net_arch=utils.get_net_arch(config)),
             action_noise=getattr(config, "action_noise", "device"), permutation=getattr(config, "permutation", "numpy"),
-            streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None))
+            streams=getattr(config, "streams", None), episode_stats=getattr(config, "episode_stats", None),
+            sde_fused_rollout=getattr(config, "sde_fused_rollout", False))
         # the constructor seeded every generator with config.seed (common/utils.py:23-39): all ranks now hold the SAME initial
         # networks; from here on rank r draws its own action noise / minibatch permutations
         D.decorrelate_streams(config.seed, rank)
@@ -274,6 +275,9 @@ def build_parser():
     a("--penalty_learning_rate", "-plr", type=float, default=0.1)
     a("--use_sde", "-us", action="store_true"); a("--use_curiosity_driven_exploration", "-ucde", action="store_true")
     a("--sde_sample_freq", "-ssf", type=int, default=-1)
+    # -us: collect the rollout as a launch of the library (PPOLagrangian sde_fused_rollout).  Opt-in, and absent from the namespace unless given:
+    # the configs that runs store and seed batches compare stay what they were
+    a("--sde_fused_rollout", "-sfr", action="store_true", default=argparse.SUPPRESS)
     a("--train_gail_lambda", "-tgl", action="store_true"); a("--n_iters", "-ni", type=int, default=100)
     a("--warmup_timesteps", "-wt", type=lambda x: int(float(x)), default=None)
     a("--forward_timesteps", "-ft", type=lambda x: int(float(x)), default=1e6); a("--backward_iters", "-bi", type=int, default=10)

@@ -256,12 +256,9 @@ class ActorTwoCriticsPolicy:
         return None if self.discrete else self.params[:self.act_dim]
 
     # ---- gSDE ---------------------------------------------------------------------------------------------------------
-    def reset_noise(self, n_envs=1, streams=None):
-        """ref: policies.py:434-441 -> distributions.py:483-496 — draw the exploration matrices E0 [H, A] and E [n_envs, H, A] from
-        Normal(0, exp(log_std)); kept on the device in the stored [64, A] shape (zero rows beyond H).  `streams.sde_noise(shape)`, where the
-        agent's streams object has it, gives the standard normals (teacher forcing); otherwise torch draws them on the device."""
-        assert self.use_sde, "reset_noise: not a gSDE policy"
-        H, A, dev = self.sde_latent, self.act_dim, self.device
+    def _sde_normals(self, streams):
+        """shape -> standard normals on the device: `streams.sde_noise(shape)` where the streams object has it, else torch's device generator"""
+        dev = self.device
         draw = getattr(streams, "sde_noise", None) if streams is not None else None
         def normals(shape):
             if draw is None:
@@ -269,6 +266,15 @@ class ActorTwoCriticsPolicy:
             z = draw(shape)
             z = z if torch.is_tensor(z) else torch.as_tensor(np.asarray(z, np.float32))
             return z.to(device=dev, dtype=torch.float32).reshape(shape)
+        return normals
+
+    def reset_noise(self, n_envs=1, streams=None):
+        """ref: policies.py:434-441 -> distributions.py:483-496 — draw the exploration matrices E0 [H, A] and E [n_envs, H, A] from
+        Normal(0, exp(log_std)); kept on the device in the stored [64, A] shape (zero rows beyond H).  `streams.sde_noise(shape)`, where the
+        agent's streams object has it, gives the standard normals (teacher forcing); otherwise torch draws them on the device."""
+        assert self.use_sde, "reset_noise: not a gSDE policy"
+        H, A = self.sde_latent, self.act_dim
+        normals = self._sde_normals(streams)
         std = torch.exp(self.log_std)
         self.set_noise(normals((H, A)) * std, normals((int(n_envs), H, A)) * std)
 
@@ -279,6 +285,37 @@ class ActorTwoCriticsPolicy:
         E = torch.as_tensor(E, device=dev).float().reshape(-1, H, A)
         self.sde_E0 = torch.zeros(HW, A, device=dev); self.sde_E0[:H] = E0
         self.sde_E = torch.zeros(E.shape[0], HW, A, device=dev); self.sde_E[:, :H] = E
+
+    @staticmethod
+    def noise_schedule_draws(T, sample_freq):
+        """how many of a rollout's draws get used: one per started block of sample_freq steps, or the one at the rollout's start."""
+        T, sf = int(T), int(sample_freq)
+        return -(-T // sf) if sf > 0 else 1
+
+    def noise_schedule(self, n_envs, T, sample_freq, streams=None):
+        """The exploration matrices of a whole rollout, drawn before its first step (icrl_rollout_collect_sde): exactly the reset_noise calls the
+        per-step loop makes, in its order — one at the rollout's start, then one at every t with sample_freq > 0 and t % sample_freq == 0, t = 0
+        included — so the generator (or `streams.sde_noise`) ends where the loop leaves it, and sde_E0 / sde_E hold the last draw as they do
+        after the loop.  Returns the matrices that get used, [D, n_envs, 64, A] with D = noise_schedule_draws(T, sample_freq): step t reads
+        draw t // sample_freq (draw 0 when sample_freq <= 0).  One env: the E0 of each draw, which _forward_sde picks for a single row."""
+        assert self.use_sde, "noise_schedule: not a gSDE policy"
+        n_envs, T, sf = int(n_envs), int(T), int(sample_freq)
+        H, A, dev = self.sde_latent, self.act_dim, self.device
+        normals = self._sde_normals(streams)
+        D = self.noise_schedule_draws(T, sf)
+        # the draws themselves stay one call per tensor, in reset_noise's order (their values depend on it); everything behind them — the
+        # scaling by exp(log_std), the padding to 64 rows — is done once for the whole schedule (log_std does not change during a rollout)
+        z0 = z = None
+        used = []
+        for d in range(1 + (D if sf > 0 else 0)):
+            z0, z = normals((H, A)), normals((n_envs, H, A))
+            if sf <= 0 or d >= 1:      # (with a cadence, the rollout's own draw is replaced at step 0 before any step reads it)
+                used.append(z0.unsqueeze(0) if n_envs == 1 else z)
+        std = torch.exp(self.log_std)
+        sched = torch.zeros(D, n_envs, HW, A, device=dev)
+        sched[:, :, :H] = torch.stack(used) * std
+        self.set_noise(z0 * std, z * std)
+        return sched
 
     def _forward_sde(self, obs, deterministic, clip):
         """icrl_policy_forward_sde with the matrices get_noise picks (distributions.py:577-587): E0 for one row or when the row count is not

@@ -10,8 +10,13 @@ the work is enqueued as kernels of libicrl_hip.so:
                       no host sync)
   train            -> icrl_ppo_lag_train   (ONE persistent launch for all epochs x minibatches); the dual variable is one
                       float32 scalar updated on the host (dual_variable.py)
-A gSDE agent (use_sde=True) runs neither fused launch: its rollout is the per-step loop around icrl_policy_forward_sde and its
-update the fine-grained loop around icrl_policy_sde_fwd_bwd (_train_sde) — both on the device, one launch per piece.
+A gSDE agent (use_sde=True; DESIGN sections 23-25) updates in one persistent launch of its own (icrl_ppo_lag_train_sde; the fine-grained loop around
+icrl_policy_sde_fwd_bwd where that does not serve the call: _train_sde).  Its rollout is the per-step loop around icrl_policy_forward_sde by
+default, and with sde_fused_rollout=True (--sde_fused_rollout, ICRL_SDE_ROLLOUT_FUSED=1) a launch of the library as well: the exploration
+matrices of the whole rollout are drawn up front in the loop's order (policy.noise_schedule) and icrl_rollout_collect_sde computes what the loop
+computes, as ONE persistent launch or 2 launches per env step.  last_sde_rollout says which ran ("fused" | "loop"), last_sde_rollout_reason why
+the loop: the switch off, a callable cost_function, a partial rollout, no fused env chain, a DiscriminatorCost, episode_stats, a schedule above
+sde_fused_max_bytes.
 """
 import os
 import time
@@ -55,10 +60,16 @@ class PPOLagrangian:
                  max_grad_norm=0.5, use_sde=False, sde_sample_freq=-1, target_kl=None, penalty_initial_value=1,
                  penalty_learning_rate=0.01, penalty_min_value=None, update_penalty_after=1, budget=0.,
                  tensorboard_log=None, create_eval_env=False, pid_kwargs=None, policy_kwargs=None, verbose=0, seed=None,
-                 device="cuda", _init_setup_model=True, action_noise="device", permutation="numpy", streams=None, episode_stats=None):
+                 device="cuda", _init_setup_model=True, action_noise="device", permutation="numpy", streams=None, episode_stats=None,
+                 sde_fused_rollout=False):
         # gSDE (ref: ppo_lag.py:207-213, on_policy_algorithm.py:362-370): the policy keeps log_std [H, A] and its exploration matrices, which are redrawn at the
         # start of every rollout and every sde_sample_freq steps (-1: only at the start)
         self.use_sde, self.sde_sample_freq = bool(use_sde), int(sde_sample_freq)
+        # sde_fused_rollout: collect a gSDE agent's rollouts in the library (icrl_rollout_collect_sde) — the matrices of the whole rollout drawn up front
+        # in the loop's order (policy.noise_schedule) — where it serves the call, see _sde_rollout_reason.  Also switched on by ICRL_SDE_ROLLOUT_FUSED=1.
+        self.sde_fused_rollout = bool(sde_fused_rollout) or os.environ.get("ICRL_SDE_ROLLOUT_FUSED", "0").strip().lower() not in ("", "0", "false", "no", "off")
+        self.sde_fused_max_bytes = 512 << 20      # largest schedule held on the device (ssf 1 at 256 AntWall envs x 2048 steps would be 1 GiB)
+        self.last_sde_rollout = self.last_sde_rollout_reason = None
         if policy not in ("TwoCriticsMlpPolicy", ActorTwoCriticsPolicy):
             raise NotImplementedError(f"policy {policy!r}: only TwoCriticsMlpPolicy is on the ICRL hot path")
         self.env: VecEnv = env
@@ -252,8 +263,14 @@ class PPOLagrangian:
     def collect_rollouts(self, env, callback, rollout_buffer, n_rollout_steps, cost_function="cost", noise=None):
         """ref: on_policy_algorithm.py:340-421."""
         assert self._last_obs is not None, "No previous observation was provided"
-        if self.use_sde:      # the exploration matrices are redrawn between steps: always the per-step loop, around icrl_policy_forward_sde
-            return self._collect_rollouts_stepped(env, callback, rollout_buffer, n_rollout_steps, cost_function, None)
+        if self.use_sde:      # the per-step loop around icrl_policy_forward_sde, or (sde_fused_rollout) the same rollout as a launch of the library
+            reason = self._sde_rollout_reason(cost_function, n_rollout_steps, rollout_buffer)
+            self.last_sde_rollout, self.last_sde_rollout_reason = ("fused" if reason is None else "loop"), reason
+            if reason is not None:
+                return self._collect_rollouts_stepped(env, callback, rollout_buffer, n_rollout_steps, cost_function, None)
+            job = self._rollout_begin_sde(callback, rollout_buffer, n_rollout_steps)
+            self._rollout_launch_sde(job)
+            return self._rollout_end(job, env, callback, rollout_buffer, n_rollout_steps)
         if not self._fused_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
             if self._host_rollout_ok(cost_function, n_rollout_steps, rollout_buffer):
                 return self._collect_rollouts_host(env, callback, rollout_buffer, n_rollout_steps, noise)
@@ -266,6 +283,72 @@ class PPOLagrangian:
 
     def _fused_rollout_ok(self, cost_function, n_rollout_steps, rollout_buffer):
         return self._fused_chain() is not None and isinstance(cost_function, str) and n_rollout_steps == rollout_buffer.buffer_size
+
+    # ---- the gSDE rollout as a launch of the library (sde_fused_rollout; csrc/rollout.hip: icrl_rollout_collect_sde) ------------------------
+    def sde_schedule_bytes(self, n_rollout_steps):
+        """device bytes of one rollout's exploration matrices, [draws, n_envs, 64, A] float32."""
+        draws = ActorTwoCriticsPolicy.noise_schedule_draws(n_rollout_steps, self.sde_sample_freq)
+        return 4 * draws * int(self.n_envs) * 64 * int(self.action_space.shape[0])
+
+    def _sde_rollout_reason(self, cost_function, n_rollout_steps, rollout_buffer):
+        """None when icrl_rollout_collect_sde serves this rollout, else why the per-step loop runs (last_sde_rollout_reason)."""
+        if not getattr(self, "sde_fused_rollout", False):
+            return "sde_fused_rollout is off"
+        if not isinstance(cost_function, str):
+            return "a callable cost_function"
+        if n_rollout_steps != rollout_buffer.buffer_size:
+            return "a partial rollout"
+        chain = self._fused_chain()
+        if chain is None:
+            return "no fused env chain (host envs, or a cost the rollout kernels do not evaluate)"
+        cw = chain[1]
+        if cw is not None and cw.discriminator_cost() is not None:
+            return "a DiscriminatorCost (the gSDE kernels have no discriminator form)"
+        if cw is not None and cw.constraint_net() is not None:
+            cs = cw.cost_struct()
+            if cs.n_hidden not in (1, 2) or cs.h1 > 64 or (cs.n_hidden == 2 and cs.h2 > 64) or cs.in_dim > 160:
+                return "a generic-shape constraint net"
+        if self._mon is not None:
+            return "episode_stats (the gSDE kernels do not store the raw-reward plane)"
+        if self.n_envs > 4096:
+            return "more than 4096 envs"
+        need, cap = self.sde_schedule_bytes(n_rollout_steps), int(getattr(self, "sde_fused_max_bytes", 512 << 20))
+        if need > cap:
+            return f"the schedule of {need} bytes exceeds sde_fused_max_bytes = {cap}"
+        return None
+
+    def _rollout_begin_sde(self, callback, rollout_buffer, n_rollout_steps):
+        """_rollout_begin for a gSDE agent, in the fused rollout's order: reset the buffer, on_rollout_start, then the draws of the whole rollout."""
+        rollout_buffer.reset()
+        if callback is not None:
+            callback.on_rollout_start()
+        nenv, cw, senv = self._fused_chain()
+        expl = self.policy.noise_schedule(self.n_envs, n_rollout_steps, self.sde_sample_freq, self.streams)
+        e, nm, pol, buf = senv.struct(), nenv.struct(), self.policy.struct(sde=True), rollout_buffer.struct()
+        cn = cw.cost_struct() if cw is not None else None
+        ag = AgentT(p(self._last_obs), p(self._ag["last_dones"]), p(self._ag["raw_rew"]), p(self._ag["raw_cost"]), p(self._ag["dones"]),
+                    p(self._ag["last_v_r"]), p(self._ag["last_v_c"]), p(self._ag["act_clipped"]), p(self._ag["status"]),
+                    p(self._ag["xch_ws"]), self._ag["xch_ws"].numel() * 8)
+        timed = getattr(self, "gae_events", None) is not None
+        flags = int(not timed) | (2 if getattr(self, "rollout_kernel", "auto") == "steps" else 0)
+        # (`noise`: what _rollout_end keeps alive until the next rollout — here the schedule)
+        return dict(env=e, nm=nm, pol=pol, cn=cn, buf=buf, ag=ag, noise=expl, flags=flags, timed=timed, chain=(nenv, cw, senv))
+
+    def _rollout_launch_sde(self, job):
+        b = _lib.byref
+        rev = None
+        if getattr(self, "rollout_events", None) is not None:
+            rev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            rev[0].record()
+        cn, expl = job["cn"], job["noise"]
+        _lib.check(_lib.lib().icrl_rollout_collect_sde(b(job["env"]), b(job["nm"]), b(job["pol"]), b(cn) if cn is not None else None, b(job["buf"]), b(job["ag"]),
+                                                       p(expl), int(expl.shape[0]), int(self.sde_sample_freq) if self.sde_sample_freq > 0 else -1,
+                                                       p(self._alow), p(self._ahigh), float(self.reward_gamma), float(self.reward_gae_lambda),
+                                                       float(self.cost_gamma), float(self.cost_gae_lambda), job["flags"], _lib.current_stream()),
+                   "icrl_rollout_collect_sde")
+        if rev is not None:
+            rev[1].record()
+            self.rollout_events.append(rev)
 
     # The fused rollout in three pieces, so that several runs sharing a GPU (icrl_amd/seed_batch.py) can put their launches into
     # ONE grid: _rollout_begin (host state + descriptors), the launch (single: _rollout_launch; batched: seed_batch), _rollout_end.
@@ -601,7 +684,8 @@ class PPOLagrangian:
                     policy_kwargs=dict(net_arch=[*self.policy.shared, dict(pi=list(self.policy.layers["policy_net"]), vf=list(self.policy.layers["value_net"]),
                                                                            cvf=list(self.policy.layers["cost_value_net"]))]))
         # the rest of what the reference's __init__ leaves in self.__dict__ and its load() / _setup_model() / predict() read
-        data.update(verbose=int(getattr(self, "verbose", 0)), use_sde=bool(self.use_sde), sde_sample_freq=int(self.sde_sample_freq), tensorboard_log=None, action_noise=None,
+        data.update(verbose=int(getattr(self, "verbose", 0)), use_sde=bool(self.use_sde), sde_sample_freq=int(self.sde_sample_freq), sde_fused_rollout=bool(getattr(self, "sde_fused_rollout", False)),
+                    tensorboard_log=None, action_noise=None,
                     _total_timesteps=int(getattr(self, "_total_timesteps", 0) or 0), _episode_num=0, start_time=None,
                     _current_progress_remaining=float(getattr(self, "_current_progress_remaining", 1.0)))
         data.update(policy_class=U.sb3_policy_class_entry(), observation_space=U.sb3_space_entry(self.observation_space),
@@ -672,6 +756,7 @@ class PPOLagrangian:
         else:
             env = _SpacesOnlyEnv(int(data.get("n_envs", 1)), data["observation_space"], data["action_space"])
         model = cls("TwoCriticsMlpPolicy", env, device=device, _init_setup_model=False)
+        env_switch = model.sde_fused_rollout      # ICRL_SDE_ROLLOUT_FUSED
         skip = {"policy_class", "observation_space", "action_space", "device", "policy_kwargs", "observation_dim", "action_dim",
                 "discrete", "policy_class_name", "adam_step", "n_envs"}
         for k, v in data.items():
@@ -682,6 +767,8 @@ class PPOLagrangian:
                 setattr(model, k, 0.2 if k == "clip_range" else None)
         model.policy_kwargs = dict(net_arch=net_arch)
         model.use_sde, model.sde_sample_freq = bool(data.get("use_sde", False)), int(data.get("sde_sample_freq", -1))
+        # (absent in an archive — every one the reference wrote — means off; the environment switch read by __init__ still holds)
+        model.sde_fused_rollout = bool(data.get("sde_fused_rollout", False)) or env_switch
         model.__dict__.update(kwargs)
         model._setup_model()
         model.load_parameters(path, dual=False)

@@ -716,7 +716,7 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
  * other two) and step to the next form silently; this says which one ran.  Host state only, thread-local like icrl_last_error():
  * a call clears its family's record on entry and writes it behind its launch, so a call refused before any launch leaves route 0.
  * out8 receives 8 int32 (unused words 0).  Returns 0; a family outside 0..2 or a NULL out8 is refused with a message.
- *   ICRL_FAMILY_ROLLOUT  icrl_rollout_collect[_ex][_mon] and icrl_rollout_collect_batch[_mon | _cost]:
+ *   ICRL_FAMILY_ROLLOUT  icrl_rollout_collect[_ex][_mon], icrl_rollout_collect_sde and icrl_rollout_collect_batch[_mon | _cost]:
  *     [0] ICRL_ROUTE_*   [1] ICRL_WS_* (a batch: of its last run)   [2] working workgroups per run   [3] envs per workgroup (0: per-step)
  *     [4] ICRL_PICK_* bits of the instantiation, the batched one-workgroup-per-env kernel's MINW at ICRL_PICK_MINW_SHIFT
  *     [5] packed XCD layout (multi kernels)   [6] n_runs   [7] launches of the rollout proper, the GAE excluded: 1, 2 T (per-step),
@@ -752,6 +752,7 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
 #define ICRL_PICK_GRAN 8
 #define ICRL_PICK_CN128 16
 #define ICRL_PICK_DISC 32     /* the constraint net read as D (icrl_cost_disc_t) */
+#define ICRL_PICK_SDE 64      /* the kernels with the gSDE head (icrl_rollout_collect_sde) */
 #define ICRL_PICK_MINW_SHIFT 8
 #define ICRL_UPDATE_GENERIC_PERSISTENT 8
 #define ICRL_UPDATE_GENERIC_LAUNCHES 9
@@ -878,6 +879,30 @@ int icrl_policy_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float*
 int icrl_policy_forward_sde(const icrl_policy_t* pol, const double* obs, const float* expl, long long expl_stride, int N, int deterministic,
                             const float* action_low, const float* action_high, float* actions, float* act_clipped, float* v_r, float* v_c,
                             float* log_prob, void* stream);
+/* The rollout of a gSDE agent in the library (csrc/rollout.hip): icrl_rollout_collect_ex for a policy with the state-dependent-noise head.
+ * The exploration matrices a rollout uses are known before its first step — one draw at the start, one every sample_freq steps — so the
+ * caller draws them up front, in the per-step loop's order (ActorTwoCriticsPolicy.noise_schedule), and the kernels compute what that loop
+ * computes around icrl_policy_forward_sde: per step the forward of the network, then the head in float64 on the float32 latent (the
+ * arithmetic of icrl_policy_forward_sde term for term), the clip, the env step, the cost, the normaliser, the buffer row.
+ *   pol   the gSDE descriptor (n_params = the diagonal layout's + 63 * act_dim), params_t as icrl_policy_prepare leaves it on the descriptor of
+ *         the network alone (see icrl_policy_forward_sde)
+ *   expl  [n_draws][N][64][act_dim] float32: the matrix of env n while draw d is current (rows beyond the latent width zero); step t uses draw
+ *         t / sample_freq when sample_freq > 0, draw 0 when it is negative; n_draws >= ceil(T / sample_freq) (or 1).  Must stay alive until
+ *         the launch has run.
+ *   cn    as for icrl_rollout_collect_ex: a constraint net of the one-workgroup-per-env image, an analytic cost (icrl_cost_fn_t) or NULL
+ *   do_gae  bit 0: the dual GAE behind the rollout; bit 1: force the per-step launches
+ * Routes: ONE persistent launch, one workgroup per env (rollout_persistent_sde_kernel: no Point env, N <= 128, N obs <= 4096, a workspace,
+ * a co-resident grid; every exchange wait bounded, a timed-out one reported through icrl_agent_t.status), else two launches per step
+ * (act_step_sde_kernel | norm_step).  Both write the ICRL_FAMILY_ROLLOUT record with ICRL_PICK_SDE set; the two routes agree bit for bit.
+ * Refused with hipErrorInvalidValue and the reason, on the host, before any device call: a NULL pointer, a diagonal-layout n_params, a discrete
+ * policy, an `arch` descriptor or hidden widths other than the stored 64 x 64, obs_dim above 128 or act_dim above 16, env / policy / buffer
+ * shapes that differ, n_draws below what T and sample_freq use, sample_freq 0, a do_gae bit above 1, a discriminator cost
+ * (icrl_cost_disc_t), a generic-shape constraint net, more than 4096 envs.
+ * Not served in this form: phase timers, the raw-reward plane (icrl_monitor_t), seed batches, the multi-env and column-partitioned kernels. */
+int icrl_rollout_collect_sde(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const icrl_costnet_t* cn,
+                             const icrl_buffer_t* buf, const icrl_agent_t* ag, const float* expl, int n_draws, int sample_freq,
+                             const float* action_low, const float* action_high, double reward_gamma, double reward_gae_lambda,
+                             double cost_gamma, double cost_gae_lambda, int do_gae, void* stream);
 size_t icrl_policy_sde_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
 int icrl_policy_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
                             const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,

@@ -10,7 +10,12 @@
             takes by default), and for the diagonal head icrl_ppo_lag_train with the column-split tiles kernel (hp._pad bit 1) — the kernel the gSDE
             launch is built from, so the difference of the two is the cost of the head.
 
-The rollout and loop figures say nothing about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
+  rollout_fused   microseconds per env step of PPOLagrangian.collect_rollouts as a launch of the library: the gSDE agent with sde_fused_rollout
+            (icrl_rollout_collect_sde, the schedule's draws included) and the diagonal head's fused rollout (icrl_rollout_collect_ex) — the
+            difference of the two is the cost of the head and of the schedule; the yardstick is the gSDE loop in the same process and run order.
+            Both at --envs envs x --steps steps and (keys ending in _64x2048) at 64 envs x 2048 steps, sde_sample_freq 8.
+
+The loop figures say nothing about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
 --warmup, one synchronisation at each end, host clock around it; --runs runs per form, interleaved.  Needs the GPU.
 
     python tools/sde_bench.py [--steps 512 --warmup 64 --runs 3 --envs 4] [--wide] [--out profiles/sde.json]
@@ -131,20 +136,39 @@ class UpdateLoop:
 
 
 class RolloutLoop:
-    def __init__(self, use_sde, envs, steps):
+    """fused: collect_rollouts as a launch of the library (gSDE: --sde_fused_rollout), else the per-step loop"""
+
+    def __init__(self, use_sde, envs, steps, fused=False):
         from icrl_amd import cpg
         argv = ["cpg", "-tei", "HCWithPos-v0", "-eei", "HCWithPosTest-v0", "-nt", str(envs), "--n_steps", str(steps), "-s", "0", "-v", "0"] + (["-us", "-ssf", "8"] if use_sde else [])
-        cfg = vars(cpg.build_parser().parse_args(argv))
+        cfg = vars(cpg.build_parser().parse_args(argv + (["-sfr"] if use_sde and fused else [])))
         cfg.update(rank=0, world_size=1)
         self.model, _cb, self.cost, _hist = cpg.setup(types.SimpleNamespace(**cfg), log=None)
-        self.steps = steps
+        self.steps, self.fused, self.use_sde = steps, fused, use_sde
         self.model._setup_learn(envs * steps)
 
     def run(self):
         m = self.model
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        assert m._collect_rollouts_stepped(m.env, None, m.rollout_buffer, self.steps, self.cost) is True
+        if self.fused:
+            assert m.collect_rollouts(m.env, None, m.rollout_buffer, self.steps, self.cost) is True
+        else:
+            assert m._collect_rollouts_stepped(m.env, None, m.rollout_buffer, self.steps, self.cost) is True
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if self.fused:      # one launch, and (gSDE) the launch with the head, not the loop
+            route = _lib.last_route(_lib.FAMILY_ROLLOUT)
+            assert route[7] == 1 and bool(route[4] & _lib.PICK_SDE) == self.use_sde and (not self.use_sde or m.last_sde_rollout == "fused"), route
+            m.check_rollout_status()
+        return 1e6 * dt / self.steps
+
+    def schedule_us(self):
+        """the up-front draws alone (policy.noise_schedule), per env step: the part of a fused gSDE rollout that is not the launch"""
+        m = self.model
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.policy.noise_schedule(m.n_envs, self.steps, m.sde_sample_freq, m.streams)
         torch.cuda.synchronize()
         return 1e6 * (time.perf_counter() - t0) / self.steps
 
@@ -164,17 +188,27 @@ def main():
                   protocol="host clock between two synchronisations around --steps steps after --warmup; --runs runs per form, interleaved; "
                            "update: obs 18, act 6, batch 64, fine-grained loop; update_fused: the same buffer and shape, one persistent launch of "
                            "steps / 32 epochs (gsde: icrl_ppo_lag_train_sde; diagonal: icrl_ppo_lag_train, tiles kernel); rollout: HCWithPos, per-step "
-                           "loop, sde_sample_freq 8")
+                           "loop, sde_sample_freq 8; rollout_fused: the same rollout as one launch of the library (gsde: icrl_rollout_collect_sde with "
+                           "the schedule's draws inside the timed region; diagonal: icrl_rollout_collect_ex); keys ending in _64x2048: 64 envs x 2048 "
+                           "steps; microseconds per env step = time of the rollout / its steps")
     upd = {k: UpdateLoop(k == "gsde") for k in ("diagonal", "gsde")}
     roll = {k: RolloutLoop(k == "gsde", a.envs, a.steps) for k in ("diagonal", "gsde")}
-    for loop in roll.values():
+    # the three rollout forms at both shapes: the gSDE loop (the yardstick), the gSDE launch, the diagonal head's launch
+    forms = {"rollout_us_per_step_gsde": (True, False), "rollout_fused_us_per_step_gsde": (True, True), "rollout_fused_us_per_step_diagonal": (False, True)}
+    shapes = {"": (a.envs, a.steps), "_64x2048": (64, 2048)}
+    fused_roll = {key + tag: (roll["gsde"] if (tag == "" and not fused) else RolloutLoop(sde, envs, steps, fused))
+                  for tag, (envs, steps) in shapes.items() for key, (sde, fused) in forms.items()}
+    for loop in list(roll.values()) + [l for l in fused_roll.values() if l is not roll["gsde"]]:
         loop.run()      # warm-up rollout
     us = {f"{what}_us_per_step_{k}": [] for what in ("update", "update_fused", "rollout") for k in ("diagonal", "gsde")}
+    us.update({k: [] for k in fused_roll})
     for _ in range(a.runs):
         for k in ("diagonal", "gsde"):
             us[f"update_us_per_step_{k}"].append(round(upd[k].run(a.steps, a.warmup), 1))
             us[f"update_fused_us_per_step_{k}"].append(round(upd[k].run_fused(a.steps, a.warmup), 2))
-            us[f"rollout_us_per_step_{k}"].append(round(roll[k].run(), 1))
+        us["rollout_us_per_step_diagonal"].append(round(roll["diagonal"].run(), 1))
+        for k, loop in fused_roll.items():      # interleaved: loop, gSDE launch, diagonal launch, per shape
+            us[k].append(round(loop.run(), 2 if "fused" in k else 1))
     if a.wide:
         wide = {k: UpdateLoop(k == "gsde", obs=113, act=8, batch=128) for k in ("diagonal", "gsde")}
         for what in ("update", "update_fused"):
@@ -185,6 +219,12 @@ def main():
                 us[f"update_us_per_step_{k}_113_8_128"].append(round(wide[k].run(a.steps, a.warmup), 1))
                 us[f"update_fused_us_per_step_{k}_113_8_128"].append(round(wide[k].run_fused(a.steps, a.warmup), 2))
     result.update(us)
+    result["not_measured"] = ("rollout_fused: other shapes and action widths, sde_sample_freq 1, a whole cpg -us -sfr run, the per-step launches' own rate; the head's share inside the kernel is the difference to the diagonal rollout less the schedule's share, not a measurement of its own")
+    for tag in shapes:      # the launch against the loop of the same process: slowest launch run over fastest loop run
+        lo, fu, di = us["rollout_us_per_step_gsde" + tag], us["rollout_fused_us_per_step_gsde" + tag], us["rollout_fused_us_per_step_diagonal" + tag]
+        result["rollout_fused_gsde_speedup_worst_case" + tag] = round(min(lo) / max(fu), 1)
+        result["rollout_fused_gsde_minus_diagonal_us" + tag] = round(sorted(fu)[len(fu) // 2] - sorted(di)[len(di) // 2], 2)
+        result["rollout_fused_gsde_schedule_us_per_step" + tag] = [round(fused_roll["rollout_fused_us_per_step_gsde" + tag].schedule_us(), 2) for _ in range(a.runs)]
     for k, v in us.items():
         print(f"{k}: {v}", flush=True)
     print(json.dumps(result))
