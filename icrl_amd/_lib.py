@@ -83,6 +83,10 @@ SIGNATURES = {
     "icrl_ppo_lag_train_sde": [c_void_p] * 11,
     # the gSDE agent's rollout in the library (csrc/rollout.hip; ppo_lag.py sde_fused_rollout): expl, n_draws, sample_freq in the noise's place
     "icrl_rollout_collect_sde": [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 2 + [c_double] * 4 + [c_int, c_void_p],
+    # sampling / evaluation episodes of a gSDE agent as one launch (utils.EpisodeRun)
+    "icrl_sample_episodes_sde": [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 6,
+    "icrl_sample_episodes_chain_sde": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong,
+                                       c_void_p],
     # the exploration callbacks' regression step and the advantage shaping (csrc/reg_mlp.hip; icrl_amd/exploration.py)
     "icrl_reg_mlp_ws_bytes": [ctypes.c_longlong] + [c_int] * 5,
     "icrl_reg_mlp_step": [c_void_p] * 7 + [ctypes.c_longlong] + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 3 + [ctypes.c_longlong, c_void_p],

@@ -3520,11 +3520,27 @@ struct ChainArgs {
 };
 constexpr unsigned CHAIN_UNSET = 0xFFFFFFFEu;      // "nothing published yet": no start ever reaches 2^31 - 1 rows
 
-template <int OCT, bool CHAIN = false>
-__device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const ChainArgs* c = nullptr) {
+// SDE (icrl_sample_episodes_sde / _chain_sde): a gSDE policy, a compile-time form like MON, DISC and SDE of rollout_persistent_body: the
+// instantiations without it keep their code.  An episode loop never redraws: one env means get_noise picks E0, so ONE matrix `expl` [MAX_H][A]
+// serves every step of every episode of the launch (NULL: the mode).  It is fetched once, in front of the step loop, into a float32 LDS image
+// [MAX_H][A] (4 KB at A = 16; as 64 registers of wave 0 the <8> kernels reached 512 VGPRs and spilled: DESIGN.md section 26), and a restart
+// of a chained stream does not refetch it; a.pl / a.PT describe the network alone (the diagonal layout, the
+// transposes behind the matrix's first 63 rows, as icrl_rollout_collect_sde builds them) and a.noise is not read.  The sampler stores no
+// log-prob, so the head is the action half of sde_head_wave alone, term for term: no variance chain, no log, no division, no exp.
+template <int OCT, bool CHAIN = false, bool SDE = false>
+__device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const ChainArgs* c = nullptr, const float* expl = nullptr) {
   __shared__ ActShared sh;
   PolRegs<OCT> R;
   load_pol_regs<OCT>(a.pl, a.PT, R);    // once for every step of every episode of this stream
+  const float* E_s = nullptr;           // SDE: the LDS image of the exploration matrix, or NULL (the mode)
+  if constexpr (SDE) {
+    __shared__ float E_img[MAX_H * MAX_ACT];
+    const float* const E_g = as_global(expl);
+    if (E_g != nullptr) {               // (read behind the barriers in front of the first step, like the dynamics matrix below)
+      for (int i = threadIdx.x; i < MAX_H * a.pl.A; i += 192) E_img[i] = E_g[i];
+      E_s = E_img;
+    }
+  }
   __shared__ int s_done;
   __shared__ double s_rew;
   __shared__ unsigned s_word;                  // CHAIN: the predecessor's position word as this step saw it
@@ -3536,7 +3552,7 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const 
   const int AS = a.pl.discrete ? 1 : A;
   icrl_env_t env = a.env; globalize(env);
   // what the step loop reads of the argument block, once (a batched launch keeps the block in LDS; pointers: common.h as_global)
-  const float* const noise_g = as_global(a.noise);
+  const float* const noise_g = SDE ? nullptr : as_global(a.noise);
   float* const actions_g = as_global(CHAIN ? c->slot_act : a.actions);
   double* const orig_obs_g = as_global(CHAIN ? c->slot_orig : a.orig_obs);
   double* const obs_g = as_global(CHAIN ? c->slot_obs : a.obs);
@@ -3598,8 +3614,27 @@ __device__ __forceinline__ void sample_episodes_body(const SampleArgs& a, const 
         if (row + 1 < row_end) noise_reg = noise_g[(row + 1) * AS + tid];      // next step's noise lands during this step
       }
       __syncthreads();
+      if constexpr (SDE) {
+        // the mean clipped to the box (the mode: what icrl_policy_forward_sde(deterministic = 1) returns), then, where the launch has a matrix, the
+        // action half of sde_head_wave on wave 0, which rewrites its own act_raw / act_clip (the latent lies behind a barrier of the forward; LDS
+        // accesses of one wave are ordered): the barrier below publishes them to the env step
+        policy_forward_block<OCT>(a.pl, R, sh, nullptr, 1, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+        if (w == 0 && E_s != nullptr && lane < A) {
+          const float mean = sh.act_raw[lane];
+          const int H2 = a.pl.H2;
+          double noise = 0.;
+#pragma unroll 8      // (one sequential chain in ascending h, as sde_head_wave's; unrolled, the operands of eight terms are fetched together)
+          for (int h = 0; h < H2; ++h) noise = fma((double)sh.g[0][h], (double)E_s[h * A + lane], noise);
+          const float act = (float)((double)mean + noise);
+          float clip = act;
+          if (has_box) clip = fminf(fmaxf(act, alow_s[lane]), ahigh_s[lane]);
+          sh.act_raw[lane] = act;
+          sh.act_clip[lane] = clip;
+        }
+      } else {
       policy_forward_block<OCT>(a.pl, R, sh, noise_g ? noise_s : nullptr, deterministic || noise_g == nullptr,
                                 has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+      }
       __syncthreads();
       const bool in_rows = CHAIN || row < row_end;      // (a stream whose speculative start row was too late can run off the arrays)
       const size_t orow = CHAIN ? slot0 + (size_t)ep_len : row;
@@ -3710,6 +3745,36 @@ __global__ void __launch_bounds__(192) sample_episodes_chain_kernel(const ChainA
 __global__ void __launch_bounds__(64) chain_prep_kernel(ChainArgs v, ChainArgs* dst, int clear_status) {
   if (threadIdx.x == 0) { *dst = v; if (clear_status) *v.status = 0u; }
   for (int i = threadIdx.x; i < v.n_streams; i += 64) v.next_start[i] = CHAIN_UNSET;
+}
+
+// ---- the samplers of a gSDE policy (icrl_sample_episodes_sde, icrl_sample_episodes_chain_sde): the bodies above with SDE = true.  SampleArgs
+// and ChainArgs keep their layout; the matrix pointer travels beside them — a second kernel argument here, per job behind the job's ChainArgs there.
+template <int OCT>
+__global__ void __launch_bounds__(192) sample_episodes_sde_kernel(SampleArgs a, const float* expl) {
+  sample_episodes_body<OCT, false, true>(a, nullptr, expl);
+}
+
+struct ChainSdeArgs {
+  ChainArgs c;
+  const float* expl;       // [MAX_H][A] float32, or NULL: this job takes the mode
+};
+
+template <int OCT>
+__global__ void __launch_bounds__(192) sample_episodes_chain_sde_kernel(const ChainSdeArgs* __restrict__ jobs) {
+  __shared__ ChainSdeArgs c;
+  {
+    const unsigned* src = reinterpret_cast<const unsigned*>(jobs + blockIdx.y);
+    unsigned* dst = reinterpret_cast<unsigned*>(&c);
+    for (unsigned i = threadIdx.x; i < sizeof(ChainSdeArgs) / 4; i += 192) dst[i] = src[i];
+  }
+  __syncthreads();
+  if ((int)blockIdx.x >= c.c.n_streams) return;
+  sample_episodes_body<OCT, true, true>(c.c.s, &c.c, c.expl);
+}
+
+__global__ void __launch_bounds__(64) chain_prep_sde_kernel(ChainSdeArgs v, ChainSdeArgs* dst, int clear_status) {
+  if (threadIdx.x == 0) { *dst = v; if (clear_status) *v.c.status = 0u; }
+  for (int i = threadIdx.x; i < v.c.n_streams; i += 64) v.c.next_start[i] = CHAIN_UNSET;
 }
 
 // =================================================================================================================
@@ -4344,6 +4409,132 @@ extern "C" int icrl_sample_episodes_chain(int n_jobs, const icrl_chain_job_t* jo
   }
   if (jobs[0].pol->obs_dim <= 32) hipLaunchKernelGGL(sample_episodes_chain_kernel<2>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
   else hipLaunchKernelGGL(sample_episodes_chain_kernel<8>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
+  return (int)hipGetLastError();
+}
+
+// ---- the samplers of a gSDE policy.  What both entry points check of one (env, normaliser, policy) triple, on the host, before any device call.
+static int sde_sample_check(const char* who, const char* where, const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol) {
+  if (env == nullptr || nm == nullptr || pol == nullptr) return fail("%s:%s NULL argument (env, nm and pol are required)", who, where);
+  if (pol->params == nullptr || pol->params_t == nullptr) return fail("%s:%s NULL argument (pol->params and pol->params_t are required)", who, where);
+  if (pol->discrete) return fail("%s:%s a discrete policy has no gSDE head", who, where);
+  if (pol->arch != nullptr || pol->h1 != MAX_H || pol->h2 != MAX_H)
+    return fail("%s:%s hidden widths (%d, %d)%s; the gSDE sampler serves the fast kind: two hidden layers per branch, stored %d x %d, no `arch`", who, where,
+                pol->h1, pol->h2, pol->arch != nullptr ? " with an `arch` descriptor" : "", MAX_H, MAX_H);
+  if (pol->obs_dim < 1 || pol->obs_dim > MAX_OBS || pol->act_dim < 1 || pol->act_dim > MAX_ACT)
+    return fail("%s:%s policy obs_dim %d (1..%d), act_dim %d (1..%d)", who, where, pol->obs_dim, MAX_OBS, pol->act_dim, MAX_ACT);
+  const int n_diag = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, 0).n, n_sde = make_sde_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2).n;
+  if (pol->n_params != n_sde)
+    return fail("%s:%s n_params %d, the gSDE (log_std [%d, act_dim]) layout of (%d, %d, %d, %d) has %d%s", who, where, pol->n_params, MAX_H, pol->obs_dim,
+                pol->act_dim, pol->h1, pol->h2, n_sde, pol->n_params == n_diag ? " (that is the diagonal layout's count: icrl_sample_episodes serves that policy)" : "");
+  if (env->obs_dim != pol->obs_dim || env->act_dim != pol->act_dim || env->n_envs < 1)
+    return fail("%s:%s env (%d streams, obs_dim %d, act_dim %d) vs policy (obs_dim %d, act_dim %d)", who, where, env->n_envs, env->obs_dim, env->act_dim,
+                pol->obs_dim, pol->act_dim);
+  if (nm->training) return fail("%s:%s the normaliser must be frozen (training = %d)", who, where, nm->training);
+  return 0;
+}
+
+// the network alone, as launch_policy_forward_sde reads it: the diagonal layout, its transposes behind the matrix's first 63 rows
+static icrl_policy_t sde_net_policy(const icrl_policy_t* pol) {
+  icrl_policy_t netpol = *pol;
+  netpol.params_t = pol->params_t + (MAX_H - 1) * pol->act_dim;
+  return netpol;
+}
+
+extern "C" int icrl_sample_episodes_sde(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const float* expl,
+                                        const float* action_low, const float* action_high, int episodes_per_stream, int rows_per_stream,
+                                        int do_reset, const int32_t* stream_row0, int total_rows, double* orig_obs, double* obs, float* actions,
+                                        double* ep_rewards, int32_t* ep_lengths, void* stream) {
+  const char* who = "icrl_sample_episodes_sde";
+  if (int e = sde_sample_check(who, "", env, nm, pol)) return e;
+  if (orig_obs == nullptr || obs == nullptr || actions == nullptr || ep_rewards == nullptr || ep_lengths == nullptr)
+    return fail("%s: NULL argument (orig_obs, obs, actions, ep_rewards and ep_lengths are required)", who);
+  if ((action_low == nullptr) != (action_high == nullptr)) return fail("%s: NULL argument (action_low and action_high: both or neither)", who);
+  if (episodes_per_stream < 1 || (long long)episodes_per_stream * env->max_steps > rows_per_stream)
+    return fail("%s: %d episodes x %d steps do not fit %d rows per stream", who, episodes_per_stream, env->max_steps, rows_per_stream);
+  if (stream_row0 != nullptr && total_rows < 1) return fail("%s: stream_row0 given with total_rows = %d", who, total_rows);
+  const icrl_policy_t netpol = sde_net_policy(pol);
+  SampleArgs a;
+  const int bad = make_sample_args(env, nm, &netpol, nullptr, action_low, action_high, episodes_per_stream, rows_per_stream, expl == nullptr, do_reset,
+                                   stream_row0, total_rows, orig_obs, obs, actions, ep_rewards, ep_lengths, a);
+  if (bad) return bad;
+  if (a.pl.O <= 32) hipLaunchKernelGGL(sample_episodes_sde_kernel<2>, dim3(env->n_envs), dim3(192), 0, (hipStream_t)stream, a, expl);
+  else hipLaunchKernelGGL(sample_episodes_sde_kernel<8>, dim3(env->n_envs), dim3(192), 0, (hipStream_t)stream, a, expl);
+  return (int)hipGetLastError();
+}
+
+extern "C" int icrl_sample_episodes_chain_sde(int n_jobs, const icrl_chain_job_t* jobs, const float* const* expl, const float* action_low,
+                                              const float* action_high, int do_reset, void* ws, long long ws_bytes, void* args_ws,
+                                              long long args_ws_bytes, void* stream) {
+  static_assert(sizeof(ChainSdeArgs) <= ICRL_BATCH_ARGS_BYTES, "ICRL_BATCH_ARGS_BYTES");
+  const char* who = "icrl_sample_episodes_chain_sde";
+  if (n_jobs < 1 || n_jobs > 65535 || jobs == nullptr) return fail("%s: n_jobs = %d (1..65535)", who, n_jobs);
+  if (expl == nullptr) return fail("%s: NULL argument (expl: one device pointer per job, NULL entries for the jobs that take the mode)", who);
+  if ((action_low == nullptr) != (action_high == nullptr)) return fail("%s: NULL argument (action_low and action_high: both or neither)", who);
+  for (int r = 0; r < n_jobs; ++r) {
+    const icrl_chain_job_t& j = jobs[r];
+    char where[24];
+    snprintf(where, sizeof(where), " job %d:", r);
+    if (int e = sde_sample_check(who, where, j.env, j.nm, j.pol)) return e;
+    if (j.orig_obs == nullptr || j.obs == nullptr || j.actions == nullptr || j.ep_rewards == nullptr || j.ep_lengths == nullptr)
+      return fail("%s: job %d: NULL argument (orig_obs, obs, actions, ep_rewards and ep_lengths are required)", who, r);
+    if (j.noise != nullptr) return fail("%s: job %d has a noise array; a gSDE policy's exploration is its matrix (expl[%d]), not a per-step draw", who, r, r);
+    if ((j.deterministic != 0) != (expl[r] == nullptr))
+      return fail("%s: job %d: deterministic = %d with expl[%d] %s (the mode has no matrix, a sampling job needs one)", who, r, j.deterministic, r,
+                  expl[r] == nullptr ? "NULL" : "set");
+  }
+  // what the chained kernel does not serve (the caller takes the multi-pass path): the reason starts with "refused", as icrl_sample_episodes_chain's
+  int max_streams = 0;
+  for (int r = 0; r < n_jobs; ++r) {
+    const icrl_chain_job_t& j = jobs[r];
+    if (j.env->reward_form >= 4) return fail("%s: refused: job %d steps a Point env (reward_form %d): the chained kernel is built without its step", who, r, j.env->reward_form);
+    if (j.episodes_per_stream != 1) return fail("%s: refused: job %d runs %d episodes per stream (1 only)", who, r, j.episodes_per_stream);
+    if ((j.pol->obs_dim <= 32) != (jobs[0].pol->obs_dim <= 32)) return fail("%s: refused: job %d and job 0 take different kernels (obs %d / %d)", who, r, j.pol->obs_dim, jobs[0].pol->obs_dim);
+    if (j.base_count == nullptr) return fail("%s: job %d: %d streams, base_count %p", who, r, j.env->n_envs, (const void*)j.base_count);
+    if ((long long)j.env->n_envs * j.env->max_steps >= (1ll << 31) - 1) return fail("%s: job %d: %d streams x %d steps do not fit a 31-bit row", who, r, j.env->n_envs, j.env->max_steps);
+    if (j.env->n_envs > max_streams) max_streams = j.env->n_envs;
+  }
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 0;
+  }
+  const int total = chain_total_streams(n_jobs, jobs);
+  if (total > n_cu) return fail("%s: refused: %d streams on %d compute units (every stream must be resident while its successors wait)", who, total, n_cu);
+  const long long need = (long long)icrl_sample_episodes_chain_ws_bytes(n_jobs, jobs);
+  if (ws == nullptr || ws_bytes < need) return fail("%s: ws holds %lld B, the jobs need %lld", who, ws_bytes, need);
+  if (args_ws == nullptr || args_ws_bytes < (long long)n_jobs * ICRL_BATCH_ARGS_BYTES)
+    return fail("%s: args_ws holds %lld B, %d jobs need %lld", who, args_ws_bytes, n_jobs, (long long)n_jobs * ICRL_BATCH_ARGS_BYTES);
+  hipStream_t s = (hipStream_t)stream;
+  ChainSdeArgs* d_args = (ChainSdeArgs*)args_ws;
+  char* const base = (char*)ws;
+  unsigned* words = (unsigned*)(base + 256);
+  char* slots = base + 256 + chain_align((size_t)total * sizeof(unsigned));
+  for (int r = 0; r < n_jobs; ++r) {
+    const icrl_chain_job_t& j = jobs[r];
+    const int rows = j.env->n_envs * j.env->max_steps;
+    const icrl_policy_t netpol = sde_net_policy(j.pol);
+    ChainSdeArgs v;
+    ChainArgs& c = v.c;
+    const int bad = make_sample_args(j.env, j.nm, &netpol, nullptr, action_low, action_high, 1, j.env->max_steps, j.deterministic, do_reset, nullptr, rows,
+                                     j.orig_obs, j.obs, j.actions, j.ep_rewards, j.ep_lengths, c.s);
+    if (bad) return bad;
+    v.expl = expl[r];
+    c.next_start = words; words += j.env->n_envs;
+    c.status = (unsigned*)base;
+    c.exec_steps = j.exec_steps;
+    c.base_count = j.base_count;
+    c.fixed_len = j.fixed_len != 0; c.n_streams = j.env->n_envs;
+    if (c.fixed_len) { c.slot_orig = j.orig_obs; c.slot_obs = j.obs; c.slot_act = j.actions; }
+    else {      // (the slot sizes of icrl_sample_episodes_chain_ws_bytes: a continuous policy, act_dim floats per row)
+      const size_t ob = chain_align((size_t)rows * j.env->obs_dim * sizeof(double));
+      c.slot_orig = (double*)slots; c.slot_obs = (double*)(slots + ob); c.slot_act = (float*)(slots + 2 * ob);
+      slots += 2 * ob + chain_align((size_t)rows * j.pol->act_dim * sizeof(float));
+    }
+    hipLaunchKernelGGL(chain_prep_sde_kernel, dim3(1), dim3(64), 0, s, v, d_args + r, (int)(r == 0));
+    if (const int e = (int)hipGetLastError()) return e;
+  }
+  if (jobs[0].pol->obs_dim <= 32) hipLaunchKernelGGL(sample_episodes_chain_sde_kernel<2>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
+  else hipLaunchKernelGGL(sample_episodes_chain_sde_kernel<8>, dim3(max_streams, n_jobs), dim3(192), 0, s, d_args);
   return (int)hipGetLastError();
 }
 

@@ -16,7 +16,8 @@ default, and with sde_fused_rollout=True (--sde_fused_rollout, ICRL_SDE_ROLLOUT_
 matrices of the whole rollout are drawn up front in the loop's order (policy.noise_schedule) and icrl_rollout_collect_sde computes what the loop
 computes, as ONE persistent launch or 2 launches per env step.  last_sde_rollout says which ran ("fused" | "loop"), last_sde_rollout_reason why
 the loop: the switch off, a callable cost_function, a partial rollout, no fused env chain, a DiscriminatorCost, episode_stats, a schedule above
-sde_fused_max_bytes.
+sde_fused_max_bytes.  Its sampling and evaluation episodes (utils.sample_from_agent / evaluate_policy / sample_and_evaluate) run as one launch of the
+sampler kernels with the gSDE head where that serves: last_sde_episodes ("fused" | "loop"), last_sde_episodes_reason.
 """
 import os
 import time
@@ -70,6 +71,10 @@ class PPOLagrangian:
         self.sde_fused_rollout = bool(sde_fused_rollout) or os.environ.get("ICRL_SDE_ROLLOUT_FUSED", "0").strip().lower() not in ("", "0", "false", "no", "off")
         self.sde_fused_max_bytes = 512 << 20      # largest schedule held on the device (ssf 1 at 256 AntWall envs x 2048 steps would be 1 GiB)
         self.last_sde_rollout = self.last_sde_rollout_reason = None
+        # sampling / evaluation episodes of a gSDE agent (utils.sample_from_agent / evaluate_policy / sample_and_evaluate): "fused" — the sampler launches
+        # with the gSDE head (icrl_sample_episodes_sde / _chain_sde), on by default where they serve — or "loop" (utils.SteppedEpisodeRun) with the
+        # reason (utils.sde_episodes_reason: ICRL_SDE_EPISODES_STEPPED=1, a host env)
+        self.last_sde_episodes = self.last_sde_episodes_reason = None
         if policy not in ("TwoCriticsMlpPolicy", ActorTwoCriticsPolicy):
             raise NotImplementedError(f"policy {policy!r}: only TwoCriticsMlpPolicy is on the ICRL hot path")
         self.env: VecEnv = env

@@ -4,6 +4,7 @@ ref: icrl/utils.py:256-303 (make_env / make_train_env / make_eval_env), :323-357
      :421-437 (compute_kl), :636-655 (get_net_arch); stable_baselines3/common/evaluation.py:10-67 (evaluate_policy);
      icrl/icrl.py:25-43 (load_expert_data); stable_baselines3/common/save_util.py:284-418 (agent zip format).
 """
+import ctypes
 import io
 import json
 import os
@@ -122,7 +123,12 @@ class EpisodeRun:
 
     Where the chained launch serves (chain_ok) the positions are settled INSIDE one launch instead — every stream learns its start
     from its predecessor while both run (icrl_sample_episodes_chain): prepare_chain(), launch_chain([runs]),
-    finish_chain(); always one pass, and the lengths are read once, with the results.  ICRL_EPISODE_CHAIN=0 keeps the passes."""
+    finish_chain(); always one pass, and the lengths are read once, with the results.  ICRL_EPISODE_CHAIN=0 keeps the passes.
+
+    A gSDE policy (use_sde) takes the same protocol through icrl_sample_episodes_sde / icrl_sample_episodes_chain_sde (DESIGN.md section
+    26): its exploration is ONE matrix for the whole run — sde_E0, which get_noise picks for one env and an episode loop never redraws —
+    or none (deterministic: the mode); `noise` is ignored and torch's generator is not touched, except for the reset_noise(1) the
+    per-step loop makes at its first step when the policy holds no matrices yet."""
 
     MAX_PASSES = 4
 
@@ -137,7 +143,18 @@ class EpisodeRun:
         self.A = 1 if pol.discrete else pol.act_dim
         self.fixed_len = not senv.wall_terminate
         self.rows = n_episodes * self.max_steps
-        if noise is None and not deterministic:
+        # gSDE (icrl_sample_episodes_sde / _chain_sde): the exploration is the policy's own matrix — get_noise picks E0 for one env, and an episode
+        # loop never redraws it — so `noise` has no meaning, as in SteppedEpisodeRun, and nothing is drawn from torch's generator: except the one
+        # reset_noise(1) that _forward_sde makes at the loop's first step when the policy holds no matrices yet
+        self.sde = bool(getattr(pol, "use_sde", False))
+        self.expl = None
+        if self.sde:
+            noise = None
+            if not deterministic:
+                if pol.sde_E is None:
+                    pol.reset_noise(1)
+                self.expl = pol.sde_E0      # (kept alive until the run is finished: set_noise installs a new tensor, it does not write this one)
+        elif noise is None and not deterministic:
             noise = torch.rand(self.rows, device=dev) if pol.discrete else torch.randn(self.rows, self.A, device=dev)
         if noise is not None:
             noise = torch.as_tensor(noise, device=dev).float().reshape(self.rows, -1).contiguous()
@@ -145,7 +162,7 @@ class EpisodeRun:
         self.base = None           # position of the env's random stream (read on first use: one small device->host copy)
         was_training = env.training
         env.training = False
-        self.nm, self.ps = env.struct(), pol.struct()
+        self.nm, self.ps = env.struct(), pol.struct(sde=True) if self.sde else pol.struct()
         env.training = was_training
         self.lo = self.hi = None
         if not pol.discrete:
@@ -188,6 +205,12 @@ class EpisodeRun:
         # streams > 0 of the parallel mode start from a reset as well: in the sequential loop their first state is the
         # auto-reset draw made at exactly this counter value
         b, out = _lib.byref, self.out
+        if self.sde:
+            _lib.check(_lib.lib().icrl_sample_episodes_sde(b(self.e), b(self.nm), b(self.ps), p(self.expl), p(self.lo), p(self.hi), self.eps_per,
+                                                           self.rows_per, 1, p(self.row0), self.rows, p(out["orig_obs"]), p(out["obs"]),
+                                                           p(out["actions"]), p(out["ep_rewards"]), p(out["ep_lengths"]), _lib.current_stream()),
+                       "icrl_sample_episodes_sde")
+            return
         _lib.check(_lib.lib().icrl_sample_episodes(b(self.e), b(self.nm), b(self.ps), p(self.noise), p(self.lo), p(self.hi), self.eps_per, self.rows_per,
                                                    int(self.deterministic), 1, p(self.row0), self.rows, p(out["orig_obs"]), p(out["obs"]),
                                                    p(out["actions"]), p(out["ep_rewards"]), p(out["ep_lengths"]), _lib.current_stream()),
@@ -273,7 +296,8 @@ def chain_enabled():
 
 def launch_chain(runs):
     """ONE launch for the prepared (prepare_chain) runs, which share the action box.  False: the entry point refused the case (its
-    reason starts with "refused"): nothing was launched and the caller takes the multi-pass path."""
+    reason starts with "refused"): nothing was launched and the caller takes the multi-pass path.  Runs of a gSDE policy (all of them or
+    none: they share the agent) go to icrl_sample_episodes_chain_sde, each with its matrix (None: the mode) beside its job."""
     r0 = runs[0]
     jobs = (ChainJobT * len(runs))(*[r.job for r in runs])
     lib = _lib.lib()
@@ -281,10 +305,16 @@ def launch_chain(runs):
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=r0.dev)
     args = torch.empty(len(runs) * _lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=r0.dev)
     try:
-        _lib.check(lib.icrl_sample_episodes_chain(len(runs), jobs, p(r0.lo), p(r0.hi), 1, p(ws), ws_bytes, p(args), args.numel(),
-                                                  _lib.current_stream()), "icrl_sample_episodes_chain")
+        if r0.sde:
+            assert all(r.sde for r in runs)
+            expl = (ctypes.c_void_p * len(runs))(*[p(r.expl) for r in runs])
+            _lib.check(lib.icrl_sample_episodes_chain_sde(len(runs), jobs, expl, p(r0.lo), p(r0.hi), 1, p(ws), ws_bytes, p(args), args.numel(),
+                                                          _lib.current_stream()), "icrl_sample_episodes_chain_sde")
+        else:
+            _lib.check(lib.icrl_sample_episodes_chain(len(runs), jobs, p(r0.lo), p(r0.hi), 1, p(ws), ws_bytes, p(args), args.numel(),
+                                                      _lib.current_stream()), "icrl_sample_episodes_chain")
     except ValueError as err:
-        if "icrl_sample_episodes_chain: refused:" in str(err):
+        if "icrl_sample_episodes_chain: refused:" in str(err) or "icrl_sample_episodes_chain_sde: refused:" in str(err):
             return False
         raise
     return True
@@ -452,10 +482,13 @@ class HostEpisodeRun:
 def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel, chain=False):
     """chain: settle early-ending episodes' positions inside ONE launch where it serves (what sample_from_agent and evaluate_policy
     ask for); the default keeps the pass-by-pass protocol of EpisodeRun.prepare / launch / finish, with run.passes counting launches."""
-    if getattr(agent.policy, "use_sde", False):     # gSDE: the per-step loop around icrl_policy_forward_sde (the sampler kernels hold the diagonal head)
-        if env.unwrapped.max_steps is None:
-            raise ValueError("sampling / evaluation with use_sde needs the env's episode limit (max_episode_steps)")
-        return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
+    if getattr(agent.policy, "use_sde", False):     # gSDE: the sampler kernels with its head where they serve, else the per-step loop
+        reason = sde_episodes_reason(agent, env)
+        _note_sde_episodes(agent, reason)
+        if reason is not None:                      # the loop around icrl_policy_forward_sde
+            if env.unwrapped.max_steps is None:
+                raise ValueError("sampling / evaluation with use_sde needs the env's episode limit (max_episode_steps)")
+            return SteppedEpisodeRun(agent, env, n_episodes, deterministic, noise)
     if isinstance(env.unwrapped, HostVecEnv):       # a host simulator: one launch per env step, or the reference's own loop
         if env.unwrapped.max_steps is None:
             raise ValueError("sampling / evaluation over a host env needs its episode limit: register it with max_episode_steps "
@@ -466,6 +499,24 @@ def _run_episodes(agent, env, n_episodes, deterministic, noise, parallel, chain=
     # (policies of the generic-shape path take the same launch: icrl_sample_episodes runs its persistent loop with the table-driven
     # forward, csrc/rollout.hip sample_episodes_generic_kernel; SteppedEpisodeRun is the same loop from the host, kept as the check)
     return _launch_and_finish(EpisodeRun(agent, env, n_episodes, deterministic, noise, parallel), chain)
+
+
+def sde_episodes_reason(agent, env):
+    """None where the sampler launches serve a gSDE agent's episodes on `env` (icrl_sample_episodes_sde / _chain_sde: a device env), else why
+    the per-step loop (SteppedEpisodeRun) runs: the switch ICRL_SDE_EPISODES_STEPPED=1, or a host env."""
+    if os.environ.get("ICRL_SDE_EPISODES_STEPPED", "0").strip().lower() not in ("", "0", "false", "no", "off"):
+        return "ICRL_SDE_EPISODES_STEPPED=1"
+    if not _is_device_env(env):
+        return "a host env (the gSDE sampler kernels step device envs only)"
+    return None
+
+
+def _note_sde_episodes(agent, reason):
+    """agent.last_sde_episodes ("fused" | "loop") and agent.last_sde_episodes_reason, like last_sde_rollout (a bare policy holder takes none)"""
+    try:
+        agent.last_sde_episodes, agent.last_sde_episodes_reason = ("fused" if reason is None else "loop"), reason
+    except AttributeError:
+        pass
 
 
 def _launch_and_finish(run, chain=True):
@@ -494,7 +545,12 @@ def sample_and_evaluate(agent, sampling_env, n_rollouts, eval_env, n_eval_episod
     deterministic, noise=eval_noise) as ONE launch of two jobs (icrl_sample_episodes_chain) where both serve, else one after the other;
     returns the pair of their results.  The caller vouches that nothing the evaluation reads (policy, normaliser statistics of eval_env)
     changes between the two phases it replaces.  Noise is drawn in the sequential order: sampling first, then evaluation."""
-    if episodes_fusable(sampling_env, eval_env) and not getattr(agent.policy, "use_sde", False):
+    fused = episodes_fusable(sampling_env, eval_env)
+    if fused and getattr(agent.policy, "use_sde", False):      # a gSDE agent: where the launch serves both envs (else the two calls below note the reason)
+        fused = sde_episodes_reason(agent, sampling_env) is None and sde_episodes_reason(agent, eval_env) is None
+        if fused:
+            _note_sde_episodes(agent, None)
+    if fused:
         s_run = EpisodeRun(agent, sampling_env, n_rollouts, False, sample_noise, parallel)
         e_run = EpisodeRun(agent, eval_env, n_eval_episodes, deterministic, eval_noise, False)
         if s_run.chain_ok() and e_run.chain_ok() and launch_chain([s_run.prepare_chain(), e_run.prepare_chain()]):

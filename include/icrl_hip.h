@@ -903,6 +903,34 @@ int icrl_rollout_collect_sde(const icrl_env_t* env, const icrl_norm_t* nm, const
                              const icrl_buffer_t* buf, const icrl_agent_t* ag, const float* expl, int n_draws, int sample_freq,
                              const float* action_low, const float* action_high, double reward_gamma, double reward_gae_lambda,
                              double cost_gamma, double cost_gae_lambda, int do_gae, void* stream);
+/* Sampling and evaluation episodes of a gSDE agent as ONE launch (csrc/rollout.hip): icrl_sample_episodes and
+ * icrl_sample_episodes_chain for a policy with the state-dependent-noise head.  In a 1-env episode loop the exploration matrices are never
+ * redrawn and get_noise picks E0, so ONE matrix serves every step of every episode: there is no schedule and no per-step noise row.  The
+ * kernels compute what the per-step loop computes around icrl_policy_forward_sde, bit for bit: the forward of the network, then on the
+ * float32 latent the float64 fma chain noise = sum_h latent[h] * expl[h][a] in ascending h, action = (float)(mean + noise), the clip, the env
+ * step, the row.  The samplers store no log-prob, so the variance half of the head is not evaluated.
+ *   pol   the gSDE descriptor (n_params = the diagonal layout's + 63 * act_dim), params_t as icrl_policy_prepare leaves it on the descriptor
+ *         of the network alone (see icrl_policy_forward_sde)
+ *   expl  icrl_sample_episodes_sde: [64][act_dim] float32 on the device, the stored shape of the policy's E0 (rows beyond the latent width
+ *         zero), or NULL: the mode (the mean clipped to the box, what icrl_policy_forward_sde(deterministic = 1) returns).
+ *         icrl_sample_episodes_chain_sde: a HOST array of n_jobs such device pointers; a NULL entry means that job takes the mode.
+ *         The matrices must stay alive until the launch has run.
+ *   Everything else is as for icrl_sample_episodes / icrl_sample_episodes_chain (jobs: icrl_chain_job_t, unchanged, its `noise` NULL and its
+ *   `deterministic` set exactly where expl[j] is NULL; ws sized by icrl_sample_episodes_chain_ws_bytes, args_ws n_jobs * ICRL_BATCH_ARGS_BYTES).
+ * Refused with hipErrorInvalidValue and the reason, on the host, before any device call: a NULL required pointer, a diagonal-layout n_params
+ * (icrl_sample_episodes serves that policy), a discrete policy, an `arch` descriptor or hidden widths other than the stored 64 x 64, obs_dim
+ * above 128 or act_dim above 16, env against policy dimensions, a training normaliser, rows that do not fit, stream_row0 without total_rows,
+ * a job with a noise array, a job whose `deterministic` disagrees with expl[j] == NULL.  The chained entry point refuses what
+ * icrl_sample_episodes_chain refuses, with a reason starting "icrl_sample_episodes_chain_sde: refused:" (callers take the multi-pass path):
+ * more streams than compute units, a Point env, episodes_per_stream != 1, observation widths on both sides of 32 in one launch.
+ * Not served in this form: a batch (seed batches), generic shapes, host envs, a log-prob output. */
+int icrl_sample_episodes_sde(const icrl_env_t* env, const icrl_norm_t* nm, const icrl_policy_t* pol, const float* expl,
+                             const float* action_low, const float* action_high, int episodes_per_stream, int rows_per_stream, int do_reset,
+                             const int32_t* stream_row0, int total_rows, double* orig_obs, double* obs, float* actions, double* ep_rewards,
+                             int32_t* ep_lengths, void* stream);
+int icrl_sample_episodes_chain_sde(int n_jobs, const icrl_chain_job_t* jobs, const float* const* expl, const float* action_low,
+                                   const float* action_high, int do_reset, void* ws, long long ws_bytes, void* args_ws, long long args_ws_bytes,
+                                   void* stream);
 size_t icrl_policy_sde_fwd_bwd_ws_bytes(const icrl_policy_t* pol, int N);
 int icrl_policy_sde_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
                             const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,

@@ -15,6 +15,13 @@
             difference of the two is the cost of the head and of the schedule; the yardstick is the gSDE loop in the same process and run order.
             Both at --envs envs x --steps steps and (keys ending in _64x2048) at 64 envs x 2048 steps, sde_sample_freq 8.
 
+  --episodes   (a mode of its own; nothing else is timed) microseconds per executed env step of utils.sample_from_agent on HCWithPos-v0 and of
+            utils.evaluate_policy(deterministic=False) on HCWithPosTest-v0, 10 episodes of at most 1000 steps each, in three forms: the gSDE per-step
+            loop (utils.SteppedEpisodeRun, ICRL_SDE_EPISODES_STEPPED=1: the yardstick), the gSDE launch (icrl_sample_episodes_chain_sde), and the
+            diagonal head's launch (icrl_sample_episodes_chain) on an agent of the same shape.  --runs interleaved runs per form in one process, the
+            first call of each form outside the timed region; the executed steps are the sum of the returned episode lengths.  With --out the
+            new keys (episodes_*) are merged into the file.
+
 The loop figures say nothing about the fused launches the diagonal head normally takes (bench.py measures those).  Per run: --steps steps after
 --warmup, one synchronisation at each end, host clock around it; --runs runs per form, interleaved.  Needs the GPU.
 
@@ -173,6 +180,86 @@ class RolloutLoop:
         return 1e6 * (time.perf_counter() - t0) / self.steps
 
 
+class EpisodeForms:
+    """sample_from_agent / evaluate_policy of a gSDE agent through the loop and through the launch, and of a diagonal agent of the same shape"""
+    N_EP = 10
+
+    def __init__(self):
+        from icrl_amd import cpg, utils
+        self.utils = utils
+        self.models = {}
+        for k, extra in (("gsde", ["-us"]), ("diagonal", [])):
+            argv = ["cpg", "-tei", "HCWithPos-v0", "-eei", "HCWithPosTest-v0", "-nt", "4", "--n_steps", "32", "-s", "0", "-v", "0"] + extra
+            cfg = vars(cpg.build_parser().parse_args(argv))
+            cfg.update(rank=0, world_size=1)
+            self.models[k] = cpg.setup(types.SimpleNamespace(**cfg), log=None)[0]
+        self.models["gsde"].policy.reset_noise(1)
+        self.envs = dict(sample=utils.make_eval_env("HCWithPos-v0", False, seed=0), eval=utils.make_eval_env("HCWithPosTest-v0", False, seed=0))
+        self.forms = dict(gsde_loop=("gsde", "1"), gsde_launch=("gsde", None), diagonal_launch=("diagonal", None))
+
+    def run(self, form, phase):
+        """(microseconds per executed env step, executed steps, milliseconds)"""
+        which, stepped = self.forms[form]
+        model, env, utils = self.models[which], self.envs[phase], self.utils
+        old = os.environ.pop("ICRL_SDE_EPISODES_STEPPED", None)
+        if stepped is not None:
+            os.environ["ICRL_SDE_EPISODES_STEPPED"] = stepped
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if phase == "sample":
+                lengths = utils.sample_from_agent(model, env, self.N_EP)[4]
+            else:
+                lengths = utils.evaluate_policy(model, env, self.N_EP, deterministic=False, return_episode_rewards=True)[1]
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+        finally:
+            os.environ.pop("ICRL_SDE_EPISODES_STEPPED", None)
+            if old is not None:
+                os.environ["ICRL_SDE_EPISODES_STEPPED"] = old
+        if which == "gsde":
+            assert model.last_sde_episodes == ("loop" if stepped else "fused"), (form, model.last_sde_episodes, model.last_sde_episodes_reason)
+        steps = int(np.sum(lengths))
+        return 1e6 * dt / steps, steps, 1e3 * dt
+
+
+def episodes_main(a):
+    ep = EpisodeForms()
+    out = dict(episodes_protocol="host clock between two synchronisations around one sample_from_agent(HCWithPos-v0, 10 episodes) / one "
+                                 "evaluate_policy(HCWithPosTest-v0, 10 episodes, deterministic=False) call; microseconds per executed env step = time "
+                                 "/ sum of the returned episode lengths; --runs runs per form, interleaved (loop, gSDE launch, diagonal launch), one "
+                                 "untimed call of each form first",
+               episodes_runs=a.runs, episodes_device=torch.cuda.get_device_name(0))
+    for phase in ("sample", "eval"):
+        for form in ep.forms:
+            ep.run(form, phase)      # outside the timed region
+        us = {form: [] for form in ep.forms}
+        ms = {form: [] for form in ep.forms}
+        steps = {}
+        for _ in range(a.runs):
+            for form in ep.forms:
+                u, n, m = ep.run(form, phase)
+                us[form].append(round(u, 2)); ms[form].append(round(m, 2)); steps[form] = n
+        for form in ep.forms:
+            out[f"episodes_{phase}_us_per_step_{form}"] = us[form]
+            out[f"episodes_{phase}_ms_{form}"] = ms[form]
+            out[f"episodes_{phase}_steps_{form}"] = steps[form]
+            print(f"episodes {phase} {form}: {us[form]} us per step, {ms[form]} ms, {steps[form]} steps", flush=True)
+        out[f"episodes_{phase}_every_launch_run_below_the_loops_fastest"] = bool(max(us["gsde_launch"]) < min(us["gsde_loop"]))
+        out[f"episodes_{phase}_gsde_launch_speedup_worst_case"] = round(min(ms["gsde_loop"]) / max(ms["gsde_launch"]), 1)
+    out["episodes_not_measured"] = "a whole icrl -us -sfr run at the reference's step counts; other envs and shapes; host envs (not served)"
+    print(json.dumps(out))
+    if a.out:
+        merged = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                merged = json.load(f)
+        merged.update(out)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(merged, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=512)
@@ -180,10 +267,13 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--envs", type=int, default=4)
     ap.add_argument("--wide", action="store_true", help="also time the update forms at (obs 113, act 8, batch 128): keys ending in _113_8_128")
+    ap.add_argument("--episodes", action="store_true", help="time sampling / evaluation episodes alone (loop, gSDE launch, diagonal launch); with --out the keys are merged into the file")
     ap.add_argument("--out", default=None, help="write the result as JSON to this file as well")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sde_bench needs the GPU: a time measured elsewhere says nothing about it")
+    if a.episodes:
+        return episodes_main(a)
     result = dict(status="measured", device=torch.cuda.get_device_name(0), steps=a.steps, warmup=a.warmup, runs=a.runs, envs=a.envs,
                   protocol="host clock between two synchronisations around --steps steps after --warmup; --runs runs per form, interleaved; "
                            "update: obs 18, act 6, batch 64, fine-grained loop; update_fused: the same buffer and shape, one persistent launch of "
