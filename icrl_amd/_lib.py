@@ -31,6 +31,7 @@ SIGNATURES = {
     "icrl_sample_episodes": [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 6,
     "icrl_cost_mlp_forward": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "icrl_cost_fn_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "icrl_cost_region_rows": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "icrl_disc_reward": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
     "icrl_synth_env_reset": [c_void_p, c_void_p],
     "icrl_synth_env_step": [c_void_p] * 5,
@@ -155,6 +156,7 @@ WS_NONE, WS_XCH, WS_PLANE = 0, 1, 2
 PICK_SMALL, PICK_ANALYTIC, PICK_MON, PICK_GRAN, PICK_CN128, PICK_MINW_SHIFT = 1, 2, 4, 8, 16, 8
 PICK_DISC = 32
 PICK_SDE = 64      # ICRL_PICK_SDE
+PICK_REGION = 128  # ICRL_PICK_REGION
 UPDATE_GENERIC_PERSISTENT, UPDATE_GENERIC_LAUNCHES = 8, 9
 GAE_ROUTE = {"none": 0, "sequential": 1, "split": 2, "regsplit": 3, "batch-split": 4, "batch-regsplit": 5, "batch-singles": 6}
 

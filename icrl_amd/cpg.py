@@ -20,7 +20,7 @@ import torch
 from . import callbacks, distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import AnalyticCost, get_true_cost_function, null_cost, true_cost_for
+from .true_constraint_net import AnalyticCost, check_cost_spec_flags, cost_for, get_true_cost_function, null_cost, true_cost_for
 from . import envs, spaces
 
 
@@ -57,6 +57,8 @@ def setup(config, log=print):
     if use_curiosity or use_lambda:      # ref: icrl/cpg.py:176-184; refused before anything is launched where the callbacks are not served
         from . import exploration
         exploration.refuse_batched(config)
+    cost_spec = getattr(config, "cost_spec", None)      # --cost_spec: a RegionCost in the place of the id's ground-truth cost
+    check_cost_spec_flags(config)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
     envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
     train_env = utils.make_train_env(env_id=config.train_env_id, save_dir=config.save_dir, use_cost_wrapper=True,
@@ -75,7 +77,9 @@ def setup(config, log=print):
         flag = "--use_curiosity_driven_exploration (-ucde)" if use_curiosity else "--use_lambda_shaping (-uls)"
         raise ValueError(f"{flag}: a Box action space is needed; {config.train_env_id} has a discrete one (the buffer stores a discrete action as "
                          "one index column, which the reference reshapes to acs_dim columns: not a meaningful network input)")
-    if config.use_null_cost:
+    if cost_spec is not None:      # (train and eval env cost, and AdjustedRewardCallback below)
+        cost_function = cost_for(config.eval_env_id, cost_spec, train_env)
+    elif config.use_null_cost:
         cost_function = AnalyticCost.null()
     elif config.cn_path is None:
         cost_function = true_cost_for(config.eval_env_id)
@@ -99,7 +103,8 @@ def setup(config, log=print):
         cost_function = constraint_net.cost_function
     # a ConstraintNet cost, an AnalyticCost (the ground-truth cost, the null cost) and the --load_gail DiscriminatorCost run inside the
     # fused rollout launch (device envs: icrl_rollout_collect_ex, host envs: icrl_host_step); ICRL_ANALYTIC_COST_STEPPED=1 /
-    # ICRL_DISC_COST_STEPPED=1 send the same cost object through the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped)
+    # ICRL_DISC_COST_STEPPED=1 send the same cost object through the per-step rollout loop (PPOLagrangian._collect_rollouts_stepped);
+    # a --cost_spec RegionCost runs inside the same launches (icrl_cost_region_t; ICRL_REGION_COST_STEPPED=1 is its per-step check)
     train_env.set_cost_function(cost_function)
     eval_env.set_cost_function(cost_function)
     model = PPOLagrangian(
@@ -129,7 +134,7 @@ def setup(config, log=print):
                                   # opt-in (a seed batch sets it): evaluation noise from the run's own streams, not the process-wide generator
                                   noise_streams=getattr(config, "streams", None) if getattr(config, "eval_noise_from_streams", False) else None,
                                   callback_on_new_best=callbacks.SaveEnvStatsCallback(train_env, config.save_dir if rank == 0 else None)),
-           callbacks.AdjustedRewardCallback(true_cost_for(config.eval_env_id))]
+           callbacks.AdjustedRewardCallback(cost_function if cost_spec is not None else true_cost_for(config.eval_env_id))]
     if use_curiosity:      # ref: icrl/cpg.py:176-184 — after AdjustedRewardCallback, exploration before lambda
         cbs.append(exploration.ExplorationRewardCallback(obs_dim, acs_dim, device=dev))
     if use_lambda:
@@ -191,6 +196,9 @@ def build_parser():
     a("--use_null_cost", "-unc", action="store_true"); a("--cn_path", "-cp", type=str, default=None)
     a("--cn_obs_select_dim", "-cosd", type=int, default=None, nargs="+"); a("--cn_acs_select_dim", "-casd", type=int, default=None, nargs="+")
     a("--cn_device", "-cd", type=str, default=None); a("--load_gail", "-lg", action="store_true")
+    # a user-defined ground-truth constraint (true_constraint_net.RegionCost: a JSON file or string) in the place of the env id's; absent
+    # from the namespace unless given, like -sfr
+    a("--cost_spec", "-csp", type=str, default=argparse.SUPPRESS)
     a("--save_dir", type=str, default=None); a("--eval_every_rollouts", type=int, default=0)
     a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")

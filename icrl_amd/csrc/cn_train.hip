@@ -647,6 +647,7 @@ static int cn_dims_checked(const icrl_costnet_t* cn, const char* who, CnDims* d,
   int H[CN_MAX_LAYERS];
   if (as_cost_fn(cn)) return refuse_cost_fn(who);      // (an icrl_cost_fn_t has no parameters: nothing to train or to prepare inputs for)
   if (as_cost_disc(cn)) return refuse_cost_disc(who);  // (an icrl_cost_disc_t is a reading of a net for the rollouts: the inner net is what trains)
+  if (as_cost_region(cn)) return refuse_cost_region(who);
   if (!cn_widths(*cn, H) || cn->in_dim < 1) return fail("%s: %d hidden layers (0..%d), in_dim %d", who, cn->n_hidden, CN_MAX_LAYERS, cn->in_dim);
   for (int l = 0; l < cn->n_hidden; ++l)
     if (H[l] < 1) return fail("%s: hidden layer %d has %d units", who, l, H[l]);
@@ -740,6 +741,7 @@ extern "C" size_t icrl_cn_train_work_floats(int n_params, int Nn, int Ne, int n_
 extern "C" int icrl_cn_prepare(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* out, void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_prepare");
   if (as_cost_disc(cn)) return refuse_cost_disc("icrl_cn_prepare");
+  if (as_cost_region(cn)) return refuse_cost_region("icrl_cn_prepare");
   if (N <= 0) return fail("icrl_cn_prepare: N = %d rows", N);
   hipLaunchKernelGGL(cn_prepare_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, *cn, obs, acs, N, out);
   return (int)hipGetLastError();
@@ -752,6 +754,7 @@ static int make_cn_train_args(const icrl_costnet_t* cn, float* exp_avg, float* e
                               const char* who = "icrl_cn_train") {
   if (as_cost_fn(cn)) return refuse_cost_fn(who);
   if (as_cost_disc(cn)) return refuse_cost_disc(who);
+  if (as_cost_region(cn)) return refuse_cost_region(who);
   if (Nn <= 0 || Ne <= 0 || n_ep <= 0 || hp->iterations < 0)
     return fail("%s: needs nominal rows (%d), expert rows (%d), episodes (%d) > 0 and iterations (%d) >= 0", who, Nn, Ne, n_ep, hp->iterations);
   size_t lds;
@@ -851,6 +854,7 @@ extern "C" int icrl_cn_train_minibatch(const icrl_costnet_t* cn, float* exp_avg,
                                        float* metrics, void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_cn_train_minibatch");
   if (as_cost_disc(cn)) return refuse_cost_disc("icrl_cn_train_minibatch");
+  if (as_cost_region(cn)) return refuse_cost_region("icrl_cn_train_minibatch");
   if (Nn <= 0 || Ne <= 0 || n_ep <= 0 || hp->iterations < 0 || batch_size <= 0 || perms == nullptr)
     return fail("icrl_cn_train_minibatch: needs nominal rows (%d), expert rows (%d), episodes (%d), batch_size (%d) > 0, iterations (%d) >= 0 "
                 "and a permutation table", Nn, Ne, n_ep, batch_size, hp->iterations);

@@ -418,6 +418,7 @@ int mg_costnet_check(const char* who, const icrl_costnet_t* cn, int N) {
   if (cn == nullptr) return fail("%s: NULL constraint-net descriptor", who);
   if (as_cost_fn(cn)) return refuse_cost_fn(who);
   if (as_cost_disc(cn)) return refuse_cost_disc(who);
+  if (as_cost_region(cn)) return refuse_cost_region(who);
   if (cn->n_hidden < 1 || cn->n_hidden > 2) return fail("%s: %d hidden layers are not served (1..2 of up to %d units)", who, cn->n_hidden, MAX_H);
   if (cn->h1 < 1 || cn->h1 > MAX_H || (cn->n_hidden == 2 && (cn->h2 < 1 || cn->h2 > MAX_H)))
     return fail("%s: hidden layers (%d, %d) are not served (1..2 of up to %d units)", who, cn->h1, cn->n_hidden == 2 ? cn->h2 : 0, MAX_H);

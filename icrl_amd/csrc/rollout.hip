@@ -582,6 +582,7 @@ struct ActStepArgs {
   union {                 // has_cn: the constraint net, or (the CIT == 0 instantiations) the analytic cost in the same bytes
     icrl_costnet_t cn;
     icrl_cost_fn_t cf;
+    icrl_cost_region_t cr;      // the REGION forms: count, combine rule and the device pointer of the clause table
   };
   icrl_buffer_t buf;
   icrl_agent_t ag;
@@ -601,11 +602,25 @@ struct ActStepArgs {
 // Here, in rollout_wide_kernel and in host_step_kernel the kernel IS the body (moving it into a by-reference body function changed the
 // register allocation of all 18 shipped instantiations), so the D form is the same kernel instantiated with CIT | CIT_DISC.
 constexpr int CIT_DISC = 0x100;
+// REGION: a region cost (icrl_cost_region_t, cost_fn.h) in the cost wave of the CIT == 0 image, a compile-time form in the same two
+// manners: CIT_REGION on the kernels that are their bodies, wrappers of their own names around a trailing `bool REGION` elsewhere.  The
+// clause table is copied from the descriptor's device pointer into LDS once, before the step loop (REGION_TABLE: the array exists in
+// the REGION instantiations alone), and the cost wave calls cost_region_wave where it called cost_fn_wave.
+constexpr int CIT_REGION = 0x200;
+#define REGION_TABLE(a_, tid_, threads_)                                                  \
+  icrl_region_clause_t* rtab = nullptr;                                                   \
+  if constexpr (REGION) {                                                                 \
+    __shared__ icrl_region_clause_t rtab_s[ICRL_REGION_MAX_CLAUSES];                      \
+    rtab = rtab_s;                                                                        \
+    region_table_load(rtab_s, (a_).cr, (tid_), (threads_));                               \
+  }
 template <int OCT, int CITF>
 __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
   constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
   constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
+  constexpr bool REGION = (CITF & CIT_REGION) != 0;    // a region cost (icrl_cost_region_t) on the CIT == 0 image
   __shared__ ActShared sh;
+  REGION_TABLE(a, (int)threadIdx.x, 256)      // (the barrier behind the observation load below publishes it)
   WaveRegs<OCT, CIT> R;                // one image: policy weights in waves 0..2, cost-net weights in wave 3
   WaveRegs<OCT, CIT>& C = R;
   load_pol_regs<OCT>(a.pl, a.PT, R);   // every weight load of the step is in flight before anything waits
@@ -640,7 +655,8 @@ __global__ void __launch_bounds__(256) act_step_kernel(ActStepArgs a, int t) {
     }
   } else if (w == 3) {
     float cost = 0.f;
-    if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+    if constexpr (REGION) cost = cost_region_wave(rtab, a.cr.n_clauses, a.cr.combine, sh.s_old, sh.act_clip, O);
+    else if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
     else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
     if (lane == 0) { a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost; }
   } else if (w == 2) {
@@ -1345,7 +1361,7 @@ static inline size_t persist_dyn_lds(int N, int O, int A) { return ((size_t)O * 
 // not change during a rollout: one exp per entry and launch, the per-call kernel's own bits — and the env's current exploration matrix
 // [MAX_H][A] float32, refilled from registers only where the draw index changes; the next draw's matrix is fetched one step ahead, as the
 // noise row is.
-template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true, bool DISC = false, bool SDE = false>
+template <int OCT, int CIT, bool GRAN, bool PROF = false, bool MON = false, bool POINT = true, bool DISC = false, bool SDE = false, bool REGION = false>
 __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, const SdeArgs& sd = SdeArgs()) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ ActShared sh;
@@ -1358,6 +1374,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
   __shared__ int done_s[128];
   __shared__ int last_done_s;
   const ActStepArgs& a = p.act;
+  REGION_TABLE(a, (int)threadIdx.x, 256)      // (published by the step loop's first barrier)
   // private copies of the structs whose pointers the step loop goes through, every pointer marked as a global-memory pointer
   // (common.h: as_global — in a batched launch the block comes from LDS / memory and the accesses would be flat_* otherwise)
   icrl_norm_t nm = p.nm; globalize(nm);
@@ -1481,7 +1498,8 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
       }
     } else if (w == 3) {
       float cost = 0.f;
-      if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+      if constexpr (REGION) cost = cost_region_wave(rtab, a.cr.n_clauses, a.cr.combine, sh.s_old, sh.act_clip, O);
+      else if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
       else if (a.has_cn) cost = cost_forward_wave<CIT>(cnet, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
       if (lane == 0) {
         if (GRAN) rstore(((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
@@ -1940,6 +1958,11 @@ template <int OCT, int CIT, bool GRAN>
 __global__ void __launch_bounds__(256) rollout_persistent_sde_kernel(PersistArgs p, SdeArgs sd) {
   rollout_persistent_body<OCT, CIT, GRAN, false, false, false, false, true>(p, sd);
 }
+// the region-cost form (REGION, see act_step_kernel) on the CIT == 0 image: single runs, no phase timers
+template <int OCT, bool GRAN, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_persistent_region_kernel(PersistArgs p) {
+  rollout_persistent_body<OCT, 0, GRAN, false, MON, false, false, false, true>(p);
+}
 static inline size_t persist_sde_dyn_lds(int N, int O, int A) { return persist_dyn_lds(N, O, A) + (size_t)MAX_H * (size_t)A * (sizeof(double) + sizeof(float)); }
 
 // several independent runs in ONE launch: grid (N, n_runs), run = blockIdx.y, argument blocks in device memory.  Workgroups are
@@ -2003,6 +2026,8 @@ template <int OCT, int CITF, bool PROF = false, bool MON = false>      // PROF: 
 __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
   constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
   constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
+  constexpr bool REGION = (CITF & CIT_REGION) != 0;    // a region cost (icrl_cost_region_t) on the CIT == 0 image
+  REGION_TABLE(p.act, (int)threadIdx.x, 256)           // (published by the barrier in front of the step loop)
   __shared__ ActShared sh[WIDE_E];
   __shared__ double Bl[MAX_OBS * MAX_ACT];
   __shared__ double colbuf[WIDE_MAX_N + 64], dev2buf[WIDE_MAX_N], retbuf[WIDE_MAX_N];
@@ -2101,7 +2126,8 @@ __global__ void __launch_bounds__(256) rollout_wide_kernel(WideArgs p) {
         }
       } else if (w == 3) {
         float cost = 0.f;
-        if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh[e].s_old, sh[e].act_clip);
+        if constexpr (REGION) cost = cost_region_wave(rtab, a.cr.n_clauses, a.cr.combine, sh[e].s_old, sh[e].act_clip, O);
+        else if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh[e].s_old, sh[e].act_clip);
         else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh[e].s_old, sh[e].act_clip, sh[e].cx, sh[e].ch, DISC ? 1 : 0);
         if (lane == 0) {
           rstore(xrs, xrec + 16 * (O + 1), rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
@@ -2491,11 +2517,12 @@ __device__ __noinline__ void env_step_wave3(int O, int A, int flags, int max_ste
   }
 }
 
-template <int OCT, int CIT, int E, bool MON, bool DISC = false>
+template <int OCT, int CIT, int E, bool MON, bool DISC = false, bool REGION = false>
 __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int g_arg) {
   extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
   __shared__ MultiShared<E, CIT> sh;
   const ActStepArgs& a = p.act;
+  REGION_TABLE(a, (int)threadIdx.x, 256)      // (published by the barriers in front of the step loop)
   // private copies of the structs whose pointers the step loop goes through, every pointer marked as a global-memory pointer
   // (common.h: as_global — in a batched launch the block comes from memory and the accesses would be flat_* otherwise)
   icrl_norm_t nm = p.nm; globalize(nm);
@@ -2784,7 +2811,9 @@ __device__ __forceinline__ void rollout_multi_body(const WideArgs& p, const int 
       // analytic cost (wave 3): one lane per env does the compare on the env's own rows
       if (lane < Eg) {
         const int n = g + lane * G;
-        const float cost = cost_fn_wave(cf, sh.s_old[lane], sh.act_clip[lane]);
+        float cost;
+        if constexpr (REGION) cost = cost_region_row(rtab, a.cr.n_clauses, a.cr.combine, sh.s_old[lane], sh.act_clip[lane], O);
+        else cost = cost_fn_wave(cf, sh.s_old[lane], sh.act_clip[lane]);
         rstore(xrs, ((par * N + n) * R16 + O + 1) * 16, rec_u4{gtag, __float_as_uint(cost), 0u, gtag});
         buf.orig_costs[(size_t)t * N + n] = cost;
         sh.cost[lane] = cost;
@@ -3113,6 +3142,15 @@ template <int OCT, int CIT, int E, bool MON = false>
 __global__ void __launch_bounds__(256) rollout_multi_net_as_discriminator_kernel(WideArgs p, int packed) {
   if (packed && (blockIdx.x & 7) != 0) return;
   rollout_multi_body<OCT, CIT, E, MON, true>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+}
+
+// the region-cost form (REGION) of rollout_multi_analytic_kernel, single runs: one lane per env walks the clause table.  It calls the
+// env_step_wave3<E, 0> instantiations, so its name sorts behind rollout_multi_net_as_discriminator_kernel's (mangled: by length first)
+// for the reason given at rollout_multi_analytic_kernel
+template <int OCT, int E, bool MON = false>
+__global__ void __launch_bounds__(256) rollout_multi_with_a_region_cost_wave_kernel(WideArgs p, int packed) {
+  if (packed && (blockIdx.x & 7) != 0) return;
+  rollout_multi_body<OCT, 0, E, MON, false, true>(p, packed ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
 }
 
 // VecNormalizeWithCost.reset (vec_normalize.py:148-157, 270-278)
@@ -3448,6 +3486,16 @@ __global__ void __launch_bounds__(256) cost_fn_rows_kernel(icrl_cost_fn_t f, con
   const int AS = f.kind == ICRL_COST_ACTION_EQUALS ? 1 : f.acs_dim;      // (the class index when discrete)
   for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
     cost[n] = cost_fn_wave(f, obs + (size_t)n * f.obs_dim, acs + (size_t)n * AS);
+}
+
+// a region cost on N rows of the caller's arrays (icrl_cost_region_rows): the clause table into LDS, then one row per thread, grid-stride
+__global__ void __launch_bounds__(256) cost_region_rows_kernel(icrl_cost_region_t r, const double* __restrict__ obs, const float* __restrict__ acs, int N,
+                                                               float* __restrict__ cost) {
+  __shared__ icrl_region_clause_t tab[ICRL_REGION_MAX_CLAUSES];
+  region_table_load(tab, r, (int)threadIdx.x, 256);
+  __syncthreads();
+  for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256)
+    cost[n] = cost_region_row(tab, r.n_clauses, r.combine, obs + (size_t)n * r.obs_dim, acs + (size_t)n * r.acs_dim, r.obs_dim);
 }
 
 __global__ void __launch_bounds__(64) env_step_kernel(icrl_env_t e, const float* actions, double* raw_rew, uint8_t* dones) {
@@ -3805,6 +3853,8 @@ template <int OCT, int CITF>      // CITF: CIT [| CIT_DISC] (act_step_kernel)
 __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
   constexpr int CIT = CITF & 0xff;                     // the cost-net image proper
   constexpr bool DISC = (CITF & CIT_DISC) != 0;        // the constraint net read as D = zeta (icrl_cost_disc_t)
+  constexpr bool REGION = (CITF & CIT_REGION) != 0;    // a region cost (icrl_cost_region_t) on the CIT == 0 image
+  REGION_TABLE(h.act, (int)threadIdx.x, 256)           // (published by the barriers in front of the act phase)
   __shared__ ActShared sh;
   __shared__ double vec[2][128], dev2[2][128], ret_s[128], cret_s[128], rawr_s[128];
   __shared__ float rawc_s[128];
@@ -3956,7 +4006,8 @@ __global__ void __launch_bounds__(256) host_step_kernel(HostStepArgs h, int k) {
     if (lane < AH) h.hs.act_host[(size_t)n * AH + lane] = sh.act_clip[lane];
   } else if (w == 3) {
     float cost = 0.f;
-    if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
+    if constexpr (REGION) cost = cost_region_wave(rtab, a.cr.n_clauses, a.cr.combine, sh.s_old, sh.act_clip, O);
+    else if constexpr (CIT == 0) cost = cost_fn_wave(cf, sh.s_old, sh.act_clip);
     else if (a.has_cn) cost = cost_forward_wave<CIT>(a.cn, a.cl, C, sh.s_old, sh.act_clip, sh.cx, sh.ch, DISC ? 1 : 0);
     if (lane == 0) {
       a.ag.raw_cost[n] = cost; a.buf.orig_costs[tn] = cost;
@@ -4086,6 +4137,7 @@ extern "C" int icrl_policy_prepare(const icrl_policy_t* p, void* stream) {
 extern "C" int icrl_costnet_prepare(const icrl_costnet_t* cn, void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_costnet_prepare");
   if (as_cost_disc(cn)) return refuse_cost_disc("icrl_costnet_prepare");      // (prepare the inner net)
+  if (as_cost_region(cn)) return refuse_cost_region("icrl_costnet_prepare");
   if (cn->n_hidden > 2 || cn->n_hidden == 0) return 0;      // served 64 rows per workgroup from `params` (cn_train.hip): no transposed copy
   if (!costnet_is_wide(cn) && !cn_ok(cn)) return bad_cn("icrl_costnet_prepare", cn);
   CnLayout L = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2);
@@ -4538,6 +4590,22 @@ extern "C" int icrl_sample_episodes_chain_sde(int n_jobs, const icrl_chain_job_t
   return (int)hipGetLastError();
 }
 
+extern "C" int icrl_cost_region_rows(const icrl_cost_region_t* cr, const double* obs, const float* acs, int N, float* cost, void* stream) {
+  if (cr == nullptr || cr->n_hidden != ICRL_COST_REGION)
+    return fail("icrl_cost_region_rows: not a region cost descriptor (icrl_cost_region_t: n_hidden must be ICRL_COST_REGION)");
+  if (int e = cost_region_check("icrl_cost_region_rows", cr, 0, 0, -1)) return e;
+  if (N <= 0 || cost == nullptr) return fail("icrl_cost_region_rows: N = %d rows, cost = %p", N, (void*)cost);
+  for (int c = 0; c < cr->n_clauses; ++c)
+    for (int k = 0; k < cr->clauses[c].n_terms; ++k) {
+      const bool is_obs = cr->clauses[c].col[k] < cr->obs_dim;
+      if ((is_obs ? (const void*)obs : (const void*)acs) == nullptr)
+        return fail("icrl_cost_region_rows: region cost (icrl_cost_region_t): clause %d, term %d reads the %s, which is NULL", c, k, is_obs ? "observations" : "actions");
+    }
+  const int grid = (N + 255) / 256 < 1024 ? (N + 255) / 256 : 1024;
+  hipLaunchKernelGGL(cost_region_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *cr, obs, acs, N, cost);
+  return (int)hipGetLastError();
+}
+
 extern "C" int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, const float* acs, int N, float* cost, void* stream) {
   if (cf == nullptr || cf->n_hidden != ICRL_COST_FN) return fail("icrl_cost_fn_rows: not an analytic cost descriptor (n_hidden must be ICRL_COST_FN)");
   if (int e = cost_fn_check("icrl_cost_fn_rows", cf, 0, 0, -1)) return e;
@@ -4553,6 +4621,7 @@ extern "C" int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, co
 extern "C" int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, float* cost,
                                      void* stream) {
   if (const icrl_cost_fn_t* cf = as_cost_fn(cn)) return icrl_cost_fn_rows(cf, obs, acs, N, cost, stream);
+  if (const icrl_cost_region_t* cr = as_cost_region(cn)) return icrl_cost_region_rows(cr, obs, acs, N, cost, stream);
   if (const icrl_cost_disc_t* cd = as_cost_disc(cn)) {      // the inner net read as D: one zeta, stored as it is
     if (int e = cost_disc_check("icrl_cost_mlp_forward", cd)) return e;
     return icrl_disc_reward(cd->net, obs, acs, N, cost, 0, stream);
@@ -4570,6 +4639,7 @@ extern "C" int icrl_disc_reward(const icrl_costnet_t* cn, const double* obs, con
                                 void* stream) {
   if (as_cost_fn(cn)) return refuse_cost_fn("icrl_disc_reward");
   if (as_cost_disc(cn)) return refuse_cost_disc("icrl_disc_reward");
+  if (as_cost_region(cn)) return refuse_cost_region("icrl_disc_reward");
   if (N <= 0) return fail("cost forward: N = %d rows", N);
   if (costnet_is_wide(cn)) return launch_cn_cost_rows(cn, obs, acs, N, out, apply_log ? 2 : 1, (hipStream_t)stream);
   if (!cn_ok(cn)) return bad_cn("cost forward", cn);
@@ -4591,6 +4661,7 @@ static int make_gail_args(const char* who, int n_runs, const icrl_gail_job_t* jo
     if (j.disc == nullptr) return fail("%s: run %d has no discriminator descriptor", who, r);
     if (as_cost_fn(j.disc)) return refuse_cost_fn(who);
     if (as_cost_disc(j.disc)) return refuse_cost_disc(who);
+    if (as_cost_region(j.disc)) return refuse_cost_region(who);
     if (j.rows <= 0) return fail("%s: run %d: rows = %d", who, r, j.rows);
     if (j.actions == nullptr || j.raw_obs == nullptr) return fail("%s: run %d: actions = %p, raw_obs = %p", who, r, (const void*)j.actions, (void*)j.raw_obs);
     if (j.disc->obs_dim < 1) return fail("%s: run %d: obs_dim = %d", who, r, j.disc->obs_dim);
@@ -4765,6 +4836,7 @@ struct KernelPick {
   bool prof = false;       // tools: the instantiations with the phase timers (do_gae bits 2 / 3)
   bool disc = false;       // an icrl_cost_disc_t behind the cost pointer: the kernels whose cost wave returns zeta; single runs, no phase timers
   bool sde = false;        // icrl_rollout_collect_sde: the kernels with the gSDE head (with_act_step_sde_kernel, with_persistent_sde_kernel)
+  bool region = false;     // an icrl_cost_region_t behind the cost pointer: the CIT == 0 image with the region cost wave; single runs, no phase timers
   int E = 0;              // multi kernels: envs per workgroup (multi_shape)
   int minw = 1;            // batched one-workgroup-per-env kernels: workgroups per CU the register allocation leaves room for
   // what the dispatch below instantiated, written by it for the route record (pick_bits): the MINW of with_persistent_batch_kernel,
@@ -4785,7 +4857,7 @@ static bool small_shape(int O, const icrl_costnet_t* net) { return O <= 32 && (n
 template <bool CN128 = false, class F>
 static int with_image(const KernelPick& k, F&& f) {
   k.used_cn128 = false;
-  if (k.analytic) return k.small ? f(Image<2, 0>{}) : f(Image<8, 0>{});
+  if (k.analytic || k.region) return k.small ? f(Image<2, 0>{}) : f(Image<8, 0>{});
   if (k.small) return f(Image<2, 2>{});
   if constexpr (CN128) {
     if (k.cn128) { k.used_cn128 = true; return f(Image<8, 8>{}); }
@@ -4798,6 +4870,8 @@ template <class F> static int with_act_step_kernel(const KernelPick& k, F&& f) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
     if constexpr (CIT != 0) {
       if (k.disc) return f(act_step_kernel<OCT, CIT | CIT_DISC>);
+    } else {
+      if (k.region) return f(act_step_kernel<OCT, CIT_REGION>);
     }
     return f(act_step_kernel<OCT, CIT>);
   });
@@ -4807,6 +4881,8 @@ template <class F> static int with_host_step_kernel(const KernelPick& k, F&& f) 
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
     if constexpr (CIT != 0) {
       if (k.disc) return f(host_step_kernel<OCT, CIT | CIT_DISC>);
+    } else {
+      if (k.region) return f(host_step_kernel<OCT, CIT_REGION>);
     }
     return f(host_step_kernel<OCT, CIT>);
   });
@@ -4826,6 +4902,8 @@ template <class F> static int with_persistent_kernel(const KernelPick& k, F&& f)
     constexpr bool GRAN = decltype(gran)::value;
     if constexpr (CIT != 0) {
       if (k.disc) return k.mon ? f(rollout_persistent_disc_kernel<OCT, CIT, GRAN, true>) : f(rollout_persistent_disc_kernel<OCT, CIT, GRAN>);
+    } else {
+      if (k.region) return k.mon ? f(rollout_persistent_region_kernel<OCT, GRAN, true>) : f(rollout_persistent_region_kernel<OCT, GRAN>);
     }
     if (k.mon) return f(rollout_persistent_kernel<OCT, CIT, GRAN, false, true>);
     if constexpr (CIT != 0) {
@@ -4848,6 +4926,8 @@ template <class F> static int with_wide_kernel(const KernelPick& k, F&& f) {
     constexpr int OCT = decltype(im)::oct, CIT = decltype(im)::cit;
     if constexpr (CIT != 0) {
       if (k.disc) return k.mon ? f(rollout_wide_kernel<OCT, CIT | CIT_DISC, false, true>) : f(rollout_wide_kernel<OCT, CIT | CIT_DISC>);
+    } else {
+      if (k.region) return k.mon ? f(rollout_wide_kernel<OCT, CIT_REGION, false, true>) : f(rollout_wide_kernel<OCT, CIT_REGION>);
     }
     if (k.mon) return f(rollout_wide_kernel<OCT, CIT, false, true>);
     if constexpr (CIT != 0) {
@@ -4886,7 +4966,7 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
       constexpr int E = decltype(e)::value;
       if constexpr (BATCH && CIT == 0) return f(rollout_multi_batch_analytic_kernel<OCT, E, MON>);
       else if constexpr (BATCH) return f(rollout_multi_batch_kernel<OCT, CIT, E, MON>);
-      else if constexpr (CIT == 0) return f(rollout_multi_analytic_kernel<OCT, E, MON>);
+      else if constexpr (CIT == 0) return k.region ? f(rollout_multi_with_a_region_cost_wave_kernel<OCT, E, MON>) : f(rollout_multi_analytic_kernel<OCT, E, MON>);
       else return k.disc ? f(rollout_multi_net_as_discriminator_kernel<OCT, CIT, E, MON>) : f(rollout_multi_kernel<OCT, CIT, E, MON>);
     };
     return k.E == 16 ? kernel(Int<16>{}) : (k.E == 8 ? kernel(Int<8>{}) : kernel(Int<4>{}));
@@ -4896,7 +4976,8 @@ template <bool BATCH, class F> static int with_multi_kernel(const KernelPick& k,
 // the route record's word 4: the KernelPick fields that chose the instantiation of `route` (ICRL_PICK_*), nothing that it ignores;
 // the <8, 8> image and MINW as the dispatch that launched it wrote them down (call this after the launch)
 static int pick_bits(const KernelPick& k, int route) {
-  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0) | (k.disc ? ICRL_PICK_DISC : 0) | (k.sde ? ICRL_PICK_SDE : 0);
+  int b = (k.small ? ICRL_PICK_SMALL : 0) | (k.analytic ? ICRL_PICK_ANALYTIC : 0) | (k.disc ? ICRL_PICK_DISC : 0) | (k.sde ? ICRL_PICK_SDE : 0) |
+          (k.region ? ICRL_PICK_REGION : 0);
   if (route == ICRL_ROUTE_PER_STEP || route == ICRL_ROUTE_GENERIC_PER_STEP) return b;
   b |= k.mon ? ICRL_PICK_MON : 0;
   if (route == ICRL_ROUTE_PERSISTENT || route == ICRL_ROUTE_PERSISTENT_BATCH) b |= k.gran ? ICRL_PICK_GRAN : 0;
@@ -5069,7 +5150,15 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   const icrl_cost_disc_t* const cd = as_cost_disc(cn_arg);
   if (cd != nullptr)
     if (int e = cost_disc_check("icrl_rollout_collect", cd)) return e;
-  const icrl_costnet_t* const net = cf != nullptr ? nullptr : (cd != nullptr ? cd->net : cn_arg);
+  // a region cost (icrl_cost_region_t): checked on its host table here, the CIT == 0 image with the region cost wave below (k.region)
+  const icrl_cost_region_t* const cr = as_cost_region(cn_arg);
+  if (cr != nullptr) {
+    if (int e = cost_region_check("icrl_rollout_collect", cr, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
+    if (policy_is_wide(pol))
+      return fail("icrl_rollout_collect: a region cost descriptor (icrl_cost_region_t) beside a generic-shape policy is not served: the "
+                  "generic-shape rollout kernels have no region form");
+  }
+  const icrl_costnet_t* const net = (cf != nullptr || cr != nullptr) ? nullptr : (cd != nullptr ? cd->net : cn_arg);
   const bool cn = cn_arg != nullptr;
   const bool generic = policy_is_wide(pol) || (net != nullptr && costnet_is_wide(net));      // shapes of the generic-shape path: per-step launches
   if (!generic && !dims_ok(pol)) return bad_dims("icrl_rollout_collect", pol);
@@ -5081,7 +5170,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
                 "numpy-ordered chain per column)", N, NORM_MAX_N);
   hipStream_t s = (hipStream_t)stream;
   KernelPick k;
-  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.disc = cd != nullptr; k.mon = raw_plane != nullptr;
+  k.small = small_shape(O, net); k.analytic = cf != nullptr; k.disc = cd != nullptr; k.region = cr != nullptr; k.mon = raw_plane != nullptr;
   auto finish = [&](int err) { return finish_with_gae(err, do_gae, buf, ag, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, stream); };
   // the route record, written where a rung returns after its launch(es): workspace source, working workgroups, envs per workgroup, packed, launches
   auto routed = [&](int err, int route, const char* ws, int wgs, int E, int packed, int launches) {
@@ -5142,6 +5231,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
   }
   ActStepArgs a;
   fill_act_args(a, env, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
+  if (cr != nullptr) { a.cr = *cr; a.has_cn = 1; }      // (the descriptor in the analytic cost's bytes; the kernels read n_clauses, combine, d_clauses)
   // several environments per workgroup, interleaved (rollout_multi_kernel): do_gae bit 5
   // (the Point envs at the sizes of the one-workgroup-per-env kernel come here too: that kernel is built without their step, env_step_wave)
   const bool point = env->reward_form >= 4;
@@ -5181,7 +5271,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
         const size_t clear = wide_ws_carve(ws, N, O, false, p);
         hipError_t e = hipMemsetAsync(p.xg, 0, clear, s);
         if (e != hipSuccess) return (int)e;
-        if (k.mon || k.analytic || k.disc) p.prof = 0;      // (with the plane, an analytic or a discriminator cost: the instantiations without phase timers)
+        if (k.mon || k.analytic || k.disc || k.region) p.prof = 0;      // (with the plane, an analytic, a discriminator or a region cost: the instantiations without phase timers)
         k.prof = p.prof != 0;
         const int err = with_wide_kernel(k, [&](auto kernel) { return (int)launch_coresident(kernel, dim3(G), dim3(256), 0, s, p); });
         if (err == (int)hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); goto per_step; }
@@ -5199,7 +5289,7 @@ extern "C" int icrl_rollout_collect_ex_mon(const icrl_env_t* env, const icrl_nor
       const size_t clear = persist_ws_carve(ws, N, O, gran, p);
       hipError_t e = hipMemsetAsync(p.counter, 0, clear, s);
       if (e != hipSuccess) return (int)e;
-      if (k.mon || k.analytic || k.disc) p.prof = 0;      // (with the plane, an analytic or a discriminator cost: the instantiations without phase timers)
+      if (k.mon || k.analytic || k.disc || k.region) p.prof = 0;      // (with the plane, an analytic, a discriminator or a region cost: the instantiations without phase timers)
       k.gran = gran; k.prof = p.prof != 0;
       const size_t dyn = persist_dyn_lds(N, O, env->act_dim);
       const int perr = with_persistent_kernel(k, [&](auto kernel) { return launch_per_env(kernel, N, dyn, s, p); });
@@ -5349,6 +5439,8 @@ extern "C" int icrl_rollout_collect_batch_mon(int n_runs, const icrl_rollout_job
     if (as_cost_fn(jobs[r].cn)) return refuse_cost_fn("icrl_rollout_collect_batch");
   for (int r = 0; r < n_runs; ++r)
     if (as_cost_disc(jobs[r].cn)) return refuse_cost_disc("icrl_rollout_collect_batch");
+  for (int r = 0; r < n_runs; ++r)
+    if (as_cost_region(jobs[r].cn)) return refuse_cost_region("icrl_rollout_collect_batch");
   return rollout_collect_batch_impl(n_runs, jobs, mons, action_low, action_high, reward_gamma, reward_gae_lambda, cost_gamma, cost_gae_lambda, do_gae,
                                     args_ws, args_ws_bytes, stream, false);
 }
@@ -5364,6 +5456,7 @@ extern "C" int icrl_rollout_collect_batch_cost(int n_runs, const icrl_rollout_jo
   int n_fn = 0, n_net = 0;
   for (int r = 0; r < n_runs; ++r) {
     if (as_cost_disc(jobs[r].cn)) return refuse_cost_disc("icrl_rollout_collect_batch_cost");
+    if (as_cost_region(jobs[r].cn)) return refuse_cost_region("icrl_rollout_collect_batch_cost");
     if (as_cost_fn(jobs[r].cn)) ++n_fn;
     else if (jobs[r].cn != nullptr) ++n_net;
   }
@@ -5432,6 +5525,7 @@ extern "C" int icrl_rollout_collect_sde(const icrl_env_t* env, const icrl_norm_t
   note_route(ICRL_FAMILY_ROLLOUT);
   if (env == nullptr || nm == nullptr || pol == nullptr || buf == nullptr || ag == nullptr || expl == nullptr)
     return fail("%s: NULL argument (env, nm, pol, buf, ag and expl are required)", who);
+  if (as_cost_region(cn_arg) != nullptr) return refuse_cost_region(who);      // (the gSDE kernels have no region form)
   if (pol->params == nullptr || pol->params_t == nullptr) return fail("%s: NULL argument (pol->params and pol->params_t are required)", who);
   if ((action_low == nullptr) != (action_high == nullptr)) return fail("%s: NULL argument (action_low and action_high: both or neither)", who);
   if (pol->discrete) return fail("%s: a discrete policy has no gSDE head", who);
@@ -5524,7 +5618,10 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   const icrl_cost_disc_t* const cd = as_cost_disc(cn);
   if (cd != nullptr)
     if (int e = cost_disc_check("icrl_host_step", cd)) return e;
-  const icrl_costnet_t* const net = cf != nullptr ? nullptr : (cd != nullptr ? cd->net : cn);      // the constraint net proper
+  const icrl_cost_region_t* const cr = as_cost_region(cn);
+  if (cr != nullptr)
+    if (int e = cost_region_check("icrl_host_step", cr, O, pol->discrete ? 0 : pol->act_dim, pol->discrete ? 1 : 0)) return e;
+  const icrl_costnet_t* const net = (cf != nullptr || cr != nullptr) ? nullptr : (cd != nullptr ? cd->net : cn);      // the constraint net proper
   if (net != nullptr && (costnet_is_wide(net) || !cn_ok(net))) return bad_cn("icrl_host_step", net);
   if (N < 1 || N > 128 || O < 1 || O > MAX_OBS || pol->obs_dim != O)
     return fail("icrl_host_step: %d envs (1..128), obs_dim %d (1..%d), policy obs_dim %d: other shapes take the per-step loop", N, O, MAX_OBS, pol->obs_dim);
@@ -5539,6 +5636,7 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   ActStepArgs& a = h.act;
   a.env.n_envs = N; a.env.obs_dim = O; a.env.act_dim = pol->discrete ? 1 : pol->act_dim;
   fill_act_args(a, nullptr, buf, ag, pol, false, net, cf, noise, action_low, action_high, raw_plane);
+  if (cr != nullptr) { a.cr = *cr; a.has_cn = 1; }
   h.nm = *nm; h.hs = *hs; h.N = N;
   // act_host is a HOST address (a pinned allocation or a registered host range): the kernel stores through the device's mapping of it
   void* act_dev = nullptr;
@@ -5549,7 +5647,7 @@ extern "C" int icrl_host_step_mon(const icrl_norm_t* nm, const icrl_policy_t* po
   h.hs.act_host = reinterpret_cast<float*>(act_dev);
   hipStream_t s = (hipStream_t)stream;
   KernelPick pick;
-  pick.small = small_shape(O, net); pick.analytic = cf != nullptr; pick.disc = cd != nullptr;
+  pick.small = small_shape(O, net); pick.analytic = cf != nullptr; pick.disc = cd != nullptr; pick.region = cr != nullptr;
   with_host_step_kernel(pick, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(N), dim3(256), 0, s, h, k); return 0; });
   return (int)hipGetLastError();
 }

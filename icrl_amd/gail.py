@@ -22,7 +22,7 @@ import torch
 from . import callbacks, distributed as D, envs, logger, spaces, utils
 from .gail_utils import GailCallback, GailDiscriminator
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import get_true_cost_function, true_cost_for
+from .true_constraint_net import check_cost_spec_flags, cost_for, get_true_cost_function, true_cost_for
 
 
 class PPO(PPOLagrangian):
@@ -46,6 +46,7 @@ def setup(config, log=print):
     sets and which are off by default so that a solo run's draws stay what they were: config.eval_noise_from_streams (evaluation noise
     from the run's own streams, as in cpg) and config.disc_perms_from_streams (the discriminator's permutation likewise)."""
     logger.configure()
+    check_cost_spec_flags(config)
     rank = getattr(config, "rank", 0)
     if getattr(config, "use_sde", False):      # -us over several ranks: refused before anything is launched
         from . import exploration
@@ -81,7 +82,7 @@ def setup(config, log=print):
                                           eps=config.disc_eps, device=dev)
     if getattr(config, "use_cost_shaping_callback", False):
         raise NotImplementedError("--use_cost_shaping_callback (a shaping ablation of the reference) is outside the hot path")
-    gail_update = GailCallback(discriminator, config.learn_cost, true_cost_for(config.eval_env_id), config.save_dir)
+    gail_update = GailCallback(discriminator, config.learn_cost, cost_for(config.eval_env_id, getattr(config, "cost_spec", None), train_env), config.save_dir)
     model = PPO(policy=config.policy_name, env=train_env, learning_rate=config.learning_rate, n_steps=config.n_steps,
                 batch_size=config.batch_size, n_epochs=config.n_epochs, gamma=config.reward_gamma, gae_lambda=config.reward_gae_lambda,
                 clip_range=config.clip_range, clip_range_vf=config.clip_range_reward_vf, ent_coef=config.ent_coef,
@@ -154,6 +155,9 @@ def build_parser():
     a("--expert_path", "-ep", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests/golden/expert_hc.npz"))
     a("--expert_rollouts", "-er", type=int, default=20); a("--num_spurious_features", "-nsf", type=int, default=None)
     a("--use_cost_shaping_callback", "-ucsc", action="store_true"); a("--use_cost_net", "-ucn", action="store_true")
+    # a user-defined ground-truth constraint (true_constraint_net.RegionCost: a JSON file or string) in the place of the env id's for
+    # true/cost and friends; absent from the namespace unless given, like -sfr
+    a("--cost_spec", "-csp", type=str, default=argparse.SUPPRESS)
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")

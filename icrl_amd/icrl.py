@@ -21,7 +21,7 @@ import torch
 from . import distributed as D, logger, utils
 from .constraint_net import ConstraintNet
 from .ppo_lag import PPOLagrangian
-from .true_constraint_net import get_true_cost_function, mean_cost, null_cost, true_cost_for
+from .true_constraint_net import check_cost_spec_flags, cost_for, get_true_cost_function, mean_cost, null_cost, true_cost_for
 from .vec_env import VecNormalize, sync_envs_normalization
 from . import envs, spaces
 
@@ -30,6 +30,7 @@ def setup(config):
     """everything of icrl() before the loop (ref: icrl/icrl.py:45-197): env stacks, expert data, constraint net, nominal agent."""
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     use_curiosity = bool(getattr(config, "use_curiosity_driven_exploration", False))
+    check_cost_spec_flags(config)
     if getattr(config, "use_sde", False):      # -us with -ucde or several ranks: refused before anything is launched
         from . import exploration
         exploration.refuse_sde(config)
@@ -100,7 +101,7 @@ def setup(config):
 
     st = dict(config=config, rank=rank, world=world, train_env=train_env, sampling_env=sampling_env, eval_env=eval_env,
               constraint_net=constraint_net, create_nominal_agent=create_nominal_agent, agent=create_nominal_agent(),
-              expert_agent=expert_agent, true_cost_function=true_cost_for(config.eval_env_id),
+              expert_agent=expert_agent, true_cost_function=cost_for(config.eval_env_id, getattr(config, "cost_spec", None), train_env),
               d_expert_obs=torch.as_tensor(np.asarray(expert_obs), device=dev),
               d_expert_acs=torch.as_tensor(np.asarray(expert_acs), device=dev),
               timesteps=0., start_time=time.time(),
@@ -293,6 +294,9 @@ def build_parser():
     a("--expert_rollouts", "-er", type=int, default=20)
     # additions of this build
     a("--expert_agent_path", type=str, default=None, help="agent zip / npz with policy.pth for the KL metrics")
+    # a user-defined ground-truth constraint (true_constraint_net.RegionCost: a JSON file or string) in the place of the env id's for
+    # true/cost and friends; absent from the namespace unless given, like -sfr
+    a("--cost_spec", "-csp", type=str, default=argparse.SUPPRESS)
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")

@@ -221,15 +221,20 @@ class PPOLagrangian:
             return env, None, cw
         if not isinstance(cw, VecCostWrapper) or not isinstance(cw.venv, HipSynthVecEnv) or not self._fused_cost_ok(cw):
             return None
+        if cw.region_cost() is not None and getattr(self.policy, "wide", False):
+            return None      # (the generic-shape rollout kernels have no region form: the per-step loop)
         return env, cw, cw.venv
 
     @staticmethod
     def _fused_cost_ok(cw):
         """a cost the rollout kernels evaluate themselves: a device ConstraintNet, an AnalyticCost (true_constraint_net.py; the ground-truth
         and null costs of cpg) unless ICRL_ANALYTIC_COST_STEPPED=1 forces the per-step loop over the same cost object, or a
-        DiscriminatorCost (gail_utils.py; cpg --load_gail) unless ICRL_DISC_COST_STEPPED=1 does."""
+        DiscriminatorCost (gail_utils.py; cpg --load_gail) unless ICRL_DISC_COST_STEPPED=1 does, or a RegionCost (true_constraint_net.py;
+        --cost_spec) unless ICRL_REGION_COST_STEPPED=1 does."""
         if cw.constraint_net() is not None:
             return True
+        if cw.region_cost() is not None:
+            return os.environ.get("ICRL_REGION_COST_STEPPED", "0") in ("", "0")
         if cw.discriminator_cost() is not None:
             return os.environ.get("ICRL_DISC_COST_STEPPED", "0") in ("", "0")
         return cw.analytic_cost() is not None and os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") in ("", "0")
@@ -309,6 +314,8 @@ class PPOLagrangian:
         cw = chain[1]
         if cw is not None and cw.discriminator_cost() is not None:
             return "a DiscriminatorCost (the gSDE kernels have no discriminator form)"
+        if cw is not None and cw.region_cost() is not None:
+            return "a RegionCost (the gSDE kernels have no region form)"
         if cw is not None and cw.constraint_net() is not None:
             cs = cw.cost_struct()
             if cs.n_hidden not in (1, 2) or cs.h1 > 64 or (cs.n_hidden == 2 and cs.h2 > 64) or cs.in_dim > 160:
@@ -546,7 +553,7 @@ class PPOLagrangian:
         """The reference's per-step loop, kept for everything the fused launch does not cover: a callable `cost_function`
         (warm-up with null_cost, icrl/icrl.py:187-193; costs are then evaluated on the observation AFTER the step and are not
         normalised, on_policy_algorithm.py:392-394), an env cost that is an arbitrary Python function (an AnalyticCost under
-        ICRL_ANALYTIC_COST_STEPPED=1 and cpg --load_gail's DiscriminatorCost under ICRL_DISC_COST_STEPPED=1 too), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
+        ICRL_ANALYTIC_COST_STEPPED=1 and cpg --load_gail's DiscriminatorCost under ICRL_DISC_COST_STEPPED=1 and a RegionCost under ICRL_REGION_COST_STEPPED=1 too), partial rollouts.  One launch per call of the fine-grained C-ABI entry points; not the benchmarked path."""
         rollout_buffer.reset()
         if callback is not None:
             callback.on_rollout_start()

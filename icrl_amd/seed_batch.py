@@ -128,6 +128,13 @@ def _gail_callbacks(cb):
     return []
 
 
+def _refuse_cost_spec(c):
+    if getattr(c, "cost_spec", None) is not None:
+        raise ValueError("seed batch: --cost_spec (cost_spec) makes the ground-truth cost a RegionCost, and the batched rollout kernels and "
+                         "rollout-end launches have no region form (single runs evaluate it inside their fused launches); a batch takes the "
+                         "env id's ground-truth cost")
+
+
 class SeedBatch:
     # observations of 65..128 (AntWall: 113): a run alone updates with FOUR workgroups per network (csrc/ppo_train_quarters*.hip), the
     # batched grid has the row-owning kernel only, whose partial sums associate differently — a batched run would no longer compute
@@ -139,6 +146,7 @@ class SeedBatch:
         if states is None:      # refused before anything is set up
             configs = list(configs)
             for c in configs:
+                _refuse_cost_spec(c)
                 exploration.refuse_batched(c, seed_batch=True)
                 exploration.refuse_sde(c, seed_batch=True)
         self.states = setup_runs(configs, on_setup) if states is None else states
@@ -554,6 +562,7 @@ class CpgSeedBatch(SeedBatch):
             raise ValueError("seed batch: no runs")
         c0 = configs[0]
         for c in configs:
+            _refuse_cost_spec(c)
             exploration.refuse_batched(c, seed_batch=True)
             exploration.refuse_sde(c, seed_batch=True)
         if os.environ.get("ICRL_ANALYTIC_COST_STEPPED", "0") not in ("", "0"):
@@ -634,6 +643,7 @@ class GailSeedBatch(SeedBatch):
             raise ValueError("seed batch: no runs")
         c0 = configs[0]
         for c in configs:      # ---- refused before anything is set up
+            _refuse_cost_spec(c)
             exploration.refuse_sde(c, seed_batch=True)
         for c in configs:
             _refuse_host_envs(c.train_env_id, c.eval_env_id)

@@ -49,6 +49,25 @@ class CostDiscT(C.Structure):
     _fields_ = [("obs_dim", i32), ("acs_dim", i32), ("in_dim", i32), ("n_hidden", i32), ("net", vp)]
 
 
+COST_REGION = -3  # ICRL_COST_REGION: the value of n_hidden that marks a region cost
+REGION_MAX_CLAUSES = REGION_MAX_TERMS = 8
+REGION_BOX, REGION_HALFSPACE, REGION_BALL = range(3)
+REGION_ANY, REGION_ALL, REGION_SUM = range(3)
+
+
+class RegionClauseT(C.Structure):
+    """icrl_region_clause_t: box (a = lo, b = hi), halfspace (a = w, c = offset) or ball (a = centre, c = radius squared)."""
+    _fields_ = [("type", i32), ("negate", i32), ("n_terms", i32), ("_pad", i32), ("col", i32 * REGION_MAX_TERMS),
+                ("a", f64 * REGION_MAX_TERMS), ("b", f64 * REGION_MAX_TERMS), ("c", f64)]
+
+
+class CostRegionT(C.Structure):
+    """icrl_cost_region_t: a region cost; its first four fields alias CostNetT's.  `clauses` is the host address of the clause table,
+    `d_clauses` the device address of the same bytes; both must outlive every call that takes this descriptor."""
+    _fields_ = [("obs_dim", i32), ("acs_dim", i32), ("in_dim", i32), ("n_hidden", i32), ("n_clauses", i32), ("combine", i32),
+                ("clauses", vp), ("d_clauses", vp)]
+
+
 class BufferT(C.Structure):
     _fields_ = [("T", i32), ("N", i32), ("obs_dim", i32), ("act_store", i32),
                 ("observations", vp), ("new_observations", vp), ("orig_observations", vp), ("new_orig_observations", vp),

@@ -501,11 +501,21 @@ class VecCostWrapper(VecEnvWrapper):
         from .gail_utils import DiscriminatorCost
         return self.cost_function if isinstance(self.cost_function, DiscriminatorCost) else None
 
+    def region_cost(self):
+        """the RegionCost behind cost_function, if that is what it is (true_constraint_net.py: --cost_spec; evaluated inside the fused
+        rollout by the kernels whose cost wave walks the clause table)."""
+        from .true_constraint_net import RegionCost
+        return self.cost_function if isinstance(self.cost_function, RegionCost) else None
+
     def cost_struct(self):
-        """the descriptor the rollout entry points take for this wrapper's cost (icrl_costnet_t, icrl_cost_fn_t or icrl_cost_disc_t), or None."""
+        """the descriptor the rollout entry points take for this wrapper's cost (icrl_costnet_t, icrl_cost_fn_t, icrl_cost_disc_t or
+        icrl_cost_region_t), or None."""
         cn = self.constraint_net()
         if cn is not None:
             return cn.struct()
+        rc = self.region_cost()
+        if rc is not None:
+            return rc.struct(getattr(self.venv, "device", None))
         dc = self.discriminator_cost()
         if dc is not None:
             return dc.struct()
@@ -529,8 +539,8 @@ class VecCostWrapper(VecEnvWrapper):
         cn = self.constraint_net()
         if cn is not None:
             cost = cn.cost_function_device(self.previous_obs, self.actions)
-        elif (self.analytic_cost() is not None or self.discriminator_cost() is not None) and torch.is_tensor(self.previous_obs) and torch.is_tensor(self.actions):
-            cost = self.cost_function(self.previous_obs, self.actions)      # icrl_cost_fn_rows / icrl_disc_reward on the device tensors: no host copies
+        elif (self.analytic_cost() is not None or self.discriminator_cost() is not None or self.region_cost() is not None) and torch.is_tensor(self.previous_obs) and torch.is_tensor(self.actions):
+            cost = self.cost_function(self.previous_obs, self.actions)      # icrl_cost_fn_rows / icrl_disc_reward / icrl_cost_region_rows on the device tensors: no host copies
         else:  # arbitrary Python callable: numpy in / numpy out, as in the reference
             po = self.previous_obs.cpu().numpy() if torch.is_tensor(self.previous_obs) else self.previous_obs
             ac = self.actions.cpu().numpy() if torch.is_tensor(self.actions) else self.actions

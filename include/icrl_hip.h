@@ -174,6 +174,46 @@ typedef struct {
   const icrl_costnet_t* net;
 } icrl_cost_disc_t;
 
+/* Region cost: a user-defined ground-truth constraint, described by data and evaluated by the rollout kernels themselves on (previous
+ * raw observation float64, clipped action float32; one column, the class index, beside a discrete policy).  The third tagged
+ * descriptor behind a `const icrl_costnet_t*`: n_hidden == ICRL_COST_REGION.  Column c < obs_dim is observation column c, column
+ * obs_dim + j action column j; every value is taken as float64 (widening a float32 is exact).  1..8 clauses of 1..8 terms each:
+ *   BOX        true iff for every term  a[k] <= x_k && x_k <= b[k]            (a = lo, b = hi; +-inf allowed)
+ *   HALFSPACE  acc = c; in term order acc = acc + a[k] * x_k; true iff acc >= 0   (a = w, c = the offset; every product and every
+ *              sum rounded once to float64, no fused multiply-add)
+ *   BALL       acc = 0; in term order d = x_k - a[k], acc = acc + d * d; true iff acc <= c   (a = centre, c = radius * radius,
+ *              computed once on the host)
+ * `negate` flips a clause; IEEE comparisons, so a NaN makes the un-negated clause false.  combine: ANY 1 if any clause is true,
+ * ALL 1 if every clause is true, SUM the number of true clauses; the result is a float.  Every analytic kind is a member of the family
+ * (wall_behind(p, i) = box on column i with hi = p; torque(t) = negated box [-t, t] over all action columns; ...).
+ * `clauses` is a HOST pointer (every check runs on it before the first HIP call), `d_clauses` a DEVICE pointer to the same
+ * n_clauses * sizeof(icrl_region_clause_t) bytes, uploaded once by the caller like a prepared params_t; the kernels copy the table into
+ * LDS before their step loop.  Served by icrl_rollout_collect[_ex][_mon] on every route of a single run but the generic-shape ones,
+ * icrl_host_step[_mon], icrl_cost_mlp_forward and icrl_cost_region_rows; refused with a reason by every *_batch* rollout,
+ * icrl_rollout_collect_sde, generic-shape policies, icrl_cn_train*, icrl_cn_prepare, icrl_costnet_prepare, icrl_disc_reward, the GAIL
+ * batch entry points and as the inner net of an icrl_cost_disc_t. */
+#define ICRL_COST_REGION (-3)        /* value of n_hidden that marks a region cost */
+#define ICRL_REGION_MAX_CLAUSES 8
+#define ICRL_REGION_MAX_TERMS 8
+#define ICRL_REGION_BOX 0
+#define ICRL_REGION_HALFSPACE 1
+#define ICRL_REGION_BALL 2
+#define ICRL_REGION_ANY 0
+#define ICRL_REGION_ALL 1
+#define ICRL_REGION_SUM 2
+typedef struct {
+  int32_t type /* ICRL_REGION_BOX | HALFSPACE | BALL */, negate, n_terms, _pad;
+  int32_t col[ICRL_REGION_MAX_TERMS];
+  double a[ICRL_REGION_MAX_TERMS], b[ICRL_REGION_MAX_TERMS];
+  double c;
+} icrl_region_clause_t;
+typedef struct {
+  int32_t obs_dim, acs_dim, in_dim /* 0 */, n_hidden /* ICRL_COST_REGION */;
+  int32_t n_clauses, combine /* ICRL_REGION_ANY | ALL | SUM */;
+  const icrl_region_clause_t* clauses;      /* host */
+  const icrl_region_clause_t* d_clauses;    /* device, the same bytes */
+} icrl_cost_region_t;
+
 /* RolloutBufferWithCost arrays (stable_baselines3/common/buffers.py:443-491), time-major [T,N,...] float32. */
 typedef struct {
   int32_t T, N, obs_dim, act_store; /* act_store = act_dim (Box) or 1 (Discrete) */
@@ -452,6 +492,11 @@ int icrl_cost_mlp_forward(const icrl_costnet_t* cn, const double* obs, const flo
  * ([N, 1] class index for ACTION_EQUALS); either may be NULL for a kind that does not read it.  icrl_cost_mlp_forward with an analytic
  * descriptor forwards here. */
 int icrl_cost_fn_rows(const icrl_cost_fn_t* cf, const double* obs, const float* acs, int N, float* cost, void* stream);
+
+/* A region cost on N rows, the twin of icrl_cost_fn_rows: cost[n] = f(obs[n], acs[n]).  obs [N, obs_dim] float64, acs [N, acs_dim]
+ * float32 ([N, 1] class index beside a discrete policy); either may be NULL when no clause reads it.  icrl_cost_mlp_forward with a
+ * region descriptor forwards here. */
+int icrl_cost_region_rows(const icrl_cost_region_t* cf, const double* obs, const float* acs, int N, float* cost, void* stream);
 
 /* GailDiscriminator.reward_function (icrl/gail_utils.py:147-157): the same network read the other way round — the
  * discriminator output D = sigmoid(MLP(prepare(obs, acs))) itself (apply_log = 0) or log(D + eps) (apply_log = 1, the
@@ -753,6 +798,7 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
 #define ICRL_PICK_CN128 16
 #define ICRL_PICK_DISC 32     /* the constraint net read as D (icrl_cost_disc_t) */
 #define ICRL_PICK_SDE 64      /* the kernels with the gSDE head (icrl_rollout_collect_sde) */
+#define ICRL_PICK_REGION 128  /* the kernels whose cost wave evaluates a region cost (icrl_cost_region_t) */
 #define ICRL_PICK_MINW_SHIFT 8
 #define ICRL_UPDATE_GENERIC_PERSISTENT 8
 #define ICRL_UPDATE_GENERIC_LAUNCHES 9
