@@ -218,6 +218,100 @@ __device__ __forceinline__ void policy_forward_block(const PolLayout& L, const R
   }
 }
 
+// policy_forward_block for the persistent rollout's step chain (rollout_persistent_body): the same three MLPs and heads, every expression
+// and its order as above, but wave 0 leaves with nothing but the action behind it.
+//  - sh.h[w] / sh.g[w] are written and read by wave w alone, so a wave-local ordering (the wave's LDS stores performed, no instruction moved
+//    across) stands where the block form has two workgroup barriers: no wave waits for another one before the caller's hand-off barrier;
+//  - the log-prob is not evaluated here: wave 0 returns `act - mean` of its lane (Gaussian head) and the caller evaluates chain_log_prob
+//    behind its record stores; the Categorical head needs the log-softmax for its sample and returns the log-prob itself;
+//  - the value waves return their value (every lane) and store it themselves; sh.scal is not written; the entropy, which no rollout
+//    kernel reads, is not computed.
+// Sampling only (no `given`, not deterministic).  Returns 0 in waves >= 3.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+  __builtin_amdgcn_wave_barrier();
+}
+template <int OCT, class Regs>
+__device__ __forceinline__ float policy_forward_chain(const PolLayout& L, const Regs& R, ActShared& sh, const float* noise_row,
+                                                      const float* alow, const float* ahigh) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (w >= 3) return 0.f;
+  {
+    f32x4 xs[4 * OCT];
+#pragma unroll
+    for (int i = 0; i < 4 * OCT; ++i) xs[i] = *reinterpret_cast<const f32x4*>(&sh.x[4 * i]);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16 * OCT; ++k) acc = fmaf(R.w1[k], xs[k >> 2][k & 3], acc);
+    sh.h[w][lane] = lane < L.H1 ? fast_tanh(acc + R.b1) : 0.f;   // pad lanes store 0 (0 * garbage would poison the next layer)
+  }
+  wave_lds_order();
+  {
+    f32x4 hs[MAX_H / 4];
+#pragma unroll
+    for (int i = 0; i < MAX_H / 4; ++i) hs[i] = *reinterpret_cast<const f32x4*>(&sh.h[w][4 * i]);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAX_H; ++k) acc = fmaf(R.w2[k], hs[k >> 2][k & 3], acc);
+    sh.g[w][lane] = lane < L.H2 ? fast_tanh(acc + R.b2) : 0.f;
+  }
+  wave_lds_order();
+  if (w != 0) {
+    float part = lane < L.H2 ? R.wh[0] * sh.g[w][lane] : 0.f;
+    part = wave_sum_fast(part);
+    return part + R.bh;
+  }
+  float mean = 0.f;
+  {
+    f32x4 gs[MAX_H / 4];
+#pragma unroll
+    for (int i = 0; i < MAX_H / 4; ++i) gs[i] = *reinterpret_cast<const f32x4*>(&sh.g[0][4 * i]);
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAX_H; ++j) acc = fmaf(R.wh[j], gs[j >> 2][j & 3], acc);
+    mean = acc + R.bh;
+  }
+  if (!L.discrete) {
+    float diff = 0.f;
+    if (lane < L.A) {
+      const float act = mean + noise_row[lane] * R.sd;   // Normal.rsample: loc + eps * scale
+      diff = act - mean;
+      sh.act_raw[lane] = act;
+      float c = act;
+      if (alow != nullptr && ahigh != nullptr) c = fminf(fmaxf(act, alow[lane]), ahigh[lane]);
+      sh.act_clip[lane] = c;
+    }
+    return diff;
+  }
+  // Categorical(logits): log-softmax, inverse-CDF sample on the injected uniform (spec: oracle/nets.py forward)
+  float m = wave_max(lane < L.A ? mean : -INFINITY);
+  float e = lane < L.A ? expf(mean - m) : 0.f;
+  float lse = m + logf(wave_sum(e));
+  float logp = mean - lse;
+  float p = lane < L.A ? expf(logp) : 0.f;
+  float cdf = 0.f;
+  const float u = noise_row[0];
+  int cnt = 0;
+  for (int a = 0; a < L.A; ++a) {     // sequential inclusive prefix sum, like th.cumsum
+    cdf += __shfl(p, a, 64);
+    cnt += (u >= cdf) ? 1 : 0;
+  }
+  const int action = cnt < L.A - 1 ? cnt : L.A - 1;
+  if (lane == 0) { sh.act_raw[0] = (float)action; sh.act_clip[0] = (float)action; }
+  return __shfl(logp, action, 64);
+}
+// the log-prob of the action policy_forward_chain sampled, from what wave 0 got back (`head`); result in every lane
+template <class Regs>
+__device__ __forceinline__ float chain_log_prob(const PolLayout& L, const Regs& R, float head) {
+  if (L.discrete) return head;
+  const int lane = threadIdx.x & 63;
+  float lp = 0.f;
+  // Normal.log_prob: -((x - mu)^2) / (2 var) - log(std) - log(sqrt(2 pi))
+  if (lane < L.A) lp = -(head * head) / R.i2v - R.lsd - LOG_SQRT_2PI_F;
+  return wave_sum_fast(lp);
+}
+
 // cost-net weights of one lane (lane j <-> hidden unit j), loaded with independent loads before they are needed (WaveRegs c0 / c1 / ...)
 template <int CIT, class Regs>
 __device__ __forceinline__ void load_cn_regs(const icrl_costnet_t& cn, const CnLayout& L, Regs& R) {
@@ -1270,6 +1364,7 @@ __global__ void __launch_bounds__(1024) norm_step_small_kernel(NormStepArgs a) {
 // =================================================================================================================
 // diagnostic: cycles per phase of workgroup 0 of the last persistent rollout (policy+env | barrier | statistics), steps
 constexpr int NORM_MAX_N_TRACE = 1024;
+constexpr int CHAIN_TRACE_BASE = 4 * 128;      // g_wide_trace words behind those of the persistent rollout's (<= 128) workgroups: its chain timers
 __device__ unsigned long long g_rollout_prof[8];
 __device__ unsigned long long g_rollout_prof_wide[16];
 __device__ unsigned long long g_wide_trace[NORM_MAX_N_TRACE * 4];   // per workgroup, one step: s_memrealtime at phase-A end / gather end / publish / statistics read     // rollout_wide_kernel: [0..7] wave 0, [8..15] wave 1 (owner) of the profiled workgroup
@@ -1443,11 +1538,20 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
   float noise_reg = (!SDE && tid < NA) ? noise_g[(size_t)n * NA + tid] : 0.f;
   double fin_rew = 0.0; float fin_cost = 0.f; int fin_done = 0;
   unsigned long long pc0 = 0, pc1 = 0, pc2 = 0, pc3 = 0, pc4 = 0, pc5 = 0, pc_rounds = 0, tl = PROF ? prof_now() : 0ull;
+  // PROF: the step chain of workgroup 0 in finer pieces, on thread 0 (wave 0 carries the chain): cycles from one mark to the next, summed over
+  // the steps — CH_FWD .. CH_REST below; fc[CH_PUB_AT]: the sum of the cycles from the step's start to the publish.  Written to g_wide_trace
+  // behind the per-workgroup words (CHAIN_TRACE_BASE), read by tools/rollout_only.py.
+  enum { CH_FWD, CH_HANDOFF, CH_ENV, CH_PUBLISH, CH_AFTER_PUB, CH_POLL, CH_SCATTER, CH_VEC, CH_COLUMNS, CH_MERGE, CH_NORMALISE, CH_REST, CH_PUB_AT, CH_N };
+  unsigned long long fc[CH_N] = {0}, fl = 0, f0 = 0;
+  auto mark = [&](int k) { if (PROF) { const unsigned long long now = prof_now(); fc[k] += now - fl; fl = now; } };
+  constexpr int TAIL = 192;      // the thread of the step's tail (and of fin_rew / fin_cost / fin_done)
   int spin_limit = 1 << 22;
+  if constexpr (!SDE) __syncthreads();      // the set-up above, once: inside the loop no wave reads what another wrote before the hand-off barrier
   for (int t = 0; t < T; ++t) {
     const int par = t & 1;
     const size_t tn = (size_t)t * N + n;
     const unsigned gtag = (unsigned)(t + 1);
+    if (PROF) { fl = prof_now(); f0 = fl; }
     if (!SDE && tid < NA) {
       noise_s[tid] = noise_reg;
       if (t + 1 < T) noise_reg = noise_g[((size_t)(t + 1) * N + n) * NA + tid];     // lands during this step
@@ -1464,20 +1568,26 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
         for (int k = 0; k < SDE_REGS; ++k) { const int i = k * 256 + tid; e_reg[k] = i < MAX_H * A ? nxt[i] : 0.f; }
       }
     }
-    __syncthreads();
+    if constexpr (SDE) __syncthreads();      // the exploration matrix is filled by all four waves
+    else wave_lds_order();                   // noise_s: written and read by wave 0
     // ---------------- phase A: kernel A's work for env n ----------------
+    float head = 0.f;      // policy_forward_chain: wave 0's log-prob operand, the value of waves 1 / 2
     if constexpr (SDE) {
       // the mean and the latent, then the head on wave 0, which rewrites its own act_raw / act_clip / scal[2] (LDS accesses of one wave are
       // ordered: no barrier in between); the barrier below publishes them to the env step, the cost wave and the buffer stores
       policy_forward_block<OCT>(a.pl, R, sh, nullptr, 1, nullptr, nullptr);
       if (w == 0) sde_head_wave(sh, A, a.pl.H2, E_s, [&](int i) { return e2_s[i]; }, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
     } else {
-      policy_forward_block<OCT>(a.pl, R, sh, noise_s, 0, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
+      head = policy_forward_chain<OCT>(a.pl, R, sh, noise_s, has_box ? alow_s : nullptr, has_box ? ahigh_s : nullptr);
     }
-    __syncthreads();
+    mark(CH_FWD);
+    __syncthreads();      // the hand-off: act_clip / act_raw (and s_old, x of the last step) to the env step, the cost wave and the storing waves
+    mark(CH_HANDOFF);
+    if (SDE && w < 3) head = sh.scal[w == 0 ? 2 : w - 1];      // (the block form's words: log-prob, v_r, v_c)
     if (w == 0) {
       double rew; int done;
       env_step_wave<POINT>(env, n, sh.s_old, sh.act_clip, e_key, e_ctr, e_tep, sh.s_new, rew, done);
+      mark(CH_ENV);
       float* nob = buf.new_orig_observations + tn * O;
       if (GRAN) {
         const int rec0 = ((par * N + n) * R16) * 16;       // byte offset of this env's records of this parity
@@ -1496,6 +1606,11 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
         for (int i = lane; i < O; i += WAVE) { const double v = sh.s_new[i]; nob[i] = (float)v; xstore(xo + i, v); }
         if (lane == 0) { xstore(as_global(p.xch_rew) + par * N + n, rew); xstore(as_global(p.xch_done) + par * N + n, (unsigned)done); }
       }
+      if (PROF) { mark(CH_PUBLISH); fc[CH_PUB_AT] += fl - f0; }
+      // the log-prob, which nothing in this step waits for: evaluated while the records are in flight
+      const float lp = SDE ? head : chain_log_prob(a.pl, R, head);
+      if (lane == 0) buf.log_probs[tn] = lp;
+      mark(CH_AFTER_PUB);
     } else if (w == 3) {
       float cost = 0.f;
       if constexpr (REGION) cost = cost_region_wave(rtab, a.cr.n_clauses, a.cr.combine, sh.s_old, sh.act_clip, O);
@@ -1512,14 +1627,13 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
       for (int i = lane; i < O; i += WAVE) { ob[i] = sh.x[i]; oob[i] = (float)sh.s_old[i]; }
       if (lane < AS) buf.actions[tn * AS + lane] = sh.act_raw[lane];
       if (lane < A && !a.pl.discrete) ag.act_clipped[(size_t)n * A + lane] = sh.act_clip[lane];
-      if (lane == 0) {
+      if (lane == 0) {       // (each wave stores what it computed: the log-prob above, v_r below)
         buf.dones[tn] = (float)last_done_s;
-        buf.reward_values[tn] = sh.scal[0];
-        buf.cost_values[tn] = sh.scal[1];
-        buf.log_probs[tn] = sh.scal[2];
-        ag.last_v_r[n] = sh.scal[0];
-        ag.last_v_c[n] = sh.scal[1];
+        buf.cost_values[tn] = head;
+        ag.last_v_c[n] = head;
       }
+    } else {
+      if (lane == 0) { buf.reward_values[tn] = head; ag.last_v_r[n] = head; }
     }
     if (PROF) { const unsigned long long tn_ = prof_now(); pc0 += tn_ - tl; tl = tn_; }
     if (PROF && t == T / 2 && lane == 0) g_wide_trace[4 * n + w] = __builtin_amdgcn_s_memrealtime();   // per wave: end of its phase-A part
@@ -1540,6 +1654,7 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
         ++rounds;
       }
       if (PROF && tid == 0) { pc_rounds += (unsigned long long)rounds; }
+      mark(CH_POLL);
       if (!ok) spin_limit = 1;      // a peer never showed up (a workgroup was not resident): stop waiting ~2 s per step; reported below
 #pragma unroll
       for (int k = 0; k < REC_MAX; ++k) {
@@ -1559,7 +1674,28 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
       grid_barrier(as_global(p.counter), N, n, (unsigned)(t + 1), spin_limit);
     }
     if (PROF) { const unsigned long long tn_ = prof_now(); pc1 += tn_ - tl; tl = tn_; }
+    mark(CH_SCATTER);
     // ---------------- phase B: kernel B's statistics, replicated; normalise own env ----------------
+    if constexpr (GRAN) {
+      // this step's running returns, on the wave that sums them below (ret: wave 3, cost_ret: wave 2) and that alone reads and writes
+      // ret_s / cret_s / vec inside the loop: a wave-local ordering, no workgroup barrier between the scatter and the column chains
+      if (w == 3) {
+        for (int i = lane; i < N; i += 64) {
+          const double rr = rawr_s[i];
+          double r = ret_s[i];
+          if (nm.training) r = r * nm.reward_gamma + rr;
+          vec[0][i] = r;
+        }
+      } else if (w == 2) {
+        for (int i = lane; i < N; i += 64) {
+          const float rc = rawc_s[i];
+          double c = has_cost ? cret_s[i] : 0.0;
+          if (nm.training && has_cost) c = c * nm.cost_gamma + (double)rc;
+          vec[1][i] = c;
+        }
+      }
+      if (w >= 2) wave_lds_order();
+    } else
     {
       if (!GRAN) {
         const double* xo = as_global(p.xch_obs) + (size_t)par * N * O;
@@ -1580,15 +1716,18 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
         }
         vec[0][tid] = r; vec[1][tid] = c;
       }
+      __syncthreads();
     }
-    __syncthreads();
     if (PROF) { const unsigned long long tn_ = prof_now(); pc3 += tn_ - tl; tl = tn_; }
+    mark(CH_VEC);
     if (nm.training) {
       if (tid < O) {           // obs_rms.update: rows added in order (numpy's axis-0 reduction)
         double bm, bv;
         column_moments_contig(chunk + tid * NP, N, bm, bv);
+        mark(CH_COLUMNS);
         chan_merge(o_mean, o_var, o_cnt, bm, bv, (double)N);
         o_cnt = (double)N + o_cnt;
+        mark(CH_MERGE);
       }
       if (w == 3 || (w == 2 && has_cost)) {     // ret_rms / cost_rms: numpy pairwise order
         const int v = w == 3 ? 0 : 1;
@@ -1614,11 +1753,21 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
     }
     __syncthreads();
     if (PROF) { const unsigned long long tn_ = prof_now(); pc5 += tn_ - tl; tl = tn_; }
+    mark(CH_NORMALISE);
+    if (GRAN) {
+      if (w == 3) {
+        for (int i = lane; i < N; i += 64) { const int d = done_s[i]; if (nm.training || d) ret_s[i] = d ? 0.0 : vec[0][i]; }
+      } else if (w == 2 && has_cost) {
+        for (int i = lane; i < N; i += 64) { const int d = done_s[i]; if (nm.training || d) cret_s[i] = d ? 0.0 : vec[1][i]; }
+      }
+    } else
     if (tid < N) {
       const int d = done_s[tid];
       if (nm.training || d) { ret_s[tid] = d ? 0.0 : vec[0][tid]; if (has_cost) cret_s[tid] = d ? 0.0 : vec[1][tid]; }
     }
-    if (tid == 0) {
+    // the step's tail — the own env's reward and cost normalised and stored, two float64 divisions — on lane 0 of the cost wave, which has
+    // nothing else to do before the next hand-off barrier (wave 0 goes straight on to the next policy forward)
+    if (tid == TAIL) {
       double r = rawr_s[n];
       fin_rew = r; fin_cost = rawc_s[n]; fin_done = done_s[n];
       if (nm.norm_reward) r = fmin(fmax(r / dens[0], -nm.clip_reward), nm.clip_reward);
@@ -1632,14 +1781,19 @@ __device__ __forceinline__ void rollout_persistent_body(const PersistArgs& p, co
       if (MON) raw_plane[tn] = fin_rew;
     }
     if (PROF) { const unsigned long long tn_ = prof_now(); pc2 += tn_ - tl; tl = tn_; }
+    mark(CH_REST);
   }
   if (PROF && n == 0 && tid == 0) { g_rollout_prof[0] = pc0; g_rollout_prof[1] = pc1; g_rollout_prof[2] = pc2; g_rollout_prof[3] = (unsigned long long)T; g_rollout_prof[4] = pc3; g_rollout_prof[5] = pc4; g_rollout_prof[6] = pc5; g_rollout_prof[7] = pc_rounds; }
+  if (PROF && n == 0 && tid == 0) {
+#pragma unroll
+    for (int k = 0; k < CH_N; ++k) g_wide_trace[CHAIN_TRACE_BASE + k] = fc[k];
+  }
   // a timed-out exchange means stale granules went into the statistics and the buffer: tell the host (it raises)
   if (spin_limit == 1 && ag.status != nullptr && (tid & 63) == 0) atomicOr(ag.status, 1);
   // ---- leave the agent / wrapper state exactly where the per-step path leaves it
   __syncthreads();
   if (tid < O) ag.last_obs[(size_t)n * O + tid] = o_last;
-  if (tid == 0) {
+  if (tid == TAIL) {
     ag.last_dones[n] = (uint8_t)last_done_s;
     ag.raw_rew[n] = fin_rew; ag.dones[n] = (uint8_t)fin_done;
     if (has_cost) ag.raw_cost[n] = fin_cost;

@@ -1,5 +1,6 @@
-"""in-loop scratch traffic and LDS waits of an update kernel's ISA (tools/asm_dump.sh output):  python tools/loop_scratch.py kernel.s
-prints, for the optimiser-step loop (the depth-1 loop that holds the MFMAs), per barrier segment: the scratch loads / stores and v_accvgpr moves, the
+"""in-loop scratch traffic and LDS waits of an update kernel's ISA (tools/asm_dump.sh output):  python tools/loop_scratch.py kernel.s [--loop-by instr]
+prints, for the optimiser-step loop (the depth-1 loop that holds the MFMAs; --loop-by instr: the depth-1 loop with the most instructions, for kernels
+without MFMAs such as the persistent rollout, whose env-step loop it then finds), per barrier segment: the scratch loads / stores and v_accvgpr moves, the
 `s_waitcnt` with lgkmcnt(0), the ds_read and how many of them are EXPOSED — followed by a full lgkmcnt wait with fewer than EXPOSED_WINDOW non-LDS
 instructions in between, i.e. the wave sits out (most of) the LDS latency of that read"""
 import re, sys
@@ -44,8 +45,10 @@ def lds_wait_counts(seg, window=EXPOSED_WINDOW):
     return waits, reads, exposed
 
 
-def step_loop(L):
-    """(first line, last line, MFMAs, header line) of the depth-1 loop with the most MFMAs"""
+def step_loop(L, by="mfma"):
+    """(first line, last line, MFMAs, header line) of the depth-1 loop with the most MFMAs (by="instr": with the most instructions)"""
+    if by not in ("mfma", "instr"):
+        raise ValueError(f"--loop-by {by}: mfma or instr")
     best = None
     for h, l in enumerate(L):
         m = re.match(r"^\.(LBB\d+_\d+):\s*; =>This Loop Header: Depth=1", l)
@@ -60,9 +63,10 @@ def step_loop(L):
         while hi + 1 < len(L) and not re.match(r"^\.LBB\d+_\d+:", L[hi + 1]):
             hi += 1
         n = sum(1 for x in L[lo:hi] if "v_mfma" in x)
-        if best is None or n > best[2]:
-            best = (lo, hi, n, h)
-    return best
+        key = n if by == "mfma" else sum(1 for x in L[lo:hi] if is_instr(x))
+        if best is None or key > best[0]:
+            best = (key, lo, hi, n, h)
+    return best[1:] if best is not None else None
 
 
 def segments(L, h, hi):
@@ -70,9 +74,9 @@ def segments(L, h, hi):
     return list(zip(bars, bars[1:]))
 
 
-def main(path):
+def main(path, by="mfma"):
     L = open(path).read().split("\n")
-    lo, hi, n, h = step_loop(L)
+    lo, hi, n, h = step_loop(L, by)
     w, r, e = lds_wait_counts(L[lo:hi])
     print(f"loop lines {lo}..{hi} (header {h}): {hi - lo} lines, {n} MFMAs, scratch {sum('scratch_' in l for l in L[lo:hi])}, "
           f"instr {sum(is_instr(l) for l in L[lo:hi])}, lgkm0 {w}, ds_read {r}, exposed {e}")
@@ -82,8 +86,15 @@ def main(path):
         w, r, e = lds_wait_counts(seg)
         print(f"  [{a}-{b}] instr {ins} scratch_load {sum('scratch_load' in l for l in seg)} scratch_store {sum('scratch_store' in l for l in seg)} "
               f"accvgpr {sum('v_accvgpr' in l for l in seg)} ds {sum(chr(9) + 'ds_' in l for l in seg)} mfma {sum('v_mfma' in l for l in seg)} branches {sum('s_cbranch' in l for l in seg)} "
-              f"lgkm0 {w} ds_read {r} exposed {e}")
+              f"lgkm0 {w} ds_read {r} exposed {e}" +
+              (f" readlane {sum('v_readlane' in l for l in seg)} f64div {sum('v_div_fixup_f64' in l for l in seg)} barriers {sum('s_barrier' in l for l in seg)}" if by == "instr" else ""))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    args = sys.argv[1:]
+    by = "mfma"
+    if "--loop-by" in args:
+        i = args.index("--loop-by")
+        by = args[i + 1]
+        del args[i:i + 2]
+    main(args[0], by)

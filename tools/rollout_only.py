@@ -58,6 +58,14 @@ def run(kind, N, T, broken=False):
         tr = (np.array(list(tr), dtype=np.float64).reshape(N, 4) - min(tr)) / 100.0
         print("   one step, end of each wave's env-phase part, us after the first (min / median / max over workgroups): " +
               ", ".join(f"wave {k}: {tr[:, k].min():.2f} / {np.median(tr[:, k]):.2f} / {tr[:, k].max():.2f}" for k in range(4)))
+        # the step chain in finer pieces (thread 0 of workgroup 0; rollout_persistent_body's CH_* marks, behind the per-workgroup trace words)
+        CHAIN_BASE, chain_names = 4 * 128, ("policy forward", "hand-off barrier", "env step", "publish (record stores issued)", "log-prob + store", "poll",
+                                            "scatter + barrier", "running returns (+ barrier)", "column chains", "Chan merge", "normalise + barrier", "rest")
+        groups = (CHAIN_BASE + len(chain_names) + 1 + 3) // 4      # (the entry point copies four words per workgroup)
+        trc = (ctypes.c_ulonglong * (4 * groups))()
+        _lib.lib().icrl_debug_rollout_trace_wide(trc, groups)
+        ch = [trc[CHAIN_BASE + k] / Tn for k in range(len(chain_names) + 1)]
+        print("   chain, cycles/step: " + ", ".join(f"{v} {ch[k]:.0f}" for k, v in enumerate(chain_names)) + f"  (sum {sum(ch[:-1]):.0f}); publish issued {ch[-1]:.0f} cycles after the step's start")
         agent.profile_phases = 0
     if os.environ.get("PHASES_MULTI"):        # phase timers of the multi-env kernel (cycles per step; wave 0 and the cost wave)
         import ctypes
