@@ -34,13 +34,18 @@ G13_WIDTHS = dict(policy_net=(32, 48), value_net=(64, 32), cost_value_net=(16, 6
 # name -> obs_dim, act_dim, discrete, hidden.  "lgw": the LapGridWorld policy (icrl_amd/vec_env.py: KINDS["lgw"] = 1 observation, Discrete(2))
 POLICY_SHAPES = OrderedDict(hc=(18, 6, False, (64, 64)), ant=(113, 8, False, (64, 64)), point=(9, 2, False, (64, 64)), lgw=(1, 2, True, (64, 64)),
                             g13=(18, 6, False, G13_WIDTHS))
+# widths between hc and ant (tests/helpers/width_cases.py): the 16-column tile edges of the observation and both extremes of the action head
+WIDTH_SHAPES = ((1, 1), (17, 5), (32, 16), (33, 1), (64, 16), (65, 1), (128, 16))
+WIDTH_ROWS = (17, 100)
+POLICY_SHAPES.update((f"o{o}a{a}", (o, a, False, (64, 64))) for o, a in WIDTH_SHAPES)
 POLICY_ROWS = (1, 15, 16, 17, 64, 100, 257)             # the row-tile edge (16), a ragged last tile, more than one workgroup
 # past the grid cap of mlp_fwd_bwd_kernel (16-row tiles on min(tiles, 64) workgroups; weight gradients stay in registers across a workgroup's
 # tiles): 1025 rows = 65 tiles, workgroup 0 alone walks a second one, which holds one live row; 2064 rows = 129 tiles, workgroup 0 walks three,
 # the others two; 65536 rows = the served maximum, 64 tiles per workgroup
 POLICY_ROWS_WALK = (1025, 2064)
 POLICY_CASES = ([(s, n) for s in ("hc", "ant", "point", "lgw") for n in POLICY_ROWS] + [("g13", 100)]
-                + [(s, n) for s in ("hc", "ant") for n in POLICY_ROWS_WALK] + [("lgw", 1025), ("hc", 65536)])
+                + [(s, n) for s in ("hc", "ant") for n in POLICY_ROWS_WALK] + [("lgw", 1025), ("hc", 65536)]
+                + [(f"o{o}a{a}", n) for o, a in WIDTH_SHAPES for n in WIDTH_ROWS])
 # name -> obs_dim, acs_dim, hidden, obs_select_dim, acs_select_dim.  "point": the Point fixture's selection (-cosd 0 1 -casd -1)
 COST_SHAPES = OrderedDict(h20=(18, 6, (20,), None, None), h64=(18, 6, (64, 64), None, None), ant=(113, 8, (40, 40), None, None),
                           point=(9, 2, (40, 40), (0, 1), (-1,)))
@@ -325,6 +330,20 @@ DEV32 = {
     'ant-2064': [0.000169, 0.000129, 4.1e-05, 9.37e-05, 3.44e-05, 8.19e-06, 3.14e-06, 1.2e-05, 2.98e-06, 1.21e-05, 3.63e-06, 1.24e-05, 3.19e-06, 0.000575, 0.00015, 2.29e-05, 1.16e-07, 1.8e-05, 8.86e-06],
     'lgw-1025': [2.04e-06, 2.55e-06, 1.18e-06, 1.24e-06, 2.43e-06, 3.72e-06, 2.12e-06, 2.54e-06, 3.59e-06, 3.74e-06, 2.55e-06, 1.62e-06, 4.87e-06, 4.1e-06, 7.4e-06, 6.65e-06, 5.42e-06, 5.69e-06],
     'hc-65536': [0.000845, 0.000307, 0.000191, 0.000253, 0.000101, 4.93e-05, 2.11e-05, 4.14e-05, 1.23e-05, 5.39e-05, 2.84e-05, 5.09e-05, 1.89e-05, 0.00121, 0.000262, 0.000571, 2.2e-05, 0.000448, 8.47e-06],
+    'o1a1-17': [3.08e-07, 3.59e-07, 3.72e-07, 1.06e-07, 1.89e-07, 6.8e-07, 7.23e-07, 1.28e-07, 4.47e-07, 4.38e-07, 3.72e-07, 8.97e-08, 1.42e-07, 7.99e-07, 5.14e-07, 6.78e-07, 1.01e-07, 4.47e-07, 3.41e-07],
+    'o1a1-100': [6.43e-06, 1.45e-06, 2.18e-06, 5.74e-07, 9.43e-07, 1.6e-06, 1.65e-06, 2.95e-07, 4.46e-07, 2.7e-06, 1.9e-06, 8.04e-07, 7.59e-07, 3.81e-06, 4.09e-06, 1.76e-06, 5.16e-08, 1.56e-06, 9.3e-07],
+    'o17a5-17': [6.23e-06, 3.62e-06, 2.16e-06, 2.16e-06, 2.15e-06, 9.06e-07, 5.99e-07, 3.54e-07, 2.98e-07, 9.45e-07, 3.83e-07, 4.51e-07, 1.54e-07, 7.62e-06, 5.6e-06, 1.14e-06, 2.7e-08, 8.95e-07, 2.12e-07],
+    'o17a5-100': [1.37e-05, 1.73e-05, 6.91e-06, 6.9e-06, 3.25e-06, 1.08e-06, 6.17e-07, 1.49e-06, 7.42e-07, 2.52e-06, 1.01e-06, 2.01e-06, 4.87e-07, 2.71e-05, 1.23e-05, 2.97e-06, 2.4e-07, 2.34e-06, 4.29e-07],
+    'o32a16-17': [5.36e-05, 3.08e-05, 1.35e-05, 7.85e-06, 6.23e-06, 7.61e-07, 3.85e-07, 4.34e-07, 2.16e-07, 7.56e-07, 3.7e-07, 3.04e-07, 3.81e-07, 3.79e-05, 1.94e-05, 1.28e-06, 5.08e-08, 1.1e-06, 5.69e-07],
+    'o32a16-100': [5.73e-05, 3.91e-05, 1.59e-05, 2.42e-05, 9.54e-06, 2.62e-06, 7.15e-07, 1.64e-06, 1.28e-06, 2.66e-06, 8.65e-07, 1.66e-06, 5.07e-07, 0.000129, 2e-05, 3.39e-06, 9.16e-07, 3.51e-06, 3.8e-07],
+    'o33a1-17': [5.32e-07, 1.59e-06, 5.14e-07, 8.22e-07, 6.87e-07, 5.81e-07, 2.44e-07, 5.21e-07, 3.19e-07, 4.14e-07, 2.29e-07, 2.52e-07, 2.77e-07, 4.05e-06, 1.42e-06, 1.66e-06, 3.43e-07, 8.21e-07, 5.59e-08],
+    'o33a1-100': [8.56e-07, 2.75e-06, 1.04e-06, 1.71e-06, 1.64e-06, 2.09e-06, 8.08e-07, 1.65e-06, 6.45e-07, 2.08e-06, 5.29e-07, 1.65e-06, 3.4e-07, 1.11e-05, 3.9e-06, 8.18e-06, 6.03e-07, 2.37e-06, 5.62e-07],
+    'o64a16-17': [2.3e-05, 9.42e-06, 4.25e-06, 8.28e-06, 3.8e-06, 7.36e-07, 3.22e-07, 4.68e-07, 1.45e-07, 7.36e-07, 4.13e-07, 5.22e-07, 4.03e-07, 2.77e-05, 6.88e-06, 8.68e-07, 1.49e-08, 1.56e-06, 1.73e-07],
+    'o64a16-100': [4.47e-05, 4.08e-05, 1.39e-05, 3.12e-05, 1.4e-05, 1.84e-06, 8.67e-07, 1.68e-06, 8.66e-07, 1.53e-06, 7.18e-07, 2.08e-06, 4.36e-07, 7.36e-05, 3.57e-05, 3.32e-06, 6.22e-07, 3.13e-06, 1.55e-06],
+    'o65a1-17': [5.18e-07, 1.51e-06, 3.34e-07, 8.09e-07, 5.41e-07, 4.99e-07, 3.25e-07, 3.58e-07, 3.52e-07, 7.32e-07, 3.09e-07, 6.46e-07, 3.22e-07, 2.64e-06, 1.11e-06, 1.62e-06, 5.96e-08, 1.16e-06, 3.99e-07],
+    'o65a1-100': [5.07e-06, 3.44e-06, 1.43e-06, 2.22e-06, 1.22e-06, 1.86e-06, 1.33e-06, 1.73e-06, 7.14e-07, 2.04e-06, 8.97e-07, 1.05e-06, 7.92e-07, 1.5e-05, 5.3e-06, 4.39e-06, 2.14e-07, 3.46e-06, 9.46e-07],
+    'o128a16-17': [1.8e-05, 1.34e-05, 7.27e-06, 9.63e-06, 5.12e-06, 6.14e-07, 3.71e-07, 4.67e-07, 4.14e-07, 1.67e-06, 8.45e-07, 1.04e-06, 2.68e-07, 3.59e-05, 1.72e-05, 1.28e-06, 4.37e-07, 1.94e-06, 5.96e-08],
+    'o128a16-100': [4.62e-05, 3.62e-05, 1.6e-05, 2.9e-05, 1.6e-05, 2.24e-06, 6.8e-07, 2.1e-06, 9.24e-07, 1.73e-06, 7.6e-07, 1.4e-06, 7.27e-07, 9.96e-05, 4.74e-05, 5.67e-06, 2.38e-07, 4.13e-06, 4.8e-07],
     'cost-h20-1': [3.22e-08, 5.11e-09, 8.86e-08, 1.7e-08],
     'cost-h20-63': [1.85e-07, 4.33e-08, 5.14e-07, 4.17e-09],
     'cost-h20-64': [1.74e-07, 3.19e-08, 9.02e-07, 3.99e-07],

@@ -80,22 +80,33 @@ BAND_SEEDS = {("hc", "wide", 8, 32, 64, 3): 4}      # (the default seed: ratio m
 STATE_BAND_SEEDS = {("hc", "", 8, 32, 64, 3, "shaped", "B"): 2, ("hc", "", 8, 32, 64, 3, "shaped", "E"): 5, ("hc", "wide", 8, 32, 64, 3, "shaped", "B"): 3,
                     ("hc", "", 8, 128, 512, 3, "shaped", "A"): 1, ("hc", "", 8, 128, 512, 3, "shaped", "B"): 4,
                     ("hc", "", 8, 32, 64, 2, "ref", "A"): 1}      # (the default seeds: a ratio margin below 1e-3 at one step)
+# ... and the widths of helpers/width_cases.py, keyed by (obs_dim, act_dim) in place of the name (tests/test_width_cases_cpu.py runs check_trace on each;
+# every one of them holds check_trace at its default seed).  97 x 3 at 4x30 B40: the seed under which the padded-norm counter-oracle of
+# width_cases.padded_norm_update moves a parameter by more than 10 bounds (12.3; the default seed: 5.1 — see PADDED_NORM there)
+STATE_BAND_SEEDS[((97, 3), "", 4, 30, 40, 2, "shaped", "A")] = 6
+
+
+def shape_of(kind):
+    """(obs_dim, act_dim, learning rate) of a case: "hc" / "ant", or (obs_dim, act_dim) — 3e-4 up to four 16-column observation tiles, 3e-5 above, as for hc / ant."""
+    od, ad = kind if isinstance(kind, tuple) else {"hc": (18, 6), "ant": (113, 8)}[kind]
+    return od, ad, (3e-4 if od <= 64 else 3e-5)
 
 
 def oracle_case(kind, shape, N, T, B, E, hset, sd0, oracle_kwargs=None, nu=None, state=None):
     """The banded buffer of one case, the permutations, and the oracle's float32 update on them — computed once per case and shared by
     every kernel family that runs it (nothing of it is modified afterwards).  state: the name of the policy state sd0 is in (part of the cache
     key and of the band seed's).  sd0: the agent's initial state dict (the same for every agent
-    of a case: seed 0); returns a dict with buf, perms, hp, lr, out (the train/* scalars), params (after the update), trace."""
+    of a case: seed 0); returns a dict with buf, perms, hp, lr, out (the train/* scalars), params and both Adam moments (after the update), trace.
+    kind: "hc" / "ant", or (obs_dim, act_dim): its draws come from seeds that include the width."""
     key = (kind, shape, N, T, B, E, hset, state)
     hit = _CASES.get(key)
     if hit is not None and hit["nu"] == nu and all(np.array_equal(hit["sd0"][k], _np(v)) for k, v in sd0.items()):
         return hit
     hp = hparams(hset)
-    od, ad = {"hc": (18, 6), "ant": (113, 8)}[kind]
-    lr = 3e-4 if kind == "hc" else 3e-5
-    rng = np.random.RandomState(N * T)                  # observations, advantages, returns, permutations: as test_train_vs_oracle draws them
-    seed = BAND_SEEDS.get((kind, shape, N, T, B, E), 7919 + N * T + B)
+    od, ad, lr = shape_of(kind)
+    width = 1009 * od + 100003 * ad if isinstance(kind, tuple) else 0
+    rng = np.random.RandomState(N * T + width)          # observations, advantages, returns, permutations: as test_train_vs_oracle draws them
+    seed = BAND_SEEDS.get((kind, shape, N, T, B, E), 7919 + N * T + B + width)
     brng = np.random.RandomState(seed if state is None else STATE_BAND_SEEDS.get((kind, shape, N, T, B, E, state, hset), seed))      # the bands
     op = o_nets.TwoCriticPolicy(od, ad, **(oracle_kwargs or {}))
     op.load_state_dict(sd0)
@@ -115,6 +126,8 @@ def oracle_case(kind, shape, N, T, B, E, hset, sd0, oracle_kwargs=None, nu=None,
     trace = []
     out = o_ppo.ppo_lag_train(op, opt, buf, perms, nu, batch_size=B, n_epochs=E, clip_range=0.2, target_kl=None, trace=trace, **hp)
     case = dict(sd0={k: _np(v).copy() for k, v in sd0.items()}, buf=buf, perms=perms, hp=hp, lr=lr, nu=nu, out=out, trace=trace,
-                params={k: p.detach().numpy().copy() for k, p in op.params.items()})
+                params={k: p.detach().numpy().copy() for k, p in op.params.items()},
+                exp_avg={k: opt.state[p]["exp_avg"].numpy().copy() for k, p in op.params.items()},
+                exp_avg_sq={k: opt.state[p]["exp_avg_sq"].numpy().copy() for k, p in op.params.items()})
     _CASES[key] = case
     return case

@@ -15,6 +15,11 @@ SHAPES = {
     "lgw-b160": (1, 2, 1, 1, 41, 8, 160, 2),
     "lgw-35": (1, 2, 1, 1, 7, 5, 64, 2),
 }
+# continuous widths away from HalfCheetah's (tests/helpers/width_cases.py): one column past the first observation tile with an odd record
+# length (17 + 5 + 7), the last width of two tiles with a one-float action (31 + 1 + 7), both tiles and every head position full (32 + 16 + 7)
+for _o, _a in ((17, 5), (31, 1), (32, 16)):
+    SHAPES[f"o{_o}a{_a}-b40"] = (_o, _a, _a, 0, 16, 8, 40, 2)
+    SHAPES[f"o{_o}a{_a}-b160"] = (_o, _a, _a, 0, 41, 8, 160, 2)
 PLANES = ("log_probs", "reward_advantages", "cost_advantages", "reward_values", "reward_returns", "cost_values", "cost_returns")
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import routes
+from helpers import routes, width_cases
 from oracle import loop as o_loop, nets as o_nets, ppo as o_ppo
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +98,10 @@ def test_learn_matches_reference_golden(golden):
                                                   # the Categorical branch of the generic-shape path (csrc/generic.hip): layers above 64 / a 320-row batch
                                                   (18, 5, 8, 32, 64, 3, 0.01, True), (1, 2, 8, 80, 320, 2, 0.02, False),
                                                   # ... and of a policy with a shared trunk / other depths (icrl_policy_t.arch)
-                                                  (18, 5, 8, 32, 64, 3, 0.01, "trunk"), (7, 3, 4, 50, 100, 2, 0.03, "deep")])
+                                                  (18, 5, 8, 32, 64, 3, 0.01, "trunk"), (7, 3, 4, 50, 100, 2, 0.03, "deep")]
+                                                 # obs 64 on the wave pairs with four observation tiles; obs 80: the four-workgroup kernel chunk by chunk (40-row
+                                                 # minibatches).  Both chunks in one pass (kind 7) has no Categorical case: that instantiation faulted
+                                                 + width_cases.CATEGORICAL)
 def test_categorical_update_vs_oracle(O, A, N, T, B, E, ent, wide):
     """the Categorical branch of the update kernel at other widths (up to 16 classes) against the oracle epoch loop."""
     _categorical_case(O, A, N, T, B, E, ent, wide)
@@ -177,9 +180,11 @@ def _categorical_case(O, A, N, T, B, E, ent, wide, hset=None, head_scale=None, t
         H.check_trace(trace, dict(hp, ent_coef=ent), n_steps=E * (-(-N * T // B)))
     agent.train(perms=perms)
     # which update ran: the generic-shape path as one persistent launch for layers above 64 / an `arch` / more than 256 rows (three launches
-    # per step under ICRL_GEN_LAUNCHES), else wave quads with four workgroups per network up to 32 observations, wave pairs up to 64 —
+    # per step under ICRL_GEN_LAUNCHES), else wave quads with four workgroups per network up to 32 observations, wave pairs up to 64, above that
+    # four workgroups per network: both chunks in one pass for minibatches of 65..128 rows, chunk by chunk otherwise —
     # or the column-split tiles kernel where the case asks for it
-    want = (9 if os.environ.get("ICRL_GEN_LAUNCHES") else 8) if (wide or B > 256) else (3 if train_kernel == "tiles" else (5 if O <= 32 else 0))
+    fast = 5 if O <= 32 else (0 if O <= 64 else (7 if 64 < B <= 128 else 6))
+    want = (9 if os.environ.get("ICRL_GEN_LAUNCHES") else 8) if (wide or B > 256) else (3 if train_kernel == "tiles" else fast)
     routes.check_update(dict(kind=want, n_runs=1), f"categorical obs {O} B {B} wide {wide}")
     lg = logger.Logger.CURRENT.name_to_value
     n_steps = agent.policy.adam_step
