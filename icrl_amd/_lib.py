@@ -82,7 +82,7 @@ SIGNATURES = {
     # the gSDE agent's update as one persistent launch (csrc/ppo_train_sde.hip, kernel in csrc/ppo_train_tiles.hip; ppo_lag.py _train_sde)
     "icrl_ppo_lag_train_sde_ws_bytes": [c_void_p] * 3,
     "icrl_ppo_lag_train_sde": [c_void_p] * 11,
-    # the gSDE agent's rollout in the library (csrc/rollout.hip; ppo_lag.py sde_fused_rollout): expl, n_draws, sample_freq in the noise's place
+    # the gSDE agent's rollout in the library (csrc/rollout_collect.hip; ppo_lag.py sde_fused_rollout): expl, n_draws, sample_freq in the noise's place
     "icrl_rollout_collect_sde": [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 2 + [c_double] * 4 + [c_int, c_void_p],
     # sampling / evaluation episodes of a gSDE agent as one launch (utils.EpisodeRun)
     "icrl_sample_episodes_sde": [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 6,

@@ -215,7 +215,7 @@ class PPOLagrangian:
             return None
         # (a policy / constraint net of the generic-shape path — layers above 64 units, shared trunk, other depths — takes the same entry
         # point; the library then runs the rollout as one persistent launch around the table-driven forward — or, for a constraint net beyond
-        # two layers of 64 units, the reference's per-step loop as four launches per step —, csrc/rollout.hip)
+        # two layers of 64 units, the reference's per-step loop as four launches per step —, csrc/rollout_collect.hip)
         cw = env.venv
         if isinstance(cw, HipSynthVecEnv):           # no cost wrapper in the chain (the GAIL baseline, icrl/gail.py:50-59): costs are 0
             return env, None, cw
@@ -294,7 +294,7 @@ class PPOLagrangian:
     def _fused_rollout_ok(self, cost_function, n_rollout_steps, rollout_buffer):
         return self._fused_chain() is not None and isinstance(cost_function, str) and n_rollout_steps == rollout_buffer.buffer_size
 
-    # ---- the gSDE rollout as a launch of the library (sde_fused_rollout; csrc/rollout.hip: icrl_rollout_collect_sde) ------------------------
+    # ---- the gSDE rollout as a launch of the library (sde_fused_rollout; csrc/rollout_collect.hip: icrl_rollout_collect_sde) ------------------------
     def sde_schedule_bytes(self, n_rollout_steps):
         """device bytes of one rollout's exploration matrices, [draws, n_envs, 64, A] float32."""
         draws = ActorTwoCriticsPolicy.noise_schedule_draws(n_rollout_steps, self.sde_sample_freq)
@@ -450,7 +450,7 @@ class PPOLagrangian:
         cn = cw.constraint_net() if cw is not None else None      # (None for an AnalyticCost: it has no shape limits of its own)
         if cn is None and cw is not None and cw.discriminator_cost() is not None:
             cn = cw.discriminator_cost().disc                    # (a DiscriminatorCost: its net, under a constraint net's limits)
-        # the limits icrl_host_step checks (csrc/rollout.hip: dims_ok / cn_ok — obs <= MAX_OBS 128, act <= MAX_ACT 16, hidden <= MAX_H 64
+        # the limits icrl_host_step checks (csrc/rollout_launch.h: dims_ok / cn_ok — obs <= MAX_OBS 128, act <= MAX_ACT 16, hidden <= MAX_H 64
         # (`wide`), cost-net inputs <= MAX_CN_IN 160 — and N <= 128); other shapes take the per-step loop
         pol_ok = not self.policy.wide and self.policy.obs_dim <= 128 and self.policy.act_dim <= 16
         cn_ok = cn is None or (not cn.wide and cn.input_dims <= 160 and cn.obs_dim <= 128 and cn.acs_dim <= 16)

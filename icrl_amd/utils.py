@@ -383,7 +383,7 @@ def _host_episode_chain(env):
 def host_episodes_ok(agent, env):
     """what icrl_host_episode_step serves: one host env under VecNormalize[WithCost] and an optional VecCostWrapper without a cost
     function or with a ConstraintNet's, an AnalyticCost's, a DiscriminatorCost's or a RegionCost's (no side effects, and episodes never read a cost, so it is skipped; an arbitrary Python callable may have
-    side effects and keeps being called: the per-step loop), and a policy of the one-workgroup-per-env kernels (csrc/rollout.hip
+    side effects and keeps being called: the per-step loop), and a policy of the one-workgroup-per-env kernels (csrc/rollout_launch.h
     dims_ok: not `wide`, obs <= MAX_OBS 128, act <= MAX_ACT 16).  ICRL_HOST_EPISODES_STEPPED=1 forces the per-step loop."""
     if os.environ.get("ICRL_HOST_EPISODES_STEPPED", "0") not in ("", "0"):
         return False

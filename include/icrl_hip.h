@@ -353,7 +353,7 @@ int icrl_policy_forward(const icrl_policy_t* pol, const double* obs, const float
 /* same, with options in `do_gae`: bit 0 = run the final dual-GAE launch (0: the caller launches icrl_gae_dual itself, e.g.
  * bracketed by events); bit 1 = force one launch pair per env step; bit 2 = diagnostic phase timers.  By default ALL T steps run in ONE persistent launch
  * where one of the kernels serves the shape — which one, in which order, and what is left to the launch pair per step (AntWall with
- * 37..114 envs, for one) is stated once, in the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip; icrl_debug_last_route reports
+ * 37..114 envs, for one) is stated once, in the comment above icrl_rollout_collect_ex_mon in csrc/rollout_collect.hip; icrl_debug_last_route reports
  * what a call took.  Up to 96 envs with N * obs_dim <= 4096 (128 envs with frozen statistics) that is one workgroup per env, one
  * device-wide barrier per step, normaliser statistics replicated bit-identically in every workgroup; its exchange scratch is
  * icrl_agent_t.xch_ws, or the not yet computed reward_advantages plane of the buffer when xch_ws is absent or too small. */
@@ -608,7 +608,7 @@ int icrl_ppo_generic_row_floats(const icrl_policy_t* pol);
 #define ICRL_BATCH_ARGS_BYTES 1024
 
 /* icrl_rollout_collect_ex for n_runs runs: ONE persistent launch + ONE batched dual-GAE launch (do_gae bit 0).  Two batched forms, in
- * the order the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip states: the multi-env kernel (several envs per workgroup) and
+ * the order the comment above icrl_rollout_collect_ex_mon in csrc/rollout_collect.hip states: the multi-env kernel (several envs per workgroup) and
  * the one-workgroup-per-env kernel, grid (n_envs, n_runs) (n_envs <= 128, n_envs x obs_dim <= 4096: BASELINE configs[1]); every run
  * needs its exchange workspace (icrl_agent_t.xch_ws) or T * N * 4 >= ICRL_ROLLOUT_WS_BYTES.
  * args_ws: 2 x n_runs x ICRL_BATCH_ARGS_BYTES (rollout + GAE argument blocks). */
@@ -757,7 +757,7 @@ int icrl_cn_train(const icrl_costnet_t* cn, float* exp_avg, float* exp_avg_sq, i
 
 /* Diagnostic: which kernels the calling host thread's last call of a fused family launched.  The entry points below choose among several
  * launch forms by shape, workspace and device (the single statement of the rollout's order is the comment above
- * icrl_rollout_collect_ex_mon in csrc/rollout.hip; prepare_train in csrc/ppo_train.hip and icrl_gae_dual_ws in csrc/gae.hip for the
+ * icrl_rollout_collect_ex_mon in csrc/rollout_collect.hip; prepare_train in csrc/ppo_train.hip and icrl_gae_dual_ws in csrc/gae.hip for the
  * other two) and step to the next form silently; this says which one ran.  Host state only, thread-local like icrl_last_error():
  * a call clears its family's record on entry and writes it behind its launch, so a call refused before any launch leaves route 0.
  * out8 receives 8 int32 (unused words 0).  Returns 0; a family outside 0..2 or a NULL out8 is refused with a message.
@@ -925,7 +925,7 @@ int icrl_policy_fwd_bwd(const icrl_policy_t* pol, const float* obs, const float*
 int icrl_policy_forward_sde(const icrl_policy_t* pol, const double* obs, const float* expl, long long expl_stride, int N, int deterministic,
                             const float* action_low, const float* action_high, float* actions, float* act_clipped, float* v_r, float* v_c,
                             float* log_prob, void* stream);
-/* The rollout of a gSDE agent in the library (csrc/rollout.hip): icrl_rollout_collect_ex for a policy with the state-dependent-noise head.
+/* The rollout of a gSDE agent in the library (csrc/rollout_collect.hip): icrl_rollout_collect_ex for a policy with the state-dependent-noise head.
  * The exploration matrices a rollout uses are known before its first step — one draw at the start, one every sample_freq steps — so the
  * caller draws them up front, in the per-step loop's order (ActorTwoCriticsPolicy.noise_schedule), and the kernels compute what that loop
  * computes around icrl_policy_forward_sde: per step the forward of the network, then the head in float64 on the float32 latent (the

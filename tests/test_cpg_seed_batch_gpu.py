@@ -126,7 +126,7 @@ def test_batched_analytic_rollouts_equal_single_run_ones(kind, N, T, costs, mon)
     call on twin chains: all 16 buffer planes, the running moments, returns, last observations / dones, env state and the agent carry are
     equal bit for bit, and the first rollout's costs equal the numpy closed form on the rollout's own buffer.
 
-    Kernels the batched call launches on an MI355X (256 CUs), as the dispatch of rollout_collect_batch_impl (csrc/rollout.hip) selects them
+    Kernels the batched call launches on an MI355X (256 CUs), as the dispatch of rollout_collect_batch_impl (csrc/rollout_collect.hip) selects them
     (`mon` adds the template argument MON = true); the selection is asserted behind every batched call from the library's own record of it
     (icrl_debug_last_route: _BATCH_ROUTES, with `few` = runs x envs within the device's compute units).
       hc-7x33-S3     rollout_persistent_batch_analytic_kernel<2, true, 1>     one workgroup per env, OCT 2, granule exchange, ragged count

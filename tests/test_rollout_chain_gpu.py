@@ -156,3 +156,42 @@ def test_antwall_width_chain_equals_per_step_launches():
 def test_profiled_chain_equals_the_production_chain():
     N, T = 33, 28
     _compare(_cn_pair("hc", N, T), T, N, _ONE, f"hc {N} prof", steps_side="auto", prof=True)
+
+
+# ---- the phase-timer words are read from the kernel family that ran last ----
+def _timer_words(entry, n, *args):
+    import ctypes
+    from icrl_amd import _lib
+    out = (ctypes.c_ulonglong * n)()
+    _lib.check(getattr(_lib.lib(), entry)(out, *args), entry)
+    return list(out)
+
+
+def test_phase_timers_are_read_from_the_family_that_ran_last():
+    """Three profiled rollouts in one process, one per kernel family that writes timer words (g_rollout_prof, g_rollout_prof_wide and
+    g_wide_trace of csrc/rollout.hip; no other test reads the icrl_debug_rollout_* entry points, the tools only print them): behind each,
+    the step count among the words is this call's T — the three T differ, so the words of an earlier call cannot pass — and the timers
+    beside it have run.  The trace check is the weakest: its first word is only known to be non-zero once a profiled family has run."""
+    torch.cuda.synchronize()
+    for kernel, N, T, route, entry, t_words in (("auto", 4, 6, "persistent", "icrl_debug_rollout_profile", (3,)),
+                                                ("wide", 24, 7, "wide", "icrl_debug_rollout_profile_wide", (5, 13)),
+                                                ("multi", 24, 9, "multi", "icrl_debug_rollout_profile_wide", (5, 13))):
+        (agent, env), _ = _cn_pair("hc", N, T)
+        agent.rollout_kernel, agent.profile_phases = kernel, 1
+        agent._setup_learn(N * T)
+        agent.collect_rollouts(env, None, agent.rollout_buffer, T, "cost", noise=_noise(agent, T, N, 1)[0])
+        got = routes.check_rollout(dict(route=route, n_runs=1, launches=1), f"profiled {kernel}")
+        if route == "multi":
+            assert got["envs_per_wg"] == 4 and got["wgs"] == 6, got
+        torch.cuda.synchronize()
+        agent.check_rollout_status()
+        words = _timer_words(entry, 8 if route == "persistent" else 16)
+        print(f"[timers] {kernel} N={N} T={T}: {words}")
+        for w in t_words:
+            assert words[w] == T, (kernel, w, words)
+            block = words[:3] + words[4:7] if route == "persistent" else words[w - 5:w]
+            assert any(block), (kernel, w, words)
+        if route != "multi":
+            trace = _timer_words("icrl_debug_rollout_trace_wide", 4 * N, N)
+            print(f"[timers] {kernel} trace: {trace[:8]}")
+            assert trace[0] != 0, (kernel, trace[:8])

@@ -325,7 +325,7 @@ def test_generic_shape_rollout_equals_python_loop(kind, shape, N, norm_kwargs=No
     """policies / constraint nets of the generic-shape path (layers above 64 units, shared trunk, other depths): icrl_rollout_collect runs the
     whole rollout as ONE persistent launch (rollout_generic_kernel: the one-workgroup-per-env loop around the table-driven forward with four
     units per lane) — or, for a constraint net beyond the register image, a policy the fast kernels serve, or more envs than granule mode
-    takes (envs x (2 obs + 4) > 3072: 33 Ant envs), the reference's per-step loop as four launches per step — (csrc/rollout.hip; which of
+    takes (envs x (2 obs + 4) > 3072: 33 Ant envs), the reference's per-step loop as four launches per step — (csrc/rollout_collect.hip; which of
     the two: _GENERIC_ROUTES) and must leave exactly what the Python loop over the fine-grained entry points leaves: every unit's value is
     the same chain of fused multiply-adds in the same order."""
     from helpers.arches import ARCHES
@@ -411,7 +411,7 @@ def test_analytic_env_cost_through_cost_wrapper():
 # per-GPU shards of BASELINE configs[3], [2] and [4].
 # ONE_LAUNCH_ROUTES: (kind, envs, rollout_kernel) -> what icrl_rollout_collect must have launched, for every case of this file and of the
 # files that call this test's body, with a training normaliser, a constraint net and Box actions.  A forced kernel that does not take a
-# shape leaves it to the next form in line (the order: the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip): `multi` needs
+# shape leaves it to the next form in line (the order: the comment above icrl_rollout_collect_ex_mon in csrc/rollout_collect.hip): `multi` needs
 # 4 envs per group of statistics owners (hc: 20 envs, ant: 116), `wide` obs + 2 workgroups (hc: 20, ant: 115).
 _HC_MULTI = {20: (4, 5), 37: (4, 10), 64: (8, 8), 128: (8, 16), 130: (8, 17), 300: (8, 38), 1000: (8, 125), 2048: (8, 256)}      # envs: (envs per workgroup, workgroups)
 ONE_LAUNCH_ROUTES = {**{("hc", n, "auto"): "persistent" for n in (7, 64)},

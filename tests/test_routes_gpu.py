@@ -1,5 +1,5 @@
 """GPU: the launch ladders at their edges.  Every fused entry point chooses among several launch forms by shape, workspace and device and
-steps to the next one silently (the rollout's order: the comment above icrl_rollout_collect_ex_mon in csrc/rollout.hip; the update's:
+steps to the next one silently (the rollout's order: the comment above icrl_rollout_collect_ex_mon in csrc/rollout_collect.hip; the update's:
 prepare_train in csrc/ppo_train.hip; the GAE's: icrl_gae_dual_ws in csrc/gae.hip).  Each case here sits on one side of a threshold, asserts
 what the call launched (icrl_debug_last_route through helpers/routes.py) and compares what it left, bit for bit, with the form on the
 other side: a ladder that moved would fail the route, a kernel that is wrong at the edge of its range the comparison.  Expectations that
@@ -141,7 +141,7 @@ def test_single_run_ladder_at_its_edges(case):
 
 # ---- 2. where the exchange workspace comes from -------------------------------------------------------------------------------------
 def _persist_ws_bytes(N, O):
-    """the one-workgroup-per-env kernel's workspace (include/icrl_hip.h, icrl_agent_t.xch_ws; csrc/rollout.hip persist_ws_carve):
+    """the one-workgroup-per-env kernel's workspace (include/icrl_hip.h, icrl_agent_t.xch_ws; csrc/rollout_collect.hip persist_ws_carve):
     xch_obs f64 [2][N][O] | xch_rew f64 [2][N] | xch_cost f32 [2][N] | xch_done u32 [2][N] | counters, to 1024 B with the padding |
     granule records u64 [2][N][2 O + 4] when N (2 O + 4) <= 256 x 12"""
     gran = N * (2 * O + 4) <= 256 * 12
