@@ -92,6 +92,10 @@ SIGNATURES = {
     "icrl_reg_mlp_ws_bytes": [ctypes.c_longlong] + [c_int] * 5,
     "icrl_reg_mlp_step": [c_void_p] * 7 + [ctypes.c_longlong] + [c_int] * 5 + [c_double] * 4 + [c_void_p] * 3 + [ctypes.c_longlong, c_void_p],
     "icrl_shape_advantages": [c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
+    # the cost-shaping callback's classifier step and its second pass (csrc/cost_shaping.hip; icrl_amd/exploration.py)
+    "icrl_cls_mlp_ws_bytes": [ctypes.c_longlong] + [c_int] * 4,
+    "icrl_cls_mlp_step": [c_void_p] * 7 + [ctypes.c_longlong] + [c_int] * 4 + [c_double] * 4 + [c_void_p] * 2 + [ctypes.c_longlong, c_void_p],
+    "icrl_cost_shaping_apply": [c_void_p] * 4 + [ctypes.c_longlong] + [c_int] * 4 + [c_void_p] * 3 + [ctypes.c_longlong, c_void_p],
     "icrl_cn_train_minibatch": [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_void_p],
     # batched forms (several independent runs in one launch, run = blockIdx.y): n_runs, jobs[n_runs], ..., args_ws, bytes, stream
@@ -109,7 +113,7 @@ SIGNATURES = {
     "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_ppo_lag_train_sde_ws_bytes": ctypes.c_size_t,"icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_ppo_lag_train_sde_ws_bytes": ctypes.c_size_t,"icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_cls_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

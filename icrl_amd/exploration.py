@@ -9,12 +9,17 @@ is one call of icrl_reg_mlp_step (csrc/reg_mlp.hip) on flat device buffers: it r
 (time-major rows, no concatenated copy), and `cost_advantages /= 1 + exploration_reward` is icrl_shape_advantages.  Each callback makes
 one device-to-host read of its scalar block per rollout end.  The networks are initialised exactly like the reference's: the torch
 modules are constructed once on the host, in the reference's order, and their tensors copied — the same draws from the global generator.
+
+The third callback of that file, CostShapingCallback (icrl/exploration.py:73-169, `gail -ucsc [-ucn]`, wired in at icrl/gail.py:128-135), is
+here too: its classifier (ClassifierNet: the same MLP with one output and a Sigmoid, BCE loss) is stepped by icrl_cls_mlp_step and read a
+second time, on the stepped parameters, by icrl_cost_shaping_apply (csrc/cost_shaping.hip).
 """
 import numpy as np
 import torch
 
 from . import _lib, callbacks, logger, spaces
 from ._lib import ptr as p
+from .structs import CostNetT, GailJobT, addr
 
 REFUSE_SEED_BATCH = ("{flag}: the exploration callbacks' networks are per-run and unbatched; a seed batch (--seeds with more than one seed) "
                      "does not take them (run the seeds one at a time)")
@@ -205,6 +210,168 @@ class LambdaShapingCallback(callbacks.BaseCallback):
         host = torch.cat([p4, c4]).cpu().numpy()
         rec = {"exploration/mean_exploration_reward": float(host[1]), "exploration/std_exploration_reward": float(host[2]),
                "exploration/predictor_network_loss": float(host[0]), "exploration/cost_network_loss": float(host[4])}
+        for k, v in rec.items():
+            logger.record(k, v)
+        self.history.append(rec)
+
+
+COST_SHAPING_FLAG = "--use_cost_shaping_callback (-ucsc)"
+
+
+def refuse_cost_shaping(config):
+    """raise, naming the flag, where `gail --use_cost_shaping_callback` is not served: several ranks and a gSDE agent.  Called before
+    anything is launched (gail.setup)."""
+    get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+    if not get("use_cost_shaping_callback", False):
+        return
+    if get("use_sde", False):
+        raise ValueError(REFUSE_SDE_CALLBACKS.format(flag=COST_SHAPING_FLAG))
+    if (get("world_size", 1) or 1) > 1:
+        raise ValueError(REFUSE_RANKS.format(flag=COST_SHAPING_FLAG))
+
+
+class ClassifierNet(RegressionNet):
+    """sigmoid(MLP(in_dim -> h1 -> ReLU -> h2 -> ReLU -> 1)) with its Adam state as flat device buffers: RegressionNet's construction (the
+    same Linear layers in the same order — the Sigmoid has no parameters — so the global generator gives the reference's initial weights)
+    and state_dict, stepped by icrl_cls_mlp_step (BCE loss) and read by icrl_cost_shaping_apply (csrc/cost_shaping.hip).  `out8` (device,
+    float64) holds {loss, mean(p), mean(target), 0} of the last step and {mean, min, max of shaped, 0} of the last apply."""
+
+    def __init__(self, in_dim, hidden_layers=(50, 50), lr=3e-3, device="cuda"):
+        super().__init__(in_dim, 1, hidden_layers, lr=lr, device=device)
+        self.out8 = torch.zeros(8, dtype=torch.float64, device=self.device)
+
+    def _workspace(self, rows, in_a, in_b):
+        h1, h2 = self.hidden_layers
+        L = _lib.lib()
+        need = int(L.icrl_cls_mlp_ws_bytes(rows, in_a, in_b, h1, h2))
+        if need == 0:
+            reason = L.icrl_last_error().decode()
+            L.icrl_clear_error()
+            raise NotImplementedError(reason)
+        if self._ws is None or self._ws.numel() * 8 < need:
+            self._ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=self.device)
+        return self._ws
+
+    def step(self, xa, xb, target):
+        """one classifier step on rows (float32(xa) | xb) -> target; returns the device block {loss, mean(p), mean(target), 0} (float64) of the
+        pre-step predictions.  xa [rows, in_a] float64 (None when in_a == 0), xb [rows, in_b] float32, target [rows] float32."""
+        rows = int(target.numel())
+        in_b = int(xb.numel() // rows)
+        in_a = self.in_dim - in_b
+        h1, h2 = self.hidden_layers
+        ws = self._workspace(rows, in_a, in_b)
+        out4 = self.out8[:4]
+        _lib.check(_lib.lib().icrl_cls_mlp_step(p(self.params), p(self.exp_avg), p(self.exp_avg_sq), p(self.adam_step), p(xa) if in_a > 0 else None, p(xb),
+                                                p(target), rows, in_a, in_b, h1, h2, self.lr, self.betas[0], self.betas[1], self.eps, p(out4), p(ws),
+                                                ws.numel() * 8, _lib.current_stream()), "icrl_cls_mlp_step")
+        return out4
+
+    def apply(self, xa, xb, target, rewards, use_nn=True):
+        """rewards += log(float32 prediction) of the parameters as they are (use_nn), or += log(1e-3) * target in float64 rounded once;
+        returns the device block {mean, min, max of the shaped cost, 0} (float64)."""
+        rows = int(rewards.numel())
+        in_b = int(xb.numel() // rows)
+        in_a = self.in_dim - in_b
+        h1, h2 = self.hidden_layers
+        ws = self._workspace(rows, in_a, in_b)
+        out4 = self.out8[4:]
+        _lib.check(_lib.lib().icrl_cost_shaping_apply(p(self.params) if use_nn else None, p(xa) if in_a > 0 else None, p(xb), p(target), rows, in_a, in_b,
+                                                      h1, h2, p(rewards), p(out4), p(ws), ws.numel() * 8, _lib.current_stream()),
+                   "icrl_cost_shaping_apply")
+        return out4
+
+
+def _check_cls_shapes(who, obs_dim, acs_dim, hidden):
+    hidden = list(hidden)
+    if len(hidden) != 2:
+        raise NotImplementedError(f"{who}: hidden layers {hidden} are not served (two hidden layers of 1..64 units each)")
+    L = _lib.lib()
+    if int(L.icrl_cls_mlp_ws_bytes(1, int(obs_dim), int(acs_dim), int(hidden[0]), int(hidden[1]))) == 0:
+        reason = L.icrl_last_error().decode()
+        L.icrl_clear_error()
+        raise NotImplementedError(f"{who}: {reason}")
+
+
+class CostShapingCallback(callbacks.BaseCallback):
+    """ref: icrl/exploration.py:73-169 (`gail -ucsc [-ucn]`, installed in the place of GailCallback) — a classifier learns the true cost
+    and its log-prediction shapes the rewards.  At every rollout end, in the reference's order:
+      1. raw observations: the buffer's plane un-normalised with the env's CURRENT statistics, float64 (icrl_gail_unnormalize_batch as a
+         batch of one: float64(obs) * sqrt(var + eps) + mean, product and sum rounded separately; unchanged with norm_obs off);
+      2. the STORED actions (not the clipped ones);
+      3. true costs of (raw observations, actions): an AnalyticCost / RegionCost through its rows kernel on the device, any other callable
+         on host copies.  The analytic torque cost compares the float32 action in the rows kernel where the reference compares its float64
+         copy: identical for every threshold of TRUE_COSTS (0.5 is exact in both formats);
+      4. ONE Adam step of the cost network on float32(raw observation | action) -> true cost, BCE loss (icrl_cls_mlp_step);
+      5. shaped = log(prediction of the STEPPED network) in float32, added to rollout_buffer.rewards (icrl_cost_shaping_apply);
+      6. CostShaping/{mean_true_cost, mean_shaped_cost, min_shaped_cost, max_shaped_cost, cost_network_loss (pre-step)}: ONE device-to-host
+         copy of the two scalar blocks.
+
+    Like the reference's, the callback runs after GAE: it changes the stored rewards, NOT the advantages / returns the update consumes, so by
+    default it has no effect on training.  `recompute_advantages=True` (library-only, no CLI flag) re-runs compute_returns_and_advantage on
+    the changed rewards with the rollout's last values and dones.
+
+    use_nn_for_shaping=False is the one place where this build does not reproduce the reference, because the reference has no behaviour to
+    reproduce: its `np.log(1e-3) * self.get_true_cost(self, obs, acs)` passes one argument too many and raises TypeError at the first
+    rollout end.  Served here is the evident intent: shaped = log(1e-3) * true cost in float64, added to the float32 plane in place (rounded
+    once); the network is still stepped and its loss logged."""
+
+    def __init__(self, true_cost_function, obs_dim, acs_dim, use_nn_for_shaping, cost_net_hidden_layers=[50, 50], device="cpu", verbose=1,
+                 recompute_advantages=False):
+        super().__init__(verbose)
+        self.true_cost_function = true_cost_function
+        self.obs_dim, self.acs_dim, self.use_nn, self.device = int(obs_dim), int(acs_dim), bool(use_nn_for_shaping), device
+        self.cost_net_hidden_layers = list(cost_net_hidden_layers)
+        self.recompute_advantages = bool(recompute_advantages)
+        _check_cls_shapes(f"CostShapingCallback ({COST_SHAPING_FLAG})", obs_dim, acs_dim, self.cost_net_hidden_layers)
+        self.cost_net = self.raw_observations = self.true_costs = self._args_ws = None
+        self.history = []
+
+    def _init_callback(self):
+        _require_box(f"CostShapingCallback ({COST_SHAPING_FLAG})", self.model)
+        self.cost_net = ClassifierNet(self.obs_dim + self.acs_dim, self.cost_net_hidden_layers, lr=3e-3, device=self.device)
+
+    def _unnormalize(self, rb, env):
+        """step 1: -> [T, N, obs] float64 on the device."""
+        norm = bool(getattr(env, "norm_obs", False))
+        rows = rb.buffer_size * rb.n_envs
+        raw = torch.empty(rb.buffer_size, rb.n_envs, self.obs_dim, dtype=torch.float64, device=rb.device)
+        if self._args_ws is None:
+            self._args_ws = torch.empty(_lib.BATCH_ARGS_BYTES, dtype=torch.uint8, device=rb.device)
+            self._cost_mean = torch.zeros(1, dtype=torch.float64, device=rb.device)
+        shape = CostNetT(obs_dim=self.obs_dim, acs_dim=self.acs_dim, in_dim=self.obs_dim + self.acs_dim, n_hidden=1, h1=1)      # read for its widths only
+        job = GailJobT(addr(shape), None, p(rb.observations), p(rb.actions), p(env.obs_rms.d_mean) if norm else None, p(env.obs_rms.d_var) if norm else None,
+                       float(getattr(env, "epsilon", 0.0)), p(raw), None, p(self._cost_mean), rows, 0)
+        _lib.check(_lib.lib().icrl_gail_unnormalize_batch(1, (GailJobT * 1)(job), p(self._args_ws), self._args_ws.numel(), _lib.current_stream()),
+                   "icrl_gail_unnormalize_batch")
+        return raw
+
+    def _true_costs(self, raw, actions):
+        """step 3: -> [rows] float32 on the device."""
+        from .true_constraint_net import AnalyticCost, RegionCost
+        tc = self.true_cost_function
+        if isinstance(tc, (AnalyticCost, RegionCost)):
+            c = tc(raw, actions)
+        else:
+            c = tc(raw.cpu().numpy(), actions.cpu().numpy().astype(float))
+            c = torch.as_tensor(np.asarray(c).astype(np.float32), device=raw.device)
+        c = c.to(torch.float32).reshape(-1).contiguous()
+        if c.numel() != raw.shape[0] * raw.shape[1]:
+            raise ValueError(f"CostShapingCallback: the true cost gave {c.numel()} values for {raw.shape[0] * raw.shape[1]} rows (the reference's "
+                             "null cost returns one per time step, and its callback fails at the loss in the same way)")
+        return c
+
+    def _on_rollout_end(self):
+        rb = self.model.rollout_buffer
+        raw = self.raw_observations = self._unnormalize(rb, self.training_env)
+        target = self.true_costs = self._true_costs(raw, rb.actions)
+        self.cost_net.step(raw, rb.actions, target)
+        self.cost_net.apply(raw, rb.actions, target, rb.rewards, use_nn=self.use_nn)
+        if self.recompute_advantages:
+            ag = self.model._ag
+            rb.compute_returns_and_advantage(ag["last_v_r"], ag["last_v_c"], ag["last_dones"])
+        host = self.cost_net.out8.cpu().numpy()
+        rec = {"CostShaping/mean_true_cost": float(host[2]), "CostShaping/mean_shaped_cost": float(host[4]), "CostShaping/min_shaped_cost": float(host[5]),
+               "CostShaping/max_shaped_cost": float(host[6]), "CostShaping/cost_network_loss": float(host[0])}
         for k, v in rec.items():
             logger.record(k, v)
         self.history.append(rec)

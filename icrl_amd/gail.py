@@ -42,14 +42,17 @@ class PPO(PPOLagrangian):
 
 
 def setup(config, log=print):
-    """everything of gail() up to the learn() call: (model, callback, discriminator, the GailCallback).  Two opt-ins, which a seed batch
+    """everything of gail() up to the learn() call: (model, callback, discriminator, the GailCallback — with --use_cost_shaping_callback
+    the exploration.CostShapingCallback that stands in its place).  Two opt-ins, which a seed batch
     sets and which are off by default so that a solo run's draws stay what they were: config.eval_noise_from_streams (evaluation noise
     from the run's own streams, as in cpg) and config.disc_perms_from_streams (the discriminator's permutation likewise)."""
     logger.configure()
     check_cost_spec_flags(config)
     rank = getattr(config, "rank", 0)
-    if getattr(config, "use_sde", False):      # -us over several ranks: refused before anything is launched
+    shaping = bool(getattr(config, "use_cost_shaping_callback", False))
+    if getattr(config, "use_sde", False) or shaping:      # -us / -ucsc over several ranks, the two together: refused before anything is launched
         from . import exploration
+        exploration.refuse_cost_shaping(config)
         exploration.refuse_sde(config)
     dev = config.device if str(config.device).startswith("cuda") else "cuda"
     envs.import_modules(getattr(config, "env_module", None))     # --env_module: modules that register host envs
@@ -80,9 +83,11 @@ def setup(config, log=print):
                                           clip_obs=config.clip_obs, action_low=action_low, action_high=action_high,
                                           num_spurious_features=config.num_spurious_features, freeze_weights=config.freeze_gail_weights,
                                           eps=config.disc_eps, device=dev)
-    if getattr(config, "use_cost_shaping_callback", False):
-        raise NotImplementedError("--use_cost_shaping_callback (a shaping ablation of the reference) is outside the hot path")
-    gail_update = GailCallback(discriminator, config.learn_cost, cost_for(config.eval_env_id, getattr(config, "cost_spec", None), train_env), config.save_dir)
+    true_cost = cost_for(config.eval_env_id, getattr(config, "cost_spec", None), train_env)
+    if shaping:      # ref: icrl/gail.py:128-135 — in the place of GailCallback; the discriminator above is built, never trained, and saved by finish()
+        gail_update = exploration.CostShapingCallback(true_cost, obs_dim, acs_dim, use_nn_for_shaping=bool(getattr(config, "use_cost_net", False)), device=dev)
+    else:
+        gail_update = GailCallback(discriminator, config.learn_cost, true_cost, config.save_dir)
     model = PPO(policy=config.policy_name, env=train_env, learning_rate=config.learning_rate, n_steps=config.n_steps,
                 batch_size=config.batch_size, n_epochs=config.n_epochs, gamma=config.reward_gamma, gae_lambda=config.reward_gae_lambda,
                 clip_range=config.clip_range, clip_range_vf=config.clip_range_reward_vf, ent_coef=config.ent_coef,

@@ -659,6 +659,14 @@ class VecNormalize(VecEnvWrapper):
         o = torch.as_tensor(obs, dtype=torch.float64, device=self.device)
         return torch.clamp((o - self.obs_rms.d_mean) / torch.sqrt(self.obs_rms.d_var + self.epsilon), -self.clip_obs, self.clip_obs)
 
+    def unnormalize_obs(self, obs):
+        """ref: vec_normalize.py:125-128, with the CURRENT statistics: float64(obs) * sqrt(var + eps) + mean, product and sum rounded
+        separately (the bits icrl_gail_unnormalize_batch gives)."""
+        if not self.norm_obs:
+            return obs
+        o = torch.as_tensor(obs, device=self.device).to(torch.float64)
+        return o * torch.sqrt(self.obs_rms.d_var + self.epsilon) + self.obs_rms.d_mean
+
     def get_original_obs(self):
         return self.old_obs.clone()
 

@@ -1035,6 +1035,39 @@ int icrl_reg_mlp_step(float* params, float* exp_avg, float* exp_avg_sq, int32_t*
  * a correctly rounded float32 division, bit for bit numpy's; rows >= 1. */
 int icrl_shape_advantages(float* adv, const float* row_err, long long rows, void* stream);
 
+/* One full-batch classifier step of sigmoid(MLP(in -> h1 -> ReLU -> h2 -> ReLU -> 1)), the reference's create_mlp(in, 1, [h1, h2]) + Sigmoid
+ * with BCELoss and Adam: the rollout-end step of CostShapingCallback (icrl/exploration.py:106-128; csrc/cost_shaping.hip).
+ * params / exp_avg / exp_avg_sq: flat float32 buffers of EXACTLY n_params = h1 (in + 1) + h2 (h1 + 1) + (h2 + 1) entries in torch's state_dict
+ * order, row-major, as in icrl_reg_mlp_step.  Inputs: xa [rows, in_a] FLOAT64 (the un-normalised observations; each value is rounded to
+ * float32 on the load, the reference's `.float()`; may be NULL when in_a == 0) and xb [rows, in_b] float32, read as ONE concatenated row;
+ * target [rows] float32.  Per call, on the parameters as they are:
+ *   p = sigmoid(MLP(x));  loss = mean_r -(y log p + (1 - y) log(1 - p)), each log clamped at -100 as torch's BCELoss does; backward of the
+ *   loss (dL/dz as torch forms it: (p - y) / max((1 - p) p, 1e-12) * (1 - p) p); one torch.optim.Adam step (bias corrections in double from
+ *   *adam_step + 1, which is then incremented on the device);
+ *   out4 (device, FLOAT64 [4]) = {loss, mean(p), mean(target), 0}, all from the PRE-step predictions.
+ * Arithmetic and structure as in icrl_reg_mlp_step: the forward pass (hidden layers on v_mfma_f64_16x16x4_f64, the one-unit head per row
+ * in unit order), the sigmoid, the logs and the row sums are float64 on the float32 parameters and inputs; the backward products of a
+ * 32-row group are float32 (v_mfma_f32_16x16x4_f32 tiles for the hidden layers, VALU products for the one-unit output layer) on the float32
+ * roundings; sums across groups, workgroups and biases are float64 in a fixed order, rounded once.  Plain launches, no cooperative launch,
+ * no waits between workgroups, no atomics; the grid is min(ceil(rows / 32), 256) workgroups: the same call from the same state gives the
+ * same bits.  Served: 1 <= h1, h2 <= 64, 0 <= in_a <= 128, 1 <= in_b <= 16, 1 <= rows <= 2^21.  Everything else, a NULL required pointer
+ * and a ws below icrl_cls_mlp_ws_bytes(...) (0 + a reason for a refused shape) return hipErrorInvalidValue with the reason, before any
+ * device call.  Allocates nothing, does not synchronise. */
+size_t icrl_cls_mlp_ws_bytes(long long rows, int in_a, int in_b, int h1, int h2);
+int icrl_cls_mlp_step(float* params, float* exp_avg, float* exp_avg_sq, int32_t* adam_step, const double* xa, const float* xb,
+                      const float* target, long long rows, int in_a, int in_b, int h1, int h2, double lr, double beta1, double beta2,
+                      double eps, double* out4, void* ws, long long ws_bytes, void* stream);
+/* The shaped cost of CostShapingCallback onto the rewards plane (icrl/exploration.py:142-162).  rewards [rows] float32, in / out.
+ * With params (the ALREADY STEPPED network, same layout and inputs as above; target unused): shaped[r] = log(float32(p[r])), the float32 log
+ * of the float32-rounded prediction as numpy takes it (-inf where that prediction is 0), and rewards[r] += shaped[r], a float32 add.
+ * With params == NULL (xa, xb unused; target required): shaped[r] = log(1e-3) * target[r] in float64 and
+ * rewards[r] = float32(float64(rewards[r]) + shaped[r]), rounded once.
+ * out4 (device, FLOAT64 [4]) = {mean, min, max of shaped, 0}: min and max exact; the mean a float64 sum in fixed order over n — without
+ * params it is formed as log(1e-3) * (sum of target / rows), so that it equals log(1e-3) * mean(target) to the bit.
+ * ws: at least 8192 bytes (icrl_cls_mlp_ws_bytes(...) always suffices).  Shapes, refusals and determinism as above. */
+int icrl_cost_shaping_apply(const float* params, const double* xa, const float* xb, const float* target, long long rows, int in_a, int in_b,
+                            int h1, int h2, float* rewards, double* out4, void* ws, long long ws_bytes, void* stream);
+
 /* Diagnostic (bench.py `roofline.copy_gbs`; no reference counterpart): the memory traffic of the streaming dual-GAE launch without
  * its recurrence.  mode 0: grid, access pattern and bytes of icrl_gae_dual at N >= 131 072 (five [T,N] float arrays read, four written,
  * 16-byte non-temporal accesses, one wave per 256 columns walking the rows downwards); mode 1: in0..in3 copied to out0..out3 by

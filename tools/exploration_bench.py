@@ -9,7 +9,12 @@
    planes, torch.cat of observations and actions, MSELoss, backward, Adam, the division, one scalar read;
 3. `cpg -tei HCWithPos-v0 -eei HCWithPosTest-v0 -nt 64 --n_steps 2048 -uls` against the same command without the flag, env-steps/s of
    learn() after one warm-up learn() in the same process.
-Medians over --reps repetitions after 5 warm-up calls; one JSON line per measurement."""
+Medians over --reps repetitions after 5 warm-up calls; one JSON line per measurement.
+
+    python tools/exploration_bench.py --cost_shaping [--reps 30]
+
+the rollout end of CostShapingCallback (`gail -ucsc -ucn`) at the same two shapes, kernels against the same callback written as torch modules
+on the device, three interleaved runs per form; results go to profiles/cost_shaping.md."""
 import argparse
 import json
 import os
@@ -92,6 +97,55 @@ def bench_callbacks(reps):
                               speedup_wall=theirs["wall_us_median"] / ours["wall_us_median"])), flush=True)
 
 
+class TorchCostShaping:
+    """the reference's CostShapingCallback._on_rollout_end (use_nn_for_shaping=True) as torch modules on the device, a wall cost on column 0."""
+
+    def __init__(self, obs, act, threshold, hidden=(50, 50)):
+        dims = [obs + act] + list(hidden) + [1]
+        mods = []
+        for k in range(3):
+            mods += [torch.nn.Linear(dims[k], dims[k + 1])] + ([torch.nn.ReLU()] if k < 2 else [])
+        self.net = torch.nn.Sequential(*mods, torch.nn.Sigmoid()).cuda()
+        self.opt, self.threshold = torch.optim.Adam(self.net.parameters(), lr=3e-3), threshold
+
+    def rollout_end(self, rb, env):
+        T, N = rb.buffer_size, rb.n_envs
+        raw = rb.observations.double() * torch.sqrt(env.obs_rms.d_var + env.epsilon) + env.obs_rms.d_mean
+        true = (raw[..., 0] <= self.threshold).double()
+        x = torch.cat((raw.reshape(T * N, -1), rb.actions.double().reshape(T * N, -1)), dim=-1).float()
+        loss = torch.nn.functional.binary_cross_entropy(self.net(x), true.reshape(-1, 1).float())
+        self.opt.zero_grad(); loss.backward(); self.opt.step()
+        with torch.no_grad():
+            shaped = torch.log(self.net(x)).view(T, N)
+        rb.rewards += shaped
+        return torch.stack([true.mean(), shaped.mean().double(), shaped.min().double(), shaped.max().double(), loss.detach().double()]).cpu()
+
+
+def bench_cost_shaping(reps, runs=3):
+    """us per rollout end of CostShapingCallback (-ucsc -ucn), kernels against torch modules: `runs` interleaved runs per form (kernels,
+    torch, kernels, torch, ...), each the median over `reps` calls after 5 warm-up calls; the figure of a form is the median of its runs."""
+    from icrl_amd import logger
+    from icrl_amd.exploration import CostShapingCallback
+    from icrl_amd.true_constraint_net import AnalyticCost
+    for T, N, obs, act in SHAPES:
+        logger.configure()
+        model = _model(T, N, obs, act)
+        rms = types.SimpleNamespace(d_mean=torch.zeros(obs, dtype=torch.float64, device="cuda"), d_var=torch.ones(obs, dtype=torch.float64, device="cuda"))
+        model.env.norm_obs, model.env.obs_rms, model.env.epsilon = True, rms, 1e-8
+        cb = CostShapingCallback(AnalyticCost.wall_behind(-0.5), obs, act, True, device="cuda")
+        cb.init_callback(model)
+        ref = TorchCostShaping(obs, act, -0.5)
+        forms = dict(kernels=cb.on_rollout_end, torch_modules=lambda: ref.rollout_end(model.rollout_buffer, model.env))
+        got = {k: [] for k in forms}
+        for _ in range(runs):
+            for k, fn in forms.items():
+                model.rollout_buffer.rewards.zero_()
+                got[k].append(_time(fn, reps))
+        wall = {k: statistics.median(r["wall_us_median"] for r in v) for k, v in got.items()}
+        print(json.dumps(dict(what="cost_shaping_rollout_end", T=T, N=N, obs=obs, act=act, rows=T * N, runs=got, wall_us=wall,
+                              speedup_wall=wall["torch_modules"] / wall["kernels"])), flush=True)
+
+
 def bench_cpg(rollouts):
     from icrl_amd import cpg as C
     out = {}
@@ -117,7 +171,11 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--rollouts", type=int, default=6)
     ap.add_argument("--skip_cpg", action="store_true")
+    ap.add_argument("--cost_shaping", action="store_true", help="the cost-shaping callback only (profiles/cost_shaping.md)")
     args = ap.parse_args()
+    if args.cost_shaping:
+        bench_cost_shaping(args.reps)
+        return
     bench_callbacks(args.reps)
     if not args.skip_cpg:
         bench_cpg(args.rollouts)
