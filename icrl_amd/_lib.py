@@ -75,6 +75,12 @@ SIGNATURES = {
     "icrl_policy_fwd_bwd": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10 + [ctypes.c_longlong, c_void_p],
     "icrl_cost_mlp_fwd_bwd_ws_bytes": [c_void_p, c_int],
     "icrl_cost_mlp_fwd_bwd": [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [ctypes.c_longlong, c_void_p],
+    # the same with the gradients of the inputs (d_obs, d_actions / d_x before ws), and the chain rule through icrl_cn_prepare
+    "icrl_policy_fwd_bwd_in_ws_bytes": [c_void_p, c_int],
+    "icrl_policy_fwd_bwd_in": [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 12 + [ctypes.c_longlong, c_void_p],
+    "icrl_cost_mlp_fwd_bwd_in_ws_bytes": [c_void_p, c_int],
+    "icrl_cost_mlp_fwd_bwd_in": [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [ctypes.c_longlong, c_void_p],
+    "icrl_cn_prepare_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     # the gSDE forms of icrl_policy_forward / icrl_policy_fwd_bwd (csrc/sde.hip; policies.py use_sde)
     "icrl_policy_forward_sde": [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int] + [c_void_p] * 8,
     "icrl_policy_sde_fwd_bwd_ws_bytes": [c_void_p, c_int],
@@ -113,7 +119,7 @@ SIGNATURES = {
     "icrl_gail_relabel_batch": [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
 }
 BATCH_ARGS_BYTES = 1024      # ICRL_BATCH_ARGS_BYTES
-RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_ppo_lag_train_sde_ws_bytes": ctypes.c_size_t,"icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_cls_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
+RESTYPES = {"icrl_ppo_stream_ws_bytes": ctypes.c_size_t, "icrl_ppo_lag_train_sde_ws_bytes": ctypes.c_size_t,"icrl_reg_mlp_ws_bytes": ctypes.c_size_t, "icrl_cls_mlp_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_sde_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_ws_bytes": ctypes.c_size_t, "icrl_policy_fwd_bwd_in_ws_bytes": ctypes.c_size_t, "icrl_cost_mlp_fwd_bwd_in_ws_bytes": ctypes.c_size_t,"icrl_cn_train_work_floats": ctypes.c_size_t, "icrl_monitor_ws_bytes": ctypes.c_size_t, "icrl_host_step_ws_bytes": ctypes.c_size_t, "icrl_gae_dual_ws_bytes": ctypes.c_size_t, "icrl_sample_episodes_chain_ws_bytes": ctypes.c_size_t, "icrl_last_error": ctypes.c_char_p, "icrl_clear_error": None}
 
 
 class HipExtensionMissing(RuntimeError):

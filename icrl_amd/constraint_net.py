@@ -138,6 +138,51 @@ class ConstraintNet:
         lead = obs.shape[:-1]
         return self.cost_function_device(obs, acs).cpu().numpy().reshape(lead)
 
+    # ---- which inputs the learned constraint depends on ------------------------------------------------------------------
+    INPUT_GRAD_ROWS = 65536      # rows of one icrl_cost_mlp_fwd_bwd_in call
+
+    def input_gradients(self, obs, acs):
+        """d cost / d obs [N, obs_dim] float64 and d cost / d acs [N, acs_dim] float32 (None for a discrete net) of cost = 1 - zeta at the
+        given rows, as device tensors: icrl_cost_mlp_fwd_bwd_in on the prepared rows (d zeta = -1), then icrl_cn_prepare_bwd through
+        prepare_data (selection, clips, normalisation), in chunks of at most 65536 rows.  A net the entry point does not serve (more than
+        two hidden layers, above 64 units, above 128 inputs) raises NotImplementedError with the library's reason: no torch fallback."""
+        dev, L = self.device, _lib.lib()
+        obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs, device=dev).detach().to(torch.float64).reshape(-1, self.obs_dim).contiguous()
+        a_w = 1 if self.is_discrete else self.acs_dim
+        acs = torch.as_tensor(np.asarray(acs) if not torch.is_tensor(acs) else acs, device=dev).detach().to(torch.float32).reshape(-1, a_w).contiguous()
+        if acs.shape[0] != obs.shape[0]:
+            raise ValueError(f"{obs.shape[0]} observations, {acs.shape[0]} actions")
+        n_all = obs.shape[0]
+        d_obs = torch.empty(n_all, self.obs_dim, dtype=torch.float64, device=dev)
+        d_acs = None if self.is_discrete else torch.empty(n_all, self.acs_dim, device=dev)
+        s, st = self.struct(), _lib.current_stream()
+        cache = self.__dict__.setdefault("_input_grad_ws", {})
+        for r0 in range(0, n_all, self.INPUT_GRAD_ROWS):
+            o, a = obs[r0:r0 + self.INPUT_GRAD_ROWS], acs[r0:r0 + self.INPUT_GRAD_ROWS]
+            n = o.shape[0]
+            if n not in cache:
+                nbytes = L.icrl_cost_mlp_fwd_bwd_in_ws_bytes(_lib.byref(s), n)
+                if nbytes == 0:
+                    reason = L.icrl_last_error().decode()
+                    L.icrl_clear_error()
+                    raise NotImplementedError(f"ConstraintNet.input_gradients: {reason}")
+                cache[n] = (torch.empty(nbytes // 8, dtype=torch.float64, device=dev), torch.full((n,), -1.0, device=dev),
+                            torch.empty(n, self.input_dims, device=dev))
+            ws, minus_one, d_x = cache[n]
+            x = self.prepare_data(o, a)
+            _lib.check(L.icrl_cost_mlp_fwd_bwd_in(_lib.byref(s), p(x), n, p(minus_one), None, None, p(d_x), p(ws), ws.numel() * 8, st),
+                       "icrl_cost_mlp_fwd_bwd_in")
+            _lib.check(L.icrl_cn_prepare_bwd(_lib.byref(s), p(o), p(a), n, p(d_x), p(d_obs[r0:r0 + n]), None if d_acs is None else p(d_acs[r0:r0 + n]), st),
+                       "icrl_cn_prepare_bwd")
+        return d_obs, d_acs
+
+    def saliency(self, obs, acs):
+        """mean over the rows of |d cost / d input| per input column: {"obs": float64 numpy [obs_dim], "acs": float64 numpy [acs_dim] or
+        None (discrete)}.  A column the net does not read (select_dim, or zero first-layer weights) gets exactly 0."""
+        d_obs, d_acs = self.input_gradients(obs, acs)
+        return {"obs": d_obs.abs().mean(dim=0).cpu().numpy().astype(np.float64),
+                "acs": None if d_acs is None else d_acs.double().abs().mean(dim=0).cpu().numpy().astype(np.float64)}
+
     # ---- state dict ------------------------------------------------------------------------------------------------
     def state_dict(self):
         out, off, flat = OrderedDict(), 0, self.params.detach().cpu()

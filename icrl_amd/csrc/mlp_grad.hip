@@ -16,6 +16,13 @@
 // workgroup writes its sums to its own float64 slice of `ws` (at most 64 slices) and a second plain launch adds the slices in index order
 // and rounds: no atomics, no waiting, the same bits on every call.
 // A forward-only call (grad == NULL) runs the same code up to the outputs, hence the same output bits.
+//
+// Input gradients (the `_in` entry points; DIN = true): d loss / d (first pre-activation) of a tile sits in LDS as float64 (sdz1) next to the
+// first layer's weights (sW1), so d loss / d x[r][k] = sum_{j < H1, ascending} sdz1[r][j] W1[j][k] is one more product per tile, a float64 fma
+// chain spread over the 256 threads.  A row belongs to one tile: nothing is summed across workgroups.  The policy's three branches share the
+// observation: each writes its float64 slice [N][K] of ws and a second plain launch adds pi + vf + cvf in that order and rounds once.  The
+// Gaussian head's d loss / d action is the negative of d loss / d mean, which the head block holds already.  The instantiations without DIN take
+// the argument block they always took and compile to what they compiled to.
 // (-ffp-contract=off as for the rest of the library: every FMA here is an explicit fma().)
 #include "common.h"
 #include "cost_fn.h"
@@ -52,6 +59,15 @@ struct MgArgs {
   float* ent;
   double* part;                     // [gridDim.x][n_params] partial sums; NULL: forward only
 };
+
+// the `_in` forms: where the input gradients go (NULL: not asked for)
+struct MgArgsIn : MgArgs {
+  double* dx64;                     // policy: [3][N][K] float64, slice = blockIdx.y; folded by mlp_dx_fold_kernel
+  float* dx32;                      // one network: d loss / d x [N, K], rounded here
+  float* d_act;                     // Gaussian head: d loss / d actions [N, act_store]
+};
+template <bool DIN> struct MgArgsOf { typedef MgArgs type; };
+template <> struct MgArgsOf<true> { typedef MgArgsIn type; };
 
 inline int mg_parts(int N) {
   const int tiles = (N + MG_ROWS - 1) / MG_ROWS;
@@ -126,8 +142,8 @@ __device__ __forceinline__ void mg_outer(double (&acc)[4][4], const double* dz, 
 // learn_features = False): log_std is a matrix [MG_H][AO] (rows beyond the last hidden width zero, like every padding), the variance of
 // action c is sum_h latent_h^2 exp(2 log_std[h][c]) + 1e-6 over the latent units in ascending order, and the latent is DETACHED in it:
 // log_std takes the log-prob's and the entropy's variance part, the network only the mean part.
-template <bool RELU, bool SDE = false>
-__global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
+template <bool RELU, bool SDE = false, bool DIN = false>
+__global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(typename MgArgsOf<DIN>::type a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const MgNet n = a.net[blockIdx.y];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -239,6 +255,9 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
           lp += -(diff * diff) / (2. * var) - ls - MG_LOG_SQRT_2PI;
           en += 0.5 + MG_LOG_SQRT_2PI + ls;
           so[r * 16 + c] = dlp * (diff / var);                               // d log_prob / d mean
+          if constexpr (DIN) {                                               // d log_prob / d action = -d log_prob / d mean
+            if (live && a.d_act != nullptr) a.d_act[(size_t)row * a.act_store + c] = (float)(-so[r * 16 + c]);
+          }
           sdf[r * 16 + c] = dlp * (diff * diff / var - 1.) + den;          // d log_prob / d log_std, d entropy / d log_std = 1
         }
         if (live && a.lp != nullptr) a.lp[row] = (float)lp;
@@ -340,6 +359,19 @@ __global__ void __launch_bounds__(MG_THREADS) mlp_fwd_bwd_kernel(MgArgs a) {
       if (bk0 + 64 * h < KP) mg_outer(accW1[h], sdz1, bj0, sx, KP, bk0 + 64 * h);
     if (tid < 64)
       for (int r = 0; r < MG_ROWS; ++r) accb += sdz1[r * MG_ASTRIDE + tid];
+    // ---- d loss / d x of the tile's rows: sdz1 and sW1 are read only until the next tile's top barrier; the padding columns k >= K of sW1
+    // are zero and not written, rows at or beyond N are not written
+    if constexpr (DIN) {
+      if (a.dx64 != nullptr || a.dx32 != nullptr)
+        for (int i = tid; i < MG_ROWS * KP; i += MG_THREADS) {
+          const int r = i / KP, k = i - r * KP, row = row0 + r;
+          if (k >= K || row >= a.N) continue;
+          double acc = 0.;
+          for (int j = 0; j < n.H1; ++j) acc = fma(sdz1[r * MG_ASTRIDE + j], (double)sW1[j * S1 + k], acc);
+          if (a.dx64 != nullptr) a.dx64[((size_t)blockIdx.y * a.N + row) * K + k] = acc;
+          else a.dx32[(size_t)row * K + k] = (float)acc;
+        }
+    }
   }
   if (a.part == nullptr) return;
 
@@ -381,6 +413,45 @@ __global__ void __launch_bounds__(256) mlp_grad_fold_kernel(const double* __rest
   grad[i] = (float)s;
 }
 
+// d_obs[i] = (float)(dx[0][i] + dx[1][i] + dx[2][i]): pi, vf, cvf in that order
+__global__ void __launch_bounds__(256) mlp_dx_fold_kernel(const double* __restrict__ dx, long long n, float* __restrict__ d_obs) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  d_obs[i] = (float)((dx[i] + dx[n + i]) + dx[2 * n + i]);
+}
+
+// [N, cols] of the source columns of icrl_cn_prepare: column s < obs_dim an observation, obs_dim + k an action (continuous nets only).
+// sum over the selected positions i with select_dim[i] == s of d_x[n][i], ascending i, float64; then the clip's derivative (1 inside the
+// closed interval, as torch.clamp) and, for a normalised observation, 1 / sqrt(var + eps): the order of autograd through prepare_data
+__global__ void __launch_bounds__(256) cn_prepare_bwd_kernel(icrl_costnet_t cn, const double* __restrict__ obs, const float* __restrict__ acs, int N,
+                                                             const float* __restrict__ d_x, double* __restrict__ d_obs, float* __restrict__ d_acs) {
+  const int cols = cn.obs_dim + (d_acs != nullptr ? cn.acs_dim : 0);
+  const long long total = (long long)N * cols;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int n = (int)(idx / cols), s = (int)(idx - (long long)n * cols);
+    if (s < cn.obs_dim && d_obs == nullptr) continue;
+    const float* g = d_x + (size_t)n * cn.in_dim;
+    double acc = 0.;
+    for (int i = 0; i < cn.in_dim; ++i)
+      if (cn.select_dim[i] == s) acc += (double)g[i];
+    if (s < cn.obs_dim) {
+      double o = obs[(size_t)n * cn.obs_dim + s], scale = 1.;
+      if (cn.obs_mean != nullptr && cn.obs_var != nullptr) {
+        const double sd = sqrt(cn.obs_var[s] + cn.eps);
+        o = (o - cn.obs_mean[s]) / sd;
+        scale = 1. / sd;
+      }
+      if (cn.clip_obs >= 0.0 && !(o >= -cn.clip_obs && o <= cn.clip_obs)) acc = 0.;
+      d_obs[(size_t)n * cn.obs_dim + s] = acc * scale;
+    } else {
+      const int k = s - cn.obs_dim;
+      const float x = acs[(size_t)n * cn.acs_dim + k];
+      if (cn.action_low != nullptr && cn.action_high != nullptr && !(x >= cn.action_low[k] && x <= cn.action_high[k])) acc = 0.;
+      d_acs[(size_t)n * cn.acs_dim + k] = (float)acc;
+    }
+  }
+}
+
 template <bool RELU, bool SDE = false>
 int mg_launch(MgArgs& a, int n_nets, int max_k, float* grad, void* ws, hipStream_t s) {
   const int parts = mg_parts(a.N);
@@ -394,6 +465,32 @@ int mg_launch(MgArgs& a, int n_nets, int max_k, float* grad, void* ws, hipStream
   hipLaunchKernelGGL((mlp_fwd_bwd_kernel<RELU, SDE>), dim3(parts, n_nets), dim3(MG_THREADS), lds, s, a);
   if (bwd) hipLaunchKernelGGL(mlp_grad_fold_kernel, dim3((a.n_params + 255) / 256), dim3(256), 0, s, (const double*)ws, parts, a.n_params, grad);
   return (int)hipGetLastError();
+}
+
+// the `_in` forms: ws = the partial sums of the parameters (always written; folded into grad when it is asked for), then, for the policy's
+// d_obs, three float64 slices [N][K]
+template <bool RELU>
+int mg_launch_in(MgArgsIn& a, int n_nets, int max_k, float* grad, float* d_x, void* ws, hipStream_t s) {
+  const int parts = mg_parts(a.N);
+  a.part = (double*)ws;
+  a.dx64 = (n_nets == 3 && d_x != nullptr) ? (double*)ws + (size_t)parts * a.n_params : nullptr;
+  a.dx32 = n_nets == 1 ? d_x : nullptr;
+  const size_t lds = mg_lds_bytes(max_k, false);
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)mlp_fwd_bwd_kernel<RELU, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((mlp_fwd_bwd_kernel<RELU, false, true>), dim3(parts, n_nets), dim3(MG_THREADS), lds, s, a);
+  if (grad != nullptr) hipLaunchKernelGGL(mlp_grad_fold_kernel, dim3((a.n_params + 255) / 256), dim3(256), 0, s, (const double*)ws, parts, a.n_params, grad);
+  if (a.dx64 != nullptr) {
+    const long long n = (long long)a.N * max_k;
+    hipLaunchKernelGGL(mlp_dx_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)a.dx64, n, d_x);
+  }
+  return (int)hipGetLastError();
+}
+
+inline long long mg_policy_in_ws(const icrl_policy_t* pol, int N) {
+  return ((long long)mg_parts(N) * pol->n_params + 3LL * N * pol->obs_dim) * (long long)sizeof(double);
 }
 
 // 0, or the fail() code of a policy these entry points do not serve
@@ -508,4 +605,84 @@ extern "C" int icrl_cost_mlp_fwd_bwd(const icrl_costnet_t* cn, const float* x, i
   n.d_out = d_zeta; n.out = zeta;
   a.params = cn->params; a.x = x; a.N = N; a.n_params = L.n;
   return mg_launch<true>(a, 1, L.in, grad, ws, (hipStream_t)stream);
+}
+
+// ---- the same two calls with the gradients of the inputs (DIN)
+extern "C" size_t icrl_policy_fwd_bwd_in_ws_bytes(const icrl_policy_t* pol, int N) {
+  if (mg_policy_check("icrl_policy_fwd_bwd_in_ws_bytes", pol, N) != 0) return 0;
+  return (size_t)mg_policy_in_ws(pol, N);
+}
+
+extern "C" int icrl_policy_fwd_bwd_in(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
+                                      const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
+                                      float* d_obs, float* d_actions, void* ws, long long ws_bytes, void* stream) {
+  const char* who = "icrl_policy_fwd_bwd_in";
+  if (const int e = mg_policy_check(who, pol, N)) return e;
+  if (pol->params == nullptr || obs == nullptr || actions == nullptr) return fail("%s: NULL argument (pol->params, obs and actions are required)", who);
+  if (grad == nullptr && d_obs == nullptr && d_actions == nullptr)
+    return fail("%s: no gradient output (grad, d_obs and d_actions are all NULL: icrl_policy_fwd_bwd is the forward-only call)", who);
+  if (d_actions != nullptr && pol->discrete)
+    return fail("%s: d_actions with a discrete policy (a class index has no gradient: pass NULL)", who);
+  const long long need = mg_policy_in_ws(pol, N);
+  if (ws == nullptr || ws_bytes < need)
+    return fail("%s: ws of %lld bytes, icrl_policy_fwd_bwd_in_ws_bytes(pol, %d) = %lld", who, ws == nullptr ? 0LL : ws_bytes, N, need);
+  const PolLayout L = make_pol_layout(pol->obs_dim, pol->act_dim, pol->h1, pol->h2, pol->discrete);
+  MgArgsIn a = {};
+  for (int b = 0; b < 3; ++b) {
+    MgNet& n = a.net[b];
+    n.K = L.O; n.H1 = L.H1; n.H2 = L.H2; n.nh = 2;
+    n.W1 = L.W1[b]; n.b1 = L.b1[b]; n.W2 = L.W2[b]; n.b2 = L.b2[b]; n.ls = L.log_std;
+  }
+  a.net[0].AO = L.A; a.net[0].kind = pol->discrete ? MG_CATEG : MG_GAUSS; a.net[0].Wh = L.Wa; a.net[0].bh = L.ba;
+  a.net[1].AO = 1; a.net[1].kind = MG_VALUE; a.net[1].Wh = L.Wv; a.net[1].bh = L.bv; a.net[1].d_out = d_v_r; a.net[1].out = v_r;
+  a.net[2].AO = 1; a.net[2].kind = MG_VALUE; a.net[2].Wh = L.Wc; a.net[2].bh = L.bc; a.net[2].d_out = d_v_c; a.net[2].out = v_c;
+  a.params = pol->params; a.x = obs; a.actions = actions; a.act_store = pol->discrete ? 1 : L.A; a.N = N; a.n_params = L.n;
+  a.d_lp = d_log_prob; a.d_ent = d_entropy; a.lp = log_prob; a.ent = entropy;
+  a.d_act = d_actions;
+  return mg_launch_in<false>(a, 3, L.O, grad, d_obs, ws, (hipStream_t)stream);
+}
+
+extern "C" size_t icrl_cost_mlp_fwd_bwd_in_ws_bytes(const icrl_costnet_t* cn, int N) {
+  if (mg_costnet_check("icrl_cost_mlp_fwd_bwd_in_ws_bytes", cn, N) != 0) return 0;
+  return (size_t)mg_parts(N) * (size_t)cn->n_params * sizeof(double);
+}
+
+extern "C" int icrl_cost_mlp_fwd_bwd_in(const icrl_costnet_t* cn, const float* x, int N, const float* d_zeta, float* zeta, float* grad, float* d_x, void* ws,
+                                        long long ws_bytes, void* stream) {
+  const char* who = "icrl_cost_mlp_fwd_bwd_in";
+  if (const int e = mg_costnet_check(who, cn, N)) return e;
+  if (cn->params == nullptr || x == nullptr) return fail("%s: NULL argument (cn->params and x are required)", who);
+  if (grad == nullptr && d_x == nullptr)
+    return fail("%s: no gradient output (grad and d_x are both NULL: icrl_cost_mlp_fwd_bwd is the forward-only call)", who);
+  if (d_zeta == nullptr) return fail("%s: d_zeta is required (d loss / d zeta per row)", who);
+  const long long need = (long long)mg_parts(N) * cn->n_params * (long long)sizeof(double);
+  if (ws == nullptr || ws_bytes < need)
+    return fail("%s: ws of %lld bytes, icrl_cost_mlp_fwd_bwd_in_ws_bytes(cn, %d) = %lld", who, ws == nullptr ? 0LL : ws_bytes, N, need);
+  const CnLayout L = make_cn_layout(cn->in_dim, cn->n_hidden, cn->h1, cn->h2);
+  MgArgsIn a = {};
+  MgNet& n = a.net[0];
+  n.K = L.in; n.H1 = L.H1; n.H2 = L.H2; n.AO = 1; n.nh = L.nh; n.kind = MG_ZETA;
+  n.W1 = L.W0; n.b1 = L.b0; n.W2 = L.W1; n.b2 = L.b1; n.Wh = L.Wo; n.bh = L.bo; n.ls = -1;
+  n.d_out = d_zeta; n.out = zeta;
+  a.params = cn->params; a.x = x; a.N = N; a.n_params = L.n;
+  return mg_launch_in<true>(a, 1, L.in, grad, d_x, ws, (hipStream_t)stream);
+}
+
+extern "C" int icrl_cn_prepare_bwd(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, const float* d_x, double* d_obs, float* d_acs,
+                                   void* stream) {
+  const char* who = "icrl_cn_prepare_bwd";
+  if (cn == nullptr) return fail("%s: NULL constraint-net descriptor", who);
+  if (as_cost_fn(cn)) return refuse_cost_fn(who);
+  if (as_cost_disc(cn)) return refuse_cost_disc(who);
+  if (as_cost_region(cn)) return refuse_cost_region(who);
+  if (N <= 0) return fail("%s: N = %d rows", who, N);
+  if (cn->in_dim < 1 || cn->obs_dim < 1 || cn->acs_dim < 1) return fail("%s: in_dim %d, obs_dim %d, acs_dim %d (each >= 1)", who, cn->in_dim, cn->obs_dim, cn->acs_dim);
+  if (d_obs == nullptr && d_acs == nullptr) return fail("%s: no gradient output (d_obs and d_acs are both NULL)", who);
+  if (d_acs != nullptr && cn->is_discrete) return fail("%s: d_acs with a discrete net (a class index has no gradient: pass NULL)", who);
+  if (d_x == nullptr || cn->select_dim == nullptr || (d_obs != nullptr && obs == nullptr) || (d_acs != nullptr && acs == nullptr))
+    return fail("%s: NULL argument (d_x and cn->select_dim are required; obs with d_obs, acs with d_acs)", who);
+  const long long total = (long long)N * (cn->obs_dim + (d_acs != nullptr ? cn->acs_dim : 0));
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(cn_prepare_bwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, *cn, obs, acs, N, d_x, d_obs, d_acs);
+  return (int)hipGetLastError();
 }

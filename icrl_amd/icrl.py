@@ -26,11 +26,44 @@ from .vec_env import VecNormalize, sync_envs_normalization
 from . import envs, spaces
 
 
+REFUSE_SALIENCY_SEED_BATCH = ("--cn_saliency: the input gradients are taken per run after its backward step, and a seed batch (--seeds with more than one "
+                              "seed) runs the backward steps of all runs as one launch sequence with no per-run hook; run the seeds one at a time")
+REFUSE_SALIENCY_RANKS = ("--cn_saliency: the saliency is a mean over ONE rank's nominal samples and is not part of the rank collective; world_size > 1 is "
+                         "not served (run one rank)")
+REFUSE_SALIENCY_NET = ("--cn_saliency: constraint-net layers {layers} are not served by icrl_cost_mlp_fwd_bwd_in (one or two hidden layers of up to 64 "
+                       "units); there is no torch fallback")
+
+
+def refuse_cn_saliency(config, seed_batch=False):
+    """raise, naming the flag, where `--cn_saliency` is not served: seed batches, several ranks, a constraint net outside the entry point's
+    shapes.  Called before anything is set up (setup below, the seed-batch constructor)."""
+    get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+    if not get("cn_saliency", False):
+        return
+    if seed_batch:
+        raise ValueError(REFUSE_SALIENCY_SEED_BATCH)
+    if (get("world_size", 1) or 1) > 1:
+        raise ValueError(REFUSE_SALIENCY_RANKS)
+    layers = list(get("cn_layers", None) or [])
+    if not 1 <= len(layers) <= 2 or max(layers) > 64 or min(layers) < 1:
+        raise NotImplementedError(REFUSE_SALIENCY_NET.format(layers=layers))
+
+
+def saliency_metrics(constraint_net, obs, acs):
+    """backward/saliency_obs_<i>, backward/saliency_acs_<j>: mean |d cost / d input| over the given rows (ConstraintNet.saliency)."""
+    sal = constraint_net.saliency(obs, acs)
+    out = {f"backward/saliency_obs_{i}": float(v) for i, v in enumerate(sal["obs"])}
+    if sal["acs"] is not None:
+        out.update({f"backward/saliency_acs_{j}": float(v) for j, v in enumerate(sal["acs"])})
+    return out
+
+
 def setup(config):
     """everything of icrl() before the loop (ref: icrl/icrl.py:45-197): env stacks, expert data, constraint net, nominal agent."""
     rank, world = getattr(config, "rank", 0), getattr(config, "world_size", 1)
     use_curiosity = bool(getattr(config, "use_curiosity_driven_exploration", False))
     check_cost_spec_flags(config)
+    refuse_cn_saliency(config)
     if getattr(config, "use_sde", False):      # -us with -ucde or several ranks: refused before anything is launched
         from . import exploration
         exploration.refuse_sde(config)
@@ -75,6 +108,13 @@ def setup(config):
         target_kl_old_new=config.cn_target_kl_old_new, target_kl_new_old=config.cn_target_kl_new_old,
         train_gail_lambda=config.train_gail_lambda, eps=config.cn_eps, device=dev)
     train_env.set_cost_function(constraint_net.cost_function)
+    if getattr(config, "cn_saliency", False):      # what the layer check above cannot see (the input width): the library's own answer, before the loop
+        from . import _lib
+        cs = constraint_net.struct()
+        if _lib.lib().icrl_cost_mlp_fwd_bwd_in_ws_bytes(_lib.byref(cs), 1) == 0:
+            reason = _lib.lib().icrl_last_error().decode()
+            _lib.lib().icrl_clear_error()
+            raise NotImplementedError(f"--cn_saliency: {reason}")
 
     def create_nominal_agent():
         agent = PPOLagrangian(
@@ -186,6 +226,8 @@ def outer_iteration(st, itr):
         cn_perms = streams.cn_permutations(config.backward_iters, min(int(orig_observations.shape[0]), int(np.asarray(constraint_net.expert_obs).shape[0])))
     backward_metrics = constraint_net.train(config.backward_iters, orig_observations, actions, lengths, mean, var,
                                             current_progress_remaining, perms=cn_perms)
+    if getattr(config, "cn_saliency", False):      # which inputs the updated constraint depends on, over this iteration's nominal samples
+        backward_metrics.update(saliency_metrics(constraint_net, orig_observations, actions))
     train_env.set_cost_function(constraint_net.cost_function)
     # ---- the single collective of the iteration
     synchronise(st)
@@ -297,6 +339,9 @@ def build_parser():
     # a user-defined ground-truth constraint (true_constraint_net.RegionCost: a JSON file or string) in the place of the env id's for
     # true/cost and friends; absent from the namespace unless given, like -sfr
     a("--cost_spec", "-csp", type=str, default=argparse.SUPPRESS)
+    # log backward/saliency_obs_<i> / backward/saliency_acs_<j> after every backward step: mean |d cost / d input| of the learned constraint over
+    # the iteration's nominal samples (ConstraintNet.saliency); absent from the namespace unless given, like -sfr
+    a("--cn_saliency", action="store_true", default=argparse.SUPPRESS)
     a("--save_dir", type=str, default=None); a("--action_noise", type=str, default="device"); a("--permutation", type=str, default="numpy")
     a("--env_module", action="append", default=None, help="import MODULE (it registers host envs: icrl_amd.envs.register); repeatable")
     a("--dummy_vec_env", action="store_true", help="host envs of the train env stepped in this process (DummyVecEnv), not one worker process each")

@@ -144,9 +144,11 @@ class SeedBatch:
 
     def __init__(self, configs=None, states=None, on_setup=None):
         if states is None:      # refused before anything is set up
+            from .icrl import refuse_cn_saliency
             configs = list(configs)
             for c in configs:
                 _refuse_cost_spec(c)
+                refuse_cn_saliency(c, seed_batch=True)
                 exploration.refuse_batched(c, seed_batch=True)
                 exploration.refuse_sde(c, seed_batch=True)
         self.states = setup_runs(configs, on_setup) if states is None else states

@@ -1008,6 +1008,43 @@ size_t icrl_cost_mlp_fwd_bwd_ws_bytes(const icrl_costnet_t* cn, int N);
 int icrl_cost_mlp_fwd_bwd(const icrl_costnet_t* cn, const float* x, int N, const float* d_zeta, float* zeta, float* grad, void* ws,
                           long long ws_bytes, void* stream);
 
+/* The two calls above with the gradients of the INPUTS (csrc/mlp_grad.hip, the DIN form of the same kernel; icrl_amd/torch_ops.py
+ * input_grads=True, ConstraintNet.input_gradients).  Opt-in beside the calls above, which keep their signatures and bits; outputs and grad
+ * of an `_in` call are bit-equal to theirs on the same arguments.
+ * icrl_policy_fwd_bwd_in: the arguments of icrl_policy_fwd_bwd plus
+ *   d_obs     [N, obs_dim]  = sum over pi, vf, cvf (in that order, float64, rounded once) of d loss / d obs through each branch,
+ *   d_actions [N, act_dim]  = -d_log_prob[n] (a - mean) / var, the Gaussian head's d loss / d action (the entropy does not depend on it).
+ *   Either may be NULL; d_actions must be NULL for a discrete policy (a class index has no gradient; the Categorical entropy's
+ *   dependence on obs goes through the logits and is in d_obs).  grad may be NULL while d_obs / d_actions are given: the parameter sums
+ *   still go to ws, only their fold into grad is skipped.  The upstream d_* are allowed whenever any of the three outputs is given; all
+ *   three NULL is refused (forward only: icrl_policy_fwd_bwd).
+ *   Per tile of 16 rows: d x[r][k] = sum_{j < h1, ascending} dz1[r][j] W1[j][k], a float64 fma chain on the float32 weights; a row
+ *   belongs to one tile, so nothing is summed across workgroups; each branch writes a float64 slice [N, obs_dim] of ws and one more plain
+ *   launch adds the three and rounds.  No atomics; the same call gives the same bits; rows at or beyond N are not written.
+ *   ws: ALWAYS needed, icrl_policy_fwd_bwd_in_ws_bytes(pol, N) = (min(ceil(N / 16), 64) n_params + 3 N obs_dim) doubles.
+ *   Served: what icrl_policy_fwd_bwd serves; a gSDE layout is refused through n_params.
+ * icrl_cost_mlp_fwd_bwd_in: the arguments of icrl_cost_mlp_fwd_bwd plus d_x [N, in_dim] = d loss / d x, the float64 value rounded once
+ *   (one network: written by the kernel itself).  d_zeta is required; grad or d_x may be NULL, not both.  ws: ALWAYS needed,
+ *   icrl_cost_mlp_fwd_bwd_in_ws_bytes(cn, N) (= icrl_cost_mlp_fwd_bwd_ws_bytes).
+ * icrl_cn_prepare_bwd: the chain rule through icrl_cn_prepare (icrl/constraint_net.py:258-299), d_x [N, in_dim] -> d_obs [N, obs_dim]
+ *   float64 and d_acs [N, acs_dim] float32 (either may be NULL, not both; d_acs must be NULL for a discrete net).  A kernel of its own,
+ *   allocates nothing.  For a source column: the d_x of the selected positions that read it are added in ascending position, in float64
+ *   (select_dim may name a column more than once, and an observation column through acs_select_dim); then the clip's derivative, 1
+ *   where -clip_obs <= normalised obs <= clip_obs resp. action_low <= a <= action_high (both ends inclusive, as torch.clamp), recomputed
+ *   from obs / acs in float64 resp. float32; then 1 / sqrt(var + eps) where the net normalises.  Columns nothing selects get 0.
+ * Everything else (the shapes the siblings refuse, the tagged descriptors, a ws below the *_ws_bytes value, d_actions / d_acs with a
+ * discrete descriptor, no output requested, a NULL required pointer) returns hipErrorInvalidValue with the reason before any device
+ * call.  The calls allocate nothing, do not synchronise and write no route record. */
+size_t icrl_policy_fwd_bwd_in_ws_bytes(const icrl_policy_t* pol, int N);
+int icrl_policy_fwd_bwd_in(const icrl_policy_t* pol, const float* obs, const float* actions, int N, const float* d_v_r, const float* d_v_c,
+                           const float* d_log_prob, const float* d_entropy, float* v_r, float* v_c, float* log_prob, float* entropy, float* grad,
+                           float* d_obs, float* d_actions, void* ws, long long ws_bytes, void* stream);
+size_t icrl_cost_mlp_fwd_bwd_in_ws_bytes(const icrl_costnet_t* cn, int N);
+int icrl_cost_mlp_fwd_bwd_in(const icrl_costnet_t* cn, const float* x, int N, const float* d_zeta, float* zeta, float* grad, float* d_x, void* ws,
+                             long long ws_bytes, void* stream);
+int icrl_cn_prepare_bwd(const icrl_costnet_t* cn, const double* obs, const float* acs, int N, const float* d_x, double* d_obs, float* d_acs,
+                        void* stream);
+
 /* One full-batch regression step of MLP(in -> h1 -> ReLU -> h2 -> ReLU -> out), the reference's create_mlp(in, out, [h1, h2]) with no
  * output squashing: the rollout-end step of the exploration callbacks (icrl/exploration.py:50-67, 227-261; csrc/reg_mlp.hip).
  * params / exp_avg / exp_avg_sq: flat float32 buffers of EXACTLY n_params = h1 (in + 1) + h2 (h1 + 1) + out (h2 + 1) entries in torch's
